@@ -11,14 +11,23 @@ the seeded 'spread' init (random-init weights of the architecture; the trained c
 tests/golden/trained are parity fixtures, not the timed workload), generated on rank 0 and
 broadcast over RCCL once at setup.
 
-Rank 0 prints ONE JSON line with the driver's keys plus:
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the
+driver's keys (metric, value, unit, ms_per_step, dtype, ...).  `--dump-outputs DIR` also
+writes what the last timed step returned to its caller (the u8 latents and reconstructions,
+the entropy bits of the 4k workload) as DIR/<name>.npy in float32: at most 64 MB in all, an
+array that does not fit whole is a fixed seeded sample of its elements (same positions in
+every run; inputs and weights are seeded, so two builds compare output for output).
+
+`--full` adds every other measurement to that line, after the timed steps:
   roofline     -- dominant kernel: algorithmic FLOP per launch / its mean launch time,
                   measured with hipEvents on the launch stream over a timed pass;
   layers       -- the same per layer;
   cpu_baseline -- the PyTorch-CPU (oneDNN) restatement of tf2_0 on this process's host
                   cores (TF itself is not installable), bounded sample, rank 0 at N=1 only;
                   the NumPy oracle's rate beside it as `numpy_oracle`;
-  parity       -- PSNR of one benchmarked image's reconstruction vs the oracle.
+  parity       -- PSNR of one benchmarked image's reconstruction vs the oracle;
+  pcie_inclusive, quality, collectives (N > 1), power_probe: see main().
+The --no-* options drop single legs of a `--full` run.
 """
 from __future__ import annotations
 
@@ -261,6 +270,25 @@ def host_box_rates(xh, enc, dec, reps):
             "decode_call_ms_median": round(float(np.median(td)) * 1e3, 3)}
 
 
+DUMP_BUDGET_BYTES = 60_000_000  # of the 64 MB a dump may hold (.npy headers, slack)
+
+
+def dump_outputs(path: str, outputs: dict, budget: int = DUMP_BUDGET_BYTES) -> None:
+    """Write {name: device tensor} as path/<name>.npy, float32, `budget` bytes in all.  Small
+    arrays go whole; one that exceeds its share is written as a 1-D sample of its flattened
+    elements at sorted positions drawn from default_rng(0) (the same in every run)."""
+    os.makedirs(path, exist_ok=True)
+    left, todo = budget // 4, sorted(outputs.items(), key=lambda kv: kv[1].numel())
+    for i, (name, t) in enumerate(todo):
+        a = t.detach().cpu().numpy()
+        share = left // (len(todo) - i)
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).integers(0, a.size, share))
+            a = a.reshape(-1)[idx]
+        left -= a.size
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32))
+
+
 def bench_weights(kind: str):
     """The timed workload's weights: the seeded 'spread' init (default), or the committed
     round-4 trained codec (entropy_loss_coef 0.01) for the informational operand comparison."""
@@ -346,6 +374,13 @@ def main():
                     help="config2: 64 x 256^2 encode+decode (BASELINE headline); kodak: 768x512 "
                          "whole images encode+decode (config 4 shape); 4k: 3840x2160 frames, "
                          "encode + per-plane histogram entropy (config 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure per-layer / roofline figures, the host-array "
+                         "surface, MS-SSIM timing, the CPU baselines, oracle parity, the power probe and "
+                         "(N > 1) the gather; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32, <= 64 MB in all; "
+                         "rank r > 0 of a multi-GPU run writes DIR/rank<r>/)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--weights", default="seeded", choices=["seeded", "trained"],
                     help="trained: the round-4 codec (entropy_loss_coef 0.01, tests/golden/trained) -- "
@@ -426,15 +461,16 @@ def main():
     hist_fold = os.environ.get("NIC_BENCH_HIST", "fold") != "sep"
     if args.workload == "4k" and hist_fold:
         def step():
-            codec.encode_entropy(x, out=z)
+            zz, bits = codec.encode_entropy(x, out=z)
+            return {"latent": zz, "entropy_bits": bits}
     elif args.workload == "4k":
         def step():
-            codec.encode(x, out=z)
-            codec.entropy(z)
+            zz = codec.encode(x, out=z)
+            return {"latent": zz, "entropy_bits": codec.entropy(zz)}
     else:
         def step():
-            codec.encode(x, out=z)
-            codec.decode(z, out=r)
+            zz = codec.encode(x, out=z)
+            return {"latent": zz, "recon": codec.decode(zz, out=r)}
 
     def barrier():
         if world > 1:
@@ -449,7 +485,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     barrier()
     el = time.perf_counter() - t0
@@ -457,6 +493,38 @@ def main():
         t = torch.tensor([el], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    if args.dump_outputs:
+        # each rank's own shard, the 64 MB shared between the ranks
+        dump_outputs(os.path.join(args.dump_outputs, f"rank{rank}") if rank else args.dump_outputs, last,
+                     DUMP_BUDGET_BYTES // world)
+
+    ms_step = el / args.steps * 1e3
+    value = world * B * H * W * args.steps / 1e6 / el
+    out = {
+        "metric": METRIC, "value": round(value, 2), "unit": "MP/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_step, 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "fp32" if args.precision == "fp32" else "fp32 (split-f16x3 MFMA)",
+        "data": "synthetic" if args.images == "random" or args.workload != "config2" else "kodim21 crops",
+        "config": {"workload": {"config2": f"config2: {B}x{H}x{W}x3 u8 synthetic per GPU, encode+decode",
+                                "kodak": f"config4 shape: {B}x{H}x{W}x3 whole images per GPU, encode+decode",
+                                "4k": f"config5: {B}x{H}x{W}x3 frames per GPU, encode + histogram entropy"
+                                }[args.workload] + " (torch seed 1000+rank)",
+                   "global_batch": world * B, "image": [H, W, 3], "parallelism": f"dp{world}",
+                   "weights": "seeded spread init (random-init weights of the architecture)" if args.weights == "seeded"
+                   else "trained codec, entropy_loss_coef 0.01 (tests/golden/trained)"},
+    }
+    if args.workload == "4k":
+        out["metric"] = "Megapixels/sec encode + entropy (4K frames)"
+        out["frames_per_s"] = round(world * B * args.steps / el, 2)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        barrier()
+        torch.cuda.synchronize()
+        codec.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # per-layer device time: hipEvents around every launch on the launch stream
     codec.set_timing(True)
@@ -635,33 +703,17 @@ def main():
                                    "frac": round(flops[l2[0]] / (ms2 * 1e-3) / 1e12 / peak, 4)}
     enc_only = args.workload == "4k"
     total_flop = sum(v for k, v in geo.items() if not (enc_only and k.startswith("dconv"))) * P
-    ms_step = el / args.steps * 1e3
-    value = world * B * H * W * args.steps / 1e6 / el
-    out = {
-        "metric": METRIC, "value": round(value, 2), "unit": "MP/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms_step, 3), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "fp32" if args.precision == "fp32" else "fp32 (split-f16x3 MFMA)",
-        "data": "synthetic" if args.images == "random" or args.workload != "config2" else "kodim21 crops",
-        "config": {"workload": {"config2": f"config2: {B}x{H}x{W}x3 u8 synthetic per GPU, encode+decode",
-                                "kodak": f"config4 shape: {B}x{H}x{W}x3 whole images per GPU, encode+decode",
-                                "4k": f"config5: {B}x{H}x{W}x3 frames per GPU, encode + histogram entropy"
-                                }[args.workload] + " (torch seed 1000+rank)",
-                   "global_batch": world * B, "image": [H, W, 3], "parallelism": f"dp{world}",
-                   "weights": "seeded spread init (random-init weights of the architecture)" if args.weights == "seeded"
-                   else "trained codec, entropy_loss_coef 0.01 (tests/golden/trained)"},
+    out.update({
         "step_tflops": round(total_flop / (ms_step * 1e-3) / 1e12, 2),
         "step_frac_peak": round(total_flop / (ms_step * 1e-3) / 1e12 / peak, 4),
         "roofline": roofline, "layers": layers,
-    }
+    })
     if quality is not None:
         out["quality"] = quality
     if coll is not None:
         out["collectives"] = coll
     if host_path is not None:
         out["pcie_inclusive"] = host_path
-    if args.workload == "4k":
-        out["metric"] = "Megapixels/sec encode + entropy (4K frames)"
-        out["frames_per_s"] = round(world * B * args.steps / el, 2)
     if world == 1 and not args.no_cpu_baseline and args.workload == "config2":
         out["cpu_baseline"] = cpu_baseline(weights, S, args.cpu_seconds)
         out["cpu_baseline"]["numpy_oracle"] = cpu_baseline_numpy(weights, S, args.cpu_seconds / 2)

@@ -50,7 +50,7 @@ def test_bench_gpus_flag_mismatch_fails():
 def test_bench_gpus2_without_launcher():
     # the world-2 codec path started by `--gpus 2` alone (both ranks share the box's one GPU
     # over gloo): rank 0's single line reports n_gpus 2 and the gathered bytes of both shards
-    out = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4", "--no-power-probe",
+    out = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4", "--full", "--no-power-probe",
                   "--no-host-path", "--no-quality"])
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -60,11 +60,59 @@ def test_bench_gpus2_without_launcher():
     assert d["collectives"]["gathered_bytes"] == 8 * (32 * 32 * 96 + 256 * 256 * 3)
 
 
+def test_dump_outputs_budget_and_sample(tmp_path):
+    # small arrays whole, the one over its share as a seeded sample: same positions every time
+    import numpy as np
+    import torch
+
+    import bench
+
+    a = torch.arange(1000, dtype=torch.uint8).reshape(10, 100)
+    b = torch.arange(50_000, dtype=torch.int32)
+    for d in ("one", "two"):
+        bench.dump_outputs(str(tmp_path / d), {"big": b, "small": a}, budget=4 * 5000)
+    small, big = np.load(tmp_path / "one" / "small.npy"), np.load(tmp_path / "one" / "big.npy")
+    assert small.dtype == np.float32 and big.dtype == np.float32
+    assert small.shape == (10, 100) and np.array_equal(small, a.numpy())
+    assert big.shape == (4000,) and small.nbytes + big.nbytes <= 4 * 5000
+    assert np.all(np.diff(big) >= 0) and len(np.unique(big)) > 3000 and big.max() > 45_000  # spread over b
+    assert np.array_equal(big, np.load(tmp_path / "two" / "big.npy"))
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    # a plain run: the driver's keys only, nothing from --full; --dump-outputs writes the last
+    # timed step's latents and reconstructions, identical from run to run
+    import numpy as np
+
+    got = []
+    for d in ("a", "b"):
+        out = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "3", "--size", "72",
+                      "--dump-outputs", str(tmp_path / d)])
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        j = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "config"):
+            assert k in j, k
+        for k in ("roofline", "layers", "cpu_baseline", "parity", "pcie_inclusive", "quality"):
+            assert k not in j, k
+        assert j["steps"] == 2 and j["value"] > 0 and j["ms_per_step"] > 0
+        assert abs(j["value"] - 3 * 72 * 72 / 1e6 / (j["ms_per_step"] * 1e-3)) <= 0.01 * j["value"]
+        assert sorted(os.listdir(tmp_path / d)) == ["latent.npy", "recon.npy"]
+        got.append({n: np.load(tmp_path / d / (n + ".npy")) for n in ("latent", "recon")})
+    a, b = got
+    assert a["latent"].dtype == np.float32 and a["latent"].shape == (3, 9, 9, 96)
+    assert a["recon"].dtype == np.float32 and a["recon"].shape == (3, 72, 72, 3)
+    assert a["latent"].std() > 0 and a["recon"].std() > 0
+    assert np.array_equal(a["latent"], b["latent"]) and np.array_equal(a["recon"], b["recon"])
+
+
 @pytest.mark.gpu
 def test_bench_json_line():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
-                          "--batch", "4", "--cpu-seconds", "1"], capture_output=True, text=True, timeout=300,
-                         cwd=ROOT)
+                          "--batch", "4", "--full", "--cpu-seconds", "1"], capture_output=True, text=True,
+                         timeout=300, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -93,7 +141,8 @@ def test_bench_world2_path_under_torchrun():
     env = dict(os.environ, NIC_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", f"--master-port={port}", os.path.join(ROOT, "bench.py"), "--gpus", "2",
-           "--steps", "2", "--warmup", "1", "--batch", "4", "--no-power-probe", "--no-host-path", "--no-quality"]
+           "--steps", "2", "--warmup", "1", "--batch", "4", "--full", "--no-power-probe", "--no-host-path",
+           "--no-quality"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -12,7 +12,7 @@ for r in $(seq 1 "$ROUNDS"); do
   for v in $VARIANTS; do
     name="${v%%=*}"; spec="${v#*=}"; lib="${spec%%,*}"; envs=""
     [[ "$spec" == *,* ]] && envs="${spec#*,}"
-    env ${envs//,/ } NIC_LIB="$ROOT/$lib" timeout -k 10 240 python bench.py $ARGS --no-cpu-baseline --no-parity \
+    env ${envs//,/ } NIC_LIB="$ROOT/$lib" timeout -k 10 240 python bench.py $ARGS --full --no-cpu-baseline --no-parity \
       > "$OUT/${TAG}_${name}_$r.json" 2> "$OUT/${TAG}_${name}_$r.err"
     rc=$?
     if [ $rc -ne 0 ]; then echo "[$name] rc=$rc: stopping"; tail -5 "$OUT/${TAG}_${name}_$r.err"; exit $rc; fi

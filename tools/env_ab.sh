@@ -5,7 +5,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT=gpurun_out/${TAG:-r5j}
 mkdir -p $OUT
-B="python bench.py --steps 30 --warmup 20 --no-cpu-baseline --no-host-path --no-quality --no-power-probe --no-parity"
+B="python bench.py --steps 30 --warmup 20 --full --no-cpu-baseline --no-host-path --no-quality --no-power-probe --no-parity"
 for r in 1 2; do
   for v in "$@"; do
     f=$(echo "$v" | tr '=-' '_m')

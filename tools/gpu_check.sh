@@ -25,13 +25,13 @@ if [[ "$STEPS" == all || "$STEPS" == *smoke* ]]; then
   rc=$?; tail -5 "$OUT/${TAG}_smoke.log"; stop_on $rc smoke
 fi
 if [[ "$STEPS" == all || "$STEPS" == *bench* ]]; then
-  timeout -k 10 300 python bench.py --steps 20 --warmup 10 > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
+  timeout -k 10 300 python bench.py --steps 20 --warmup 10 --full > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
   rc=$?; cat "$OUT/${TAG}_bench.json"; tail -5 "$OUT/${TAG}_bench.err"; stop_on $rc bench
 fi
 if [[ "$STEPS" == all || "$STEPS" == *prof* ]]; then
   export TMPDIR=/tmp
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${TAG}_prof" -o kt \
-    -- python3 "$ROOT/bench.py" --steps 20 --warmup 10 --no-cpu-baseline --no-parity --no-power-probe --no-host-path --no-quality > "$OUT/${TAG}_prof.log" 2>&1
+    -- python3 "$ROOT/bench.py" --steps 20 --warmup 10 --full --no-cpu-baseline --no-parity --no-power-probe --no-host-path --no-quality > "$OUT/${TAG}_prof.log" 2>&1
   rc=$?; tail -3 "$OUT/${TAG}_prof.log"; stop_on $rc rocprof
   find "$OUT/${TAG}_prof" -name "*kernel_stats.csv" -exec cat {} \; | cut -c1-220
 fi

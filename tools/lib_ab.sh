@@ -4,7 +4,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT=gpurun_out/${TAG:-r5g}
 mkdir -p $OUT
-B="python bench.py --steps 30 --warmup 20 --no-cpu-baseline --no-host-path --no-quality --no-power-probe --no-parity"
+B="python bench.py --steps 30 --warmup 20 --full --no-cpu-baseline --no-host-path --no-quality --no-power-probe --no-parity"
 for r in 1 2; do
   for v in "$@"; do
     lib=$PWD/neural_network_image_compression_amd/libnic${v:+_$v}.so

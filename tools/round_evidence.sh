@@ -16,12 +16,12 @@ stop_on() {
 }
 STEPS=tests,smoke,bench,prof bash tools/gpu_check.sh "$TAG" || exit $?
 bash tools/pmc.sh "$TAG" || exit $?
-timeout -k 10 300 python bench.py --workload kodak --steps 20 --warmup 10 --no-power-probe > "$OUT/${TAG}_kodak_bench.json" 2> "$OUT/${TAG}_kodak.err"
+timeout -k 10 300 python bench.py --workload kodak --steps 20 --warmup 10 --full --no-power-probe > "$OUT/${TAG}_kodak_bench.json" 2> "$OUT/${TAG}_kodak.err"
 stop_on $? kodak
-timeout -k 10 300 python bench.py --workload 4k --steps 20 --warmup 10 > "$OUT/${TAG}_4k_bench.json" 2> "$OUT/${TAG}_4k.err"
+timeout -k 10 300 python bench.py --workload 4k --steps 20 --warmup 10 --full > "$OUT/${TAG}_4k_bench.json" 2> "$OUT/${TAG}_4k.err"
 stop_on $? 4k
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${TAG}_4kprof" -o k \
-  -- python3 "$ROOT/bench.py" --workload 4k --steps 20 --warmup 10 > "$OUT/${TAG}_4kprof.log" 2>&1
+  -- python3 "$ROOT/bench.py" --workload 4k --steps 20 --warmup 10 --full > "$OUT/${TAG}_4kprof.log" 2>&1
 stop_on $? 4kprof
 python3 tools/pmc_summary.py "$OUT/${TAG}_pmc" > "$OUT/${TAG}_traffic.json" 2> /dev/null
 echo "[done]"
