@@ -56,7 +56,8 @@ enum {
   NIC_ENOWEIGHTS = -3,  /* encode/decode before every tensor was set       */
   NIC_EHIP = -4,        /* HIP runtime error                               */
   NIC_ENOMEM = -5,      /* device allocation failed                        */
-  NIC_ERANGE = -6       /* NIC_RANGE_ERROR: a split-f16 activation left the f16 range */
+  NIC_ERANGE = -6,      /* NIC_RANGE_ERROR: a split-f16 activation left the f16 range */
+  NIC_ECORRUPT = -7     /* nic_rans_inspect: not a well-formed .nic file              */
 };
 
 /* model_id values for nic_set_weights (checkpoint names encoder{Y,CbCr}, decoder{Y,CbCr},
@@ -223,6 +224,44 @@ int nic_png_sizes(const uint8_t* images, int m, int h, int w, int channels, int6
  * plane a raw C-order reshape (utils.py:35-36, 39-40). */
 int nic_pack_latent(const uint8_t* latent, int n, int h8, int w8, uint8_t* packed, void* stream);
 int nic_unpack_latent(const uint8_t* packed, int n, int h8, int w8, uint8_t* latent, void* stream);
+
+/* ---- The .nic container (version 1): a native bitstream beside the reference's PNG ----------
+ * One file per image, a static per-channel byte-wise rANS code of the latent, written and read
+ * on the device (format: DESIGN.md, "The .nic container"):
+ *   header 16 B: "NICR", u8 version 1, u8 probability bits 12, u16 seg_pixels, u32 h8, u32 w8
+ *   96 tables (channel order of the latent): u8 n-1, then n x (u8 symbol, u16 freq), symbols
+ *     ascending, freqs in 1..4096 summing to 4096
+ *   nseg = ceil(h8 w8 / seg_pixels) u32 segment lengths, then the segments' bytes
+ * Segment k codes the latent bytes [k K, min((k+1) K, 96 h8 w8)), K = 96 seg_pixels, in NHWC
+ * order.  Little-endian throughout, except each segment's leading 4-byte final state.
+ *
+ * nic_rans_bound: the largest file of an (h8, w8) latent (every table full, 12 bits per symbol):
+ *     the minimum `stride` of nic_rans_encode.  h8 * w8 <= 2^23, seg_pixels in 1..65535.
+ * nic_rans_reserve: grow the workspace so nic_rans_encode / nic_rans_decode of (n, h8, w8)
+ *     latents allocate nothing.  Synchronous.
+ * nic_rans_encode: latent (n,h8,w8,96) u8 (16-byte aligned) -> file i at out + i * stride, its
+ *     byte count in sizes[i] (DEVICE int64[n]).  Counting, table normalisation, coding and file
+ *     assembly all run on `stream`; no host synchronisation.  An image's file depends on that
+ *     image alone.
+ * nic_rans_decode: files at files + i * stride of sizes[i] bytes (DEVICE int64[n]), all of one
+ *     (h8, w8) (seg_pixels is read per file on the device) -> latent (n,h8,w8,96) and status[i]
+ *     (DEVICE int32[n]): 0 ok; bit 0: a segment did not end with its state at 2^23 on its last
+ *     byte; bit 1: the header is not a version-1 header of an (h8, w8) latent (that image's
+ *     latent is left unwritten); bit 2: a table breaks its invariants.  Tables are parsed on the
+ *     device.  No input bytes can take the kernels out of bounds: file reads are clamped to the
+ *     segment, table lookups resolve inside the 4096 slots, and stores go to the lane's own
+ *     latent bytes.
+ * nic_rans_inspect: HOST-only check of one file in host memory (no GPU, no ctx): magic, version,
+ *     probability bits, seg_pixels >= 1, h8 w8 in range, every table's invariants, and header +
+ *     tables + segment table + sum of segment lengths == size.  NIC_ECORRUPT (nic_last_error
+ *     says what) otherwise; h8 / w8 / seg_pixels (each nullable) on success. */
+int nic_rans_bound(int h8, int w8, int seg_pixels, int64_t* bytes);
+int nic_rans_reserve(nic_ctx* ctx, int n, int h8, int w8, int seg_pixels);
+int nic_rans_encode(nic_ctx* ctx, const uint8_t* latent, int n, int h8, int w8, int seg_pixels, uint8_t* out,
+                    int64_t stride, int64_t* sizes, void* stream);
+int nic_rans_decode(nic_ctx* ctx, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, int h8, int w8,
+                    uint8_t* latent, int32_t* status, void* stream);
+int nic_rans_inspect(const uint8_t* host_file, int64_t size, int* h8, int* w8, int* seg_pixels);
 
 /* ---- Training side path (tf2_0/src/training.py:74-151): the step's convolutions ------------
  * NHWC fp32 device tensors, split-f16x3 MFMA (fp32-class), kernels of Keras layouts, no ctx.

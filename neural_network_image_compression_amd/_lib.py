@@ -31,6 +31,7 @@ NIC_ENOWEIGHTS = -3
 NIC_EHIP = -4
 NIC_ENOMEM = -5
 NIC_ERANGE = -6
+NIC_ECORRUPT = -7
 
 RANGE_POLICIES = {"fallback": 0, "error": 1}  # nic.h NIC_RANGE_FALLBACK / NIC_RANGE_ERROR
 
@@ -78,6 +79,12 @@ _SIGNATURES = {
     "nic_sq_err": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int64, c_vp, c_vp]),
     "nic_pack_latent": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
     "nic_unpack_latent": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
+    # .nic container (nic_rans.hip)
+    "nic_rans_bound": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int64)]),
+    "nic_rans_reserve": (ctypes.c_int, [c_vp] + [ctypes.c_int] * 4),
+    "nic_rans_encode": (ctypes.c_int, [c_vp, c_vp] + [ctypes.c_int] * 4 + [c_vp, ctypes.c_int64, c_vp, c_vp]),
+    "nic_rans_decode": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp] + [ctypes.c_int] * 3 + [c_vp, c_vp, c_vp]),
+    "nic_rans_inspect": (ctypes.c_int, [c_vp, ctypes.c_int64] + [ctypes.POINTER(ctypes.c_int)] * 3),
     # training side path (nic_train.hip)
     "nic_conv_gather_work": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_int64)]),
     "nic_conv_gather": (ctypes.c_int, [c_vp] + [ctypes.c_int] * 4 + [c_vp] + [ctypes.c_int] * 7 + [c_vp] * 4

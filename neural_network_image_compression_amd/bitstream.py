@@ -8,6 +8,11 @@ The reference's on-disk bitstream is a PNG: the 96-channel u8 latent is reinterp
 
 The pack/unpack reshape runs on the GPU (``nic_pack_latent``/``nic_unpack_latent``); PNG
 coding (zlib) stays on the host, outside the measured encode/decode surface.
+
+Beside it stands the native ``.nic`` container (``container="nic"``): a static per-channel rANS
+code of the latent, written and read on the device (``nic_rans_encode``/``nic_rans_decode``;
+format in DESIGN.md), so the host only moves and writes finished files.  PNG stays the default
+and the parity format.
 """
 from __future__ import annotations
 
@@ -120,6 +125,76 @@ def png_bpp(packed: np.ndarray, pixels: int, optimize: bool = True) -> float:
     return 8.0 * len(png_bytes(packed, optimize)) / float(pixels)
 
 
+CONTAINERS = ("png", "nic")
+NIC_SEG_PIXELS = 32  # latent pixels per rANS segment (one device lane each) of the files written here
+
+
+def nic_inspect(data: bytes) -> Tuple[int, int, int]:
+    """(h8, w8, seg_pixels) of a well-formed .nic file; ValueError (nic_rans_inspect's text)
+    otherwise.  Host only."""
+    import ctypes
+
+    from . import _lib
+
+    a = np.frombuffer(data, np.uint8)
+    h8, w8, sp = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    rc = _lib.lib().nic_rans_inspect(a.ctypes.data_as(ctypes.c_void_p), len(data), ctypes.byref(h8), ctypes.byref(w8),
+                                     ctypes.byref(sp))
+    if rc != _lib.NIC_OK:
+        raise ValueError(f"[{rc}] {_lib.last_error()}")
+    return h8.value, w8.value, sp.value
+
+
+def nic_files(codec, z, seg_pixels: int = NIC_SEG_PIXELS) -> List[bytes]:
+    """The .nic file of every latent of z (N,h,w,96), a u8 tensor on the codec's device: coded
+    and assembled there (Codec.rans_encode), then one copy of the files to the host."""
+    buf, sizes = codec.rans_encode(z, seg_pixels)
+    if buf.shape[0] == 0:
+        return []
+    sizes = sizes.cpu().numpy()
+    host = buf[:, :int(sizes.max())].contiguous().cpu().numpy()
+    return [host[i, :sizes[i]].tobytes() for i in range(host.shape[0])]
+
+
+def read_nic(codec, files: Sequence[bytes]) -> list:
+    """The latents of .nic files: a list of (h8,w8,96) u8 tensors on the codec's device, in the
+    files' order.  Every file is checked on the host first (nic_inspect: ValueError naming the
+    file's index); files of equal (h8, w8, seg_pixels) are decoded as one device batch."""
+    import torch
+
+    groups = {}
+    for i, data in enumerate(files):
+        try:
+            groups.setdefault(nic_inspect(data), []).append(i)
+        except ValueError as e:
+            raise ValueError(f"read_nic: file {i}: {e}") from None
+    out = [None] * len(files)
+    for (h8, w8, _), idx in groups.items():
+        stride = max(len(files[i]) for i in idx)
+        host = np.zeros((len(idx), stride), np.uint8)
+        for r, i in enumerate(idx):
+            host[r, :len(files[i])] = np.frombuffer(files[i], np.uint8)
+        sizes = torch.tensor([len(files[i]) for i in idx], dtype=torch.int64)
+        dev = f"cuda:{codec.device}"
+        try:
+            z = codec.rans_decode(torch.from_numpy(host).to(dev), sizes.to(dev), h8, w8)
+        except ValueError as e:
+            raise ValueError(f"read_nic: files {idx}: {e}") from None
+        for r, i in enumerate(idx):
+            out[i] = z[r]
+    return out
+
+
+def _write_files(datas: Sequence[bytes], output_dir: str, filenames: Sequence[str], ext: str) -> List[str]:
+    paths = []
+    for data, name in zip(datas, filenames):
+        path = os.path.join(output_dir, name + ext)
+        with open(path, "wb") as f:
+            f.write(data)
+        paths.append(path)
+    return paths
+
+
 def _batches(shapes: Sequence[tuple], batch_size: int):
     """Consecutive runs of equal-shaped images, at most batch_size long (utils.py:53-62)."""
     i = 0
@@ -132,12 +207,15 @@ def _batches(shapes: Sequence[tuple], batch_size: int):
 
 
 def feed_batch(model, x: np.ndarray, filenames: Sequence[str], output_dir: str, in_cshape: int,
-               pool=None, png_threads: int = 16) -> list:
+               pool=None, png_threads: int = 16, container: str = "png") -> list:
     """utils.py:30-44 for one batch: unpack (decoder side), run the codec, pack (encoder side), save.
 
     The batch's PNG files are encoded natively on ``png_threads`` host threads (nic_png_encode,
     byte-identical to Pillow's optimize=True).  With a pool the encode + write is submitted to
-    it and its future returned, so the caller runs the next batch on the GPU meanwhile."""
+    it and its future returned, so the caller runs the next batch on the GPU meanwhile.
+
+    container "nic" (encoder side): the latents are coded into .nic files on the device
+    (nic_files), copied to the host once, and the writer only writes them."""
     import torch
 
     codec = model.codec
@@ -146,6 +224,12 @@ def feed_batch(model, x: np.ndarray, filenames: Sequence[str], output_dir: str, 
     if in_cshape == 96 and c == 3:
         dev = codec.unpack(dev)
     out = model._device_call(dev)
+    if container == "nic" and out.shape[-1] == 96:
+        datas = nic_files(codec, out)
+        if pool is None:
+            _write_files(datas, output_dir, filenames, ".nic")
+            return []
+        return [pool.submit(_write_files, datas, output_dir, list(filenames), ".nic")]
     if out.shape[-1] == 96:
         out = codec.pack(out)
     host = out.cpu().numpy()
@@ -185,7 +269,7 @@ BATCH_PIXELS = 64 * 512 * 768  # pixels staged per device batch (use_model): 64 
 
 
 def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, in_cshape: int,
-              batch_size: int = 64, workers=None) -> None:
+              batch_size: int = 64, workers=None, container: str = "png") -> None:
     """utils.py:46-62: every colour image of ``dataset_path`` (sorted; read_dataset's filter)
     through the codec into ``output_dir``, one PNG per image named after its source.
 
@@ -197,13 +281,22 @@ def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, i
     threads (default: every CPU this process may use, at most 16) while the next batches are
     read and run; at most ``WRITES_IN_FLIGHT`` batches wait for the writer, so host memory stays
     bounded however large the directory.  Every image's output depends on that
-    image alone (the kernels are batch-invariant), so the files are byte-identical either way."""
+    image alone (the kernels are batch-invariant), so the files are byte-identical either way.
+
+    ``container="nic"``: the encoder side writes ``<stem>.nic`` files coded on the device instead
+    of packed PNGs; the decoder side reads the directory's ``.nic`` files (sorted) and writes the
+    same reconstruction PNGs (use_model_nic_in)."""
+    if container not in CONTAINERS:
+        raise ValueError(f"container must be one of {CONTAINERS}, got {container!r}")
+    if container == "nic" and in_cshape == 96:
+        return use_model_nic_in(model, dataset_path, checkpoint_path, output_dir, batch_size=batch_size, workers=workers)
+    extra = {"container": container} if container != "png" else {}
     os.makedirs(output_dir, exist_ok=True)
     model.load(checkpoint_path)
     if workers is not None and workers <= 0:
         imgs, names = read_dataset(dataset_path)
         for i, j in _batches([a.shape for a in imgs], batch_size):
-            feed_batch(model, np.stack(imgs[i:j]), names[i:j], output_dir, in_cshape)
+            feed_batch(model, np.stack(imgs[i:j]), names[i:j], output_dir, in_cshape, **extra)
         return
     from concurrent.futures import ThreadPoolExecutor
 
@@ -221,7 +314,7 @@ def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, i
                 while len(futures) >= WRITES_IN_FLIGHT:
                     futures.pop(0).result()  # re-raises a write error
                 futures.extend(feed_batch(model, np.stack(batch), list(names), output_dir, in_cshape, pool=writer,
-                                          png_threads=png_threads))
+                                          png_threads=png_threads, **extra))
                 batch.clear()
                 names.clear()
             while futures and futures[0].done():
@@ -240,5 +333,54 @@ def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, i
             batch.append(a.astype(np.uint8, copy=False))
             names.append(".".join(fn.split(".")[:-1]))
         flush()
+        for f in futures:
+            f.result()  # re-raise any write error
+
+
+def _read_bytes(path: str) -> bytes:
+    with open(path, "rb") as f:
+        return f.read()
+
+
+def use_model_nic_in(model, dataset_path: str, checkpoint_path: str, output_dir: str, batch_size: int = 64,
+                     workers=None) -> None:
+    """The decoder side of ``container="nic"``: every ``.nic`` file of ``dataset_path`` (sorted)
+    -> ``<stem>.png`` reconstructions in ``output_dir``, the same files the PNG route writes.
+    The files are read by a pool, checked on the host (nic_rans_inspect) and decoded on the device
+    ``batch_size`` at a time (read_nic groups them by latent shape); the PNG encode + write of a
+    batch runs on the writer thread while the next batch is decoded (``workers=0``: inline)."""
+    import torch
+    from concurrent.futures import ThreadPoolExecutor
+
+    os.makedirs(output_dir, exist_ok=True)
+    model.load(checkpoint_path)
+    codec = model.codec
+    files = [fn for fn in sorted(os.listdir(dataset_path)) if fn.endswith(".nic")]
+    serial = workers is not None and workers <= 0
+    threads = _host_threads()
+    png_threads = 1 if serial else (int(workers) if workers else min(16, threads))
+    step = max(1, batch_size)
+    with ThreadPoolExecutor(max_workers=min(8, threads)) as readers, ThreadPoolExecutor(max_workers=1) as writer:
+        futures = []
+        chunks = [files[i:i + step] for i in range(0, len(files), step)]
+        pending = [readers.map(_read_bytes, [os.path.join(dataset_path, fn) for fn in ch]) for ch in chunks[:2]]
+        for k, ch in enumerate(chunks):
+            datas = list(pending[k])
+            pending[k] = None
+            if k + 2 < len(chunks):  # two chunks of reads in flight ahead of the device
+                pending.append(readers.map(_read_bytes, [os.path.join(dataset_path, fn) for fn in chunks[k + 2]]))
+            try:
+                latents = read_nic(codec, datas)
+            except ValueError as e:
+                raise ValueError(f"{dataset_path}: files {ch[0]}..{ch[-1]}: {e}") from None
+            names = [fn[:-4] for fn in ch]
+            for i, j in _batches([tuple(z.shape) for z in latents], step):
+                rec = model._device_call(torch.stack(latents[i:j])).cpu().numpy()
+                while len(futures) >= WRITES_IN_FLIGHT:
+                    futures.pop(0).result()
+                if serial:
+                    save_imgs(rec, output_dir, names[i:j], threads=1)
+                else:
+                    futures.append(writer.submit(save_imgs, rec, output_dir, names[i:j], png_threads))
         for f in futures:
             f.result()  # re-raise any write error

@@ -298,6 +298,57 @@ class Codec:
             return np.array([db(s, per) for s in sse])
         return db(float(sse.sum()), per * n)
 
+    # -- .nic container: device rANS coder (nic_rans_*) -----------------------------------
+    def rans_reserve(self, n: int, h8: int, w8: int, seg_pixels: int = 32) -> None:
+        """Grow the workspace so rans_encode / rans_decode of (n, h8, w8) latents allocate nothing."""
+        _lib.check(self._L.nic_rans_reserve(self._h, n, h8, w8, seg_pixels), "nic_rans_reserve")
+
+    def rans_encode(self, z, seg_pixels: int = 32):
+        """(N,h,w,96) u8 latent -> (buf (N, stride) u8, sizes (N,) int64), device tensors: image
+        i's complete .nic file is buf[i, :sizes[i]] (nic_rans_encode; no host synchronisation)."""
+        torch = _torch()
+        z = self._check_dev(z, 4, 96, "rans_encode")
+        n, h8, w8, _ = z.shape
+        if z.data_ptr() % 16:  # a view at an odd offset: the kernels read 16-byte words
+            z = z.clone()
+        stride = ctypes.c_int64()
+        _lib.check(self._L.nic_rans_bound(h8, w8, int(seg_pixels), ctypes.byref(stride)), "nic_rans_bound")
+        buf = torch.empty((n, stride.value), dtype=torch.uint8, device=z.device)
+        sizes = torch.zeros((n,), dtype=torch.int64, device=z.device)
+        _lib.check(self._L.nic_rans_encode(self._h, z.data_ptr(), n, h8, w8, int(seg_pixels), buf.data_ptr(), stride.value,
+                                           sizes.data_ptr(), _stream_ptr(torch, self.device)), "nic_rans_encode")
+        return buf, sizes
+
+    def rans_decode_status(self, buf, sizes, h8: int, w8: int):
+        """rans_decode without the check: (latent, status (N,) int32 device tensor; nic.h)."""
+        torch = _torch()
+        if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.device.type != "cuda" or buf.ndim != 2:
+            raise TypeError("rans_decode: expected an (N, stride) cuda torch.uint8 tensor of files")
+        if not isinstance(sizes, torch.Tensor) or sizes.dtype != torch.int64 or sizes.shape != (buf.shape[0],):
+            raise TypeError("rans_decode: expected an (N,) torch.int64 tensor of sizes")
+        if buf.device.index != self.device or sizes.device != buf.device:
+            raise ValueError(f"rans_decode: tensors must be on cuda:{self.device}")
+        buf, sizes = buf.contiguous(), sizes.contiguous()
+        n, stride = buf.shape
+        z = torch.empty((n, h8, w8, 96), dtype=torch.uint8, device=buf.device)
+        status = torch.zeros((n,), dtype=torch.int32, device=buf.device)
+        _lib.check(self._L.nic_rans_decode(self._h, buf.data_ptr(), stride, sizes.data_ptr(), n, int(h8), int(w8),
+                                           z.data_ptr(), status.data_ptr(), _stream_ptr(torch, self.device)),
+                   "nic_rans_decode")
+        return z, status
+
+    def rans_decode(self, buf, sizes, h8: int, w8: int):
+        """.nic files buf[i, :sizes[i]] (device tensors, as rans_encode returns) of (h8, w8)
+        latents -> (N,h8,w8,96) u8.  Reads the statuses back (synchronises) and raises ValueError
+        naming the first image whose file did not decode cleanly."""
+        z, status = self.rans_decode_status(buf, sizes, h8, w8)
+        st = status.cpu().numpy()
+        bad = np.nonzero(st)[0]
+        if bad.size:
+            raise ValueError(f"rans_decode: image {int(bad[0])} is corrupt (status {int(st[bad[0]])}; "
+                             f"corrupt images: {bad.tolist()})")
+        return z
+
     def pack(self, z):
         """(N,h,w,96) -> (N,4h,8w,3) bitstream image (utils.py:39-40)."""
         torch = _torch()
@@ -374,14 +425,17 @@ class Encoder(ProClass):
             raise ValueError(f"Encoder: expected shape (N,H,W,3), got {a.shape}")
         return self.codec.encode_host(a, self.host_chunks)
 
-    def compress(self, dataset_path: str, checkpoint_path: str, batch_size: int = 64, workers=None) -> None:
+    def compress(self, dataset_path: str, checkpoint_path: str, batch_size: int = 64, workers=None,
+                 container: str = "png") -> None:
         """encoder.py:49-51: every image in ``dataset_path`` -> ``dataset_path + '_compressed'``.
         Pipelined over the host cores in batches of ``batch_size`` (bitstream.use_model);
-        ``workers=0, batch_size=4`` is the reference's serial loop (same files)."""
+        ``workers=0, batch_size=4`` is the reference's serial loop (same files).
+        ``container="nic"`` writes ``<stem>.nic`` files, entropy-coded on the device, instead of
+        the reference's packed PNGs (the default)."""
         from .bitstream import use_model
 
         use_model(self, dataset_path, checkpoint_path, dataset_path + "_compressed", in_cshape=3,
-                  batch_size=batch_size, workers=workers)
+                  batch_size=batch_size, workers=workers, container=container)
 
 
 class Decoder(ProClass):
@@ -397,10 +451,12 @@ class Decoder(ProClass):
             raise ValueError(f"Decoder: expected shape (N,h,w,96), got {a.shape}")
         return self.codec.decode_host(a, self.host_chunks)
 
-    def uncompress(self, dataset_path: str, checkpoint_path: str, batch_size: int = 64, workers=None) -> None:
+    def uncompress(self, dataset_path: str, checkpoint_path: str, batch_size: int = 64, workers=None,
+                   container: str = "png") -> None:
         """decoder.py:50-52: packed PNGs in ``dataset_path`` -> ``dataset_path.replace('compressed','uncompressed')``.
-        Pipelined as compress (``workers=0, batch_size=4``: the reference's serial loop)."""
+        Pipelined as compress (``workers=0, batch_size=4``: the reference's serial loop).
+        ``container="nic"`` reads the directory's ``.nic`` files instead (same reconstructions)."""
         from .bitstream import use_model
 
         use_model(self, dataset_path, checkpoint_path, dataset_path.replace("compressed", "uncompressed"),
-                  in_cshape=96, batch_size=batch_size, workers=workers)
+                  in_cshape=96, batch_size=batch_size, workers=workers, container=container)

@@ -457,7 +457,7 @@ bool models_ready(const nic_ctx* c, int m0) {
 
 extern "C" {
 
-int nic_version(void) { return 200; }
+int nic_version(void) { return 300; }
 
 int nic_constants(float* ycbcr9, float* ycbcr_inv9, float* off3) {
   // host copy of what nic_create uploads; lets tests compare with np.linalg.inv (utils.py:8)
@@ -1369,6 +1369,61 @@ int nic_unpack_latent(const uint8_t* packed, int n, int h8, int w8, uint8_t* lat
   if (n == 0) return NIC_OK;
   if (!latent || !packed) return fail(NIC_EINVAL, "nic_unpack_latent: NULL argument");
   HIP_TRY(launch_pack(packed, latent, n, h8, w8, true, (hipStream_t)stream));
+  return NIC_OK;
+}
+
+// ---- .nic container (nic_rans.hip; nic_rans_bound and nic_rans_inspect are host-only there) ----
+static int rans_check(const char* fn, int n, int h8, int w8, int seg_pixels) {
+  if (n < 0 || h8 <= 0 || w8 <= 0) return fail(NIC_ESHAPE, "%s: bad latent shape (%d,%d,%d,96)", fn, n, h8, w8);
+  if (!rans_shape_ok(h8, w8)) return fail(NIC_ESHAPE, "%s: latent %dx%d exceeds 2^23 pixels", fn, h8, w8);
+  if (seg_pixels < 1 || seg_pixels > 65535) return fail(NIC_ESHAPE, "%s: seg_pixels %d not in 1..65535", fn, seg_pixels);
+  if (n > 65535) return fail(NIC_ESHAPE, "%s: batch %d exceeds 65535 images per call", fn, n);
+  return NIC_OK;
+}
+
+int nic_rans_reserve(nic_ctx* c, int n, int h8, int w8, int seg_pixels) {
+  int rc = rans_check("nic_rans_reserve", n, h8, w8, seg_pixels);
+  if (rc || n == 0) return rc;
+  if (!c) return fail(NIC_EINVAL, "nic_rans_reserve: NULL ctx");
+  DeviceGuard guard(c->device);
+  RansPlan enc, dec;
+  rans_plan(n, h8, w8, seg_pixels, false, &enc);
+  rans_plan(n, h8, w8, seg_pixels, true, &dec);
+  return ensure_ws(c, std::max(enc.bytes, dec.bytes));
+}
+
+int nic_rans_encode(nic_ctx* c, const uint8_t* latent, int n, int h8, int w8, int seg_pixels, uint8_t* out, int64_t stride,
+                    int64_t* sizes, void* stream) {
+  int rc = rans_check("nic_rans_encode", n, h8, w8, seg_pixels);
+  if (rc || n == 0) return rc;
+  if (!c) return fail(NIC_EINVAL, "nic_rans_encode: NULL ctx");
+  if (!latent || !out || !sizes) return fail(NIC_EINVAL, "nic_rans_encode: NULL buffer");
+  if ((uintptr_t)latent % 16) return fail(NIC_EINVAL, "nic_rans_encode: latent must be 16-byte aligned");
+  int64_t bound = 0;
+  nic_rans_bound(h8, w8, seg_pixels, &bound);
+  if (stride < bound)
+    return fail(NIC_ESHAPE, "nic_rans_encode: stride %lld is below nic_rans_bound = %lld", (long long)stride, (long long)bound);
+  DeviceGuard guard(c->device);
+  RansPlan pl;
+  rans_plan(n, h8, w8, seg_pixels, false, &pl);
+  if ((rc = ensure_ws(c, pl.bytes))) return rc;
+  HIP_TRY(launch_rans_encode(latent, n, h8, w8, seg_pixels, c->ws, pl, out, stride, (long long*)sizes, (hipStream_t)stream));
+  return NIC_OK;
+}
+
+int nic_rans_decode(nic_ctx* c, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, int h8, int w8,
+                    uint8_t* latent, int32_t* status, void* stream) {
+  int rc = rans_check("nic_rans_decode", n, h8, w8, 1);
+  if (rc || n == 0) return rc;
+  if (!c) return fail(NIC_EINVAL, "nic_rans_decode: NULL ctx");
+  if (!files || !sizes || !latent || !status) return fail(NIC_EINVAL, "nic_rans_decode: NULL buffer");
+  if ((uintptr_t)latent % 16) return fail(NIC_EINVAL, "nic_rans_decode: latent must be 16-byte aligned");
+  if (stride < 16) return fail(NIC_ESHAPE, "nic_rans_decode: stride %lld is below the 16-byte header", (long long)stride);
+  DeviceGuard guard(c->device);
+  RansPlan pl;
+  rans_plan(n, h8, w8, 1, true, &pl);
+  if ((rc = ensure_ws(c, pl.bytes))) return rc;
+  HIP_TRY(launch_rans_decode(files, stride, (const long long*)sizes, n, h8, w8, c->ws, pl, latent, status, (hipStream_t)stream));
   return NIC_OK;
 }
 

@@ -165,6 +165,22 @@ hipError_t launch_hist_fold(uint32_t* part, const uint8_t* z, int nimg, int h8, 
                             uint32_t* counts, float* bits, hipStream_t st);
 hipError_t launch_pack(const uint8_t* src, uint8_t* dst, int nimg, int h8, int w8, bool unpack, hipStream_t st);
 
+// --- .nic container: device rANS coder (nic_rans.hip) ---------------------------------------
+// Byte offsets of one call's scratch inside the ctx workspace (256-B aligned), from rans_plan.
+// Encode: nseg / cap for the call's seg_pixels.  Decode: nseg = h8 * w8, the segment count of
+// seg_pixels = 1 (the files' own seg_pixels is read on the device).
+struct RansPlan {
+  int nseg;
+  uint32_t cap;  // encode: bytes of one segment's worst-case region
+  size_t counts, cum, tab, tablen, taboff, seglen, segoff, meta, scratch, bytes;
+};
+bool rans_shape_ok(int h8, int w8);
+void rans_plan(int n, int h8, int w8, int seg_pixels, bool decode, RansPlan* plan);
+hipError_t launch_rans_encode(const uint8_t* z, int n, int h8, int w8, int seg_pixels, char* ws, const RansPlan& plan,
+                              uint8_t* out, long long stride, long long* sizes, hipStream_t st);
+hipError_t launch_rans_decode(const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8, char* ws,
+                              const RansPlan& plan, uint8_t* z, int* status, hipStream_t st);
+
 // --- quality metrics (nic_quality.hip) ---------------------------------------------------
 constexpr int kSsimScales = 5;  // tf.image.ssim_multiscale power_factors
 

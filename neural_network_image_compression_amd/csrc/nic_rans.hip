@@ -1,0 +1,585 @@
+// The .nic container (version 1): a static per-channel byte-wise rANS bitstream, coded and
+// decoded on the device (format: DESIGN.md "The .nic container"; entry points: include/nic.h
+// nic_rans_*).  One file per image:
+//   header 16 B | 96 channel tables | nseg u32 segment lengths | the segments' bytes
+// Segment k codes the latent bytes [k K, min((k+1) K, 96 h8 w8)), K = 96 seg_pixels, in NHWC
+// order; the byte at offset j is a symbol of channel j % 96.  One lane codes one segment, so
+// every lane of a wave is at the same channel at the same time and reads the same table row.
+//
+// Encode: rans_hist (96 histograms per image) -> rans_normalise (12-bit tables, their file
+// bytes and cumulative rows) -> rans_encode_segments (each lane walks its segment backwards
+// and writes backwards into its own worst-case region of the scratch) -> rans_layout (prefix
+// sums of table and segment lengths, file sizes) -> rans_assemble (header, tables, segment
+// table and payload into out + i * stride).
+// Decode: rans_parse (header check, tables -> cumulative rows, segment offsets; all on the
+// device) -> rans_decode_segments (binary search of the LDS cumulative row per slot).
+
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <cstring>
+
+#include "../../include/nic.h"
+#include "nic_kernels.h"
+
+namespace nic {
+
+namespace {
+
+constexpr int kCh = 96;                  // latent channels
+constexpr int kProbBits = 12;
+constexpr uint32_t kProbScale = 1u << kProbBits;
+constexpr uint32_t kRansL = 1u << 23;    // lower bound of the normalised state interval
+constexpr int kCumRow = 257;             // start[0..256] of one channel
+constexpr int kCumWords = kCh * kCumRow; // u16 per image (49,344 B: the LDS table)
+constexpr int kTabRow = 772;             // >= 1 + 3 * 256 file bytes of one channel's table
+constexpr int kHeader = 16;
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint32_t t = __shfl_xor(v, o, 64);
+    v = t > v ? t : v;
+  }
+  return v;
+}
+// exclusive prefix sum over the 64 lanes
+__device__ __forceinline__ uint32_t wave_excl(uint32_t v, int lane) {
+  uint32_t inc = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t t = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += t;
+  }
+  return inc - v;
+}
+
+// ---- encode 1: per-image, per-channel counts ----------------------------------------------
+// grid (ceil(npix / 256), 3, n), block 256: thread = pixel, blockIdx.y = a third of the channels
+// (32 LDS histograms = 32 KB); each thread reads its pixel's 32 bytes as two 16-B loads.
+__global__ __launch_bounds__(256) void rans_hist(const uint8_t* __restrict__ z, int npix, uint32_t* __restrict__ counts) {
+  __shared__ uint32_t h[32 * 256];
+  const int tid = threadIdx.x, third = blockIdx.y, img = blockIdx.z;
+  for (int i = tid; i < 32 * 256; i += 256) h[i] = 0;
+  __syncthreads();
+  const int p = blockIdx.x * 256 + tid;
+  if (p < npix) {
+    const uint4* src = (const uint4*)(z + ((size_t)img * npix + p) * kCh + 32 * third);
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const uint4 v = src[q];
+      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int b = 0; b < 16; ++b) atomicAdd(&h[(16 * q + b) * 256 + ((w[b >> 2] >> (8 * (b & 3))) & 255u)], 1u);
+    }
+  }
+  __syncthreads();
+  uint32_t* dst = counts + ((size_t)img * kCh + 32 * third) * 256;
+  for (int i = tid; i < 32 * 256; i += 256)
+    if (h[i]) atomicAdd(&dst[i], h[i]);
+}
+
+// ---- encode 2: 12-bit tables ---------------------------------------------------------------
+// grid (96, n), block 64: one wave per channel, lane l owns symbols 4l..4l+3.
+//   f = max(1, floor(c 4096 / N)) for every used symbol; a deficit goes onto the largest entry;
+//   a surplus (at most 255, from the floor-to-zero bumps) is taken one at a time from the
+//   currently largest entry (lowest symbol on ties), which never takes an entry below 1.
+// Writes the channel's cumulative row start[0..256], its file bytes and their count.
+__global__ __launch_bounds__(64) void rans_normalise(const uint32_t* __restrict__ counts, int npix, uint16_t* __restrict__ cum,
+                                                      uint8_t* __restrict__ tab, uint32_t* __restrict__ tablen) {
+  const int lane = threadIdx.x, c = blockIdx.x, img = blockIdx.y;
+  const size_t row = (size_t)img * kCh + c;
+  const uint4 cv = ((const uint4*)(counts + row * 256))[lane];
+  const uint32_t cnt[4] = {cv.x, cv.y, cv.z, cv.w};
+  uint32_t f[4], sum = 0, used = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    f[k] = 0;
+    if (cnt[k]) {
+      const uint32_t q = (uint32_t)(((unsigned long long)cnt[k] << kProbBits) / (unsigned long long)npix);
+      f[k] = q ? q : 1u;
+      ++used;
+    }
+    sum += f[k];
+  }
+  sum = wave_sum(sum);
+  int diff = (int)kProbScale - (int)sum;
+  // (f << 8) | (255 - s): the largest f, the lowest symbol on ties
+  auto best = [&]() {
+    uint32_t key = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint32_t kk = (f[k] << 8) | (uint32_t)(255 - (4 * lane + k));
+      key = kk > key ? kk : key;
+    }
+    return wave_max(key);
+  };
+  if (diff > 0) {
+    const int s = 255 - (int)(best() & 255u);
+    if ((s >> 2) == lane) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k == (s & 3)) f[k] += (uint32_t)diff;
+    }
+  }
+  for (; diff < 0; ++diff) {  // wave-uniform trip count, at most 255
+    const int s = 255 - (int)(best() & 255u);
+    if ((s >> 2) == lane) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k == (s & 3)) f[k] -= 1u;
+    }
+  }
+  const uint32_t mine = f[0] + f[1] + f[2] + f[3];
+  uint32_t run = wave_excl(mine, lane);
+  uint32_t idx = wave_excl(used, lane);
+  const uint32_t nsym = wave_sum(used);
+  uint16_t* crow = cum + row * kCumRow;
+  uint8_t* trow = tab + row * kTabRow;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    crow[4 * lane + k] = (uint16_t)run;
+    if (f[k]) {
+      uint8_t* e = trow + 1 + 3 * idx;
+      e[0] = (uint8_t)(4 * lane + k);
+      e[1] = (uint8_t)(f[k] & 255u);
+      e[2] = (uint8_t)(f[k] >> 8);
+      ++idx;
+    }
+    run += f[k];
+  }
+  if (lane == 63) crow[256] = (uint16_t)run;  // 4096
+  if (lane == 0) {
+    trow[0] = (uint8_t)(nsym - 1);
+    tablen[row] = 1 + 3 * nsym;
+  }
+}
+
+// the image's 96 cumulative rows into LDS (kCumWords u16 = 24,672 dwords)
+__device__ __forceinline__ void load_cum(uint16_t* lds, const uint16_t* __restrict__ src, int tid, int nthreads) {
+  const uint32_t* s = (const uint32_t*)src;  // kCumWords is even and every image's rows start 4-B aligned
+  uint32_t* d = (uint32_t*)lds;
+  for (int i = tid; i < kCumWords / 2; i += nthreads) d[i] = s[i];
+}
+
+// ---- encode 3: segment coding, one lane per segment -----------------------------------------
+// grid (ceil(nseg / 64), n), block 64.  The lane's symbols are read pixel by pixel from the
+// last to the first as six per-lane-contiguous 16-B loads (a segment starts at a multiple of
+// 96 B); bytes are written backwards from the end of the lane's region of `cap` bytes, so the
+// finished segment is region[cap - len, cap).
+__global__ __launch_bounds__(64) void rans_encode_segments(const uint8_t* __restrict__ z, int npix, int seg_pixels, int nseg,
+                                                            const uint16_t* __restrict__ cum, uint8_t* __restrict__ scratch,
+                                                            uint32_t cap, uint32_t* __restrict__ seglen) {
+  __shared__ uint16_t start[kCumWords];
+  const int lane = threadIdx.x, img = blockIdx.y;
+  load_cum(start, cum + (size_t)img * kCumWords, lane, 64);
+  __syncthreads();
+  const int seg = blockIdx.x * 64 + lane;
+  const bool live = seg < nseg;
+  const int p0 = live ? seg * seg_pixels : 0;
+  const int mypix = live ? min(seg_pixels, npix - p0) : 0;
+  const uint8_t* src = z + ((size_t)img * npix + p0) * kCh;
+  uint8_t* region = scratch + ((size_t)img * nseg + (live ? seg : 0)) * cap;
+  uint32_t pos = cap, x = kRansL;
+  auto emit = [&](uint32_t b) {
+    if (pos > 0) region[--pos] = (uint8_t)b;  // pos > 0 always holds: cap is the worst case
+  };
+  int maxpix = mypix;  // wave-uniform trip count
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) maxpix = max(maxpix, __shfl_xor(maxpix, o, 64));
+  for (int p = maxpix - 1; p >= 0; --p) {
+    const bool on = p < mypix;
+    for (int q = 5; q >= 0; --q) {
+      uint4 v = make_uint4(0, 0, 0, 0);
+      if (on) v = *(const uint4*)(src + (size_t)p * kCh + 16 * q);
+      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int b = 15; b >= 0; --b) {
+        const uint32_t s = (w[b >> 2] >> (8 * (b & 3))) & 255u;
+        const uint16_t* row = start + (16 * q + b) * kCumRow;
+        const uint32_t lo = row[s], freq = row[s + 1] - lo;
+        // freq == 4096: the channel's only symbol, x is unchanged and nothing is emitted
+        if (on && freq != kProbScale) {
+          const uint32_t xmax = freq << 19;
+          if (x >= xmax) {
+            emit(x & 255u);
+            x >>= 8;
+            if (x >= xmax) {
+              emit(x & 255u);
+              x >>= 8;
+            }
+          }
+          const uint32_t qd = x / freq;
+          x = (qd << kProbBits) + (x - qd * freq) + lo;
+        }
+      }
+    }
+  }
+  if (live) {
+    emit(x & 255u);
+    emit((x >> 8) & 255u);
+    emit((x >> 16) & 255u);
+    emit(x >> 24);
+    seglen[(size_t)img * nseg + seg] = cap - pos;
+  }
+}
+
+// exclusive prefix sums of len[0..count) into off[0..count] (off[count] = total, saturating at
+// `limit`) by one block of 256 threads
+__device__ void block_offsets(const uint32_t* __restrict__ len, int count, uint32_t* __restrict__ off, uint32_t limit,
+                              uint32_t* sh /* 257 words */) {
+  const int tid = threadIdx.x;
+  uint32_t carry = 0;
+  for (int base = 0; base < count; base += 256) {
+    const int i = base + tid;
+    const uint32_t v = i < count ? min(len[i], limit) : 0u;
+    sh[tid] = v;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {
+      const uint32_t t = tid >= o ? sh[tid - o] : 0u;
+      __syncthreads();
+      sh[tid] = (uint32_t)min((unsigned long long)sh[tid] + t, (unsigned long long)limit);
+      __syncthreads();
+    }
+    const uint32_t incl = (uint32_t)min((unsigned long long)sh[tid] + carry, (unsigned long long)limit);
+    if (i < count) off[i] = (uint32_t)min((unsigned long long)(incl - min(incl, v)), (unsigned long long)limit);
+    const uint32_t total = (uint32_t)min((unsigned long long)sh[255] + carry, (unsigned long long)limit);
+    __syncthreads();
+    carry = total;
+  }
+  if (tid == 0) off[count] = carry;
+}
+
+// ---- encode 4a: offsets and file sizes.  grid (n), block 256 --------------------------------
+__global__ __launch_bounds__(256) void rans_layout(const uint32_t* __restrict__ tablen, uint32_t* __restrict__ taboff,
+                                                    const uint32_t* __restrict__ seglen, uint32_t* __restrict__ segoff, int nseg,
+                                                    long long* __restrict__ sizes) {
+  __shared__ uint32_t sh[257];
+  const int img = blockIdx.x;
+  block_offsets(tablen + (size_t)img * kCh, kCh, taboff + (size_t)img * (kCh + 1), 0x7fffffffu, sh);
+  __syncthreads();
+  block_offsets(seglen + (size_t)img * nseg, nseg, segoff + (size_t)img * (nseg + 1), 0x7fffffffu, sh);
+  __syncthreads();
+  if (threadIdx.x == 0)
+    sizes[img] = (long long)kHeader + taboff[(size_t)img * (kCh + 1) + kCh] + 4ll * nseg +
+                 segoff[(size_t)img * (nseg + 1) + nseg];
+}
+
+// ---- encode 4b: the files.  grid (ceil((96 + nseg) / 4), n), block 256: one wave per item ----
+// item c < 96: channel c's table (item 0 also the header); item 96 + k: segment k's length and bytes
+__global__ __launch_bounds__(256) void rans_assemble(const uint8_t* __restrict__ tab, const uint32_t* __restrict__ tablen,
+                                                      const uint32_t* __restrict__ taboff, const uint8_t* __restrict__ scratch,
+                                                      uint32_t cap, const uint32_t* __restrict__ seglen,
+                                                      const uint32_t* __restrict__ segoff, int nseg, int seg_pixels, int h8, int w8,
+                                                      uint8_t* __restrict__ out, long long stride) {
+  const int lane = threadIdx.x & 63, item = blockIdx.x * 4 + (threadIdx.x >> 6), img = blockIdx.y;
+  if (item >= kCh + nseg) return;
+  uint8_t* file = out + (size_t)img * (size_t)stride;
+  const uint32_t* toff = taboff + (size_t)img * (kCh + 1);
+  if (item < kCh) {
+    if (item == 0 && lane < kHeader) {
+      const uint32_t hw[2] = {(uint32_t)h8, (uint32_t)w8};
+      uint8_t b;
+      if (lane < 4) b = (uint8_t)("NICR"[lane]);
+      else if (lane == 4) b = 1;
+      else if (lane == 5) b = (uint8_t)kProbBits;
+      else if (lane < 8) b = (uint8_t)(((uint32_t)seg_pixels >> (8 * (lane - 6))) & 255u);
+      else b = (uint8_t)((hw[(lane - 8) >> 2] >> (8 * (lane & 3))) & 255u);
+      file[lane] = b;
+    }
+    const size_t row = (size_t)img * kCh + item;
+    const uint8_t* src = tab + row * kTabRow;
+    uint8_t* dst = file + kHeader + toff[item];
+    for (uint32_t i = lane; i < tablen[row]; i += 64) dst[i] = src[i];  // < 16 + 96 * 769 <= stride
+    return;
+  }
+  const int k = item - kCh;
+  const uint32_t len = seglen[(size_t)img * nseg + k];
+  uint8_t* segtab = file + kHeader + toff[kCh];
+  if (lane < 4) segtab[4 * k + lane] = (uint8_t)((len >> (8 * lane)) & 255u);
+  const uint8_t* src = scratch + ((size_t)img * nseg + k) * cap + (cap - len);
+  // stride >= nic_rans_bound covers every payload (a file's symbols cost well under 12 bits on
+  // average under its own tables); the clamp keeps even a miscounted one inside the image's slot
+  const size_t at = (size_t)kHeader + toff[kCh] + 4 * (size_t)nseg + segoff[(size_t)img * (nseg + 1) + k];
+  for (uint32_t i = lane; i < len; i += 64)
+    if (at + i < (size_t)stride) file[at + i] = src[i];
+}
+
+// ---- decode 1: parse.  grid (n), block 256 ---------------------------------------------------
+// Every read of a file byte is clamped to [0, size).  meta[img] = {nseg, seg_pixels, payload
+// begin, size}; a header that does not describe an (h8, w8) version-1 file leaves nseg = 0 and
+// status 2 (nothing of that image is decoded); a table that breaks the invariants sets status
+// bit 4 and still yields cumulative rows that resolve every slot (start[0] = 0, non-decreasing,
+// start[256] = 4096).
+__global__ __launch_bounds__(256) void rans_parse(const uint8_t* __restrict__ files, long long stride,
+                                                   const long long* __restrict__ sizes, int h8, int w8, uint16_t* __restrict__ cum,
+                                                   uint32_t* __restrict__ seglen, uint32_t* __restrict__ segoff, int maxseg,
+                                                   uint32_t* __restrict__ meta, int* __restrict__ status) {
+  __shared__ uint32_t sh[257];
+  __shared__ uint32_t choff[kCh + 1];
+  __shared__ int s_bad, s_nseg;
+  const int tid = threadIdx.x, img = blockIdx.x;
+  const uint8_t* f = files + (size_t)img * (size_t)stride;
+  long long sz = sizes[img];
+  sz = sz < 0 ? 0 : (sz > stride ? stride : sz);
+  sz = sz > 0x7fffffffll ? 0x7fffffffll : sz;
+  const uint32_t size = (uint32_t)sz;
+  auto rd = [&](uint32_t i) -> uint32_t { return i < size ? (uint32_t)f[i] : 0u; };
+  const int npix = h8 * w8;
+  if (tid == 0) {
+    const uint32_t S = rd(6) | (rd(7) << 8);
+    const uint32_t fh = rd(8) | (rd(9) << 8) | (rd(10) << 16) | (rd(11) << 24);
+    const uint32_t fw = rd(12) | (rd(13) << 8) | (rd(14) << 16) | (rd(15) << 24);
+    const bool ok = size >= (uint32_t)kHeader && rd(0) == 'N' && rd(1) == 'I' && rd(2) == 'C' && rd(3) == 'R' && rd(4) == 1 &&
+                    rd(5) == (uint32_t)kProbBits && S >= 1 && fh == (uint32_t)h8 && fw == (uint32_t)w8;
+    const int nseg = ok ? (int)(((uint32_t)npix + S - 1) / S) : 0;  // <= npix = maxseg
+    uint32_t off = kHeader;
+    for (int c = 0; c < kCh; ++c) {
+      choff[c] = off;
+      off += 1 + 3 * (rd(off) + 1);
+    }
+    choff[kCh] = off;
+    s_nseg = nseg;
+    s_bad = ok ? 0 : 2;
+    meta[4 * img + 0] = (uint32_t)nseg;
+    meta[4 * img + 1] = ok ? S : 1u;
+    meta[4 * img + 2] = min(off + 4u * (uint32_t)nseg, size);
+    meta[4 * img + 3] = size;
+  }
+  __syncthreads();
+  const int nseg = s_nseg;
+  if (nseg > 0 && tid < kCh) {
+    uint16_t* row = cum + ((size_t)img * kCh + tid) * kCumRow;
+    const uint32_t base = choff[tid], nsym = rd(base) + 1;
+    uint32_t e = 0, run = 0, es = rd(base + 1), ef = rd(base + 2) | (rd(base + 3) << 8);
+    for (uint32_t s = 0; s < 256; ++s) {
+      row[s] = (uint16_t)run;
+      if (e < nsym && es == s) {
+        run = min(run + ef, kProbScale);
+        ++e;
+        es = rd(base + 1 + 3 * e);
+        ef = rd(base + 2 + 3 * e) | (rd(base + 3 + 3 * e) << 8);
+      }
+    }
+    row[256] = (uint16_t)kProbScale;
+    if (e != nsym || run != kProbScale) atomicOr(&s_bad, 4);
+  }
+  // the segment table -> clamped lengths -> offsets
+  const uint32_t segtab = choff[kCh];
+  uint32_t* len = seglen + (size_t)img * maxseg;
+  for (int k = tid; k < nseg; k += 256) {
+    const uint32_t a = segtab + 4u * (uint32_t)k;  // < 2^31 + 2^27: no wrap
+    len[k] = rd(a) | (rd(a + 1) << 8) | (rd(a + 2) << 16) | (rd(a + 3) << 24);
+  }
+  __syncthreads();
+  block_offsets(len, nseg, segoff + (size_t)img * (maxseg + 1), size, sh);
+  __syncthreads();
+  if (tid == 0) status[img] = s_bad;
+}
+
+// ---- decode 2: segments, one lane per segment -----------------------------------------------
+// grid (ceil(maxseg / 64), n), block 64; the grid covers seg_pixels = 1, blocks past the file's
+// own nseg exit.  Lane reads only file bytes of its segment [begin, end) (a read past end gives
+// 0), looks symbols up in rows that resolve every slot, and writes only its own latent bytes.
+__global__ __launch_bounds__(64) void rans_decode_segments(const uint8_t* __restrict__ files, long long stride, int npix,
+                                                            const uint16_t* __restrict__ cum, const uint32_t* __restrict__ segoff,
+                                                            int maxseg, const uint32_t* __restrict__ meta, uint8_t* __restrict__ z,
+                                                            int* __restrict__ status) {
+  __shared__ uint16_t start[kCumWords];
+  const int lane = threadIdx.x, img = blockIdx.y;
+  const int nseg = (int)meta[4 * img + 0];
+  if ((int)blockIdx.x * 64 >= nseg) return;  // block-uniform
+  const int seg_pixels = (int)meta[4 * img + 1];
+  const uint32_t pay = meta[4 * img + 2], size = meta[4 * img + 3];
+  load_cum(start, cum + (size_t)img * kCumWords, lane, 64);
+  __syncthreads();
+  const int seg = blockIdx.x * 64 + lane;
+  const bool live = seg < nseg;
+  const long long p0 = live ? (long long)seg * seg_pixels : 0;  // < npix: seg < nseg = ceil(npix / seg_pixels)
+  const int mypix = live ? (int)min((long long)seg_pixels, (long long)npix - p0) : 0;
+  const uint32_t* off = segoff + (size_t)img * (maxseg + 1);
+  const uint32_t begin = live ? min(pay + off[seg], size) : 0u;
+  const uint32_t end = live ? min(pay + off[seg + 1], size) : 0u;
+  const uint8_t* f = files + (size_t)img * (size_t)stride;
+  uint32_t ptr = begin;
+  auto next = [&]() -> uint32_t {
+    const uint32_t b = ptr < end ? (uint32_t)f[ptr] : 0u;
+    ++ptr;  // counts reads past end too: the segment then fails ptr == end
+    return b;
+  };
+  uint32_t x = 0;
+  if (live) {
+    x = next() << 24;
+    x |= next() << 16;
+    x |= next() << 8;
+    x |= next();
+  }
+  uint8_t* dst = z + ((size_t)img * npix + (size_t)p0) * kCh;
+  int maxpix = mypix;  // wave-uniform trip count
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) maxpix = max(maxpix, __shfl_xor(maxpix, o, 64));
+  for (int p = 0; p < maxpix; ++p) {
+    const bool on = p < mypix;
+    for (int q = 0; q < 6; ++q) {
+      uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int b = 0; b < 16; ++b) {
+        const uint16_t* row = start + (16 * q + b) * kCumRow;
+        const uint32_t slot = x & (kProbScale - 1);
+        // largest s with row[s] <= slot: row[0] = 0 <= slot < 4096 = row[256]
+        uint32_t s = 0;
+#pragma unroll
+        for (uint32_t step = 128; step > 0; step >>= 1)
+          if (row[s + step] <= slot) s += step;
+        const uint32_t lo = row[s], freq = row[s + 1] - lo;
+        if (on) {  // a lane past its last pixel keeps its final state
+          x = freq * (x >> kProbBits) + slot - lo;
+          if (x < kRansL) {
+            x = (x << 8) | next();
+            if (x < kRansL) x = (x << 8) | next();
+          }
+        }
+        w[b >> 2] |= s << (8 * (b & 3));
+      }
+      if (on) *(uint4*)(dst + (size_t)p * kCh + 16 * q) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+  }
+  if (live && !(x == kRansL && ptr == end)) atomicOr(&status[img], 1);
+}
+
+size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+}  // namespace
+
+bool rans_shape_ok(int h8, int w8) {
+  // file offsets, segment offsets and symbol counts are 32-bit: 144 B / pixel worst case
+  return h8 > 0 && w8 > 0 && (long long)h8 * w8 <= (1ll << 23);
+}
+
+void rans_plan(int n, int h8, int w8, int seg_pixels, bool decode, RansPlan* pl) {
+  const size_t npix = (size_t)h8 * w8, N = (size_t)n;
+  const int S = decode ? 1 : seg_pixels;  // decode sizes its offsets for the smallest segments
+  pl->nseg = (int)((npix + S - 1) / S);
+  // a symbol of freq 1 costs 12 + log2(1 + 2^-11) bits in the worst case (the state may sit at
+  // the bottom of its interval): 144 B per pixel, under 1/64 B per pixel of slack, the 4 state bytes
+  pl->cap = decode ? 0 : (uint32_t)(144u * (uint32_t)seg_pixels + (uint32_t)seg_pixels / 64u + 8u);
+  size_t o = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = o;
+    o += align256(bytes);
+    return at;
+  };
+  pl->counts = take(decode ? 0 : N * kCh * 256 * 4);
+  pl->cum = take(N * kCumWords * 2);
+  pl->tab = take(decode ? 0 : N * kCh * kTabRow);
+  pl->tablen = take(decode ? 0 : N * kCh * 4);
+  pl->taboff = take(decode ? 0 : N * (kCh + 1) * 4);
+  pl->seglen = take(N * pl->nseg * 4);
+  pl->segoff = take(N * ((size_t)pl->nseg + 1) * 4);
+  pl->meta = take(decode ? N * 16 : 0);
+  pl->scratch = take(N * pl->nseg * pl->cap);
+  pl->bytes = o;
+}
+
+hipError_t launch_rans_encode(const uint8_t* z, int n, int h8, int w8, int seg_pixels, char* ws, const RansPlan& pl,
+                              uint8_t* out, long long stride, long long* sizes, hipStream_t st) {
+  const int npix = h8 * w8, nseg = pl.nseg;
+  uint32_t* counts = (uint32_t*)(ws + pl.counts);
+  uint16_t* cum = (uint16_t*)(ws + pl.cum);
+  uint8_t* tab = (uint8_t*)(ws + pl.tab);
+  uint32_t* tablen = (uint32_t*)(ws + pl.tablen);
+  uint32_t* taboff = (uint32_t*)(ws + pl.taboff);
+  uint32_t* seglen = (uint32_t*)(ws + pl.seglen);
+  uint32_t* segoff = (uint32_t*)(ws + pl.segoff);
+  uint8_t* scratch = (uint8_t*)(ws + pl.scratch);
+  hipError_t e = hipMemsetAsync(counts, 0, (size_t)n * kCh * 256 * 4, st);
+  if (e != hipSuccess) return e;
+  rans_hist<<<dim3((npix + 255) / 256, 3, n), 256, 0, st>>>(z, npix, counts);
+  rans_normalise<<<dim3(kCh, n), 64, 0, st>>>(counts, npix, cum, tab, tablen);
+  rans_encode_segments<<<dim3((nseg + 63) / 64, n), 64, 0, st>>>(z, npix, seg_pixels, nseg, cum, scratch, pl.cap, seglen);
+  rans_layout<<<dim3(n), 256, 0, st>>>(tablen, taboff, seglen, segoff, nseg, sizes);
+  rans_assemble<<<dim3((kCh + nseg + 3) / 4, n), 256, 0, st>>>(tab, tablen, taboff, scratch, pl.cap, seglen, segoff, nseg,
+                                                              seg_pixels, h8, w8, out, stride);
+  return hipGetLastError();
+}
+
+hipError_t launch_rans_decode(const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8, char* ws,
+                              const RansPlan& pl, uint8_t* z, int* status, hipStream_t st) {
+  const int npix = h8 * w8, maxseg = pl.nseg;
+  uint16_t* cum = (uint16_t*)(ws + pl.cum);
+  uint32_t* seglen = (uint32_t*)(ws + pl.seglen);
+  uint32_t* segoff = (uint32_t*)(ws + pl.segoff);
+  uint32_t* meta = (uint32_t*)(ws + pl.meta);
+  rans_parse<<<dim3(n), 256, 0, st>>>(files, stride, sizes, h8, w8, cum, seglen, segoff, maxseg, meta, status);
+  rans_decode_segments<<<dim3((maxseg + 63) / 64, n), 64, 0, st>>>(files, stride, npix, cum, segoff, maxseg, meta, z, status);
+  return hipGetLastError();
+}
+
+}  // namespace nic
+
+// ---- host-only entry points ------------------------------------------------------------------
+
+extern "C" {
+
+int nic_rans_bound(int h8, int w8, int seg_pixels, int64_t* bytes) {
+  if (!bytes) return nic::set_error(NIC_EINVAL, "nic_rans_bound: bytes is NULL");
+  if (!nic::rans_shape_ok(h8, w8)) return nic::set_error(NIC_ESHAPE, "nic_rans_bound: latent size out of range");
+  if (seg_pixels < 1 || seg_pixels > 65535) return nic::set_error(NIC_ESHAPE, "nic_rans_bound: seg_pixels not in 1..65535");
+  const int64_t npix = (int64_t)h8 * w8, nseg = (npix + seg_pixels - 1) / seg_pixels;
+  // header, 96 full tables, the segment table, 12 bits per symbol and 4 state bytes per segment
+  *bytes = nic::kHeader + (int64_t)nic::kCh * (1 + 3 * 256) + 4 * nseg + 144 * npix + 4 * nseg;
+  return NIC_OK;
+}
+
+int nic_rans_inspect(const uint8_t* f, int64_t size, int* h8, int* w8, int* seg_pixels) {
+  char msg[160];
+  auto corrupt = [&](const char* what, long long a = 0, long long b = 0) {
+    snprintf(msg, sizeof(msg), what, a, b);
+    return nic::set_error(NIC_ECORRUPT, msg);
+  };
+  if (!f) return nic::set_error(NIC_EINVAL, "nic_rans_inspect: file is NULL");
+  if (size < nic::kHeader) return corrupt("nic_rans_inspect: %lld bytes are less than the 16-byte header", size);
+  if (std::memcmp(f, "NICR", 4) != 0) return corrupt("nic_rans_inspect: bad magic");
+  if (f[4] != 1) return corrupt("nic_rans_inspect: version %lld, expected 1", f[4]);
+  if (f[5] != nic::kProbBits) return corrupt("nic_rans_inspect: %lld probability bits, expected 12", f[5]);
+  auto u32 = [&](int64_t at) { return (uint32_t)f[at] | ((uint32_t)f[at + 1] << 8) | ((uint32_t)f[at + 2] << 16) | ((uint32_t)f[at + 3] << 24); };
+  const uint32_t S = (uint32_t)f[6] | ((uint32_t)f[7] << 8), fh = u32(8), fw = u32(12);
+  if (S == 0) return corrupt("nic_rans_inspect: seg_pixels is 0");
+  if (fh == 0 || fw == 0 || fh > (1u << 23) || fw > (1u << 23) || !nic::rans_shape_ok((int)fh, (int)fw))
+    return corrupt("nic_rans_inspect: latent size %lld x %lld out of range", fh, fw);
+  int64_t at = nic::kHeader;
+  for (int c = 0; c < nic::kCh; ++c) {
+    if (at >= size) return corrupt("nic_rans_inspect: truncated in the table of channel %lld", c);
+    const int nsym = f[at] + 1;
+    if (at + 1 + 3 * nsym > size) return corrupt("nic_rans_inspect: truncated in the table of channel %lld", c);
+    int prev = -1;
+    uint32_t sum = 0;
+    for (int e = 0; e < nsym; ++e) {
+      const int s = f[at + 1 + 3 * e];
+      const uint32_t fr = (uint32_t)f[at + 2 + 3 * e] | ((uint32_t)f[at + 3 + 3 * e] << 8);
+      if (s <= prev) return corrupt("nic_rans_inspect: channel %lld: symbols not strictly ascending", c);
+      if (fr < 1 || fr > nic::kProbScale) return corrupt("nic_rans_inspect: channel %lld: freq %lld not in 1..4096", c, fr);
+      prev = s;
+      sum += fr;
+    }
+    if (sum != nic::kProbScale) return corrupt("nic_rans_inspect: channel %lld: freqs sum to %lld, not 4096", c, sum);
+    at += 1 + 3 * nsym;
+  }
+  const int64_t npix = (int64_t)fh * fw, nseg = (npix + S - 1) / S;
+  if (at + 4 * nseg > size) return corrupt("nic_rans_inspect: truncated in the segment table");
+  int64_t pay = 0;
+  for (int64_t k = 0; k < nseg; ++k) pay += u32(at + 4 * k);
+  if (at + 4 * nseg + pay != size)
+    return corrupt("nic_rans_inspect: header, tables and segments need %lld bytes, the file has %lld", at + 4 * nseg + pay, size);
+  if (h8) *h8 = (int)fh;
+  if (w8) *w8 = (int)fw;
+  if (seg_pixels) *seg_pixels = (int)S;
+  return NIC_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,191 @@
+"""CPU checks of the .nic container: the pure-Python reference coder (tests/rans_ref.py) on the
+golden latents, and the host-only entry points nic_rans_inspect / nic_rans_bound plus the
+argument checks of the device entry points (no GPU calls here)."""
+import ctypes
+import glob
+import os
+import struct
+
+import numpy as np
+import pytest
+
+from neural_network_image_compression_amd import _lib
+from neural_network_image_compression_amd import bitstream as B
+from oracle import nic_oracle as O
+from tests import rans_ref as R
+from tests.conftest import GOLDEN, load_case
+
+CASES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, "*.npz")))
+TRAINED_256 = ("kodim21_256_trained", "kodim21_256_trained_c0.02", "kodim21_256_trained_c0.03")
+
+
+@pytest.fixture(scope="module")
+def ref_files():
+    """{case: [(latent (h8,w8,96), file bytes)]} with the reference writer, default segments."""
+    cache = {}
+
+    def get(case):
+        if case not in cache:
+            cache[case] = [(z, R.write_file(z)) for z in load_case(case)["latent"]]
+        return cache[case]
+
+    return get
+
+
+def inspect(data):
+    h8, w8, sp = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_int(-1)
+    buf = np.frombuffer(data, np.uint8)
+    rc = _lib.lib().nic_rans_inspect(buf.ctypes.data, len(data), ctypes.byref(h8), ctypes.byref(w8), ctypes.byref(sp))
+    return rc, (h8.value, w8.value, sp.value)
+
+
+def test_golden_set_is_complete():
+    assert len(CASES) >= 12 and set(TRAINED_256) <= set(CASES) and "odd37x53" in CASES
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_reference_round_trips_and_is_near_ideal(case, ref_files):
+    for z, data in ref_files(case):
+        np.testing.assert_array_equal(R.read_file(data), z)
+        info = R.parse_file(data)
+        nseg = len(info["seg_lengths"])
+        assert nseg == -(-z.shape[0] * z.shape[1] // 32)
+        payload = sum(info["seg_lengths"])
+        ideal = R.ideal_payload_bytes(z, info["tables"])
+        print(f"{case}: file {len(data)} tables {info['table_bytes']} payload {payload} ideal {ideal:.1f} nseg {nseg}")
+        # 4 state bytes and 1 byte of granularity per segment
+        assert payload <= ideal + 5 * nseg
+        # a symbol has an entry iff it occurs in that channel
+        flat = z.reshape(-1, 96)
+        for c in range(96):
+            assert [s for s in range(256) if info["tables"][c][s]] == np.unique(flat[:, c]).tolist()
+
+
+@pytest.mark.parametrize("case", TRAINED_256)
+def test_reference_file_is_smaller_than_the_png(case, ref_files):
+    (z, data), = ref_files(case)
+    png = len(B.png_bytes(O.pack_latent(z[None])[0]))
+    print(f"{case}: nic {len(data)} png {png}")
+    assert len(data) < png
+
+
+@pytest.mark.parametrize("seg_pixels", [1, 7, 4096])
+def test_reference_other_segment_sizes(seg_pixels, golden):
+    z = golden("odd37x53")["latent"][0]
+    data = R.write_file(z, seg_pixels)
+    assert len(R.parse_file(data)["seg_lengths"]) == -(-35 // seg_pixels)
+    np.testing.assert_array_equal(R.read_file(data), z)
+    assert inspect(data) == (_lib.NIC_OK, (5, 7, seg_pixels))
+
+
+def test_normalise_invariants_on_hard_histograms():
+    hard = {
+        "all 256 symbols equally": [20] * 256,
+        "one symbol": [0] * 255 + [5184],
+        "one occurrence among many": [5183, 1] + [0] * 254,
+        "200 singletons and 56 sharing the rest": [1] * 200 + [89] * 56,
+        "128 rare and 128 equal (overshoot above the largest freq)": [1] * 128 + [1000] * 128,
+    }
+    for name, counts in hard.items():
+        f = R.normalise(counts)
+        assert sum(f) == 4096 and all((c > 0) == (v > 0) for c, v in zip(counts, f)), name
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_inspect_accepts_reference_files(case, ref_files):
+    for z, data in ref_files(case):
+        assert inspect(data) == (_lib.NIC_OK, (z.shape[0], z.shape[1], 32))
+    # the outputs are optional
+    buf = np.frombuffer(data, np.uint8)
+    assert _lib.lib().nic_rans_inspect(buf.ctypes.data, len(data), None, None, None) == _lib.NIC_OK
+
+
+def _table_offsets(data):
+    at, offs = 16, []
+    for _ in range(96):
+        offs.append(at)
+        at += 1 + 3 * (data[at] + 1)
+    return offs, at
+
+
+def _corruptions(data):
+    """name -> a damaged copy of a well-formed file."""
+    out = {}
+    out["bad magic"] = b"NICX" + data[4:]
+    out["version 2"] = data[:4] + b"\x02" + data[5:]
+    out["probability bits 11"] = data[:5] + b"\x0b" + data[6:]
+    out["truncated by one byte"] = data[:-1]
+    out["one byte appended"] = data + b"\x00"
+    offs, segtab = _table_offsets(data)
+    first = struct.unpack("<I", data[segtab:segtab + 4])[0]
+    out["segment length raised by one"] = data[:segtab] + struct.pack("<I", first + 1) + data[segtab + 4:]
+    # a channel with at least two entries: lower one freq (sum 4095), or swap its first two symbols
+    c = next(i for i in range(96) if data[offs[i]] >= 1)
+    e0 = offs[c] + 1
+    s0, f0 = struct.unpack("<BH", data[e0:e0 + 3])
+    s1, f1 = struct.unpack("<BH", data[e0 + 3:e0 + 6])
+    low = (s0, f0 - 1) if f0 > 1 else (s0, f0)
+    low2 = (s1, f1) if f0 > 1 else (s1, f1 - 1)
+    out["freqs sum to 4095"] = data[:e0] + struct.pack("<BH", *low) + struct.pack("<BH", *low2) + data[e0 + 6:]
+    out["descending symbols"] = data[:e0] + struct.pack("<BH", s1, f0) + struct.pack("<BH", s0, f1) + data[e0 + 6:]
+    out["equal symbols"] = data[:e0] + struct.pack("<BH", s0, f0) + struct.pack("<BH", s0, f1) + data[e0 + 6:]
+    out["seg_pixels 0"] = data[:6] + b"\x00\x00" + data[8:]
+    out["h8 0"] = data[:8] + struct.pack("<I", 0) + data[12:]
+    out["header only"] = data[:16]
+    out["shorter than the header"] = data[:9]
+    return out
+
+
+def test_inspect_rejects_corrupt_files(ref_files):
+    (_, data), = ref_files("kodim21_256_trained")
+    bad = _corruptions(data)
+    for must in ("bad magic", "version 2", "truncated by one byte", "segment length raised by one", "freqs sum to 4095",
+                 "descending symbols", "seg_pixels 0"):
+        assert must in bad
+    for name, d in bad.items():
+        rc, _ = inspect(d)
+        assert rc == _lib.NIC_ECORRUPT, name
+        assert "nic_rans_inspect" in _lib.last_error(), name
+        with pytest.raises(ValueError):
+            R.parse_file(d)
+
+
+def test_bound_is_the_worst_case_file():
+    L = _lib.lib()
+    b = ctypes.c_int64()
+    for h8, w8, sp in ((1, 1, 32), (5, 7, 32), (32, 32, 1), (32, 32, 4096), (270, 480, 32)):
+        assert L.nic_rans_bound(h8, w8, sp, ctypes.byref(b)) == _lib.NIC_OK
+        npix = h8 * w8
+        nseg = -(-npix // sp)
+        assert b.value == 16 + 96 * 769 + 4 * nseg + 144 * npix + 4 * nseg
+    # every channel cycling through all 256 symbols: full tables, 8 bits per symbol
+    z = (np.arange(72 * 72 * 96) // 96 % 256).astype(np.uint8).reshape(72, 72, 96)
+    data = R.write_file(z)
+    assert L.nic_rans_bound(72, 72, 32, ctypes.byref(b)) == _lib.NIC_OK and len(data) <= b.value
+    assert R.parse_file(data)["table_bytes"] == 96 * 769
+
+
+def test_entry_points_validate_without_a_gpu():
+    L = _lib.lib()
+    b = ctypes.c_int64()
+    assert L.nic_version() >= 300
+    assert L.nic_rans_bound(1, 1, 32, None) == _lib.NIC_EINVAL
+    assert L.nic_rans_bound(0, 1, 32, ctypes.byref(b)) == _lib.NIC_ESHAPE
+    assert L.nic_rans_bound(1, 1, 0, ctypes.byref(b)) == _lib.NIC_ESHAPE
+    assert L.nic_rans_bound(1, 1, 65536, ctypes.byref(b)) == _lib.NIC_ESHAPE
+    assert L.nic_rans_bound(4096, 4096, 32, ctypes.byref(b)) == _lib.NIC_ESHAPE  # over 2^23 latent pixels
+    assert L.nic_rans_inspect(None, 100, None, None, None) == _lib.NIC_EINVAL
+    assert "NULL" in _lib.last_error()
+    # device entry points: shape, empty batch, then NULL, all before any HIP call
+    assert L.nic_rans_encode(None, None, 1, 4, 4, 32, None, 1 << 20, None, None) == _lib.NIC_EINVAL
+    assert "NULL" in _lib.last_error()
+    assert L.nic_rans_encode(None, None, 1, 0, 4, 32, None, 1 << 20, None, None) == _lib.NIC_ESHAPE
+    assert L.nic_rans_encode(None, None, -1, 4, 4, 32, None, 1 << 20, None, None) == _lib.NIC_ESHAPE
+    assert L.nic_rans_encode(None, None, 1, 4, 4, 0, None, 1 << 20, None, None) == _lib.NIC_ESHAPE
+    assert L.nic_rans_encode(None, None, 0, 4, 4, 32, None, 0, None, None) == _lib.NIC_OK  # empty batch
+    assert L.nic_rans_decode(None, None, 1 << 20, None, 1, 4, 4, None, None, None) == _lib.NIC_EINVAL
+    assert L.nic_rans_decode(None, None, 1 << 20, None, 1, 4, 0, None, None, None) == _lib.NIC_ESHAPE
+    assert L.nic_rans_decode(None, None, 0, None, 0, 4, 4, None, None, None) == _lib.NIC_OK
+    assert L.nic_rans_reserve(None, 1, 4, 4, 32) == _lib.NIC_EINVAL
+    assert L.nic_rans_reserve(None, 1, 4, 4, 70000) == _lib.NIC_ESHAPE
+    assert L.nic_rans_reserve(None, 0, 4, 4, 32) == _lib.NIC_OK

@@ -5,6 +5,13 @@ shifted into `--images` distinct ones).  Reports images/s and MP/s per driver mo
 writes, round 5's pipeline) on the kodim21 tiles and on data/imagenet_patches_1k, and whether
 every mode wrote the same bytes.
 
+`--container png nic` (the default measures both after the driver modes; naming containers runs
+only this part) compares the on-disk containers in one run on the kodim21 tiles with the default
+pipeline: the reference's packed PNG against the device-coded .nic (bitstream.py), images/s of
+compress / uncompress, the mean file size of each, and whether both routes reconstruct the same
+PNGs.  `--weights trained` (default for this part) uses the committed coef-0.01 codec, whose
+latents are what the containers are meant for; `spread` the seeded dense ones.
+
 Output: one JSON line.  Needs the GPU (the codec) and the built library."""
 import argparse
 import json
@@ -68,8 +75,41 @@ def run_modes(enc, dec, tmp, ds, ck, n, px, modes, repeat):
     return res, same
 
 
+def run_containers(enc, dec, tmp, ds, ck, n, px, containers, repeat):
+    """Best-of-`repeat` compress / uncompress wall time and mean file size per container."""
+    res, recon = {}, {}
+    for cont in containers:
+        best = {}
+        for r in range(repeat + 1):
+            for d in ("_compressed", "_uncompressed"):
+                shutil.rmtree(ds + d, ignore_errors=True)
+            t0 = time.perf_counter()
+            enc.compress(ds, os.path.join(ck, "encoder"), container=cont)
+            t1 = time.perf_counter()
+            dec.uncompress(ds + "_compressed", os.path.join(ck, "decoder"), container=cont)
+            t2 = time.perf_counter()
+            if r:
+                best["compress_s"] = min(best.get("compress_s", 1e9), t1 - t0)
+                best["uncompress_s"] = min(best.get("uncompress_s", 1e9), t2 - t1)
+        sizes = [os.path.getsize(os.path.join(ds + "_compressed", f)) for f in os.listdir(ds + "_compressed")]
+        res[cont] = {"compress_s": round(best["compress_s"], 4), "uncompress_s": round(best["uncompress_s"], 4),
+                     "compress_img_s": round(n / best["compress_s"], 1),
+                     "uncompress_img_s": round(n / best["uncompress_s"], 1),
+                     "compress_MP_s": round(n * px / 1e6 / best["compress_s"], 2),
+                     "uncompress_MP_s": round(n * px / 1e6 / best["uncompress_s"], 2),
+                     "files": len(sizes), "mean_file_bytes": round(float(np.mean(sizes)), 1)}
+        recon[cont] = {f: open(os.path.join(ds + "_uncompressed", f), "rb").read()
+                       for f in sorted(os.listdir(ds + "_uncompressed"))}
+    same = all(recon[c] == recon[containers[0]] for c in recon)
+    return res, same
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--container", nargs="+", choices=("png", "nic"), default=None,
+                    help="compare these on-disk containers only (default: the driver modes, then both)")
+    ap.add_argument("--weights", choices=("trained", "spread"), default="trained",
+                    help="codec of the container comparison")
     ap.add_argument("--images", type=int, default=192)
     ap.add_argument("--repeat", type=int, default=2)
     ap.add_argument("--imagenet", default=os.path.join(ROOT, "data", "imagenet_patches_1k"))
@@ -95,10 +135,21 @@ def main():
         modes = [("serial_b4", {"batch_size": 4, "workers": 0}), ("r4_b4_w8", {"batch_size": 4, "workers": 8}),
                  ("pipeline_b64", {})]
         out = {"tool": "compress_bench", "host_cpus": len(os.sched_getaffinity(0))}
-        res, same = run_modes(enc, dec, tmp, ds, ck, args.images, 65536, modes, args.repeat)
-        out["kodim21_tiles"] = {"images": args.images, "tile": "256x256x3 kodim21 tiles", "modes": res,
-                                "files_identical_across_modes": same}
-        if os.path.isdir(args.imagenet):
+        if args.container is None:
+            res, same = run_modes(enc, dec, tmp, ds, ck, args.images, 65536, modes, args.repeat)
+            out["kodim21_tiles"] = {"images": args.images, "tile": "256x256x3 kodim21 tiles", "modes": res,
+                                    "files_identical_across_modes": same}
+        ckc = ck
+        if args.weights == "trained":
+            ckc = os.path.join(tmp, "ck_trained")
+            pre = os.path.join(ROOT, "tests", "golden", "trained", "coef0.01_")
+            W.save(W.load(pre + "encoder", "encoder"), os.path.join(ckc, "encoder"), "encoder")
+            W.save(W.load(pre + "decoder", "decoder"), os.path.join(ckc, "decoder"), "decoder")
+        res, same = run_containers(enc, dec, tmp, ds, ckc, args.images, 65536, args.container or ["png", "nic"],
+                                   args.repeat)
+        out["containers"] = {"images": args.images, "tile": "256x256x3 kodim21 tiles", "weights": args.weights,
+                             "driver": "pipeline_b64", "by_container": res, "reconstructions_identical": same}
+        if args.container is None and os.path.isdir(args.imagenet):
             inet = os.path.join(tmp, "inet")
             shutil.copytree(args.imagenet, inet)
             n = len([f for f in os.listdir(inet) if f.endswith(".jpg")])
