@@ -263,6 +263,34 @@ int nic_rans_decode(nic_ctx* ctx, const uint8_t* files, int64_t stride, const in
                     uint8_t* latent, int32_t* status, void* stream);
 int nic_rans_inspect(const uint8_t* host_file, int64_t size, int* h8, int* w8, int* seg_pixels);
 
+/* ---- The device PNG writer: complete PNG files written on the device --------------------------
+ * An optional writer for reconstructions (Pillow's optimize=True file, nic_png_encode, stays the
+ * default and the bitstream's format).  Format: DESIGN.md, "The device PNG writer":
+ *   signature, IHDR (8-bit, colour type 0 or 2), one IDAT, IEND; no ancillary chunks
+ *   IDAT = zlib header 78 01, deflate blocks, Adler-32 of the filtered stream
+ *   filtered stream: per row the filter byte and the filtered row; NIC_PNG_FILTER_ADAPTIVE is
+ *     nic_png_encode's heuristic (the stream inside Pillow's optimize=True file, byte for byte),
+ *     0..4 one fixed filter (None, Sub, Up, Average, Paeth) for every row
+ *   the stream is cut into blocks of nic_png_device_block_bytes(); every block is one dynamic-
+ *     Huffman block of literals + end-of-block followed by an empty stored block (byte alignment),
+ *     or a stored block where that is no larger; no LZ77 matching
+ * An image's file depends on that image and the arguments alone.
+ *
+ * nic_png_device_bound: the largest file of an (h, w, channels) image, the minimum `stride`:
+ *     63 + T + 5 * ceil(T / block_bytes), T = h * (w * channels + 1).  w * channels <= 16384,
+ *     T <= 2^30, channels 1 or 3.
+ * nic_png_device_reserve: grow the workspace so nic_png_device_encode of n such images allocates
+ *     nothing.  Synchronous.
+ * nic_png_device_encode: images (n,h,w,channels) u8 on the DEVICE -> file i at out + i * stride
+ *     (DEVICE), its byte count in sizes[i] (DEVICE int64[n]).  Everything runs on `stream`; no
+ *     host synchronisation.  n <= 65535. */
+#define NIC_PNG_FILTER_ADAPTIVE (-1)
+int nic_png_device_block_bytes(void);
+int nic_png_device_bound(int h, int w, int channels, int64_t* bytes);
+int nic_png_device_reserve(nic_ctx* ctx, int n, int h, int w, int channels);
+int nic_png_device_encode(nic_ctx* ctx, const uint8_t* images, int n, int h, int w, int channels, int filter,
+                          uint8_t* out, int64_t stride, int64_t* sizes, void* stream);
+
 /* ---- Training side path (tf2_0/src/training.py:74-151): the step's convolutions ------------
  * NHWC fp32 device tensors, split-f16x3 MFMA (fp32-class), kernels of Keras layouts, no ctx.
  * Every forward and backward convolution of the step is one of two GEMMs:

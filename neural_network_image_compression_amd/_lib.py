@@ -34,6 +34,7 @@ NIC_ERANGE = -6
 NIC_ECORRUPT = -7
 
 RANGE_POLICIES = {"fallback": 0, "error": 1}  # nic.h NIC_RANGE_FALLBACK / NIC_RANGE_ERROR
+PNG_FILTER_ADAPTIVE = -1  # nic.h NIC_PNG_FILTER_ADAPTIVE
 
 _lib: Optional[ctypes.CDLL] = None
 _lock = threading.Lock()
@@ -85,6 +86,11 @@ _SIGNATURES = {
     "nic_rans_encode": (ctypes.c_int, [c_vp, c_vp] + [ctypes.c_int] * 4 + [c_vp, ctypes.c_int64, c_vp, c_vp]),
     "nic_rans_decode": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp] + [ctypes.c_int] * 3 + [c_vp, c_vp, c_vp]),
     "nic_rans_inspect": (ctypes.c_int, [c_vp, ctypes.c_int64] + [ctypes.POINTER(ctypes.c_int)] * 3),
+    # device PNG writer (nic_png_dev.hip)
+    "nic_png_device_block_bytes": (ctypes.c_int, []),
+    "nic_png_device_bound": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int64)]),
+    "nic_png_device_reserve": (ctypes.c_int, [c_vp] + [ctypes.c_int] * 4),
+    "nic_png_device_encode": (ctypes.c_int, [c_vp, c_vp] + [ctypes.c_int] * 5 + [c_vp, ctypes.c_int64, c_vp, c_vp]),
     # training side path (nic_train.hip)
     "nic_conv_gather_work": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_int64)]),
     "nic_conv_gather": (ctypes.c_int, [c_vp] + [ctypes.c_int] * 4 + [c_vp] + [ctypes.c_int] * 7 + [c_vp] * 4

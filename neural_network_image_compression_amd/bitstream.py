@@ -13,6 +13,11 @@ Beside it stands the native ``.nic`` container (``container="nic"``): a static p
 code of the latent, written and read on the device (``nic_rans_encode``/``nic_rans_decode``;
 format in DESIGN.md), so the host only moves and writes finished files.  PNG stays the default
 and the parity format.
+
+Reconstructions are written by Pillow's encoder by default (``png_writer="pillow"``); with
+``png_writer="device"`` the decoder side writes them with the device PNG writer
+(``nic_png_device_encode``; format in DESIGN.md): the same pixels, files of its own bytes, and
+the host again only moves and writes finished files.
 """
 from __future__ import annotations
 
@@ -185,6 +190,28 @@ def read_nic(codec, files: Sequence[bytes]) -> list:
     return out
 
 
+PNG_WRITERS = ("pillow", "device")
+
+
+def _check_png_writer(png_writer: str, decoder_side: bool) -> None:
+    if png_writer not in PNG_WRITERS:
+        raise ValueError(f"png_writer must be one of {PNG_WRITERS}, got {png_writer!r}")
+    if png_writer == "device" and not decoder_side:
+        raise ValueError('png_writer="device" applies to the decoder side only: the compressed PNG is the reference '
+                         "bitstream and stays Pillow's bytes")
+
+
+def png_files_device(codec, x, filter="adaptive") -> List[bytes]:
+    """The PNG file of every image of x (N,H,W,3) or (N,H,W,1), a u8 tensor on the codec's device:
+    filtered, coded and framed there (Codec.png_encode), then one copy of the files to the host."""
+    buf, sizes = codec.png_encode(x, filter)
+    if buf.shape[0] == 0:
+        return []
+    sizes = sizes.cpu().numpy()
+    host = buf[:, :int(sizes.max())].contiguous().cpu().numpy()
+    return [host[i, :sizes[i]].tobytes() for i in range(host.shape[0])]
+
+
 def _write_files(datas: Sequence[bytes], output_dir: str, filenames: Sequence[str], ext: str) -> List[str]:
     paths = []
     for data, name in zip(datas, filenames):
@@ -207,7 +234,7 @@ def _batches(shapes: Sequence[tuple], batch_size: int):
 
 
 def feed_batch(model, x: np.ndarray, filenames: Sequence[str], output_dir: str, in_cshape: int,
-               pool=None, png_threads: int = 16, container: str = "png") -> list:
+               pool=None, png_threads: int = 16, container: str = "png", png_writer: str = "pillow") -> list:
     """utils.py:30-44 for one batch: unpack (decoder side), run the codec, pack (encoder side), save.
 
     The batch's PNG files are encoded natively on ``png_threads`` host threads (nic_png_encode,
@@ -215,7 +242,10 @@ def feed_batch(model, x: np.ndarray, filenames: Sequence[str], output_dir: str, 
     it and its future returned, so the caller runs the next batch on the GPU meanwhile.
 
     container "nic" (encoder side): the latents are coded into .nic files on the device
-    (nic_files), copied to the host once, and the writer only writes them."""
+    (nic_files), copied to the host once, and the writer only writes them.
+
+    png_writer "device" (decoder side): the reconstructions are made into PNG files on the device
+    (png_files_device) and never reach the host as pixels; the writer only writes them."""
     import torch
 
     codec = model.codec
@@ -230,6 +260,12 @@ def feed_batch(model, x: np.ndarray, filenames: Sequence[str], output_dir: str, 
             _write_files(datas, output_dir, filenames, ".nic")
             return []
         return [pool.submit(_write_files, datas, output_dir, list(filenames), ".nic")]
+    if png_writer == "device" and out.shape[-1] == 3:
+        datas = png_files_device(codec, out)
+        if pool is None:
+            _write_files(datas, output_dir, filenames, ".png")
+            return []
+        return [pool.submit(_write_files, datas, output_dir, list(filenames), ".png")]
     if out.shape[-1] == 96:
         out = codec.pack(out)
     host = out.cpu().numpy()
@@ -269,7 +305,7 @@ BATCH_PIXELS = 64 * 512 * 768  # pixels staged per device batch (use_model): 64 
 
 
 def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, in_cshape: int,
-              batch_size: int = 64, workers=None, container: str = "png") -> None:
+              batch_size: int = 64, workers=None, container: str = "png", png_writer: str = "pillow") -> None:
     """utils.py:46-62: every colour image of ``dataset_path`` (sorted; read_dataset's filter)
     through the codec into ``output_dir``, one PNG per image named after its source.
 
@@ -285,12 +321,20 @@ def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, i
 
     ``container="nic"``: the encoder side writes ``<stem>.nic`` files coded on the device instead
     of packed PNGs; the decoder side reads the directory's ``.nic`` files (sorted) and writes the
-    same reconstruction PNGs (use_model_nic_in)."""
+    same reconstruction PNGs (use_model_nic_in).
+
+    ``png_writer="device"`` (decoder side only; ValueError on the encoder side, whose PNG is the
+    reference bitstream): the reconstructions are written by the device PNG writer instead of
+    Pillow's encoder -- the same pixels in files of other bytes."""
     if container not in CONTAINERS:
         raise ValueError(f"container must be one of {CONTAINERS}, got {container!r}")
+    _check_png_writer(png_writer, decoder_side=in_cshape == 96)
     if container == "nic" and in_cshape == 96:
-        return use_model_nic_in(model, dataset_path, checkpoint_path, output_dir, batch_size=batch_size, workers=workers)
+        return use_model_nic_in(model, dataset_path, checkpoint_path, output_dir, batch_size=batch_size, workers=workers,
+                                png_writer=png_writer)
     extra = {"container": container} if container != "png" else {}
+    if png_writer != "pillow":
+        extra["png_writer"] = png_writer
     os.makedirs(output_dir, exist_ok=True)
     model.load(checkpoint_path)
     if workers is not None and workers <= 0:
@@ -343,15 +387,18 @@ def _read_bytes(path: str) -> bytes:
 
 
 def use_model_nic_in(model, dataset_path: str, checkpoint_path: str, output_dir: str, batch_size: int = 64,
-                     workers=None) -> None:
+                     workers=None, png_writer: str = "pillow") -> None:
     """The decoder side of ``container="nic"``: every ``.nic`` file of ``dataset_path`` (sorted)
     -> ``<stem>.png`` reconstructions in ``output_dir``, the same files the PNG route writes.
     The files are read by a pool, checked on the host (nic_rans_inspect) and decoded on the device
     ``batch_size`` at a time (read_nic groups them by latent shape); the PNG encode + write of a
-    batch runs on the writer thread while the next batch is decoded (``workers=0``: inline)."""
+    batch runs on the writer thread while the next batch is decoded (``workers=0``: inline).
+    ``png_writer="device"``: the PNG files are made on the device (png_files_device) and the writer
+    thread only writes them."""
     import torch
     from concurrent.futures import ThreadPoolExecutor
 
+    _check_png_writer(png_writer, decoder_side=True)
     os.makedirs(output_dir, exist_ok=True)
     model.load(checkpoint_path)
     codec = model.codec
@@ -375,7 +422,17 @@ def use_model_nic_in(model, dataset_path: str, checkpoint_path: str, output_dir:
                 raise ValueError(f"{dataset_path}: files {ch[0]}..{ch[-1]}: {e}") from None
             names = [fn[:-4] for fn in ch]
             for i, j in _batches([tuple(z.shape) for z in latents], step):
-                rec = model._device_call(torch.stack(latents[i:j])).cpu().numpy()
+                rec = model._device_call(torch.stack(latents[i:j]))
+                if png_writer == "device":
+                    datas = png_files_device(codec, rec)
+                    while len(futures) >= WRITES_IN_FLIGHT:
+                        futures.pop(0).result()
+                    if serial:
+                        _write_files(datas, output_dir, names[i:j], ".png")
+                    else:
+                        futures.append(writer.submit(_write_files, datas, output_dir, names[i:j], ".png"))
+                    continue
+                rec = rec.cpu().numpy()
                 while len(futures) >= WRITES_IN_FLIGHT:
                     futures.pop(0).result()
                 if serial:

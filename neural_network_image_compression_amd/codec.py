@@ -349,6 +349,36 @@ class Codec:
                              f"corrupt images: {bad.tolist()})")
         return z
 
+    # -- device PNG writer (nic_png_device_*) -------------------------------------------------
+    def png_reserve(self, n: int, h: int, w: int, channels: int = 3) -> None:
+        """Grow the workspace so png_encode of n (h, w, channels) images allocates nothing."""
+        _lib.check(self._L.nic_png_device_reserve(self._h, n, h, w, channels), "nic_png_device_reserve")
+
+    def png_encode(self, x, filter="adaptive", stride: Optional[int] = None):
+        """(N,H,W,3), (N,H,W,1) or (N,H,W) u8 device images -> (buf (N, stride) u8, sizes (N,)
+        int64), device tensors: image i's complete PNG file is buf[i, :sizes[i]], written on the
+        device (nic_png_device_encode; no host synchronisation).  filter: "adaptive" (Pillow's
+        per-row choice) or 0..4 for one fixed PNG filter; stride: bytes between files, at least
+        nic_png_device_bound (the default)."""
+        torch = _torch()
+        if isinstance(x, torch.Tensor) and x.ndim == 3:
+            x = x.unsqueeze(-1)
+        if not isinstance(x, torch.Tensor) or x.ndim != 4 or x.shape[3] not in (1, 3):
+            raise ValueError("png_encode: expected an (N,H,W,3), (N,H,W,1) or (N,H,W) tensor")
+        x = self._check_dev(x, 4, int(x.shape[3]), "png_encode")
+        n, h, w, ch = x.shape
+        if filter != "adaptive" and filter not in (0, 1, 2, 3, 4):
+            raise ValueError(f"png_encode: filter must be 'adaptive' or 0..4, got {filter!r}")
+        f = _lib.PNG_FILTER_ADAPTIVE if filter == "adaptive" else int(filter)
+        bound = ctypes.c_int64()
+        _lib.check(self._L.nic_png_device_bound(h, w, ch, ctypes.byref(bound)), "nic_png_device_bound")
+        stride = bound.value if stride is None else int(stride)
+        buf = torch.empty((n, stride), dtype=torch.uint8, device=x.device)
+        sizes = torch.zeros((n,), dtype=torch.int64, device=x.device)
+        _lib.check(self._L.nic_png_device_encode(self._h, x.data_ptr(), n, h, w, ch, f, buf.data_ptr(), stride,
+                                                 sizes.data_ptr(), _stream_ptr(torch, self.device)), "nic_png_device_encode")
+        return buf, sizes
+
     def pack(self, z):
         """(N,h,w,96) -> (N,4h,8w,3) bitstream image (utils.py:39-40)."""
         torch = _torch()
@@ -452,11 +482,13 @@ class Decoder(ProClass):
         return self.codec.decode_host(a, self.host_chunks)
 
     def uncompress(self, dataset_path: str, checkpoint_path: str, batch_size: int = 64, workers=None,
-                   container: str = "png") -> None:
+                   container: str = "png", png_writer: str = "pillow") -> None:
         """decoder.py:50-52: packed PNGs in ``dataset_path`` -> ``dataset_path.replace('compressed','uncompressed')``.
         Pipelined as compress (``workers=0, batch_size=4``: the reference's serial loop).
-        ``container="nic"`` reads the directory's ``.nic`` files instead (same reconstructions)."""
+        ``container="nic"`` reads the directory's ``.nic`` files instead (same reconstructions).
+        ``png_writer="device"`` writes the reconstructions with the device PNG writer (the same
+        pixels in files of its own format) instead of Pillow's optimize=True bytes."""
         from .bitstream import use_model
 
         use_model(self, dataset_path, checkpoint_path, dataset_path.replace("compressed", "uncompressed"),
-                  in_cshape=96, batch_size=batch_size, workers=workers, container=container)
+                  in_cshape=96, batch_size=batch_size, workers=workers, container=container, png_writer=png_writer)

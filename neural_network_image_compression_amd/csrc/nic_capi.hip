@@ -457,7 +457,7 @@ bool models_ready(const nic_ctx* c, int m0) {
 
 extern "C" {
 
-int nic_version(void) { return 300; }
+int nic_version(void) { return 400; }
 
 int nic_constants(float* ycbcr9, float* ycbcr_inv9, float* off3) {
   // host copy of what nic_create uploads; lets tests compare with np.linalg.inv (utils.py:8)
@@ -1424,6 +1424,47 @@ int nic_rans_decode(nic_ctx* c, const uint8_t* files, int64_t stride, const int6
   rans_plan(n, h8, w8, 1, true, &pl);
   if ((rc = ensure_ws(c, pl.bytes))) return rc;
   HIP_TRY(launch_rans_decode(files, stride, (const long long*)sizes, n, h8, w8, c->ws, pl, latent, status, (hipStream_t)stream));
+  return NIC_OK;
+}
+
+// ---- device PNG writer (nic_png_dev.hip; nic_png_device_block_bytes and nic_png_device_bound are host-only there) ----
+static int png_dev_check(const char* fn, int n, int h, int w, int channels, int filter) {
+  if (channels != 1 && channels != 3) return fail(NIC_EINVAL, "%s: channels must be 1 or 3, got %d", fn, channels);
+  if (filter < NIC_PNG_FILTER_ADAPTIVE || filter > 4) return fail(NIC_EINVAL, "%s: filter %d not in -1..4", fn, filter);
+  if (n < 0 || h <= 0 || w <= 0) return fail(NIC_ESHAPE, "%s: bad image shape (%d,%d,%d,%d)", fn, n, h, w, channels);
+  if (!png_dev_shape_ok(h, w, channels))
+    return fail(NIC_ESHAPE, "%s: rows wider than 16384 bytes or images above 1 GB", fn);
+  if (n > 65535) return fail(NIC_ESHAPE, "%s: batch %d exceeds 65535 images per call", fn, n);
+  return NIC_OK;
+}
+
+int nic_png_device_reserve(nic_ctx* c, int n, int h, int w, int channels) {
+  int rc = png_dev_check("nic_png_device_reserve", n, h, w, channels, NIC_PNG_FILTER_ADAPTIVE);
+  if (rc || n == 0) return rc;
+  if (!c) return fail(NIC_EINVAL, "nic_png_device_reserve: NULL ctx");
+  DeviceGuard guard(c->device);
+  PngDevPlan pl;
+  png_dev_plan(n, h, w, channels, &pl);
+  return ensure_ws(c, pl.bytes);
+}
+
+int nic_png_device_encode(nic_ctx* c, const uint8_t* images, int n, int h, int w, int channels, int filter, uint8_t* out,
+                          int64_t stride, int64_t* sizes, void* stream) {
+  int rc = png_dev_check("nic_png_device_encode", n, h, w, channels, filter);
+  if (rc || n == 0) return rc;
+  int64_t bound = 0;
+  nic_png_device_bound(h, w, channels, &bound);
+  if (stride < bound)
+    return fail(NIC_ESHAPE, "nic_png_device_encode: stride %lld is below nic_png_device_bound = %lld", (long long)stride,
+                (long long)bound);
+  if (!c) return fail(NIC_EINVAL, "nic_png_device_encode: NULL ctx");
+  if (!images || !out || !sizes) return fail(NIC_EINVAL, "nic_png_device_encode: NULL buffer");
+  DeviceGuard guard(c->device);
+  PngDevPlan pl;
+  png_dev_plan(n, h, w, channels, &pl);
+  if ((rc = ensure_ws(c, pl.bytes))) return rc;
+  HIP_TRY(launch_png_dev_encode(images, n, h, w, channels, filter, c->ws, pl, out, stride, (long long*)sizes,
+                                (hipStream_t)stream));
   return NIC_OK;
 }
 

@@ -181,6 +181,20 @@ hipError_t launch_rans_encode(const uint8_t* z, int n, int h8, int w8, int seg_p
 hipError_t launch_rans_decode(const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8, char* ws,
                               const RansPlan& plan, uint8_t* z, int* status, hipStream_t st);
 
+// --- device PNG writer (nic_png_dev.hip) ------------------------------------------------------
+// Byte offsets of one call's scratch inside the ctx workspace (256-B aligned), from png_dev_plan:
+// the filtered streams (fstride bytes per image), and per deflate block its code table, header
+// bits and sizes / checksums.
+struct PngDevPlan {
+  int nblocks;       // deflate blocks per image
+  uint32_t total;    // filtered bytes per image: h * (w * channels + 1)
+  size_t fstride, filt, tab, hdr, meta, imeta, bytes;
+};
+bool png_dev_shape_ok(int h, int w, int channels);
+void png_dev_plan(int n, int h, int w, int channels, PngDevPlan* plan);
+hipError_t launch_png_dev_encode(const uint8_t* images, int n, int h, int w, int channels, int filter, char* ws,
+                                 const PngDevPlan& plan, uint8_t* out, long long stride, long long* sizes, hipStream_t st);
+
 // --- quality metrics (nic_quality.hip) ---------------------------------------------------
 constexpr int kSsimScales = 5;  // tf.image.ssim_multiscale power_factors
 

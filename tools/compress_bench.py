@@ -11,6 +11,10 @@ pipeline: the reference's packed PNG against the device-coded .nic (bitstream.py
 compress / uncompress, the mean file size of each, and whether both routes reconstruct the same
 PNGs.  `--weights trained` (default for this part) uses the committed coef-0.01 codec, whose
 latents are what the containers are meant for; `spread` the seeded dense ones.
+`--png-writer pillow device` loops the reconstruction writers of uncompress as well (Pillow's
+encoder on host threads against the device PNG writer): every (container, writer) pair in the same
+run, keyed "<container>+<writer>", with every repeat's uncompress time, the mean size of the
+reconstruction files and whether all pairs decode to the same pixels.
 
 Output: one JSON line.  Needs the GPU (the codec) and the built library."""
 import argparse
@@ -75,32 +79,49 @@ def run_modes(enc, dec, tmp, ds, ck, n, px, modes, repeat):
     return res, same
 
 
-def run_containers(enc, dec, tmp, ds, ck, n, px, containers, repeat):
-    """Best-of-`repeat` compress / uncompress wall time and mean file size per container."""
+def recon_pixels(path):
+    from PIL import Image
+
+    with Image.open(path) as im:
+        return np.array(im).tobytes()
+
+
+def run_containers(enc, dec, tmp, ds, ck, n, px, containers, repeat, writers=None):
+    """Best-of-`repeat` compress / uncompress wall time and mean file size per container (and per
+    reconstruction writer, when writers are named)."""
     res, recon = {}, {}
-    for cont in containers:
-        best = {}
+    for cont, writer in [(c, w) for c in containers for w in (writers or [None])]:
+        best, runs = {}, []
+        ukw = {"png_writer": writer} if writer else {}
         for r in range(repeat + 1):
             for d in ("_compressed", "_uncompressed"):
                 shutil.rmtree(ds + d, ignore_errors=True)
             t0 = time.perf_counter()
             enc.compress(ds, os.path.join(ck, "encoder"), container=cont)
             t1 = time.perf_counter()
-            dec.uncompress(ds + "_compressed", os.path.join(ck, "decoder"), container=cont)
+            dec.uncompress(ds + "_compressed", os.path.join(ck, "decoder"), container=cont, **ukw)
             t2 = time.perf_counter()
             if r:
                 best["compress_s"] = min(best.get("compress_s", 1e9), t1 - t0)
                 best["uncompress_s"] = min(best.get("uncompress_s", 1e9), t2 - t1)
+                runs.append(round(t2 - t1, 4))
         sizes = [os.path.getsize(os.path.join(ds + "_compressed", f)) for f in os.listdir(ds + "_compressed")]
-        res[cont] = {"compress_s": round(best["compress_s"], 4), "uncompress_s": round(best["uncompress_s"], 4),
+        key = f"{cont}+{writer}" if writer else cont
+        if writer:
+            rs = [os.path.getsize(os.path.join(ds + "_uncompressed", f)) for f in os.listdir(ds + "_uncompressed")]
+            res[key] = {"uncompress_s_runs": runs, "mean_recon_file_bytes": round(float(np.mean(rs)), 1)}
+            recon[key] = {f: recon_pixels(os.path.join(ds + "_uncompressed", f)) for f in sorted(os.listdir(ds + "_uncompressed"))}
+        else:
+            res[key] = {}
+            recon[key] = {f: open(os.path.join(ds + "_uncompressed", f), "rb").read()
+                          for f in sorted(os.listdir(ds + "_uncompressed"))}
+        res[key].update({"compress_s": round(best["compress_s"], 4), "uncompress_s": round(best["uncompress_s"], 4),
                      "compress_img_s": round(n / best["compress_s"], 1),
                      "uncompress_img_s": round(n / best["uncompress_s"], 1),
                      "compress_MP_s": round(n * px / 1e6 / best["compress_s"], 2),
                      "uncompress_MP_s": round(n * px / 1e6 / best["uncompress_s"], 2),
-                     "files": len(sizes), "mean_file_bytes": round(float(np.mean(sizes)), 1)}
-        recon[cont] = {f: open(os.path.join(ds + "_uncompressed", f), "rb").read()
-                       for f in sorted(os.listdir(ds + "_uncompressed"))}
-    same = all(recon[c] == recon[containers[0]] for c in recon)
+                     "files": len(sizes), "mean_file_bytes": round(float(np.mean(sizes)), 1)})
+    same = all(recon[c] == next(iter(recon.values())) for c in recon)
     return res, same
 
 
@@ -108,6 +129,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--container", nargs="+", choices=("png", "nic"), default=None,
                     help="compare these on-disk containers only (default: the driver modes, then both)")
+    ap.add_argument("--png-writer", nargs="+", choices=("pillow", "device"), default=None,
+                    help="also loop these reconstruction writers of uncompress (default: Pillow's only)")
     ap.add_argument("--weights", choices=("trained", "spread"), default="trained",
                     help="codec of the container comparison")
     ap.add_argument("--images", type=int, default=192)
@@ -135,7 +158,7 @@ def main():
         modes = [("serial_b4", {"batch_size": 4, "workers": 0}), ("r4_b4_w8", {"batch_size": 4, "workers": 8}),
                  ("pipeline_b64", {})]
         out = {"tool": "compress_bench", "host_cpus": len(os.sched_getaffinity(0))}
-        if args.container is None:
+        if args.container is None and args.png_writer is None:
             res, same = run_modes(enc, dec, tmp, ds, ck, args.images, 65536, modes, args.repeat)
             out["kodim21_tiles"] = {"images": args.images, "tile": "256x256x3 kodim21 tiles", "modes": res,
                                     "files_identical_across_modes": same}
@@ -146,10 +169,12 @@ def main():
             W.save(W.load(pre + "encoder", "encoder"), os.path.join(ckc, "encoder"), "encoder")
             W.save(W.load(pre + "decoder", "decoder"), os.path.join(ckc, "decoder"), "decoder")
         res, same = run_containers(enc, dec, tmp, ds, ckc, args.images, 65536, args.container or ["png", "nic"],
-                                   args.repeat)
+                                   args.repeat, writers=args.png_writer)
         out["containers"] = {"images": args.images, "tile": "256x256x3 kodim21 tiles", "weights": args.weights,
                              "driver": "pipeline_b64", "by_container": res, "reconstructions_identical": same}
-        if args.container is None and os.path.isdir(args.imagenet):
+        if args.png_writer:  # files differ between writers by design: the comparison is of decoded pixels
+            out["containers"]["compared"] = "decoded pixels"
+        if args.container is None and args.png_writer is None and os.path.isdir(args.imagenet):
             inet = os.path.join(tmp, "inet")
             shutil.copytree(args.imagenet, inet)
             n = len([f for f in os.listdir(inet) if f.endswith(".jpg")])
