@@ -57,7 +57,8 @@ enum {
   NIC_EHIP = -4,        /* HIP runtime error                               */
   NIC_ENOMEM = -5,      /* device allocation failed                        */
   NIC_ERANGE = -6,      /* NIC_RANGE_ERROR: a split-f16 activation left the f16 range */
-  NIC_ECORRUPT = -7     /* nic_rans_inspect: not a well-formed .nic file              */
+  NIC_ECORRUPT = -7,    /* nic_rans_inspect: not a well-formed .nic file              */
+  NIC_ENOPRIOR = -8     /* nic_rans2_encode / nic_rans2_decode before nic_rans_prior_set */
 };
 
 /* model_id values for nic_set_weights (checkpoint names encoder{Y,CbCr}, decoder{Y,CbCr},
@@ -262,6 +263,56 @@ int nic_rans_encode(nic_ctx* ctx, const uint8_t* latent, int n, int h8, int w8, 
 int nic_rans_decode(nic_ctx* ctx, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, int h8, int w8,
                     uint8_t* latent, int32_t* status, void* stream);
 int nic_rans_inspect(const uint8_t* host_file, int64_t size, int* h8, int* w8, int* seg_pixels);
+
+/* ---- The .nic container, version 2: a codec-level prior, so files need not carry tables ---------
+ * The prior is the entropy model shipped with the codec: 96 x 256 freqs (channel order of the
+ * latent), each in 1..4096, every channel summing to 4096, fitted once over a corpus.  Its id is
+ * the CRC-32 (IEEE) of the 49,152 bytes of the freqs as little-endian u16, channel-major.  Format
+ * ("The .nic container, version 2"):
+ *   header 40 B: "NICR", u8 version 2, u8 probability bits 12, u16 seg_pixels, u32 h8, u32 w8,
+ *     u32 H, u32 W (the image's own size: h8 = ceil(H/8), w8 = ceil(W/8)), u32 prior_id, 12-byte
+ *     channel mask (channel c is bit c & 7 of byte c >> 3)
+ *   a version-1 table for every channel whose mask bit is 1, in channel order; the others are
+ *     coded with the prior's row
+ *   the segment table and the segments, exactly as in version 1
+ * The encoder keeps a channel's own table iff it pays for itself: with cost16[f] =
+ * floor((12 - log2 f) 65536 + 0.5), own = sum c cost16[f_own] + (8 (1 + 3 n) << 16) < prior =
+ * sum c cost16[f_prior] (u64; a tie goes to the prior).
+ *
+ * nic_rans_cost_table: HOST only.  out[0] = 0, out[f] = cost16[f] for f in 1..4096.
+ * nic_rans_prior_check: HOST only.  Checks the invariants of 96 x 256 host freqs and returns the
+ *     id (nullable); NIC_ECORRUPT naming the channel otherwise.
+ * nic_rans_prior_set: checks, then uploads the freqs, their cumulative rows and the cost table.
+ *     Synchronous (waits for the device).  NULL freqs clears the prior.  id nullable.
+ * nic_rans_prior_count: adds the counts of latent (n,h8,w8,96) u8 (16-byte aligned) into the
+ *     caller's DEVICE uint64[96 * 256] accumulator (zeroed by the caller) with 64-bit integer
+ *     atomics: deterministic, accumulates across calls.  On `stream`, no host synchronisation.
+ * nic_rans_prior_build: accumulated counts -> DEVICE uint16[96 * 256] freqs: for a channel's
+ *     counts c[256] of total N, f = max(1, floor(c 4096 / N)) for every symbol; a deficit goes onto
+ *     the largest entry; a surplus is taken one at a time from the currently largest entry (lowest
+ *     symbol on ties); N = 0 gives sixteen everywhere.  N must stay below 2^52 per channel.
+ * nic_rans2_bound = nic_rans_bound + 24.  nic_rans2_reserve: as nic_rans_reserve.
+ * nic_rans2_encode: as nic_rans_encode; every image of the call is H x W.  NIC_ENOPRIOR before
+ *     nic_rans_prior_set.
+ * nic_rans2_decode: as nic_rans_decode; status bit 1: not a version-2 header of an (h8, w8) latent
+ *     with a consistent (H, W); bit 3 (value 8): the file's prior_id is not the ctx's (that
+ *     image's latent is left unwritten).  NIC_ENOPRIOR before nic_rans_prior_set.
+ * nic_rans2_inspect: HOST only: nic_rans_inspect's checks on a version-2 file (tables of the
+ *     masked channels only) plus the H / W relation; every output nullable.
+ * Arguments are validated before any HIP call: shape, empty batch (OK), NULL, then the prior. */
+int nic_rans_cost_table(uint32_t* out4097);
+int nic_rans_prior_check(const uint16_t* host_freqs, uint32_t* id);
+int nic_rans_prior_set(nic_ctx* ctx, const uint16_t* host_freqs, uint32_t* id);
+int nic_rans_prior_count(nic_ctx* ctx, const uint8_t* latent, int n, int h8, int w8, uint64_t* counts_dev, void* stream);
+int nic_rans_prior_build(nic_ctx* ctx, const uint64_t* counts_dev, uint16_t* freqs_dev, void* stream);
+int nic_rans2_bound(int h8, int w8, int seg_pixels, int64_t* bytes);
+int nic_rans2_reserve(nic_ctx* ctx, int n, int h8, int w8, int seg_pixels);
+int nic_rans2_encode(nic_ctx* ctx, const uint8_t* latent, int n, int h8, int w8, int H, int W, int seg_pixels,
+                     uint8_t* out, int64_t stride, int64_t* sizes, void* stream);
+int nic_rans2_decode(nic_ctx* ctx, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, int h8, int w8,
+                     uint8_t* latent, int32_t* status, void* stream);
+int nic_rans2_inspect(const uint8_t* host_file, int64_t size, int* h8, int* w8, int* seg_pixels, int* H, int* W,
+                      uint32_t* prior_id);
 
 /* ---- The device PNG writer: complete PNG files written on the device --------------------------
  * An optional writer for reconstructions (Pillow's optimize=True file, nic_png_encode, stays the

@@ -32,6 +32,7 @@ NIC_EHIP = -4
 NIC_ENOMEM = -5
 NIC_ERANGE = -6
 NIC_ECORRUPT = -7
+NIC_ENOPRIOR = -8
 
 RANGE_POLICIES = {"fallback": 0, "error": 1}  # nic.h NIC_RANGE_FALLBACK / NIC_RANGE_ERROR
 PNG_FILTER_ADAPTIVE = -1  # nic.h NIC_PNG_FILTER_ADAPTIVE
@@ -86,6 +87,18 @@ _SIGNATURES = {
     "nic_rans_encode": (ctypes.c_int, [c_vp, c_vp] + [ctypes.c_int] * 4 + [c_vp, ctypes.c_int64, c_vp, c_vp]),
     "nic_rans_decode": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp] + [ctypes.c_int] * 3 + [c_vp, c_vp, c_vp]),
     "nic_rans_inspect": (ctypes.c_int, [c_vp, ctypes.c_int64] + [ctypes.POINTER(ctypes.c_int)] * 3),
+    # .nic version 2: the codec-level prior (nic_rans.hip)
+    "nic_rans_cost_table": (ctypes.c_int, [c_vp]),
+    "nic_rans_prior_check": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_uint32)]),
+    "nic_rans_prior_set": (ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(ctypes.c_uint32)]),
+    "nic_rans_prior_count": (ctypes.c_int, [c_vp, c_vp] + [ctypes.c_int] * 3 + [c_vp, c_vp]),
+    "nic_rans_prior_build": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
+    "nic_rans2_bound": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int64)]),
+    "nic_rans2_reserve": (ctypes.c_int, [c_vp] + [ctypes.c_int] * 4),
+    "nic_rans2_encode": (ctypes.c_int, [c_vp, c_vp] + [ctypes.c_int] * 6 + [c_vp, ctypes.c_int64, c_vp, c_vp]),
+    "nic_rans2_decode": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp] + [ctypes.c_int] * 3 + [c_vp, c_vp, c_vp]),
+    "nic_rans2_inspect": (ctypes.c_int, [c_vp, ctypes.c_int64] + [ctypes.POINTER(ctypes.c_int)] * 5
+                          + [ctypes.POINTER(ctypes.c_uint32)]),
     # device PNG writer (nic_png_dev.hip)
     "nic_png_device_block_bytes": (ctypes.c_int, []),
     "nic_png_device_bound": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int64)]),

@@ -23,6 +23,7 @@ from __future__ import annotations
 
 import io
 import os
+import re
 from typing import List, Sequence, Tuple
 
 import numpy as np
@@ -150,10 +151,32 @@ def nic_inspect(data: bytes) -> Tuple[int, int, int]:
     return h8.value, w8.value, sp.value
 
 
-def nic_files(codec, z, seg_pixels: int = NIC_SEG_PIXELS) -> List[bytes]:
+def nic2_inspect(data: bytes) -> Tuple[int, int, int, int, int, int]:
+    """(h8, w8, seg_pixels, H, W, prior_id) of a well-formed version-2 .nic file; ValueError
+    (nic_rans2_inspect's text) otherwise.  Host only."""
+    import ctypes
+
+    from . import _lib
+
+    a = np.frombuffer(data, np.uint8)
+    v = [ctypes.c_int() for _ in range(5)]
+    pid = ctypes.c_uint32()
+    rc = _lib.lib().nic_rans2_inspect(a.ctypes.data_as(ctypes.c_void_p), len(data), *[ctypes.byref(t) for t in v],
+                                      ctypes.byref(pid))
+    if rc != _lib.NIC_OK:
+        raise ValueError(f"[{rc}] {_lib.last_error()}")
+    return tuple(t.value for t in v) + (int(pid.value),)
+
+
+def nic_files(codec, z, seg_pixels: int = NIC_SEG_PIXELS, size=None) -> List[bytes]:
     """The .nic file of every latent of z (N,h,w,96), a u8 tensor on the codec's device: coded
-    and assembled there (Codec.rans_encode), then one copy of the files to the host."""
-    buf, sizes = codec.rans_encode(z, seg_pixels)
+    and assembled there (Codec.rans_encode), then one copy of the files to the host.  With a
+    prior set on the codec the files are version 2 (Codec.rans2_encode) and record the images'
+    size=(H, W) (default 8h x 8w); without one they are version 1 and size is not stored."""
+    if codec.prior is not None:
+        buf, sizes = codec.rans2_encode(z, seg_pixels, size)
+    else:
+        buf, sizes = codec.rans_encode(z, seg_pixels)
     if buf.shape[0] == 0:
         return []
     sizes = sizes.cpu().numpy()
@@ -161,33 +184,59 @@ def nic_files(codec, z, seg_pixels: int = NIC_SEG_PIXELS) -> List[bytes]:
     return [host[i, :sizes[i]].tobytes() for i in range(host.shape[0])]
 
 
-def read_nic(codec, files: Sequence[bytes]) -> list:
+def _inspect_any(codec, i: int, data: bytes):
+    """The decode group and the image size of file i: byte 4 says which version's checks apply.
+    A version-2 file also needs the codec's prior to be the one it was written under."""
+    try:
+        if len(data) > 4 and data[4] == 2:
+            h8, w8, _, H, W, pid = nic2_inspect(data)
+            have = codec.prior
+            if have is None or have.id != pid:
+                raise ValueError(f"written under prior {pid:08x}, the codec's prior is "
+                                 + ("not set" if have is None else f"{have.id:08x}"))
+            return (2, h8, w8), (H, W)
+        h8, w8, sp = nic_inspect(data)
+        return (1, h8, w8, sp), (8 * h8, 8 * w8)
+    except ValueError as e:
+        raise ValueError(f"read_nic: file {i}: {e}") from None
+
+
+def read_nic_sizes(codec, files: Sequence[bytes]) -> List[Tuple[int, int]]:
+    """The image size (H, W) each .nic file stands for: a version-2 file's own, 8 h8 x 8 w8 for a
+    version-1 file (which does not record it).  The same host checks as read_nic."""
+    return [_inspect_any(codec, i, data)[1] for i, data in enumerate(files)]
+
+
+def read_nic(codec, files: Sequence[bytes], sizes: bool = False) -> list:
     """The latents of .nic files: a list of (h8,w8,96) u8 tensors on the codec's device, in the
-    files' order.  Every file is checked on the host first (nic_inspect: ValueError naming the
-    file's index); files of equal (h8, w8, seg_pixels) are decoded as one device batch."""
+    files' order.  Every file is checked on the host first (nic_inspect, or nic2_inspect for a
+    version-2 file: ValueError naming the file's index); version-1 files of equal (h8, w8,
+    seg_pixels) and version-2 files of equal (h8, w8) are decoded as one device batch each.
+    sizes=True: also the files' image sizes, (latents, [(H, W)])."""
     import torch
 
-    groups = {}
+    groups, hw = {}, []
     for i, data in enumerate(files):
-        try:
-            groups.setdefault(nic_inspect(data), []).append(i)
-        except ValueError as e:
-            raise ValueError(f"read_nic: file {i}: {e}") from None
+        key, size = _inspect_any(codec, i, data)
+        groups.setdefault(key, []).append(i)
+        hw.append(size)
     out = [None] * len(files)
-    for (h8, w8, _), idx in groups.items():
+    for key, idx in groups.items():
+        h8, w8 = key[1], key[2]
         stride = max(len(files[i]) for i in idx)
         host = np.zeros((len(idx), stride), np.uint8)
         for r, i in enumerate(idx):
             host[r, :len(files[i])] = np.frombuffer(files[i], np.uint8)
-        sizes = torch.tensor([len(files[i]) for i in idx], dtype=torch.int64)
+        lens = torch.tensor([len(files[i]) for i in idx], dtype=torch.int64)
         dev = f"cuda:{codec.device}"
         try:
-            z = codec.rans_decode(torch.from_numpy(host).to(dev), sizes.to(dev), h8, w8)
+            decode = codec.rans2_decode if key[0] == 2 else codec.rans_decode
+            z = decode(torch.from_numpy(host).to(dev), lens.to(dev), h8, w8)
         except ValueError as e:
             raise ValueError(f"read_nic: files {idx}: {e}") from None
         for r, i in enumerate(idx):
             out[i] = z[r]
-    return out
+    return (out, hw) if sizes else out
 
 
 PNG_WRITERS = ("pillow", "device")
@@ -255,7 +304,7 @@ def feed_batch(model, x: np.ndarray, filenames: Sequence[str], output_dir: str, 
         dev = codec.unpack(dev)
     out = model._device_call(dev)
     if container == "nic" and out.shape[-1] == 96:
-        datas = nic_files(codec, out)
+        datas = nic_files(codec, out, size=(h, w))  # version 2 (a prior is set) records the images' own size
         if pool is None:
             _write_files(datas, output_dir, filenames, ".nic")
             return []
@@ -305,7 +354,8 @@ BATCH_PIXELS = 64 * 512 * 768  # pixels staged per device batch (use_model): 64 
 
 
 def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, in_cshape: int,
-              batch_size: int = 64, workers=None, container: str = "png", png_writer: str = "pillow") -> None:
+              batch_size: int = 64, workers=None, container: str = "png", png_writer: str = "pillow",
+              prior=None) -> None:
     """utils.py:46-62: every colour image of ``dataset_path`` (sorted; read_dataset's filter)
     through the codec into ``output_dir``, one PNG per image named after its source.
 
@@ -325,10 +375,22 @@ def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, i
 
     ``png_writer="device"`` (decoder side only; ValueError on the encoder side, whose PNG is the
     reference bitstream): the reconstructions are written by the device PNG writer instead of
-    Pillow's encoder -- the same pixels in files of other bytes."""
+    Pillow's encoder -- the same pixels in files of other bytes.
+
+    ``prior`` (a prior.Prior or a ``.nicp`` path; ``container="nic"`` only, ValueError otherwise):
+    set on the model's codec for this and later calls.  The encoder side then writes version-2
+    files, which carry each image's true H x W; the decoder side reads directories that mix both
+    versions and crops the reconstructions of version-2 files to H x W.  Without it everything
+    behaves and writes as before."""
     if container not in CONTAINERS:
         raise ValueError(f"container must be one of {CONTAINERS}, got {container!r}")
     _check_png_writer(png_writer, decoder_side=in_cshape == 96)
+    if prior is not None:
+        if container != "nic":
+            raise ValueError('prior applies to container="nic" only: the PNG container has no entropy model')
+        from .prior import as_prior
+
+        model.codec.set_prior(as_prior(prior))
     if container == "nic" and in_cshape == 96:
         return use_model_nic_in(model, dataset_path, checkpoint_path, output_dir, batch_size=batch_size, workers=workers,
                                 png_writer=png_writer)
@@ -387,18 +449,24 @@ def _read_bytes(path: str) -> bytes:
 
 
 def use_model_nic_in(model, dataset_path: str, checkpoint_path: str, output_dir: str, batch_size: int = 64,
-                     workers=None, png_writer: str = "pillow") -> None:
+                     workers=None, png_writer: str = "pillow", prior=None) -> None:
     """The decoder side of ``container="nic"``: every ``.nic`` file of ``dataset_path`` (sorted)
     -> ``<stem>.png`` reconstructions in ``output_dir``, the same files the PNG route writes.
     The files are read by a pool, checked on the host (nic_rans_inspect) and decoded on the device
     ``batch_size`` at a time (read_nic groups them by latent shape); the PNG encode + write of a
     batch runs on the writer thread while the next batch is decoded (``workers=0``: inline).
     ``png_writer="device"``: the PNG files are made on the device (png_files_device) and the writer
-    thread only writes them."""
+    thread only writes them.  ``prior``: set on the model's codec first; version-2 files need the
+    prior they were written under (ValueError naming the file and both ids otherwise), and their
+    reconstructions are cropped on the device to the H x W they record, before either PNG writer."""
     import torch
     from concurrent.futures import ThreadPoolExecutor
 
     _check_png_writer(png_writer, decoder_side=True)
+    if prior is not None:
+        from .prior import as_prior
+
+        model.codec.set_prior(as_prior(prior))
     os.makedirs(output_dir, exist_ok=True)
     model.load(checkpoint_path)
     codec = model.codec
@@ -417,12 +485,16 @@ def use_model_nic_in(model, dataset_path: str, checkpoint_path: str, output_dir:
             if k + 2 < len(chunks):  # two chunks of reads in flight ahead of the device
                 pending.append(readers.map(_read_bytes, [os.path.join(dataset_path, fn) for fn in chunks[k + 2]]))
             try:
-                latents = read_nic(codec, datas)
+                latents, hw = read_nic(codec, datas, sizes=True)
             except ValueError as e:
-                raise ValueError(f"{dataset_path}: files {ch[0]}..{ch[-1]}: {e}") from None
+                m = re.match(r"read_nic: file (\d+): ", str(e))
+                which = ch[int(m.group(1))] if m else f"files {ch[0]}..{ch[-1]}"
+                raise ValueError(f"{dataset_path}: {which}: {e}") from None
             names = [fn[:-4] for fn in ch]
-            for i, j in _batches([tuple(z.shape) for z in latents], step):
+            for i, j in _batches([(tuple(z.shape), size) for z, size in zip(latents, hw)], step):
                 rec = model._device_call(torch.stack(latents[i:j]))
+                if hw[i] != tuple(rec.shape[1:3]):  # a version-2 file's own size: the top-left corner
+                    rec = rec[:, :hw[i][0], :hw[i][1]].contiguous()
                 if png_writer == "device":
                     datas = png_files_device(codec, rec)
                     while len(futures) >= WRITES_IN_FLIGHT:

@@ -349,6 +349,112 @@ class Codec:
                              f"corrupt images: {bad.tolist()})")
         return z
 
+    # -- .nic version 2: the codec-level prior (nic_rans_prior_*, nic_rans2_*) -----------------
+    #: the Prior set by set_prior (None: version-1 files only)
+    prior = None
+
+    def set_prior(self, prior) -> None:
+        """The prior (prior.Prior) of rans2_encode / rans2_decode, or None to clear it
+        (nic_rans_prior_set: synchronous)."""
+        if prior is None:
+            _lib.check(self._L.nic_rans_prior_set(self._h, None, None), "nic_rans_prior_set")
+            self.prior = None
+            return
+        pid = ctypes.c_uint32()
+        _lib.check(self._L.nic_rans_prior_set(self._h, prior.freqs.ctypes.data_as(ctypes.c_void_p), ctypes.byref(pid)),
+                   "nic_rans_prior_set")
+        assert pid.value == prior.id
+        self.prior = prior
+
+    def prior_count(self, z, counts) -> None:
+        """Adds the per-channel symbol counts of the latents z (N,h,w,96) into counts, a (96, 256)
+        int64 device tensor read as uint64 (nic_rans_prior_count; no host synchronisation)."""
+        torch = _torch()
+        z = self._check_dev(z, 4, 96, "prior_count")
+        if (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int64 or counts.shape != (96, 256)
+                or counts.device != z.device or not counts.is_contiguous()):
+            raise TypeError("prior_count: counts must be a contiguous (96, 256) torch.int64 tensor on the codec's device")
+        n, h8, w8, _ = z.shape
+        if z.data_ptr() % 16:
+            z = z.clone()
+        _lib.check(self._L.nic_rans_prior_count(self._h, z.data_ptr(), n, h8, w8, counts.data_ptr(),
+                                                _stream_ptr(torch, self.device)), "nic_rans_prior_count")
+
+    def prior_build(self, counts):
+        """(96, 256) int64 device counts -> (96, 256) freqs as an int32 device tensor
+        (nic_rans_prior_build; no host synchronisation)."""
+        torch = _torch()
+        if (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int64 or counts.shape != (96, 256)
+                or counts.device.type != "cuda" or counts.device.index != self.device):
+            raise TypeError("prior_build: counts must be a (96, 256) torch.int64 tensor on the codec's device")
+        counts = counts.contiguous()
+        freqs = torch.empty((96, 256), dtype=torch.int16, device=counts.device)  # u16 bits, all <= 4096
+        _lib.check(self._L.nic_rans_prior_build(self._h, counts.data_ptr(), freqs.data_ptr(),
+                                                _stream_ptr(torch, self.device)), "nic_rans_prior_build")
+        return freqs.to(torch.int32)
+
+    def rans2_reserve(self, n: int, h8: int, w8: int, seg_pixels: int = 32) -> None:
+        """Grow the workspace so rans2_encode / rans2_decode of (n, h8, w8) latents allocate nothing."""
+        _lib.check(self._L.nic_rans2_reserve(self._h, n, h8, w8, seg_pixels), "nic_rans2_reserve")
+
+    def rans2_encode(self, z, seg_pixels: int = 32, size=None):
+        """rans_encode with the codec's prior: version-2 files, which store a table only for the
+        channels where it pays and record the images' own size=(H, W) (default 8 h x 8 w).
+        NicError(NIC_ENOPRIOR) without a prior."""
+        torch = _torch()
+        z = self._check_dev(z, 4, 96, "rans2_encode")
+        n, h8, w8, _ = z.shape
+        H, W = (8 * h8, 8 * w8) if size is None else (int(size[0]), int(size[1]))
+        if z.data_ptr() % 16:  # a view at an odd offset: the kernels read 16-byte words
+            z = z.clone()
+        stride = ctypes.c_int64()
+        _lib.check(self._L.nic_rans2_bound(h8, w8, int(seg_pixels), ctypes.byref(stride)), "nic_rans2_bound")
+        buf = torch.empty((n, stride.value), dtype=torch.uint8, device=z.device)
+        sizes = torch.zeros((n,), dtype=torch.int64, device=z.device)
+        _lib.check(self._L.nic_rans2_encode(self._h, z.data_ptr(), n, h8, w8, H, W, int(seg_pixels), buf.data_ptr(),
+                                            stride.value, sizes.data_ptr(), _stream_ptr(torch, self.device)),
+                   "nic_rans2_encode")
+        return buf, sizes
+
+    def rans2_decode_status(self, buf, sizes, h8: int, w8: int, out=None):
+        """rans2_decode without the check: (latent, status (N,) int32 device tensor; nic.h).
+        out: the (N,h8,w8,96) u8 tensor to decode into (default: a new one)."""
+        torch = _torch()
+        if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.device.type != "cuda" or buf.ndim != 2:
+            raise TypeError("rans2_decode: expected an (N, stride) cuda torch.uint8 tensor of files")
+        if not isinstance(sizes, torch.Tensor) or sizes.dtype != torch.int64 or sizes.shape != (buf.shape[0],):
+            raise TypeError("rans2_decode: expected an (N,) torch.int64 tensor of sizes")
+        if buf.device.index != self.device or sizes.device != buf.device:
+            raise ValueError(f"rans2_decode: tensors must be on cuda:{self.device}")
+        buf, sizes = buf.contiguous(), sizes.contiguous()
+        n, stride = buf.shape
+        if out is None:
+            out = torch.empty((n, h8, w8, 96), dtype=torch.uint8, device=buf.device)
+        elif (out.dtype != torch.uint8 or tuple(out.shape) != (n, h8, w8, 96) or out.device != buf.device
+              or not out.is_contiguous()):
+            raise TypeError("rans2_decode: out must be a contiguous (N,h8,w8,96) torch.uint8 tensor on the codec's device")
+        status = torch.zeros((n,), dtype=torch.int32, device=buf.device)
+        _lib.check(self._L.nic_rans2_decode(self._h, buf.data_ptr(), stride, sizes.data_ptr(), n, int(h8), int(w8),
+                                            out.data_ptr(), status.data_ptr(), _stream_ptr(torch, self.device)),
+                   "nic_rans2_decode")
+        return out, status
+
+    def rans2_decode(self, buf, sizes, h8: int, w8: int):
+        """Version-2 .nic files buf[i, :sizes[i]] of (h8, w8) latents -> (N,h8,w8,96) u8.  Reads the
+        statuses back (synchronises) and raises ValueError naming the first image whose file did
+        not decode cleanly; a file written under another prior is reported with both ids."""
+        z, status = self.rans2_decode_status(buf, sizes, h8, w8)
+        st = status.cpu().numpy()
+        bad = np.nonzero(st)[0]
+        if bad.size:
+            i = int(bad[0])
+            if st[i] & 8:
+                pid = int.from_bytes(bytes(buf[i, 24:28].cpu().numpy().tolist()), "little")
+                raise ValueError(f"rans2_decode: image {i} was written under prior {pid:08x}, the codec's prior is "
+                                 f"{self.prior.id:08x} (status {int(st[i])}; refused images: {bad.tolist()})")
+            raise ValueError(f"rans2_decode: image {i} is corrupt (status {int(st[i])}; corrupt images: {bad.tolist()})")
+        return z
+
     # -- device PNG writer (nic_png_device_*) -------------------------------------------------
     def png_reserve(self, n: int, h: int, w: int, channels: int = 3) -> None:
         """Grow the workspace so png_encode of n (h, w, channels) images allocates nothing."""
@@ -456,16 +562,18 @@ class Encoder(ProClass):
         return self.codec.encode_host(a, self.host_chunks)
 
     def compress(self, dataset_path: str, checkpoint_path: str, batch_size: int = 64, workers=None,
-                 container: str = "png") -> None:
+                 container: str = "png", prior=None) -> None:
         """encoder.py:49-51: every image in ``dataset_path`` -> ``dataset_path + '_compressed'``.
         Pipelined over the host cores in batches of ``batch_size`` (bitstream.use_model);
         ``workers=0, batch_size=4`` is the reference's serial loop (same files).
         ``container="nic"`` writes ``<stem>.nic`` files, entropy-coded on the device, instead of
-        the reference's packed PNGs (the default)."""
+        the reference's packed PNGs (the default).  ``prior`` (a prior.Prior or a ``.nicp`` path;
+        ``container="nic"`` only): version-2 files, coded against the prior and carrying each
+        image's true H x W."""
         from .bitstream import use_model
 
         use_model(self, dataset_path, checkpoint_path, dataset_path + "_compressed", in_cshape=3,
-                  batch_size=batch_size, workers=workers, container=container)
+                  batch_size=batch_size, workers=workers, container=container, prior=prior)
 
 
 class Decoder(ProClass):
@@ -482,13 +590,17 @@ class Decoder(ProClass):
         return self.codec.decode_host(a, self.host_chunks)
 
     def uncompress(self, dataset_path: str, checkpoint_path: str, batch_size: int = 64, workers=None,
-                   container: str = "png", png_writer: str = "pillow") -> None:
+                   container: str = "png", png_writer: str = "pillow", prior=None) -> None:
         """decoder.py:50-52: packed PNGs in ``dataset_path`` -> ``dataset_path.replace('compressed','uncompressed')``.
         Pipelined as compress (``workers=0, batch_size=4``: the reference's serial loop).
         ``container="nic"`` reads the directory's ``.nic`` files instead (same reconstructions).
         ``png_writer="device"`` writes the reconstructions with the device PNG writer (the same
-        pixels in files of its own format) instead of Pillow's optimize=True bytes."""
+        pixels in files of its own format) instead of Pillow's optimize=True bytes.
+        ``prior`` (``container="nic"`` only): the prior the directory's version-2 files were written
+        under; their reconstructions are cropped to the recorded H x W.  Version-1 files are read
+        as before."""
         from .bitstream import use_model
 
         use_model(self, dataset_path, checkpoint_path, dataset_path.replace("compressed", "uncompressed"),
-                  in_cshape=96, batch_size=batch_size, workers=workers, container=container, png_writer=png_writer)
+                  in_cshape=96, batch_size=batch_size, workers=workers, container=container, png_writer=png_writer,
+                  prior=prior)

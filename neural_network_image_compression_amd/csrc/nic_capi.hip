@@ -294,6 +294,10 @@ struct nic_ctx {
   uint32_t* fold_part = nullptr;
   uint32_t* fold_acc = nullptr;
   size_t fold_acc_bytes = 0;
+  // the .nic version-2 prior (nic_rans_prior_set): freqs, cumulative rows and the cost table
+  char* prior = nullptr;
+  uint32_t prior_id = 0;
+  bool have_prior = false;
   char* qs = nullptr;  // MS-SSIM scratch (pooled scales + tile sums), grown on demand
   size_t qs_bytes = 0;
   // optional per-layer HIP-event timing (nic_set_timing): one event pair per layer and
@@ -457,7 +461,7 @@ bool models_ready(const nic_ctx* c, int m0) {
 
 extern "C" {
 
-int nic_version(void) { return 400; }
+int nic_version(void) { return 500; }
 
 int nic_constants(float* ycbcr9, float* ycbcr_inv9, float* off3) {
   // host copy of what nic_create uploads; lets tests compare with np.linalg.inv (utils.py:8)
@@ -554,6 +558,7 @@ int nic_destroy(nic_ctx* c) {
   if (c->counts) (void)hipFree(c->counts);
   if (c->fold_acc) (void)hipFree(c->fold_acc);
   if (c->qs) (void)hipFree(c->qs);
+  if (c->prior) (void)hipFree(c->prior);
   if (c->zero16) (void)hipFree(c->zero16);
   if (c->wproj) (void)hipFree(c->wproj);
   if (c->range) (void)hipFree(c->range);
@@ -1424,6 +1429,127 @@ int nic_rans_decode(nic_ctx* c, const uint8_t* files, int64_t stride, const int6
   rans_plan(n, h8, w8, 1, true, &pl);
   if ((rc = ensure_ws(c, pl.bytes))) return rc;
   HIP_TRY(launch_rans_decode(files, stride, (const long long*)sizes, n, h8, w8, c->ws, pl, latent, status, (hipStream_t)stream));
+  return NIC_OK;
+}
+
+// ---- .nic version 2: the codec-level prior (nic_rans.hip; nic_rans_cost_table, nic_rans_prior_check,
+// nic_rans2_bound and nic_rans2_inspect are host-only there) ----
+static RansPrior ctx_prior(const nic_ctx* c) {
+  size_t cum_at, cost_at;
+  rans_prior_bytes(&cum_at, &cost_at);
+  return {(const uint16_t*)c->prior, (const uint16_t*)(c->prior + cum_at), (const uint32_t*)(c->prior + cost_at), c->prior_id};
+}
+
+int nic_rans_prior_set(nic_ctx* c, const uint16_t* freqs, uint32_t* id) {
+  if (!c) return fail(NIC_EINVAL, "nic_rans_prior_set: NULL ctx");
+  if (!freqs) {  // back to no prior
+    c->have_prior = false;
+    return NIC_OK;
+  }
+  uint32_t pid = 0;
+  int rc = nic_rans_prior_check(freqs, &pid);
+  if (rc) return rc;
+  size_t cum_at, cost_at;
+  const size_t bytes = rans_prior_bytes(&cum_at, &cost_at);
+  std::vector<char> host(bytes);
+  std::memcpy(host.data(), freqs, cum_at);
+  uint16_t* cum = (uint16_t*)(host.data() + cum_at);
+  for (int ch = 0; ch < 96; ++ch) {
+    uint32_t run = 0;
+    for (int s = 0; s < 256; ++s) {
+      cum[ch * 257 + s] = (uint16_t)run;
+      run += freqs[ch * 256 + s];
+    }
+    cum[ch * 257 + 256] = (uint16_t)run;  // 4096
+  }
+  nic_rans_cost_table((uint32_t*)(host.data() + cost_at));
+  DeviceGuard guard(c->device);
+  c->have_prior = false;
+  if (!c->prior && hipMalloc(&c->prior, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    c->prior = nullptr;
+    return fail(NIC_ENOMEM, "nic_rans_prior_set: allocation of %zu bytes failed", bytes);
+  }
+  HIP_TRY(hipDeviceSynchronize());  // queued coding may still read the previous prior
+  HIP_TRY(hipMemcpy(c->prior, host.data(), bytes, hipMemcpyHostToDevice));
+  c->prior_id = pid;
+  c->have_prior = true;
+  if (id) *id = pid;
+  return NIC_OK;
+}
+
+int nic_rans_prior_count(nic_ctx* c, const uint8_t* latent, int n, int h8, int w8, uint64_t* counts, void* stream) {
+  int rc = rans_check("nic_rans_prior_count", n, h8, w8, 1);
+  if (rc || n == 0) return rc;
+  if (!c) return fail(NIC_EINVAL, "nic_rans_prior_count: NULL ctx");
+  if (!latent || !counts) return fail(NIC_EINVAL, "nic_rans_prior_count: NULL buffer");
+  if ((uintptr_t)latent % 16 || (uintptr_t)counts % 8)
+    return fail(NIC_EINVAL, "nic_rans_prior_count: latent must be 16-byte and counts 8-byte aligned");
+  DeviceGuard guard(c->device);
+  HIP_TRY(launch_rans_prior_count(latent, n, h8, w8, (unsigned long long*)counts, (hipStream_t)stream));
+  return NIC_OK;
+}
+
+int nic_rans_prior_build(nic_ctx* c, const uint64_t* counts, uint16_t* freqs, void* stream) {
+  if (!c) return fail(NIC_EINVAL, "nic_rans_prior_build: NULL ctx");
+  if (!counts || !freqs) return fail(NIC_EINVAL, "nic_rans_prior_build: NULL buffer");
+  if ((uintptr_t)counts % 8 || (uintptr_t)freqs % 2)
+    return fail(NIC_EINVAL, "nic_rans_prior_build: counts must be 8-byte and freqs 2-byte aligned");
+  DeviceGuard guard(c->device);
+  HIP_TRY(launch_rans_prior_build((const unsigned long long*)counts, freqs, (hipStream_t)stream));
+  return NIC_OK;
+}
+
+int nic_rans2_reserve(nic_ctx* c, int n, int h8, int w8, int seg_pixels) {
+  int rc = rans_check("nic_rans2_reserve", n, h8, w8, seg_pixels);
+  if (rc || n == 0) return rc;
+  if (!c) return fail(NIC_EINVAL, "nic_rans2_reserve: NULL ctx");
+  DeviceGuard guard(c->device);
+  RansPlan enc, dec;
+  rans_plan(n, h8, w8, seg_pixels, false, &enc, true);
+  rans_plan(n, h8, w8, seg_pixels, true, &dec, true);
+  return ensure_ws(c, std::max(enc.bytes, dec.bytes));
+}
+
+int nic_rans2_encode(nic_ctx* c, const uint8_t* latent, int n, int h8, int w8, int H, int W, int seg_pixels, uint8_t* out,
+                     int64_t stride, int64_t* sizes, void* stream) {
+  int rc = rans_check("nic_rans2_encode", n, h8, w8, seg_pixels);
+  if (rc) return rc;
+  if (H <= 0 || W <= 0 || (H + 7) / 8 != h8 || (W + 7) / 8 != w8)
+    return fail(NIC_ESHAPE, "nic_rans2_encode: a %dx%d image does not have a %dx%d latent", H, W, h8, w8);
+  if (n == 0) return NIC_OK;
+  if (!c) return fail(NIC_EINVAL, "nic_rans2_encode: NULL ctx");
+  if (!latent || !out || !sizes) return fail(NIC_EINVAL, "nic_rans2_encode: NULL buffer");
+  if ((uintptr_t)latent % 16) return fail(NIC_EINVAL, "nic_rans2_encode: latent must be 16-byte aligned");
+  int64_t bound = 0;
+  nic_rans2_bound(h8, w8, seg_pixels, &bound);
+  if (stride < bound)
+    return fail(NIC_ESHAPE, "nic_rans2_encode: stride %lld is below nic_rans2_bound = %lld", (long long)stride, (long long)bound);
+  if (!c->have_prior) return fail(NIC_ENOPRIOR, "nic_rans2_encode: no prior is set (nic_rans_prior_set)");
+  DeviceGuard guard(c->device);
+  RansPlan pl;
+  rans_plan(n, h8, w8, seg_pixels, false, &pl, true);
+  if ((rc = ensure_ws(c, pl.bytes))) return rc;
+  HIP_TRY(launch_rans2_encode(latent, n, h8, w8, H, W, seg_pixels, ctx_prior(c), c->ws, pl, out, stride, (long long*)sizes,
+                              (hipStream_t)stream));
+  return NIC_OK;
+}
+
+int nic_rans2_decode(nic_ctx* c, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, int h8, int w8,
+                     uint8_t* latent, int32_t* status, void* stream) {
+  int rc = rans_check("nic_rans2_decode", n, h8, w8, 1);
+  if (rc || n == 0) return rc;
+  if (!c) return fail(NIC_EINVAL, "nic_rans2_decode: NULL ctx");
+  if (!files || !sizes || !latent || !status) return fail(NIC_EINVAL, "nic_rans2_decode: NULL buffer");
+  if ((uintptr_t)latent % 16) return fail(NIC_EINVAL, "nic_rans2_decode: latent must be 16-byte aligned");
+  if (stride < 40) return fail(NIC_ESHAPE, "nic_rans2_decode: stride %lld is below the 40-byte header", (long long)stride);
+  if (!c->have_prior) return fail(NIC_ENOPRIOR, "nic_rans2_decode: no prior is set (nic_rans_prior_set)");
+  DeviceGuard guard(c->device);
+  RansPlan pl;
+  rans_plan(n, h8, w8, 1, true, &pl, true);
+  if ((rc = ensure_ws(c, pl.bytes))) return rc;
+  HIP_TRY(launch_rans2_decode(files, stride, (const long long*)sizes, n, h8, w8, ctx_prior(c), c->ws, pl, latent, status,
+                              (hipStream_t)stream));
   return NIC_OK;
 }
 

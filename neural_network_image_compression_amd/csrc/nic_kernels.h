@@ -172,14 +172,29 @@ hipError_t launch_pack(const uint8_t* src, uint8_t* dst, int nimg, int h8, int w
 struct RansPlan {
   int nseg;
   uint32_t cap;  // encode: bytes of one segment's worst-case region
-  size_t counts, cum, tab, tablen, taboff, seglen, segoff, meta, scratch, bytes;
+  size_t counts, cum, tab, tablen, taboff, keep, seglen, segoff, meta, scratch, bytes;
+};
+// The ctx's prior on the device (version 2): 96 x 256 freqs, their 96 x 257 cumulative rows and
+// the 4,097-entry cost table, in one allocation of rans_prior_bytes() bytes.
+struct RansPrior {
+  const uint16_t* freq;
+  const uint16_t* cum;
+  const uint32_t* cost16;
+  uint32_t id;
 };
 bool rans_shape_ok(int h8, int w8);
-void rans_plan(int n, int h8, int w8, int seg_pixels, bool decode, RansPlan* plan);
+void rans_plan(int n, int h8, int w8, int seg_pixels, bool decode, RansPlan* plan, bool v2 = false);  // v2: + keep[96] per image
 hipError_t launch_rans_encode(const uint8_t* z, int n, int h8, int w8, int seg_pixels, char* ws, const RansPlan& plan,
                               uint8_t* out, long long stride, long long* sizes, hipStream_t st);
 hipError_t launch_rans_decode(const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8, char* ws,
                               const RansPlan& plan, uint8_t* z, int* status, hipStream_t st);
+size_t rans_prior_bytes(size_t* cum_at, size_t* cost_at);
+hipError_t launch_rans_prior_count(const uint8_t* z, int n, int h8, int w8, unsigned long long* counts, hipStream_t st);
+hipError_t launch_rans_prior_build(const unsigned long long* counts, uint16_t* freqs, hipStream_t st);
+hipError_t launch_rans2_encode(const uint8_t* z, int n, int h8, int w8, int H, int W, int seg_pixels, const RansPrior& prior,
+                               char* ws, const RansPlan& plan, uint8_t* out, long long stride, long long* sizes, hipStream_t st);
+hipError_t launch_rans2_decode(const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8,
+                               const RansPrior& prior, char* ws, const RansPlan& plan, uint8_t* z, int* status, hipStream_t st);
 
 // --- device PNG writer (nic_png_dev.hip) ------------------------------------------------------
 // Byte offsets of one call's scratch inside the ctx workspace (256-B aligned), from png_dev_plan:

@@ -16,6 +16,9 @@
 
 #include <hip/hip_runtime.h>
 
+#include <zlib.h>
+
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 
@@ -34,6 +37,7 @@ constexpr int kCumRow = 257;             // start[0..256] of one channel
 constexpr int kCumWords = kCh * kCumRow; // u16 per image (49,344 B: the LDS table)
 constexpr int kTabRow = 772;             // >= 1 + 3 * 256 file bytes of one channel's table
 constexpr int kHeader = 16;
+constexpr int kHeader2 = 40;             // version 2: + u32 H, u32 W, u32 prior_id, 12-byte channel mask
 
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 #pragma unroll
@@ -90,13 +94,12 @@ __global__ __launch_bounds__(256) void rans_hist(const uint8_t* __restrict__ z, 
 //   a surplus (at most 255, from the floor-to-zero bumps) is taken one at a time from the
 //   currently largest entry (lowest symbol on ties), which never takes an entry below 1.
 // Writes the channel's cumulative row start[0..256], its file bytes and their count.
-__global__ __launch_bounds__(64) void rans_normalise(const uint32_t* __restrict__ counts, int npix, uint16_t* __restrict__ cum,
-                                                      uint8_t* __restrict__ tab, uint32_t* __restrict__ tablen) {
-  const int lane = threadIdx.x, c = blockIdx.x, img = blockIdx.y;
-  const size_t row = (size_t)img * kCh + c;
-  const uint4 cv = ((const uint4*)(counts + row * 256))[lane];
-  const uint32_t cnt[4] = {cv.x, cv.y, cv.z, cv.w};
-  uint32_t f[4], sum = 0, used = 0;
+// The steps are device functions of the whole wave, shared with the version-2 tables kernel.
+
+// lane l's four counts -> its four freqs (0 for an unused symbol) and how many it uses
+__device__ __forceinline__ void normalise_own(const uint32_t cnt[4], int npix, int lane, uint32_t f[4], uint32_t& used) {
+  uint32_t sum = 0;
+  used = 0;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     f[k] = 0;
@@ -135,15 +138,15 @@ __global__ __launch_bounds__(64) void rans_normalise(const uint32_t* __restrict_
         if (k == (s & 3)) f[k] -= 1u;
     }
   }
-  const uint32_t mine = f[0] + f[1] + f[2] + f[3];
-  uint32_t run = wave_excl(mine, lane);
+}
+
+// The channel's table as the file stores it (u8 n-1, n x (u8 symbol, u16 freq)) and its length.
+__device__ __forceinline__ void write_table(const uint32_t f[4], uint32_t used, int lane, uint8_t* __restrict__ trow,
+                                            uint32_t* __restrict__ tablen_row) {
   uint32_t idx = wave_excl(used, lane);
   const uint32_t nsym = wave_sum(used);
-  uint16_t* crow = cum + row * kCumRow;
-  uint8_t* trow = tab + row * kTabRow;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    crow[4 * lane + k] = (uint16_t)run;
+  for (int k = 0; k < 4; ++k)
     if (f[k]) {
       uint8_t* e = trow + 1 + 3 * idx;
       e[0] = (uint8_t)(4 * lane + k);
@@ -151,13 +154,33 @@ __global__ __launch_bounds__(64) void rans_normalise(const uint32_t* __restrict_
       e[2] = (uint8_t)(f[k] >> 8);
       ++idx;
     }
+  if (lane == 0) {
+    trow[0] = (uint8_t)(nsym - 1);
+    *tablen_row = 1 + 3 * nsym;
+  }
+}
+
+// The channel's cumulative row start[0..256] from the lanes' freqs.
+__device__ __forceinline__ void write_cum(const uint32_t f[4], int lane, uint16_t* __restrict__ crow) {
+  uint32_t run = wave_excl(f[0] + f[1] + f[2] + f[3], lane);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    crow[4 * lane + k] = (uint16_t)run;
     run += f[k];
   }
   if (lane == 63) crow[256] = (uint16_t)run;  // 4096
-  if (lane == 0) {
-    trow[0] = (uint8_t)(nsym - 1);
-    tablen[row] = 1 + 3 * nsym;
-  }
+}
+
+__global__ __launch_bounds__(64) void rans_normalise(const uint32_t* __restrict__ counts, int npix, uint16_t* __restrict__ cum,
+                                                      uint8_t* __restrict__ tab, uint32_t* __restrict__ tablen) {
+  const int lane = threadIdx.x, c = blockIdx.x, img = blockIdx.y;
+  const size_t row = (size_t)img * kCh + c;
+  const uint4 cv = ((const uint4*)(counts + row * 256))[lane];
+  const uint32_t cnt[4] = {cv.x, cv.y, cv.z, cv.w};
+  uint32_t f[4], used;
+  normalise_own(cnt, npix, lane, f, used);
+  write_cum(f, lane, cum + row * kCumRow);
+  write_table(f, used, lane, tab + row * kTabRow, tablen + row);
 }
 
 // the image's 96 cumulative rows into LDS (kCumWords u16 = 24,672 dwords)
@@ -256,6 +279,8 @@ __device__ void block_offsets(const uint32_t* __restrict__ len, int count, uint3
 }
 
 // ---- encode 4a: offsets and file sizes.  grid (n), block 256 --------------------------------
+// kVer: the container version, 1 or 2 (a 40-byte header; prior channels have tablen 0)
+template <int kVer>
 __global__ __launch_bounds__(256) void rans_layout(const uint32_t* __restrict__ tablen, uint32_t* __restrict__ taboff,
                                                     const uint32_t* __restrict__ seglen, uint32_t* __restrict__ segoff, int nseg,
                                                     long long* __restrict__ sizes) {
@@ -266,46 +291,58 @@ __global__ __launch_bounds__(256) void rans_layout(const uint32_t* __restrict__ 
   block_offsets(seglen + (size_t)img * nseg, nseg, segoff + (size_t)img * (nseg + 1), 0x7fffffffu, sh);
   __syncthreads();
   if (threadIdx.x == 0)
-    sizes[img] = (long long)kHeader + taboff[(size_t)img * (kCh + 1) + kCh] + 4ll * nseg +
+    sizes[img] = (long long)(kVer == 1 ? kHeader : kHeader2) + taboff[(size_t)img * (kCh + 1) + kCh] + 4ll * nseg +
                  segoff[(size_t)img * (nseg + 1) + nseg];
 }
 
 // ---- encode 4b: the files.  grid (ceil((96 + nseg) / 4), n), block 256: one wave per item ----
 // item c < 96: channel c's table (item 0 also the header); item 96 + k: segment k's length and bytes
+// Version 2 (kVer = 2): the header also holds (H, W), prior_id and the mask gathered from keep[96]
+// (1: the channel stores its own table); a prior channel's tablen is 0, so nothing is copied for it.
+template <int kVer>
 __global__ __launch_bounds__(256) void rans_assemble(const uint8_t* __restrict__ tab, const uint32_t* __restrict__ tablen,
                                                       const uint32_t* __restrict__ taboff, const uint8_t* __restrict__ scratch,
                                                       uint32_t cap, const uint32_t* __restrict__ seglen,
                                                       const uint32_t* __restrict__ segoff, int nseg, int seg_pixels, int h8, int w8,
-                                                      uint8_t* __restrict__ out, long long stride) {
+                                                      uint8_t* __restrict__ out, long long stride, uint32_t H, uint32_t W,
+                                                      uint32_t prior_id, const uint32_t* __restrict__ keep) {
+  constexpr int kHdr = kVer == 1 ? kHeader : kHeader2;
   const int lane = threadIdx.x & 63, item = blockIdx.x * 4 + (threadIdx.x >> 6), img = blockIdx.y;
   if (item >= kCh + nseg) return;
   uint8_t* file = out + (size_t)img * (size_t)stride;
   const uint32_t* toff = taboff + (size_t)img * (kCh + 1);
   if (item < kCh) {
-    if (item == 0 && lane < kHeader) {
-      const uint32_t hw[2] = {(uint32_t)h8, (uint32_t)w8};
+    if (item == 0 && lane < kHdr) {
+      const uint32_t hw[5] = {(uint32_t)h8, (uint32_t)w8, H, W, prior_id};
       uint8_t b;
       if (lane < 4) b = (uint8_t)("NICR"[lane]);
-      else if (lane == 4) b = 1;
+      else if (lane == 4) b = (uint8_t)kVer;
       else if (lane == 5) b = (uint8_t)kProbBits;
       else if (lane < 8) b = (uint8_t)(((uint32_t)seg_pixels >> (8 * (lane - 6))) & 255u);
-      else b = (uint8_t)((hw[(lane - 8) >> 2] >> (8 * (lane & 3))) & 255u);
+      else if (lane < 28) b = (uint8_t)((hw[(lane - 8) >> 2] >> (8 * (lane & 3))) & 255u);
+      else {  // version 2 only: channel c is bit c & 7 of mask byte c >> 3
+        const uint32_t* k8 = keep + (size_t)img * kCh + 8 * (lane - 28);
+        uint32_t m = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) m |= (k8[j] ? 1u : 0u) << j;
+        b = (uint8_t)m;
+      }
       file[lane] = b;
     }
     const size_t row = (size_t)img * kCh + item;
     const uint8_t* src = tab + row * kTabRow;
-    uint8_t* dst = file + kHeader + toff[item];
+    uint8_t* dst = file + kHdr + toff[item];
     for (uint32_t i = lane; i < tablen[row]; i += 64) dst[i] = src[i];  // < 16 + 96 * 769 <= stride
     return;
   }
   const int k = item - kCh;
   const uint32_t len = seglen[(size_t)img * nseg + k];
-  uint8_t* segtab = file + kHeader + toff[kCh];
+  uint8_t* segtab = file + kHdr + toff[kCh];
   if (lane < 4) segtab[4 * k + lane] = (uint8_t)((len >> (8 * lane)) & 255u);
   const uint8_t* src = scratch + ((size_t)img * nseg + k) * cap + (cap - len);
   // stride >= nic_rans_bound covers every payload (a file's symbols cost well under 12 bits on
   // average under its own tables); the clamp keeps even a miscounted one inside the image's slot
-  const size_t at = (size_t)kHeader + toff[kCh] + 4 * (size_t)nseg + segoff[(size_t)img * (nseg + 1) + k];
+  const size_t at = (size_t)kHdr + toff[kCh] + 4 * (size_t)nseg + segoff[(size_t)img * (nseg + 1) + k];
   for (uint32_t i = lane; i < len; i += 64)
     if (at + i < (size_t)stride) file[at + i] = src[i];
 }
@@ -452,6 +489,221 @@ __global__ __launch_bounds__(64) void rans_decode_segments(const uint8_t* __rest
   if (live && !(x == kRansL && ptr == end)) atomicOr(&status[img], 1);
 }
 
+// ==== version 2: a codec-level prior ("The .nic container, version 2") =============
+// The prior is 96 x 256 freqs in 1..4096, every channel summing to 4096, fitted once over a
+// corpus and shared by every file.  A version-2 file stores a table only for the channels whose
+// own table pays for itself; the others are coded with the prior's row.  The segment coder and
+// decoder above run unchanged on the per-image cumulative rows.
+
+__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint32_t lo = __shfl_xor((uint32_t)v, o, 64), hi = __shfl_xor((uint32_t)(v >> 32), o, 64);
+    v += ((unsigned long long)hi << 32) | lo;
+  }
+  return v;
+}
+
+// ---- prior 1: counts of a batch's latents into one accumulator ------------------------------
+// rans_hist's grid and LDS histograms; the flush adds into the caller's uint64[96][256] with
+// 64-bit integer atomics, so the totals do not depend on the order and accumulate across calls.
+__global__ __launch_bounds__(256) void rans_prior_count(const uint8_t* __restrict__ z, int npix,
+                                                         unsigned long long* __restrict__ counts) {
+  __shared__ uint32_t h[32 * 256];
+  const int tid = threadIdx.x, third = blockIdx.y, img = blockIdx.z;
+  for (int i = tid; i < 32 * 256; i += 256) h[i] = 0;
+  __syncthreads();
+  const int p = blockIdx.x * 256 + tid;
+  if (p < npix) {
+    const uint4* src = (const uint4*)(z + ((size_t)img * npix + p) * kCh + 32 * third);
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const uint4 v = src[q];
+      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int b = 0; b < 16; ++b) atomicAdd(&h[(16 * q + b) * 256 + ((w[b >> 2] >> (8 * (b & 3))) & 255u)], 1u);
+    }
+  }
+  __syncthreads();
+  unsigned long long* dst = counts + (size_t)(32 * third) * 256;
+  for (int i = tid; i < 32 * 256; i += 256)
+    if (h[i]) atomicAdd(&dst[i], (unsigned long long)h[i]);
+}
+
+// ---- prior 2: counts -> freqs.  grid (96), block 64: one wave per channel ---------------------
+// Version 1's rule with all 256 symbols "used": f = max(1, floor(c 4096 / N)); a deficit goes onto
+// the largest entry; a surplus (at most 255) is taken one at a time from the currently largest
+// entry (lowest symbol on ties).  N = 0: sixteen everywhere.  c 4096 must fit 64 bits: N < 2^52.
+__global__ __launch_bounds__(64) void rans_prior_normalise(const unsigned long long* __restrict__ counts,
+                                                            uint16_t* __restrict__ freqs) {
+  const int lane = threadIdx.x, c = blockIdx.x;
+  unsigned long long cnt[4], mine = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    cnt[k] = counts[(size_t)c * 256 + 4 * lane + k];
+    mine += cnt[k];
+  }
+  const unsigned long long N = wave_sum64(mine);
+  uint32_t f[4], sum = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const uint32_t q = N ? (uint32_t)((cnt[k] << kProbBits) / N) : 16u;
+    f[k] = q ? q : 1u;
+    sum += f[k];
+  }
+  sum = wave_sum(sum);
+  int diff = (int)kProbScale - (int)sum;
+  auto best = [&]() {  // (f << 8) | (255 - s): the largest f, the lowest symbol on ties
+    uint32_t key = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint32_t kk = (f[k] << 8) | (uint32_t)(255 - (4 * lane + k));
+      key = kk > key ? kk : key;
+    }
+    return wave_max(key);
+  };
+  if (diff > 0) {
+    const int s = 255 - (int)(best() & 255u);
+    if ((s >> 2) == lane) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k == (s & 3)) f[k] += (uint32_t)diff;
+    }
+  }
+  for (; diff < 0; ++diff) {  // wave-uniform trip count, at most 255; the largest entry stays >= 16
+    const int s = 255 - (int)(best() & 255u);
+    if ((s >> 2) == lane) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k == (s & 3)) f[k] -= 1u;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) freqs[(size_t)c * 256 + 4 * lane + k] = (uint16_t)f[k];
+}
+
+// ---- version-2 encode 2: tables and the per-channel choice.  grid (96, n), block 64 ------------
+// Version 1's normalisation of the image's counts, then with cost16[f] = round((12 - log2 f) 2^16):
+//   own = sum c cost16[f_own] + (8 (1 + 3 n) << 16),  prior = sum c cost16[f_prior]   (u64)
+// The channel keeps its own table iff own < prior.  Writes the channel's cumulative row (its own
+// or the prior's), the table's file bytes and their length (0 for a prior channel) and keep[].
+__global__ __launch_bounds__(64) void rans2_tables(const uint32_t* __restrict__ counts, int npix,
+                                                    const uint16_t* __restrict__ prior_freq,
+                                                    const uint16_t* __restrict__ prior_cum, const uint32_t* __restrict__ cost16,
+                                                    uint16_t* __restrict__ cum, uint8_t* __restrict__ tab,
+                                                    uint32_t* __restrict__ tablen, uint32_t* __restrict__ keep) {
+  const int lane = threadIdx.x, c = blockIdx.x, img = blockIdx.y;
+  const size_t row = (size_t)img * kCh + c;
+  const uint4 cv = ((const uint4*)(counts + row * 256))[lane];
+  const uint32_t cnt[4] = {cv.x, cv.y, cv.z, cv.w};
+  uint32_t f[4], used;
+  normalise_own(cnt, npix, lane, f, used);
+  const uint2 pv = ((const uint2*)(prior_freq + (size_t)c * 256))[lane];  // four u16 freqs, each in 1..4096 (checked on upload)
+  const uint32_t pf[4] = {pv.x & 0xffffu, pv.x >> 16, pv.y & 0xffffu, pv.y >> 16};
+  unsigned long long own = 0, pri = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    own += (unsigned long long)cnt[k] * cost16[f[k]];  // f <= 4096; cost16[0] = 0 (and c = 0 there)
+    pri += (unsigned long long)cnt[k] * cost16[min(pf[k], kProbScale)];
+  }
+  const uint32_t nsym = wave_sum(used);
+  own = wave_sum64(own) + ((unsigned long long)(8u * (1u + 3u * nsym)) << 16);
+  pri = wave_sum64(pri);
+  uint16_t* crow = cum + row * kCumRow;
+  if (own < pri) {  // wave-uniform
+    write_cum(f, lane, crow);
+    write_table(f, used, lane, tab + row * kTabRow, tablen + row);
+    if (lane == 0) keep[row] = 1u;
+  } else {
+    const uint16_t* prow = prior_cum + (size_t)c * kCumRow;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) crow[4 * lane + k] = prow[4 * lane + k];
+    if (lane == 63) crow[256] = prow[256];
+    if (lane == 0) {
+      tablen[row] = 0u;
+      keep[row] = 0u;
+    }
+  }
+}
+
+// ---- version-2 decode 1: parse.  grid (n), block 256 ------------------------------------------
+// As rans_parse, with the 40-byte header: the file must describe an (h8, w8) latent of an H x W
+// image (h8 = ceil(H / 8), w8 = ceil(W / 8)), else status 2; its prior_id must be the ctx's, else
+// status 8; either way nseg = 0 and nothing of that image is decoded.  Tables are walked for the
+// masked channels only; the other rows are copies of the prior's cumulative rows.
+__global__ __launch_bounds__(256) void rans2_parse(const uint8_t* __restrict__ files, long long stride,
+                                                    const long long* __restrict__ sizes, int h8, int w8,
+                                                    const uint16_t* __restrict__ prior_cum, uint32_t prior_id,
+                                                    uint16_t* __restrict__ cum, uint32_t* __restrict__ seglen,
+                                                    uint32_t* __restrict__ segoff, int maxseg, uint32_t* __restrict__ meta,
+                                                    int* __restrict__ status) {
+  __shared__ uint32_t sh[257];
+  __shared__ uint32_t choff[kCh + 1];
+  __shared__ uint32_t own[kCh];
+  __shared__ int s_bad, s_nseg;
+  const int tid = threadIdx.x, img = blockIdx.x;
+  const uint8_t* f = files + (size_t)img * (size_t)stride;
+  long long sz = sizes[img];
+  sz = sz < 0 ? 0 : (sz > stride ? stride : sz);
+  sz = sz > 0x7fffffffll ? 0x7fffffffll : sz;
+  const uint32_t size = (uint32_t)sz;
+  auto rd = [&](uint32_t i) -> uint32_t { return i < size ? (uint32_t)f[i] : 0u; };
+  auto rd32 = [&](uint32_t i) -> uint32_t { return rd(i) | (rd(i + 1) << 8) | (rd(i + 2) << 16) | (rd(i + 3) << 24); };
+  const int npix = h8 * w8;
+  if (tid == 0) {
+    const uint32_t S = rd(6) | (rd(7) << 8);
+    const uint32_t fh = rd32(8), fw = rd32(12), H = rd32(16), W = rd32(20), pid = rd32(24);
+    const bool ok = size >= (uint32_t)kHeader2 && rd(0) == 'N' && rd(1) == 'I' && rd(2) == 'C' && rd(3) == 'R' && rd(4) == 2 &&
+                    rd(5) == (uint32_t)kProbBits && S >= 1 && fh == (uint32_t)h8 && fw == (uint32_t)w8 &&
+                    (H >> 3) + ((H & 7u) != 0u) == fh && (W >> 3) + ((W & 7u) != 0u) == fw;
+    const bool mine = pid == prior_id;
+    const int nseg = ok && mine ? (int)(((uint32_t)npix + S - 1) / S) : 0;  // <= npix = maxseg
+    uint32_t off = kHeader2;
+    for (int c = 0; c < kCh; ++c) {
+      choff[c] = off;
+      own[c] = (rd(28 + (c >> 3)) >> (c & 7)) & 1u;
+      if (own[c]) off += 1 + 3 * (rd(off) + 1);  // <= 40 + 96 * 769
+    }
+    choff[kCh] = off;
+    s_nseg = nseg;
+    s_bad = !ok ? 2 : (mine ? 0 : 8);
+    meta[4 * img + 0] = (uint32_t)nseg;
+    meta[4 * img + 1] = ok ? S : 1u;
+    meta[4 * img + 2] = min(off + 4u * (uint32_t)nseg, size);
+    meta[4 * img + 3] = size;
+  }
+  __syncthreads();
+  const int nseg = s_nseg;
+  uint16_t* rows = cum + (size_t)img * kCumWords;
+  if (nseg > 0 && tid < kCh && own[tid]) {
+    uint16_t* row = rows + tid * kCumRow;
+    const uint32_t base = choff[tid], nsym = rd(base) + 1;
+    uint32_t e = 0, run = 0, es = rd(base + 1), ef = rd(base + 2) | (rd(base + 3) << 8);
+    for (uint32_t s = 0; s < 256; ++s) {
+      row[s] = (uint16_t)run;
+      if (e < nsym && es == s) {
+        run = min(run + ef, kProbScale);
+        ++e;
+        es = rd(base + 1 + 3 * e);
+        ef = rd(base + 2 + 3 * e) | (rd(base + 3 + 3 * e) << 8);
+      }
+    }
+    row[256] = (uint16_t)kProbScale;
+    if (e != nsym || run != kProbScale) atomicOr(&s_bad, 4);
+  }
+  if (nseg > 0)  // the prior's rows (start[0] = 0, non-decreasing, start[256] = 4096 by construction)
+    for (int i = tid; i < kCumWords; i += 256)
+      if (!own[i / kCumRow]) rows[i] = prior_cum[i];
+  // the segment table -> clamped lengths -> offsets
+  const uint32_t segtab = choff[kCh];
+  uint32_t* len = seglen + (size_t)img * maxseg;
+  for (int k = tid; k < nseg; k += 256) len[k] = rd32(segtab + 4u * (uint32_t)k);  // < 2^31 + 2^27: no wrap
+  __syncthreads();
+  block_offsets(len, nseg, segoff + (size_t)img * (maxseg + 1), size, sh);
+  __syncthreads();
+  if (tid == 0) status[img] = s_bad;
+}
+
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
@@ -461,7 +713,7 @@ bool rans_shape_ok(int h8, int w8) {
   return h8 > 0 && w8 > 0 && (long long)h8 * w8 <= (1ll << 23);
 }
 
-void rans_plan(int n, int h8, int w8, int seg_pixels, bool decode, RansPlan* pl) {
+void rans_plan(int n, int h8, int w8, int seg_pixels, bool decode, RansPlan* pl, bool v2) {
   const size_t npix = (size_t)h8 * w8, N = (size_t)n;
   const int S = decode ? 1 : seg_pixels;  // decode sizes its offsets for the smallest segments
   pl->nseg = (int)((npix + S - 1) / S);
@@ -479,6 +731,7 @@ void rans_plan(int n, int h8, int w8, int seg_pixels, bool decode, RansPlan* pl)
   pl->tab = take(decode ? 0 : N * kCh * kTabRow);
   pl->tablen = take(decode ? 0 : N * kCh * 4);
   pl->taboff = take(decode ? 0 : N * (kCh + 1) * 4);
+  pl->keep = take(decode || !v2 ? 0 : N * kCh * 4);
   pl->seglen = take(N * pl->nseg * 4);
   pl->segoff = take(N * ((size_t)pl->nseg + 1) * 4);
   pl->meta = take(decode ? N * 16 : 0);
@@ -502,9 +755,9 @@ hipError_t launch_rans_encode(const uint8_t* z, int n, int h8, int w8, int seg_p
   rans_hist<<<dim3((npix + 255) / 256, 3, n), 256, 0, st>>>(z, npix, counts);
   rans_normalise<<<dim3(kCh, n), 64, 0, st>>>(counts, npix, cum, tab, tablen);
   rans_encode_segments<<<dim3((nseg + 63) / 64, n), 64, 0, st>>>(z, npix, seg_pixels, nseg, cum, scratch, pl.cap, seglen);
-  rans_layout<<<dim3(n), 256, 0, st>>>(tablen, taboff, seglen, segoff, nseg, sizes);
-  rans_assemble<<<dim3((kCh + nseg + 3) / 4, n), 256, 0, st>>>(tab, tablen, taboff, scratch, pl.cap, seglen, segoff, nseg,
-                                                              seg_pixels, h8, w8, out, stride);
+  rans_layout<1><<<dim3(n), 256, 0, st>>>(tablen, taboff, seglen, segoff, nseg, sizes);
+  rans_assemble<1><<<dim3((kCh + nseg + 3) / 4, n), 256, 0, st>>>(tab, tablen, taboff, scratch, pl.cap, seglen, segoff, nseg,
+                                                                 seg_pixels, h8, w8, out, stride, 0u, 0u, 0u, nullptr);
   return hipGetLastError();
 }
 
@@ -516,6 +769,59 @@ hipError_t launch_rans_decode(const uint8_t* files, long long stride, const long
   uint32_t* segoff = (uint32_t*)(ws + pl.segoff);
   uint32_t* meta = (uint32_t*)(ws + pl.meta);
   rans_parse<<<dim3(n), 256, 0, st>>>(files, stride, sizes, h8, w8, cum, seglen, segoff, maxseg, meta, status);
+  rans_decode_segments<<<dim3((maxseg + 63) / 64, n), 64, 0, st>>>(files, stride, npix, cum, segoff, maxseg, meta, z, status);
+  return hipGetLastError();
+}
+
+hipError_t launch_rans_prior_count(const uint8_t* z, int n, int h8, int w8, unsigned long long* counts, hipStream_t st) {
+  const int npix = h8 * w8;
+  rans_prior_count<<<dim3((npix + 255) / 256, 3, n), 256, 0, st>>>(z, npix, counts);
+  return hipGetLastError();
+}
+
+hipError_t launch_rans_prior_build(const unsigned long long* counts, uint16_t* freqs, hipStream_t st) {
+  rans_prior_normalise<<<dim3(kCh), 64, 0, st>>>(counts, freqs);
+  return hipGetLastError();
+}
+
+size_t rans_prior_bytes(size_t* cum_at, size_t* cost_at) {
+  *cum_at = (size_t)kCh * 256 * 2;
+  *cost_at = *cum_at + (size_t)kCumWords * 2;  // a multiple of 4
+  return *cost_at + (kProbScale + 1) * 4;
+}
+
+hipError_t launch_rans2_encode(const uint8_t* z, int n, int h8, int w8, int H, int W, int seg_pixels, const RansPrior& pr,
+                               char* ws, const RansPlan& pl, uint8_t* out, long long stride, long long* sizes, hipStream_t st) {
+  const int npix = h8 * w8, nseg = pl.nseg;
+  uint32_t* counts = (uint32_t*)(ws + pl.counts);
+  uint16_t* cum = (uint16_t*)(ws + pl.cum);
+  uint8_t* tab = (uint8_t*)(ws + pl.tab);
+  uint32_t* tablen = (uint32_t*)(ws + pl.tablen);
+  uint32_t* taboff = (uint32_t*)(ws + pl.taboff);
+  uint32_t* keep = (uint32_t*)(ws + pl.keep);
+  uint32_t* seglen = (uint32_t*)(ws + pl.seglen);
+  uint32_t* segoff = (uint32_t*)(ws + pl.segoff);
+  uint8_t* scratch = (uint8_t*)(ws + pl.scratch);
+  hipError_t e = hipMemsetAsync(counts, 0, (size_t)n * kCh * 256 * 4, st);
+  if (e != hipSuccess) return e;
+  rans_hist<<<dim3((npix + 255) / 256, 3, n), 256, 0, st>>>(z, npix, counts);
+  rans2_tables<<<dim3(kCh, n), 64, 0, st>>>(counts, npix, pr.freq, pr.cum, pr.cost16, cum, tab, tablen, keep);
+  rans_encode_segments<<<dim3((nseg + 63) / 64, n), 64, 0, st>>>(z, npix, seg_pixels, nseg, cum, scratch, pl.cap, seglen);
+  rans_layout<2><<<dim3(n), 256, 0, st>>>(tablen, taboff, seglen, segoff, nseg, sizes);
+  rans_assemble<2><<<dim3((kCh + nseg + 3) / 4, n), 256, 0, st>>>(tab, tablen, taboff, scratch, pl.cap, seglen, segoff, nseg,
+                                                                 seg_pixels, h8, w8, out, stride, (uint32_t)H, (uint32_t)W,
+                                                                 pr.id, keep);
+  return hipGetLastError();
+}
+
+hipError_t launch_rans2_decode(const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8,
+                               const RansPrior& pr, char* ws, const RansPlan& pl, uint8_t* z, int* status, hipStream_t st) {
+  const int npix = h8 * w8, maxseg = pl.nseg;
+  uint16_t* cum = (uint16_t*)(ws + pl.cum);
+  uint32_t* seglen = (uint32_t*)(ws + pl.seglen);
+  uint32_t* segoff = (uint32_t*)(ws + pl.segoff);
+  uint32_t* meta = (uint32_t*)(ws + pl.meta);
+  rans2_parse<<<dim3(n), 256, 0, st>>>(files, stride, sizes, h8, w8, pr.cum, pr.id, cum, seglen, segoff, maxseg, meta, status);
   rans_decode_segments<<<dim3((maxseg + 63) / 64, n), 64, 0, st>>>(files, stride, npix, cum, segoff, maxseg, meta, z, status);
   return hipGetLastError();
 }
@@ -579,6 +885,106 @@ int nic_rans_inspect(const uint8_t* f, int64_t size, int* h8, int* w8, int* seg_
   if (h8) *h8 = (int)fh;
   if (w8) *w8 = (int)fw;
   if (seg_pixels) *seg_pixels = (int)S;
+  return NIC_OK;
+}
+
+int nic_rans_cost_table(uint32_t* out4097) {
+  if (!out4097) return nic::set_error(NIC_EINVAL, "nic_rans_cost_table: out is NULL");
+  out4097[0] = 0;
+  for (uint32_t f = 1; f <= nic::kProbScale; ++f)
+    out4097[f] = (uint32_t)std::floor((12.0 - std::log2((double)f)) * 65536.0 + 0.5);
+  return NIC_OK;
+}
+
+int nic_rans_prior_check(const uint16_t* freqs, uint32_t* id) {
+  char msg[160];
+  if (!freqs) return nic::set_error(NIC_EINVAL, "nic_rans_prior_check: freqs is NULL");
+  for (int c = 0; c < nic::kCh; ++c) {
+    uint32_t sum = 0;
+    for (int s = 0; s < 256; ++s) {
+      const uint32_t fr = freqs[c * 256 + s];
+      if (fr < 1 || fr > nic::kProbScale) {
+        snprintf(msg, sizeof(msg), "nic_rans_prior_check: channel %d: freq %u of symbol %d not in 1..4096", c, fr, s);
+        return nic::set_error(NIC_ECORRUPT, msg);
+      }
+      sum += fr;
+    }
+    if (sum != nic::kProbScale) {
+      snprintf(msg, sizeof(msg), "nic_rans_prior_check: channel %d: freqs sum to %u, not 4096", c, sum);
+      return nic::set_error(NIC_ECORRUPT, msg);
+    }
+  }
+  if (id) {  // CRC-32 of the freqs as little-endian u16, channel-major
+    uint8_t le[512];
+    uLong crc = crc32(0L, Z_NULL, 0);
+    for (int c = 0; c < nic::kCh; ++c) {
+      for (int s = 0; s < 256; ++s) {
+        le[2 * s] = (uint8_t)(freqs[c * 256 + s] & 255u);
+        le[2 * s + 1] = (uint8_t)(freqs[c * 256 + s] >> 8);
+      }
+      crc = crc32(crc, le, sizeof(le));
+    }
+    *id = (uint32_t)crc;
+  }
+  return NIC_OK;
+}
+
+int nic_rans2_bound(int h8, int w8, int seg_pixels, int64_t* bytes) {
+  const int rc = nic_rans_bound(h8, w8, seg_pixels, bytes);
+  if (rc == NIC_OK) *bytes += nic::kHeader2 - nic::kHeader;
+  return rc;
+}
+
+int nic_rans2_inspect(const uint8_t* f, int64_t size, int* h8, int* w8, int* seg_pixels, int* H, int* W, uint32_t* prior_id) {
+  char msg[160];
+  auto corrupt = [&](const char* what, long long a = 0, long long b = 0) {
+    snprintf(msg, sizeof(msg), what, a, b);
+    return nic::set_error(NIC_ECORRUPT, msg);
+  };
+  if (!f) return nic::set_error(NIC_EINVAL, "nic_rans2_inspect: file is NULL");
+  if (size < nic::kHeader) return corrupt("nic_rans2_inspect: %lld bytes are less than the 40-byte header", size);
+  if (std::memcmp(f, "NICR", 4) != 0) return corrupt("nic_rans2_inspect: bad magic");
+  if (f[4] != 2) return corrupt("nic_rans2_inspect: version %lld, expected 2", f[4]);
+  if (size < nic::kHeader2) return corrupt("nic_rans2_inspect: %lld bytes are less than the 40-byte header", size);
+  if (f[5] != nic::kProbBits) return corrupt("nic_rans2_inspect: %lld probability bits, expected 12", f[5]);
+  auto u32 = [&](int64_t at) { return (uint32_t)f[at] | ((uint32_t)f[at + 1] << 8) | ((uint32_t)f[at + 2] << 16) | ((uint32_t)f[at + 3] << 24); };
+  const uint32_t S = (uint32_t)f[6] | ((uint32_t)f[7] << 8), fh = u32(8), fw = u32(12), ih = u32(16), iw = u32(20);
+  if (S == 0) return corrupt("nic_rans2_inspect: seg_pixels is 0");
+  if (fh == 0 || fw == 0 || fh > (1u << 23) || fw > (1u << 23) || !nic::rans_shape_ok((int)fh, (int)fw))
+    return corrupt("nic_rans2_inspect: latent size %lld x %lld out of range", fh, fw);
+  if ((ih >> 3) + ((ih & 7u) != 0u) != fh) return corrupt("nic_rans2_inspect: image height %lld does not give h8 = %lld", ih, fh);
+  if ((iw >> 3) + ((iw & 7u) != 0u) != fw) return corrupt("nic_rans2_inspect: image width %lld does not give w8 = %lld", iw, fw);
+  int64_t at = nic::kHeader2;
+  for (int c = 0; c < nic::kCh; ++c) {
+    if (!((f[28 + (c >> 3)] >> (c & 7)) & 1)) continue;  // the prior's row
+    if (at >= size) return corrupt("nic_rans2_inspect: truncated in the table of channel %lld", c);
+    const int nsym = f[at] + 1;
+    if (at + 1 + 3 * nsym > size) return corrupt("nic_rans2_inspect: truncated in the table of channel %lld", c);
+    int prev = -1;
+    uint32_t sum = 0;
+    for (int e = 0; e < nsym; ++e) {
+      const int s = f[at + 1 + 3 * e];
+      const uint32_t fr = (uint32_t)f[at + 2 + 3 * e] | ((uint32_t)f[at + 3 + 3 * e] << 8);
+      if (s <= prev) return corrupt("nic_rans2_inspect: channel %lld: symbols not strictly ascending", c);
+      if (fr < 1 || fr > nic::kProbScale) return corrupt("nic_rans2_inspect: channel %lld: freq %lld not in 1..4096", c, fr);
+      prev = s;
+      sum += fr;
+    }
+    if (sum != nic::kProbScale) return corrupt("nic_rans2_inspect: channel %lld: freqs sum to %lld, not 4096", c, sum);
+    at += 1 + 3 * nsym;
+  }
+  const int64_t npix = (int64_t)fh * fw, nseg = (npix + S - 1) / S;
+  if (at + 4 * nseg > size) return corrupt("nic_rans2_inspect: truncated in the segment table");
+  int64_t pay = 0;
+  for (int64_t k = 0; k < nseg; ++k) pay += u32(at + 4 * k);
+  if (at + 4 * nseg + pay != size)
+    return corrupt("nic_rans2_inspect: header, tables and segments need %lld bytes, the file has %lld", at + 4 * nseg + pay, size);
+  if (h8) *h8 = (int)fh;
+  if (w8) *w8 = (int)fw;
+  if (seg_pixels) *seg_pixels = (int)S;
+  if (H) *H = (int)ih;
+  if (W) *W = (int)iw;
+  if (prior_id) *prior_id = u32(24);
   return NIC_OK;
 }
 
