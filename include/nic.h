@@ -314,6 +314,50 @@ int nic_rans2_decode(nic_ctx* ctx, const uint8_t* files, int64_t stride, const i
 int nic_rans2_inspect(const uint8_t* host_file, int64_t size, int* h8, int* w8, int* seg_pixels, int* H, int* W,
                       uint32_t* prior_id);
 
+/* ---- The .nic container, version 3: a context prior conditioned on the left neighbour -----------
+ * The context prior holds, for each of the 96 channels, one anchor symbol a_c (u8) and 3 contexts
+ * x 256 freqs (each in 1..4096, every (channel, context) row summing to 4096).  Its id is the
+ * CRC-32 (IEEE) of the 96 anchors followed by the 147,456 bytes of the freqs as little-endian u16,
+ * channel-major, then context, then symbol.  Format ("The .nic container, version 3"):
+ *   the version-2 file with version byte 3 and the context prior's id in prior_id
+ *   the byte at segment-relative offset j (channel c = j mod 96, pixel q = j div 96) is coded
+ *     under row (c, k): k = 0 if q = 0, else min(2, |z[j - 96] - a_c|) -- the previous pixel in
+ *     memory order, never a pixel of another segment
+ *   a masked channel stores a version-1 table and is coded under it in every context
+ * The per-channel choice is version 2's rule with prior = sum_k sum_s c_k[s] cost16[f[c][k][s]],
+ * c_k the image's counts of channel c in context k under the call's seg_pixels.
+ *
+ * nic_rans_cprior_check: HOST only.  Checks 96 host anchors and 96 x 3 x 256 host freqs and returns
+ *     the id (nullable); NIC_ECORRUPT naming the channel and the context otherwise.
+ * nic_rans_cprior_set: checks, then uploads the anchors, freqs, cumulative rows and the cost table.
+ *     Synchronous.  anchors = freqs = NULL clears the context prior.  id nullable.  The context
+ *     prior and nic_rans_prior_set's prior are independent of each other.
+ * nic_rans_cprior_count: adds the context counts of latent (n,h8,w8,96) u8 (16-byte aligned), cut
+ *     into segments of seg_pixels, under the DEVICE anchors uint8[96] into the caller's DEVICE
+ *     uint64[96 * 3 * 256] accumulator (zeroed by the caller) with 64-bit integer atomics:
+ *     deterministic, accumulates across calls.  On `stream`, no host synchronisation.
+ * nic_rans_cprior_build: accumulated counts -> DEVICE uint16[96 * 3 * 256] freqs, every row by
+ *     nic_rans_prior_build's rule (N = 0 gives sixteen everywhere).
+ * nic_rans3_bound = nic_rans2_bound.  nic_rans3_reserve / nic_rans3_encode / nic_rans3_decode /
+ *     nic_rans3_inspect: as their version-2 namesakes, with the context prior: NIC_ENOPRIOR before
+ *     nic_rans_cprior_set; decode status bit 1: not a version-3 header of an (h8, w8) latent with a
+ *     consistent (H, W); bit 3 (value 8): the file's prior_id is not the ctx's context prior's
+ *     (that image's latent is left unwritten).
+ * Arguments are validated before any HIP call: shape, empty batch (OK), NULL, then the prior. */
+int nic_rans_cprior_check(const uint8_t* host_anchors, const uint16_t* host_freqs, uint32_t* id);
+int nic_rans_cprior_set(nic_ctx* ctx, const uint8_t* host_anchors, const uint16_t* host_freqs, uint32_t* id);
+int nic_rans_cprior_count(nic_ctx* ctx, const uint8_t* latent, int n, int h8, int w8, int seg_pixels,
+                          const uint8_t* anchors_dev, uint64_t* counts_dev, void* stream);
+int nic_rans_cprior_build(nic_ctx* ctx, const uint64_t* counts_dev, uint16_t* freqs_dev, void* stream);
+int nic_rans3_bound(int h8, int w8, int seg_pixels, int64_t* bytes);
+int nic_rans3_reserve(nic_ctx* ctx, int n, int h8, int w8, int seg_pixels);
+int nic_rans3_encode(nic_ctx* ctx, const uint8_t* latent, int n, int h8, int w8, int H, int W, int seg_pixels,
+                     uint8_t* out, int64_t stride, int64_t* sizes, void* stream);
+int nic_rans3_decode(nic_ctx* ctx, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, int h8, int w8,
+                     uint8_t* latent, int32_t* status, void* stream);
+int nic_rans3_inspect(const uint8_t* host_file, int64_t size, int* h8, int* w8, int* seg_pixels, int* H, int* W,
+                      uint32_t* prior_id);
+
 /* ---- The device PNG writer: complete PNG files written on the device --------------------------
  * An optional writer for reconstructions (Pillow's optimize=True file, nic_png_encode, stays the
  * default and the bitstream's format).  Format: DESIGN.md, "The device PNG writer":

@@ -99,6 +99,17 @@ _SIGNATURES = {
     "nic_rans2_decode": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp] + [ctypes.c_int] * 3 + [c_vp, c_vp, c_vp]),
     "nic_rans2_inspect": (ctypes.c_int, [c_vp, ctypes.c_int64] + [ctypes.POINTER(ctypes.c_int)] * 5
                           + [ctypes.POINTER(ctypes.c_uint32)]),
+    # .nic version 3: the context prior (nic_rans.hip)
+    "nic_rans_cprior_check": (ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(ctypes.c_uint32)]),
+    "nic_rans_cprior_set": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.POINTER(ctypes.c_uint32)]),
+    "nic_rans_cprior_count": (ctypes.c_int, [c_vp, c_vp] + [ctypes.c_int] * 4 + [c_vp, c_vp, c_vp]),
+    "nic_rans_cprior_build": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
+    "nic_rans3_bound": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int64)]),
+    "nic_rans3_reserve": (ctypes.c_int, [c_vp] + [ctypes.c_int] * 4),
+    "nic_rans3_encode": (ctypes.c_int, [c_vp, c_vp] + [ctypes.c_int] * 6 + [c_vp, ctypes.c_int64, c_vp, c_vp]),
+    "nic_rans3_decode": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp] + [ctypes.c_int] * 3 + [c_vp, c_vp, c_vp]),
+    "nic_rans3_inspect": (ctypes.c_int, [c_vp, ctypes.c_int64] + [ctypes.POINTER(ctypes.c_int)] * 5
+                          + [ctypes.POINTER(ctypes.c_uint32)]),
     # device PNG writer (nic_png_dev.hip)
     "nic_png_device_block_bytes": (ctypes.c_int, []),
     "nic_png_device_bound": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int64)]),

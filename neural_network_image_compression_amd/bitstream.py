@@ -168,12 +168,32 @@ def nic2_inspect(data: bytes) -> Tuple[int, int, int, int, int, int]:
     return tuple(t.value for t in v) + (int(pid.value),)
 
 
+def nic3_inspect(data: bytes) -> Tuple[int, int, int, int, int, int]:
+    """(h8, w8, seg_pixels, H, W, prior_id) of a well-formed version-3 .nic file; ValueError
+    (nic_rans3_inspect's text) otherwise.  Host only."""
+    import ctypes
+
+    from . import _lib
+
+    a = np.frombuffer(data, np.uint8)
+    v = [ctypes.c_int() for _ in range(5)]
+    pid = ctypes.c_uint32()
+    rc = _lib.lib().nic_rans3_inspect(a.ctypes.data_as(ctypes.c_void_p), len(data), *[ctypes.byref(t) for t in v],
+                                      ctypes.byref(pid))
+    if rc != _lib.NIC_OK:
+        raise ValueError(f"[{rc}] {_lib.last_error()}")
+    return tuple(t.value for t in v) + (int(pid.value),)
+
+
 def nic_files(codec, z, seg_pixels: int = NIC_SEG_PIXELS, size=None) -> List[bytes]:
     """The .nic file of every latent of z (N,h,w,96), a u8 tensor on the codec's device: coded
     and assembled there (Codec.rans_encode), then one copy of the files to the host.  With a
-    prior set on the codec the files are version 2 (Codec.rans2_encode) and record the images'
-    size=(H, W) (default 8h x 8w); without one they are version 1 and size is not stored."""
-    if codec.prior is not None:
+    context prior set on the codec the files are version 3 (Codec.rans3_encode); else with a
+    prior set they are version 2 (Codec.rans2_encode); both record the images' size=(H, W)
+    (default 8h x 8w).  Without either they are version 1 and size is not stored."""
+    if codec.context_prior is not None:
+        buf, sizes = codec.rans3_encode(z, seg_pixels, size)
+    elif codec.prior is not None:
         buf, sizes = codec.rans2_encode(z, seg_pixels, size)
     else:
         buf, sizes = codec.rans_encode(z, seg_pixels)
@@ -186,15 +206,17 @@ def nic_files(codec, z, seg_pixels: int = NIC_SEG_PIXELS, size=None) -> List[byt
 
 def _inspect_any(codec, i: int, data: bytes):
     """The decode group and the image size of file i: byte 4 says which version's checks apply.
-    A version-2 file also needs the codec's prior to be the one it was written under."""
+    A version-2 file also needs the codec's prior to be the one it was written under, a version-3
+    file the codec's context prior."""
     try:
-        if len(data) > 4 and data[4] == 2:
-            h8, w8, _, H, W, pid = nic2_inspect(data)
-            have = codec.prior
+        if len(data) > 4 and data[4] in (2, 3):
+            ver = data[4]
+            h8, w8, _, H, W, pid = (nic2_inspect if ver == 2 else nic3_inspect)(data)
+            have = codec.prior if ver == 2 else codec.context_prior
             if have is None or have.id != pid:
                 raise ValueError(f"written under prior {pid:08x}, the codec's prior is "
                                  + ("not set" if have is None else f"{have.id:08x}"))
-            return (2, h8, w8), (H, W)
+            return (ver, h8, w8), (H, W)
         h8, w8, sp = nic_inspect(data)
         return (1, h8, w8, sp), (8 * h8, 8 * w8)
     except ValueError as e:
@@ -202,16 +224,17 @@ def _inspect_any(codec, i: int, data: bytes):
 
 
 def read_nic_sizes(codec, files: Sequence[bytes]) -> List[Tuple[int, int]]:
-    """The image size (H, W) each .nic file stands for: a version-2 file's own, 8 h8 x 8 w8 for a
-    version-1 file (which does not record it).  The same host checks as read_nic."""
+    """The image size (H, W) each .nic file stands for: a version-2 or version-3 file's own,
+    8 h8 x 8 w8 for a version-1 file (which does not record it).  The same host checks as read_nic."""
     return [_inspect_any(codec, i, data)[1] for i, data in enumerate(files)]
 
 
 def read_nic(codec, files: Sequence[bytes], sizes: bool = False) -> list:
     """The latents of .nic files: a list of (h8,w8,96) u8 tensors on the codec's device, in the
-    files' order.  Every file is checked on the host first (nic_inspect, or nic2_inspect for a
-    version-2 file: ValueError naming the file's index); version-1 files of equal (h8, w8,
-    seg_pixels) and version-2 files of equal (h8, w8) are decoded as one device batch each.
+    files' order.  Every file is checked on the host first (nic_inspect, or nic2_inspect /
+    nic3_inspect for a version-2 / version-3 file: ValueError naming the file's index); version-1
+    files of equal (h8, w8, seg_pixels) and version-2 or version-3 files of equal (h8, w8) are
+    decoded as one device batch each.
     sizes=True: also the files' image sizes, (latents, [(H, W)])."""
     import torch
 
@@ -230,7 +253,7 @@ def read_nic(codec, files: Sequence[bytes], sizes: bool = False) -> list:
         lens = torch.tensor([len(files[i]) for i in idx], dtype=torch.int64)
         dev = f"cuda:{codec.device}"
         try:
-            decode = codec.rans2_decode if key[0] == 2 else codec.rans_decode
+            decode = {1: codec.rans_decode, 2: codec.rans2_decode, 3: codec.rans3_decode}[key[0]]
             z = decode(torch.from_numpy(host).to(dev), lens.to(dev), h8, w8)
         except ValueError as e:
             raise ValueError(f"read_nic: files {idx}: {e}") from None
@@ -304,7 +327,7 @@ def feed_batch(model, x: np.ndarray, filenames: Sequence[str], output_dir: str, 
         dev = codec.unpack(dev)
     out = model._device_call(dev)
     if container == "nic" and out.shape[-1] == 96:
-        datas = nic_files(codec, out, size=(h, w))  # version 2 (a prior is set) records the images' own size
+        datas = nic_files(codec, out, size=(h, w))  # versions 2 and 3 (a prior is set) record the images' own size
         if pool is None:
             _write_files(datas, output_dir, filenames, ".nic")
             return []
@@ -353,6 +376,18 @@ WRITES_IN_FLIGHT = 2  # batches handed to the PNG writer and not yet written (us
 BATCH_PIXELS = 64 * 512 * 768  # pixels staged per device batch (use_model): 64 Kodak-sized images, 3 4K frames
 
 
+def _set_any_prior(codec, prior) -> None:
+    """prior= of the drivers: a prior.Prior or a .nicp path sets the codec's prior (version 2), a
+    prior.ContextPrior or a .nicc path its context prior (version 3); a path by its magic."""
+    from .prior import ContextPrior, as_any_prior
+
+    prior = as_any_prior(prior)
+    if isinstance(prior, ContextPrior):
+        codec.set_context_prior(prior)
+    else:
+        codec.set_prior(prior)
+
+
 def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, in_cshape: int,
               batch_size: int = 64, workers=None, container: str = "png", png_writer: str = "pillow",
               prior=None) -> None:
@@ -380,17 +415,16 @@ def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, i
     ``prior`` (a prior.Prior or a ``.nicp`` path; ``container="nic"`` only, ValueError otherwise):
     set on the model's codec for this and later calls.  The encoder side then writes version-2
     files, which carry each image's true H x W; the decoder side reads directories that mix both
-    versions and crops the reconstructions of version-2 files to H x W.  Without it everything
-    behaves and writes as before."""
+    versions and crops the reconstructions of version-2 files to H x W.  A prior.ContextPrior or
+    a ``.nicc`` path does the same with version 3 (a context prior takes precedence on the encoder
+    side when the codec has both).  Without it everything behaves and writes as before."""
     if container not in CONTAINERS:
         raise ValueError(f"container must be one of {CONTAINERS}, got {container!r}")
     _check_png_writer(png_writer, decoder_side=in_cshape == 96)
     if prior is not None:
         if container != "nic":
             raise ValueError('prior applies to container="nic" only: the PNG container has no entropy model')
-        from .prior import as_prior
-
-        model.codec.set_prior(as_prior(prior))
+        _set_any_prior(model.codec, prior)
     if container == "nic" and in_cshape == 96:
         return use_model_nic_in(model, dataset_path, checkpoint_path, output_dir, batch_size=batch_size, workers=workers,
                                 png_writer=png_writer)
@@ -464,9 +498,7 @@ def use_model_nic_in(model, dataset_path: str, checkpoint_path: str, output_dir:
 
     _check_png_writer(png_writer, decoder_side=True)
     if prior is not None:
-        from .prior import as_prior
-
-        model.codec.set_prior(as_prior(prior))
+        _set_any_prior(model.codec, prior)
     os.makedirs(output_dir, exist_ok=True)
     model.load(checkpoint_path)
     codec = model.codec

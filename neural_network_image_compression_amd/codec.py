@@ -455,6 +455,116 @@ class Codec:
             raise ValueError(f"rans2_decode: image {i} is corrupt (status {int(st[i])}; corrupt images: {bad.tolist()})")
         return z
 
+    # -- .nic version 3: the context prior (nic_rans_cprior_*, nic_rans3_*) ---------------------
+    #: the ContextPrior set by set_context_prior (None: no version-3 files)
+    context_prior = None
+
+    def set_context_prior(self, cprior) -> None:
+        """The context prior (prior.ContextPrior) of rans3_encode / rans3_decode, or None to clear
+        it (nic_rans_cprior_set: synchronous).  Independent of set_prior."""
+        if cprior is None:
+            _lib.check(self._L.nic_rans_cprior_set(self._h, None, None, None), "nic_rans_cprior_set")
+            self.context_prior = None
+            return
+        pid = ctypes.c_uint32()
+        _lib.check(self._L.nic_rans_cprior_set(self._h, cprior.anchors.ctypes.data_as(ctypes.c_void_p),
+                                               cprior.freqs.ctypes.data_as(ctypes.c_void_p), ctypes.byref(pid)),
+                   "nic_rans_cprior_set")
+        assert pid.value == cprior.id
+        self.context_prior = cprior
+
+    def cprior_count(self, z, anchors, counts, seg_pixels: int = 32) -> None:
+        """Adds the context counts of the latents z (N,h,w,96), cut into segments of seg_pixels,
+        under anchors ((96,) u8 device tensor) into counts, a (96, 3, 256) int64 device tensor read
+        as uint64 (nic_rans_cprior_count; no host synchronisation)."""
+        torch = _torch()
+        z = self._check_dev(z, 4, 96, "cprior_count")
+        if (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int64 or counts.shape != (96, 3, 256)
+                or counts.device != z.device or not counts.is_contiguous()):
+            raise TypeError("cprior_count: counts must be a contiguous (96, 3, 256) torch.int64 tensor on the codec's device")
+        if (not isinstance(anchors, torch.Tensor) or anchors.dtype != torch.uint8 or anchors.shape != (96,)
+                or anchors.device != z.device or not anchors.is_contiguous()):
+            raise TypeError("cprior_count: anchors must be a contiguous (96,) torch.uint8 tensor on the codec's device")
+        n, h8, w8, _ = z.shape
+        if z.data_ptr() % 16:
+            z = z.clone()
+        _lib.check(self._L.nic_rans_cprior_count(self._h, z.data_ptr(), n, h8, w8, int(seg_pixels), anchors.data_ptr(),
+                                                 counts.data_ptr(), _stream_ptr(torch, self.device)), "nic_rans_cprior_count")
+
+    def cprior_build(self, counts):
+        """(96, 3, 256) int64 device counts -> (96, 3, 256) freqs as an int32 device tensor
+        (nic_rans_cprior_build; no host synchronisation)."""
+        torch = _torch()
+        if (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int64 or counts.shape != (96, 3, 256)
+                or counts.device.type != "cuda" or counts.device.index != self.device):
+            raise TypeError("cprior_build: counts must be a (96, 3, 256) torch.int64 tensor on the codec's device")
+        counts = counts.contiguous()
+        freqs = torch.empty((96, 3, 256), dtype=torch.int16, device=counts.device)  # u16 bits, all <= 4096
+        _lib.check(self._L.nic_rans_cprior_build(self._h, counts.data_ptr(), freqs.data_ptr(),
+                                                 _stream_ptr(torch, self.device)), "nic_rans_cprior_build")
+        return freqs.to(torch.int32)
+
+    def rans3_reserve(self, n: int, h8: int, w8: int, seg_pixels: int = 32) -> None:
+        """Grow the workspace so rans3_encode / rans3_decode of (n, h8, w8) latents allocate nothing."""
+        _lib.check(self._L.nic_rans3_reserve(self._h, n, h8, w8, seg_pixels), "nic_rans3_reserve")
+
+    def rans3_encode(self, z, seg_pixels: int = 32, size=None):
+        """rans2_encode with the codec's context prior: version-3 files, whose symbols are coded
+        under the row their left neighbour selects.  NicError(NIC_ENOPRIOR) without a context prior."""
+        torch = _torch()
+        z = self._check_dev(z, 4, 96, "rans3_encode")
+        n, h8, w8, _ = z.shape
+        H, W = (8 * h8, 8 * w8) if size is None else (int(size[0]), int(size[1]))
+        if z.data_ptr() % 16:  # a view at an odd offset: the kernels read 16-byte words
+            z = z.clone()
+        stride = ctypes.c_int64()
+        _lib.check(self._L.nic_rans3_bound(h8, w8, int(seg_pixels), ctypes.byref(stride)), "nic_rans3_bound")
+        buf = torch.empty((n, stride.value), dtype=torch.uint8, device=z.device)
+        sizes = torch.zeros((n,), dtype=torch.int64, device=z.device)
+        _lib.check(self._L.nic_rans3_encode(self._h, z.data_ptr(), n, h8, w8, H, W, int(seg_pixels), buf.data_ptr(),
+                                            stride.value, sizes.data_ptr(), _stream_ptr(torch, self.device)),
+                   "nic_rans3_encode")
+        return buf, sizes
+
+    def rans3_decode_status(self, buf, sizes, h8: int, w8: int, out=None):
+        """rans3_decode without the check: (latent, status (N,) int32 device tensor; nic.h).
+        out: the (N,h8,w8,96) u8 tensor to decode into (default: a new one)."""
+        torch = _torch()
+        if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.device.type != "cuda" or buf.ndim != 2:
+            raise TypeError("rans3_decode: expected an (N, stride) cuda torch.uint8 tensor of files")
+        if not isinstance(sizes, torch.Tensor) or sizes.dtype != torch.int64 or sizes.shape != (buf.shape[0],):
+            raise TypeError("rans3_decode: expected an (N,) torch.int64 tensor of sizes")
+        if buf.device.index != self.device or sizes.device != buf.device:
+            raise ValueError(f"rans3_decode: tensors must be on cuda:{self.device}")
+        buf, sizes = buf.contiguous(), sizes.contiguous()
+        n, stride = buf.shape
+        if out is None:
+            out = torch.empty((n, h8, w8, 96), dtype=torch.uint8, device=buf.device)
+        elif (out.dtype != torch.uint8 or tuple(out.shape) != (n, h8, w8, 96) or out.device != buf.device
+              or not out.is_contiguous()):
+            raise TypeError("rans3_decode: out must be a contiguous (N,h8,w8,96) torch.uint8 tensor on the codec's device")
+        status = torch.zeros((n,), dtype=torch.int32, device=buf.device)
+        _lib.check(self._L.nic_rans3_decode(self._h, buf.data_ptr(), stride, sizes.data_ptr(), n, int(h8), int(w8),
+                                            out.data_ptr(), status.data_ptr(), _stream_ptr(torch, self.device)),
+                   "nic_rans3_decode")
+        return out, status
+
+    def rans3_decode(self, buf, sizes, h8: int, w8: int):
+        """Version-3 .nic files buf[i, :sizes[i]] of (h8, w8) latents -> (N,h8,w8,96) u8.  Reads the
+        statuses back (synchronises) and raises ValueError naming the first image whose file did
+        not decode cleanly; a file written under another context prior is reported with both ids."""
+        z, status = self.rans3_decode_status(buf, sizes, h8, w8)
+        st = status.cpu().numpy()
+        bad = np.nonzero(st)[0]
+        if bad.size:
+            i = int(bad[0])
+            if st[i] & 8:
+                pid = int.from_bytes(bytes(buf[i, 24:28].cpu().numpy().tolist()), "little")
+                raise ValueError(f"rans3_decode: image {i} was written under prior {pid:08x}, the codec's prior is "
+                                 f"{self.context_prior.id:08x} (status {int(st[i])}; refused images: {bad.tolist()})")
+            raise ValueError(f"rans3_decode: image {i} is corrupt (status {int(st[i])}; corrupt images: {bad.tolist()})")
+        return z
+
     # -- device PNG writer (nic_png_device_*) -------------------------------------------------
     def png_reserve(self, n: int, h: int, w: int, channels: int = 3) -> None:
         """Grow the workspace so png_encode of n (h, w, channels) images allocates nothing."""
@@ -569,7 +679,8 @@ class Encoder(ProClass):
         ``container="nic"`` writes ``<stem>.nic`` files, entropy-coded on the device, instead of
         the reference's packed PNGs (the default).  ``prior`` (a prior.Prior or a ``.nicp`` path;
         ``container="nic"`` only): version-2 files, coded against the prior and carrying each
-        image's true H x W."""
+        image's true H x W.  A prior.ContextPrior or a ``.nicc`` path: version-3 files, coded
+        against the context prior."""
         from .bitstream import use_model
 
         use_model(self, dataset_path, checkpoint_path, dataset_path + "_compressed", in_cshape=3,
@@ -597,8 +708,8 @@ class Decoder(ProClass):
         ``png_writer="device"`` writes the reconstructions with the device PNG writer (the same
         pixels in files of its own format) instead of Pillow's optimize=True bytes.
         ``prior`` (``container="nic"`` only): the prior the directory's version-2 files were written
-        under; their reconstructions are cropped to the recorded H x W.  Version-1 files are read
-        as before."""
+        under (a prior.ContextPrior or a ``.nicc`` path for version-3 files); their reconstructions
+        are cropped to the recorded H x W.  Version-1 files are read as before."""
         from .bitstream import use_model
 
         use_model(self, dataset_path, checkpoint_path, dataset_path.replace("compressed", "uncompressed"),

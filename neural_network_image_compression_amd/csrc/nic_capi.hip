@@ -298,6 +298,10 @@ struct nic_ctx {
   char* prior = nullptr;
   uint32_t prior_id = 0;
   bool have_prior = false;
+  // the .nic version-3 context prior (nic_rans_cprior_set): freqs, cumulative rows, anchors and the cost table
+  char* cprior = nullptr;
+  uint32_t cprior_id = 0;
+  bool have_cprior = false;
   char* qs = nullptr;  // MS-SSIM scratch (pooled scales + tile sums), grown on demand
   size_t qs_bytes = 0;
   // optional per-layer HIP-event timing (nic_set_timing): one event pair per layer and
@@ -461,7 +465,7 @@ bool models_ready(const nic_ctx* c, int m0) {
 
 extern "C" {
 
-int nic_version(void) { return 500; }
+int nic_version(void) { return 600; }
 
 int nic_constants(float* ycbcr9, float* ycbcr_inv9, float* off3) {
   // host copy of what nic_create uploads; lets tests compare with np.linalg.inv (utils.py:8)
@@ -559,6 +563,7 @@ int nic_destroy(nic_ctx* c) {
   if (c->fold_acc) (void)hipFree(c->fold_acc);
   if (c->qs) (void)hipFree(c->qs);
   if (c->prior) (void)hipFree(c->prior);
+  if (c->cprior) (void)hipFree(c->cprior);
   if (c->zero16) (void)hipFree(c->zero16);
   if (c->wproj) (void)hipFree(c->wproj);
   if (c->range) (void)hipFree(c->range);
@@ -1506,8 +1511,8 @@ int nic_rans2_reserve(nic_ctx* c, int n, int h8, int w8, int seg_pixels) {
   if (!c) return fail(NIC_EINVAL, "nic_rans2_reserve: NULL ctx");
   DeviceGuard guard(c->device);
   RansPlan enc, dec;
-  rans_plan(n, h8, w8, seg_pixels, false, &enc, true);
-  rans_plan(n, h8, w8, seg_pixels, true, &dec, true);
+  rans_plan(n, h8, w8, seg_pixels, false, &enc, 2);
+  rans_plan(n, h8, w8, seg_pixels, true, &dec, 2);
   return ensure_ws(c, std::max(enc.bytes, dec.bytes));
 }
 
@@ -1528,7 +1533,7 @@ int nic_rans2_encode(nic_ctx* c, const uint8_t* latent, int n, int h8, int w8, i
   if (!c->have_prior) return fail(NIC_ENOPRIOR, "nic_rans2_encode: no prior is set (nic_rans_prior_set)");
   DeviceGuard guard(c->device);
   RansPlan pl;
-  rans_plan(n, h8, w8, seg_pixels, false, &pl, true);
+  rans_plan(n, h8, w8, seg_pixels, false, &pl, 2);
   if ((rc = ensure_ws(c, pl.bytes))) return rc;
   HIP_TRY(launch_rans2_encode(latent, n, h8, w8, H, W, seg_pixels, ctx_prior(c), c->ws, pl, out, stride, (long long*)sizes,
                               (hipStream_t)stream));
@@ -1546,9 +1551,134 @@ int nic_rans2_decode(nic_ctx* c, const uint8_t* files, int64_t stride, const int
   if (!c->have_prior) return fail(NIC_ENOPRIOR, "nic_rans2_decode: no prior is set (nic_rans_prior_set)");
   DeviceGuard guard(c->device);
   RansPlan pl;
-  rans_plan(n, h8, w8, 1, true, &pl, true);
+  rans_plan(n, h8, w8, 1, true, &pl, 2);
   if ((rc = ensure_ws(c, pl.bytes))) return rc;
   HIP_TRY(launch_rans2_decode(files, stride, (const long long*)sizes, n, h8, w8, ctx_prior(c), c->ws, pl, latent, status,
+                              (hipStream_t)stream));
+  return NIC_OK;
+}
+
+// ---- .nic version 3: the context prior (nic_rans.hip; nic_rans_cprior_check, nic_rans3_bound and
+// nic_rans3_inspect are host-only there) ----
+static RansCPrior ctx_cprior(const nic_ctx* c) {
+  size_t cum_at, anchor_at, cost_at;
+  rans_cprior_bytes(&cum_at, &anchor_at, &cost_at);
+  return {(const uint16_t*)c->cprior, (const uint16_t*)(c->cprior + cum_at), (const uint8_t*)(c->cprior + anchor_at),
+          (const uint32_t*)(c->cprior + cost_at), c->cprior_id};
+}
+
+int nic_rans_cprior_set(nic_ctx* c, const uint8_t* anchors, const uint16_t* freqs, uint32_t* id) {
+  if (!c) return fail(NIC_EINVAL, "nic_rans_cprior_set: NULL ctx");
+  if (!anchors && !freqs) {  // back to no context prior
+    c->have_cprior = false;
+    return NIC_OK;
+  }
+  uint32_t pid = 0;
+  int rc = nic_rans_cprior_check(anchors, freqs, &pid);
+  if (rc) return rc;
+  size_t cum_at, anchor_at, cost_at;
+  const size_t bytes = rans_cprior_bytes(&cum_at, &anchor_at, &cost_at);
+  const int pitch = rans_cprior_row_pitch();
+  std::vector<char> host(bytes, 0);
+  std::memcpy(host.data(), freqs, cum_at);
+  uint16_t* cum = (uint16_t*)(host.data() + cum_at);
+  for (int row = 0; row < 96 * 3; ++row) {
+    uint32_t run = 0;
+    for (int s = 0; s < 256; ++s) {
+      cum[row * pitch + s] = (uint16_t)run;
+      run += freqs[row * 256 + s];
+    }
+    cum[row * pitch + 256] = (uint16_t)run;  // 4096
+  }
+  std::memcpy(host.data() + anchor_at, anchors, 96);
+  nic_rans_cost_table((uint32_t*)(host.data() + cost_at));
+  DeviceGuard guard(c->device);
+  c->have_cprior = false;
+  if (!c->cprior && hipMalloc(&c->cprior, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    c->cprior = nullptr;
+    return fail(NIC_ENOMEM, "nic_rans_cprior_set: allocation of %zu bytes failed", bytes);
+  }
+  HIP_TRY(hipDeviceSynchronize());  // queued coding may still read the previous prior
+  HIP_TRY(hipMemcpy(c->cprior, host.data(), bytes, hipMemcpyHostToDevice));
+  c->cprior_id = pid;
+  c->have_cprior = true;
+  if (id) *id = pid;
+  return NIC_OK;
+}
+
+int nic_rans_cprior_count(nic_ctx* c, const uint8_t* latent, int n, int h8, int w8, int seg_pixels, const uint8_t* anchors,
+                          uint64_t* counts, void* stream) {
+  int rc = rans_check("nic_rans_cprior_count", n, h8, w8, seg_pixels);
+  if (rc || n == 0) return rc;
+  if (!c) return fail(NIC_EINVAL, "nic_rans_cprior_count: NULL ctx");
+  if (!latent || !anchors || !counts) return fail(NIC_EINVAL, "nic_rans_cprior_count: NULL buffer");
+  if ((uintptr_t)latent % 16 || (uintptr_t)counts % 8)
+    return fail(NIC_EINVAL, "nic_rans_cprior_count: latent must be 16-byte and counts 8-byte aligned");
+  DeviceGuard guard(c->device);
+  HIP_TRY(launch_rans_cprior_count(latent, n, h8, w8, seg_pixels, anchors, (unsigned long long*)counts, (hipStream_t)stream));
+  return NIC_OK;
+}
+
+int nic_rans_cprior_build(nic_ctx* c, const uint64_t* counts, uint16_t* freqs, void* stream) {
+  if (!c) return fail(NIC_EINVAL, "nic_rans_cprior_build: NULL ctx");
+  if (!counts || !freqs) return fail(NIC_EINVAL, "nic_rans_cprior_build: NULL buffer");
+  if ((uintptr_t)counts % 8 || (uintptr_t)freqs % 2)
+    return fail(NIC_EINVAL, "nic_rans_cprior_build: counts must be 8-byte and freqs 2-byte aligned");
+  DeviceGuard guard(c->device);
+  HIP_TRY(launch_rans_cprior_build((const unsigned long long*)counts, freqs, (hipStream_t)stream));
+  return NIC_OK;
+}
+
+int nic_rans3_reserve(nic_ctx* c, int n, int h8, int w8, int seg_pixels) {
+  int rc = rans_check("nic_rans3_reserve", n, h8, w8, seg_pixels);
+  if (rc || n == 0) return rc;
+  if (!c) return fail(NIC_EINVAL, "nic_rans3_reserve: NULL ctx");
+  DeviceGuard guard(c->device);
+  RansPlan enc, dec;
+  rans_plan(n, h8, w8, seg_pixels, false, &enc, 3);
+  rans_plan(n, h8, w8, seg_pixels, true, &dec, 3);
+  return ensure_ws(c, std::max(enc.bytes, dec.bytes));
+}
+
+int nic_rans3_encode(nic_ctx* c, const uint8_t* latent, int n, int h8, int w8, int H, int W, int seg_pixels, uint8_t* out,
+                     int64_t stride, int64_t* sizes, void* stream) {
+  int rc = rans_check("nic_rans3_encode", n, h8, w8, seg_pixels);
+  if (rc) return rc;
+  if (H <= 0 || W <= 0 || (H + 7) / 8 != h8 || (W + 7) / 8 != w8)
+    return fail(NIC_ESHAPE, "nic_rans3_encode: a %dx%d image does not have a %dx%d latent", H, W, h8, w8);
+  if (n == 0) return NIC_OK;
+  if (!c) return fail(NIC_EINVAL, "nic_rans3_encode: NULL ctx");
+  if (!latent || !out || !sizes) return fail(NIC_EINVAL, "nic_rans3_encode: NULL buffer");
+  if ((uintptr_t)latent % 16) return fail(NIC_EINVAL, "nic_rans3_encode: latent must be 16-byte aligned");
+  int64_t bound = 0;
+  nic_rans3_bound(h8, w8, seg_pixels, &bound);
+  if (stride < bound)
+    return fail(NIC_ESHAPE, "nic_rans3_encode: stride %lld is below nic_rans3_bound = %lld", (long long)stride, (long long)bound);
+  if (!c->have_cprior) return fail(NIC_ENOPRIOR, "nic_rans3_encode: no context prior is set (nic_rans_cprior_set)");
+  DeviceGuard guard(c->device);
+  RansPlan pl;
+  rans_plan(n, h8, w8, seg_pixels, false, &pl, 3);
+  if ((rc = ensure_ws(c, pl.bytes))) return rc;
+  HIP_TRY(launch_rans3_encode(latent, n, h8, w8, H, W, seg_pixels, ctx_cprior(c), c->ws, pl, out, stride, (long long*)sizes,
+                              (hipStream_t)stream));
+  return NIC_OK;
+}
+
+int nic_rans3_decode(nic_ctx* c, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, int h8, int w8,
+                     uint8_t* latent, int32_t* status, void* stream) {
+  int rc = rans_check("nic_rans3_decode", n, h8, w8, 1);
+  if (rc || n == 0) return rc;
+  if (!c) return fail(NIC_EINVAL, "nic_rans3_decode: NULL ctx");
+  if (!files || !sizes || !latent || !status) return fail(NIC_EINVAL, "nic_rans3_decode: NULL buffer");
+  if ((uintptr_t)latent % 16) return fail(NIC_EINVAL, "nic_rans3_decode: latent must be 16-byte aligned");
+  if (stride < 40) return fail(NIC_ESHAPE, "nic_rans3_decode: stride %lld is below the 40-byte header", (long long)stride);
+  if (!c->have_cprior) return fail(NIC_ENOPRIOR, "nic_rans3_decode: no context prior is set (nic_rans_cprior_set)");
+  DeviceGuard guard(c->device);
+  RansPlan pl;
+  rans_plan(n, h8, w8, 1, true, &pl, 3);
+  if ((rc = ensure_ws(c, pl.bytes))) return rc;
+  HIP_TRY(launch_rans3_decode(files, stride, (const long long*)sizes, n, h8, w8, ctx_cprior(c), c->ws, pl, latent, status,
                               (hipStream_t)stream));
   return NIC_OK;
 }

@@ -183,7 +183,8 @@ struct RansPrior {
   uint32_t id;
 };
 bool rans_shape_ok(int h8, int w8);
-void rans_plan(int n, int h8, int w8, int seg_pixels, bool decode, RansPlan* plan, bool v2 = false);  // v2: + keep[96] per image
+// ver: the container version; 2 and 3: + keep[96] per image; 3: three rows and three histograms per channel
+void rans_plan(int n, int h8, int w8, int seg_pixels, bool decode, RansPlan* plan, int ver = 1);
 hipError_t launch_rans_encode(const uint8_t* z, int n, int h8, int w8, int seg_pixels, char* ws, const RansPlan& plan,
                               uint8_t* out, long long stride, long long* sizes, hipStream_t st);
 hipError_t launch_rans_decode(const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8, char* ws,
@@ -195,6 +196,25 @@ hipError_t launch_rans2_encode(const uint8_t* z, int n, int h8, int w8, int H, i
                                char* ws, const RansPlan& plan, uint8_t* out, long long stride, long long* sizes, hipStream_t st);
 hipError_t launch_rans2_decode(const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8,
                                const RansPrior& prior, char* ws, const RansPlan& plan, uint8_t* z, int* status, hipStream_t st);
+// The ctx's context prior on the device (version 3): 96 x 3 x 256 freqs, their cumulative rows at
+// the segment kernels' row pitch (rans_cprior_row_pitch() u16 per row), the 96 anchors and the cost
+// table, in one allocation of rans_cprior_bytes() bytes.
+struct RansCPrior {
+  const uint16_t* freq;
+  const uint16_t* cum;
+  const uint8_t* anchor;
+  const uint32_t* cost16;
+  uint32_t id;
+};
+size_t rans_cprior_bytes(size_t* cum_at, size_t* anchor_at, size_t* cost_at);
+int rans_cprior_row_pitch();
+hipError_t launch_rans_cprior_count(const uint8_t* z, int n, int h8, int w8, int seg_pixels, const uint8_t* anchor,
+                                    unsigned long long* counts, hipStream_t st);
+hipError_t launch_rans_cprior_build(const unsigned long long* counts, uint16_t* freqs, hipStream_t st);
+hipError_t launch_rans3_encode(const uint8_t* z, int n, int h8, int w8, int H, int W, int seg_pixels, const RansCPrior& prior,
+                               char* ws, const RansPlan& plan, uint8_t* out, long long stride, long long* sizes, hipStream_t st);
+hipError_t launch_rans3_decode(const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8,
+                               const RansCPrior& prior, char* ws, const RansPlan& plan, uint8_t* z, int* status, hipStream_t st);
 
 // --- device PNG writer (nic_png_dev.hip) ------------------------------------------------------
 // Byte offsets of one call's scratch inside the ctx workspace (256-B aligned), from png_dev_plan:

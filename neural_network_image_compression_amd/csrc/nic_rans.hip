@@ -279,7 +279,7 @@ __device__ void block_offsets(const uint32_t* __restrict__ len, int count, uint3
 }
 
 // ---- encode 4a: offsets and file sizes.  grid (n), block 256 --------------------------------
-// kVer: the container version, 1 or 2 (a 40-byte header; prior channels have tablen 0)
+// kVer: the container version, 1, 2 or 3 (2 and 3: a 40-byte header; prior channels have tablen 0)
 template <int kVer>
 __global__ __launch_bounds__(256) void rans_layout(const uint32_t* __restrict__ tablen, uint32_t* __restrict__ taboff,
                                                     const uint32_t* __restrict__ seglen, uint32_t* __restrict__ segoff, int nseg,
@@ -297,7 +297,7 @@ __global__ __launch_bounds__(256) void rans_layout(const uint32_t* __restrict__ 
 
 // ---- encode 4b: the files.  grid (ceil((96 + nseg) / 4), n), block 256: one wave per item ----
 // item c < 96: channel c's table (item 0 also the header); item 96 + k: segment k's length and bytes
-// Version 2 (kVer = 2): the header also holds (H, W), prior_id and the mask gathered from keep[96]
+// Versions 2 and 3: the header also holds (H, W), prior_id and the mask gathered from keep[96]
 // (1: the channel stores its own table); a prior channel's tablen is 0, so nothing is copied for it.
 template <int kVer>
 __global__ __launch_bounds__(256) void rans_assemble(const uint8_t* __restrict__ tab, const uint32_t* __restrict__ tablen,
@@ -320,7 +320,7 @@ __global__ __launch_bounds__(256) void rans_assemble(const uint8_t* __restrict__
       else if (lane == 5) b = (uint8_t)kProbBits;
       else if (lane < 8) b = (uint8_t)(((uint32_t)seg_pixels >> (8 * (lane - 6))) & 255u);
       else if (lane < 28) b = (uint8_t)((hw[(lane - 8) >> 2] >> (8 * (lane & 3))) & 255u);
-      else {  // version 2 only: channel c is bit c & 7 of mask byte c >> 3
+      else {  // versions 2 and 3 only: channel c is bit c & 7 of mask byte c >> 3
         const uint32_t* k8 = keep + (size_t)img * kCh + 8 * (lane - 28);
         uint32_t m = 0;
 #pragma unroll
@@ -530,7 +530,8 @@ __global__ __launch_bounds__(256) void rans_prior_count(const uint8_t* __restric
     if (h[i]) atomicAdd(&dst[i], (unsigned long long)h[i]);
 }
 
-// ---- prior 2: counts -> freqs.  grid (96), block 64: one wave per channel ---------------------
+// ---- prior 2: counts -> freqs.  grid (rows), block 64: one wave per row of 256 counts -----------
+// (96 channels of the static prior; 96 x 3 (channel, context) rows of the context prior)
 // Version 1's rule with all 256 symbols "used": f = max(1, floor(c 4096 / N)); a deficit goes onto
 // the largest entry; a surplus (at most 255) is taken one at a time from the currently largest
 // entry (lowest symbol on ties).  N = 0: sixteen everywhere.  c 4096 must fit 64 bits: N < 2^52.
@@ -704,6 +705,348 @@ __global__ __launch_bounds__(256) void rans2_parse(const uint8_t* __restrict__ f
   if (tid == 0) status[img] = s_bad;
 }
 
+// ==== version 3: a context prior conditioned on the left neighbour ("The .nic container,
+// version 3") ====
+// The context prior is 96 anchors and 96 x 3 x 256 freqs.  The byte at segment-relative offset j
+// (channel c = j % 96, pixel q = j / 96) is coded under row (c, k): k = 0 for the segment's first
+// pixel, else min(2, |z[j - 96] - anchor[c]|).  A channel that keeps its own table is coded under
+// it in every context, so the segment kernels always see three rows per channel.  The rows of one
+// image are u16[96][3][kCtxRow] in global memory and in LDS alike (copied as dwords).
+
+// The row pitch in LDS: all 64 lanes are at one channel, spread over its three rows, and most of
+// them at symbols near the anchor.  At 257 u16 (128.5 dwords) the same symbol of the three rows
+// falls onto one or two neighbouring banks; at 278 u16 (139 dwords = 4 x 32 + 11) the rows sit 11
+// and 22 banks apart.  288 rows x 556 B = 160,128 B of the 163,840.
+constexpr int kCtx = 3;
+constexpr int kCtxRow = 278;
+constexpr int kCtxWords = kCh * kCtx * kCtxRow;  // u16 per image
+static_assert(kCtxRow % 2 == 0 && kCtxRow >= kCumRow && kCtxWords * 2 + 64 <= 160 * 1024, "the rows must fit the LDS");
+
+__device__ __forceinline__ uint32_t ctx_of(uint32_t left, uint32_t anchor) {
+  const int d = (int)left - (int)anchor;
+  const uint32_t a = (uint32_t)(d < 0 ? -d : d);
+  return a < 2u ? a : 2u;
+}
+
+// ---- context counts ---------------------------------------------------------------------------
+// grid (ceil(npix / 256), 6, n), block 256: rans_hist's structure with a sixth of the channels per
+// block (16 x 3 LDS histograms = 48 KB); a thread reads its pixel's 16 bytes and, unless the pixel
+// opens a segment, the 16 bytes of the pixel before it.  T = uint32_t: per-image counts
+// [n][96][3][256] (img_stride = 96 * 3 * 256); T = unsigned long long: one corpus accumulator
+// (img_stride = 0), integer atomics, so the totals do not depend on the order.
+template <typename T>
+__global__ __launch_bounds__(256) void rans3_hist(const uint8_t* __restrict__ z, int npix, int seg_pixels,
+                                                   const uint8_t* __restrict__ anchor, T* __restrict__ counts,
+                                                   size_t img_stride) {
+  __shared__ uint32_t h[16 * kCtx * 256];
+  const int tid = threadIdx.x, part = blockIdx.y, img = blockIdx.z;
+  for (int i = tid; i < 16 * kCtx * 256; i += 256) h[i] = 0;
+  __syncthreads();
+  const int p = blockIdx.x * 256 + tid;
+  if (p < npix) {
+    const uint8_t* at = z + ((size_t)img * npix + p) * kCh + 16 * part;
+    const bool first = p % seg_pixels == 0;
+    const uint4 v = *(const uint4*)at;
+    uint4 u = make_uint4(0, 0, 0, 0);
+    if (!first) u = *(const uint4*)(at - kCh);  // p >= 1 here
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w}, l[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+    for (int b = 0; b < 16; ++b) {
+      const uint32_t s = (w[b >> 2] >> (8 * (b & 3))) & 255u, left = (l[b >> 2] >> (8 * (b & 3))) & 255u;
+      const uint32_t k = first ? 0u : ctx_of(left, anchor[16 * part + b]);
+      atomicAdd(&h[(b * kCtx + k) * 256 + s], 1u);
+    }
+  }
+  __syncthreads();
+  T* dst = counts + (size_t)img * img_stride + (size_t)(16 * part) * kCtx * 256;
+  for (int i = tid; i < 16 * kCtx * 256; i += 256)
+    if (h[i]) atomicAdd(&dst[i], (T)h[i]);
+}
+
+// ---- version-3 encode 2: tables and the per-channel choice.  grid (96, n), block 64 ------------
+// counts: the image's [96][3][256]; their sum over the contexts is version 1's histogram.  own as
+// in rans2_tables; prior = sum over the contexts of c_k cost16[f[c][k]].  Writes the channel's three
+// cumulative rows: the context prior's, or its own row three times.
+__global__ __launch_bounds__(64) void rans3_tables(const uint32_t* __restrict__ counts, int npix,
+                                                    const uint16_t* __restrict__ prior_freq,
+                                                    const uint16_t* __restrict__ prior_cum, const uint32_t* __restrict__ cost16,
+                                                    uint16_t* __restrict__ cum, uint8_t* __restrict__ tab,
+                                                    uint32_t* __restrict__ tablen, uint32_t* __restrict__ keep) {
+  const int lane = threadIdx.x, c = blockIdx.x, img = blockIdx.y;
+  const size_t row = (size_t)img * kCh + c;
+  uint32_t cnt[4] = {0, 0, 0, 0};
+  unsigned long long pri = 0;
+#pragma unroll
+  for (int k = 0; k < kCtx; ++k) {
+    const uint4 cv = ((const uint4*)(counts + (row * kCtx + k) * 256))[lane];
+    const uint32_t ck[4] = {cv.x, cv.y, cv.z, cv.w};
+    const uint2 pv = ((const uint2*)(prior_freq + ((size_t)c * kCtx + k) * 256))[lane];  // each in 1..4096 (checked on upload)
+    const uint32_t pf[4] = {pv.x & 0xffffu, pv.x >> 16, pv.y & 0xffffu, pv.y >> 16};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      cnt[j] += ck[j];
+      pri += (unsigned long long)ck[j] * cost16[min(pf[j], kProbScale)];
+    }
+  }
+  uint32_t f[4], used;
+  normalise_own(cnt, npix, lane, f, used);
+  unsigned long long own = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) own += (unsigned long long)cnt[j] * cost16[f[j]];  // f <= 4096; cost16[0] = 0 (and c = 0 there)
+  const uint32_t nsym = wave_sum(used);
+  own = wave_sum64(own) + ((unsigned long long)(8u * (1u + 3u * nsym)) << 16);
+  pri = wave_sum64(pri);
+  uint16_t* crow = cum + (size_t)img * kCtxWords + (size_t)c * kCtx * kCtxRow;
+  if (own < pri) {  // wave-uniform
+#pragma unroll
+    for (int k = 0; k < kCtx; ++k) write_cum(f, lane, crow + k * kCtxRow);
+    write_table(f, used, lane, tab + row * kTabRow, tablen + row);
+    if (lane == 0) keep[row] = 1u;
+  } else {
+    const uint16_t* prow = prior_cum + (size_t)c * kCtx * kCtxRow;
+#pragma unroll
+    for (int k = 0; k < kCtx; ++k) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) crow[k * kCtxRow + 4 * lane + j] = prow[k * kCtxRow + 4 * lane + j];
+      if (lane == 63) crow[k * kCtxRow + 256] = prow[k * kCtxRow + 256];
+    }
+    if (lane == 0) {
+      tablen[row] = 0u;
+      keep[row] = 0u;
+    }
+  }
+}
+
+// the image's 288 rows into LDS (kCtxWords u16 = 40,032 dwords; the pad of a row is copied, never read)
+__device__ __forceinline__ void load_ctx_rows(uint16_t* lds, const uint16_t* __restrict__ src, int tid, int nthreads) {
+  const uint32_t* s = (const uint32_t*)src;  // kCtxWords is even and every image's rows start 4-B aligned
+  uint32_t* d = (uint32_t*)lds;
+  for (int i = tid; i < kCtxWords / 2; i += nthreads) d[i] = s[i];
+}
+
+// ---- version-3 encode 3: segment coding, one lane per segment -----------------------------------
+// rans_encode_segments with the row chosen per symbol.  The lane walks from its last pixel to its
+// first, so beside the 16 bytes of pixel p it loads the same 16 bytes of pixel p - 1 (its first
+// pixel has none: context 0).  The lanes of the wave are at one channel, in up to three rows.
+__global__ __launch_bounds__(64) void rans3_encode_segments(const uint8_t* __restrict__ z, int npix, int seg_pixels, int nseg,
+                                                             const uint16_t* __restrict__ cum,
+                                                             const uint8_t* __restrict__ anchor, uint8_t* __restrict__ scratch,
+                                                             uint32_t cap, uint32_t* __restrict__ seglen) {
+  __shared__ uint16_t start[kCtxWords];
+  const int lane = threadIdx.x, img = blockIdx.y;
+  load_ctx_rows(start, cum + (size_t)img * kCtxWords, lane, 64);
+  __syncthreads();
+  const int seg = blockIdx.x * 64 + lane;
+  const bool live = seg < nseg;
+  const int p0 = live ? seg * seg_pixels : 0;
+  const int mypix = live ? min(seg_pixels, npix - p0) : 0;
+  const uint8_t* src = z + ((size_t)img * npix + p0) * kCh;
+  uint8_t* region = scratch + ((size_t)img * nseg + (live ? seg : 0)) * cap;
+  uint32_t pos = cap, x = kRansL;
+  auto emit = [&](uint32_t b) {
+    if (pos > 0) region[--pos] = (uint8_t)b;  // pos > 0 always holds: cap is the worst case
+  };
+  int maxpix = mypix;  // wave-uniform trip count
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) maxpix = max(maxpix, __shfl_xor(maxpix, o, 64));
+  for (int p = maxpix - 1; p >= 0; --p) {
+    const bool on = p < mypix;
+    for (int q = 5; q >= 0; --q) {
+      uint4 v = make_uint4(0, 0, 0, 0), u = make_uint4(0, 0, 0, 0);
+      if (on) v = *(const uint4*)(src + (size_t)p * kCh + 16 * q);
+      if (on && p > 0) u = *(const uint4*)(src + (size_t)(p - 1) * kCh + 16 * q);
+      const uint32_t w[4] = {v.x, v.y, v.z, v.w}, l[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+      for (int b = 15; b >= 0; --b) {
+        const uint32_t s = (w[b >> 2] >> (8 * (b & 3))) & 255u, left = (l[b >> 2] >> (8 * (b & 3))) & 255u;
+        const uint32_t k = p > 0 ? ctx_of(left, anchor[16 * q + b]) : 0u;
+        const uint16_t* row = start + ((16 * q + b) * kCtx + k) * kCtxRow;
+        const uint32_t lo = row[s], freq = row[s + 1] - lo;
+        // freq == 4096: the row's only symbol, x is unchanged and nothing is emitted
+        if (on && freq != kProbScale) {
+          const uint32_t xmax = freq << 19;
+          if (x >= xmax) {
+            emit(x & 255u);
+            x >>= 8;
+            if (x >= xmax) {
+              emit(x & 255u);
+              x >>= 8;
+            }
+          }
+          const uint32_t qd = x / freq;
+          x = (qd << kProbBits) + (x - qd * freq) + lo;
+        }
+      }
+    }
+  }
+  if (live) {
+    emit(x & 255u);
+    emit((x >> 8) & 255u);
+    emit((x >> 16) & 255u);
+    emit(x >> 24);
+    seglen[(size_t)img * nseg + seg] = cap - pos;
+  }
+}
+
+// ---- version-3 decode 1: parse.  grid (n), block 256 ------------------------------------------
+// rans2_parse's rules with version byte 3 and three rows per channel: a masked channel's table is
+// walked once and stored into all three, the other channels' rows are copies of the context prior's.
+__global__ __launch_bounds__(256) void rans3_parse(const uint8_t* __restrict__ files, long long stride,
+                                                    const long long* __restrict__ sizes, int h8, int w8,
+                                                    const uint16_t* __restrict__ prior_cum, uint32_t prior_id,
+                                                    uint16_t* __restrict__ cum, uint32_t* __restrict__ seglen,
+                                                    uint32_t* __restrict__ segoff, int maxseg, uint32_t* __restrict__ meta,
+                                                    int* __restrict__ status) {
+  __shared__ uint32_t sh[257];
+  __shared__ uint32_t choff[kCh + 1];
+  __shared__ uint32_t own[kCh];
+  __shared__ int s_bad, s_nseg;
+  const int tid = threadIdx.x, img = blockIdx.x;
+  const uint8_t* f = files + (size_t)img * (size_t)stride;
+  long long sz = sizes[img];
+  sz = sz < 0 ? 0 : (sz > stride ? stride : sz);
+  sz = sz > 0x7fffffffll ? 0x7fffffffll : sz;
+  const uint32_t size = (uint32_t)sz;
+  auto rd = [&](uint32_t i) -> uint32_t { return i < size ? (uint32_t)f[i] : 0u; };
+  auto rd32 = [&](uint32_t i) -> uint32_t { return rd(i) | (rd(i + 1) << 8) | (rd(i + 2) << 16) | (rd(i + 3) << 24); };
+  const int npix = h8 * w8;
+  if (tid == 0) {
+    const uint32_t S = rd(6) | (rd(7) << 8);
+    const uint32_t fh = rd32(8), fw = rd32(12), H = rd32(16), W = rd32(20), pid = rd32(24);
+    const bool ok = size >= (uint32_t)kHeader2 && rd(0) == 'N' && rd(1) == 'I' && rd(2) == 'C' && rd(3) == 'R' && rd(4) == 3 &&
+                    rd(5) == (uint32_t)kProbBits && S >= 1 && fh == (uint32_t)h8 && fw == (uint32_t)w8 &&
+                    (H >> 3) + ((H & 7u) != 0u) == fh && (W >> 3) + ((W & 7u) != 0u) == fw;
+    const bool mine = pid == prior_id;
+    const int nseg = ok && mine ? (int)(((uint32_t)npix + S - 1) / S) : 0;  // <= npix = maxseg
+    uint32_t off = kHeader2;
+    for (int c = 0; c < kCh; ++c) {
+      choff[c] = off;
+      own[c] = (rd(28 + (c >> 3)) >> (c & 7)) & 1u;
+      if (own[c]) off += 1 + 3 * (rd(off) + 1);  // <= 40 + 96 * 769
+    }
+    choff[kCh] = off;
+    s_nseg = nseg;
+    s_bad = !ok ? 2 : (mine ? 0 : 8);
+    meta[4 * img + 0] = (uint32_t)nseg;
+    meta[4 * img + 1] = ok ? S : 1u;
+    meta[4 * img + 2] = min(off + 4u * (uint32_t)nseg, size);
+    meta[4 * img + 3] = size;
+  }
+  __syncthreads();
+  const int nseg = s_nseg;
+  uint16_t* rows = cum + (size_t)img * kCtxWords;
+  if (nseg > 0 && tid < kCh && own[tid]) {
+    uint16_t* row = rows + tid * kCtx * kCtxRow;
+    const uint32_t base = choff[tid], nsym = rd(base) + 1;
+    uint32_t e = 0, run = 0, es = rd(base + 1), ef = rd(base + 2) | (rd(base + 3) << 8);
+    for (uint32_t s = 0; s < 256; ++s) {
+#pragma unroll
+      for (int k = 0; k < kCtx; ++k) row[k * kCtxRow + s] = (uint16_t)run;
+      if (e < nsym && es == s) {
+        run = min(run + ef, kProbScale);
+        ++e;
+        es = rd(base + 1 + 3 * e);
+        ef = rd(base + 2 + 3 * e) | (rd(base + 3 + 3 * e) << 8);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < kCtx; ++k) row[k * kCtxRow + 256] = (uint16_t)kProbScale;
+    if (e != nsym || run != kProbScale) atomicOr(&s_bad, 4);
+  }
+  if (nseg > 0)  // the prior's rows (start[0] = 0, non-decreasing, start[256] = 4096 by construction)
+    for (int i = tid; i < kCtxWords; i += 256)
+      if (!own[i / (kCtx * kCtxRow)] && i % kCtxRow < kCumRow) rows[i] = prior_cum[i];
+  // the segment table -> clamped lengths -> offsets
+  const uint32_t segtab = choff[kCh];
+  uint32_t* len = seglen + (size_t)img * maxseg;
+  for (int k = tid; k < nseg; k += 256) len[k] = rd32(segtab + 4u * (uint32_t)k);  // < 2^31 + 2^27: no wrap
+  __syncthreads();
+  block_offsets(len, nseg, segoff + (size_t)img * (maxseg + 1), size, sh);
+  __syncthreads();
+  if (tid == 0) status[img] = s_bad;
+}
+
+// ---- version-3 decode 2: segments, one lane per segment -----------------------------------------
+// rans_decode_segments with the row chosen per symbol from the pixel decoded before.  That pixel's
+// 96 symbols stay in 24 registers: chunk q of the left pixel is prev[0..3] in every iteration, and
+// the array is rotated by one chunk after it, so every index is static and the q loop stays rolled.
+__global__ __launch_bounds__(64) void rans3_decode_segments(const uint8_t* __restrict__ files, long long stride, int npix,
+                                                             const uint16_t* __restrict__ cum,
+                                                             const uint8_t* __restrict__ anchor,
+                                                             const uint32_t* __restrict__ segoff, int maxseg,
+                                                             const uint32_t* __restrict__ meta, uint8_t* __restrict__ z,
+                                                             int* __restrict__ status) {
+  __shared__ uint16_t start[kCtxWords];
+  const int lane = threadIdx.x, img = blockIdx.y;
+  const int nseg = (int)meta[4 * img + 0];
+  if ((int)blockIdx.x * 64 >= nseg) return;  // block-uniform
+  const int seg_pixels = (int)meta[4 * img + 1];
+  const uint32_t pay = meta[4 * img + 2], size = meta[4 * img + 3];
+  load_ctx_rows(start, cum + (size_t)img * kCtxWords, lane, 64);
+  __syncthreads();
+  const int seg = blockIdx.x * 64 + lane;
+  const bool live = seg < nseg;
+  const long long p0 = live ? (long long)seg * seg_pixels : 0;  // < npix: seg < nseg = ceil(npix / seg_pixels)
+  const int mypix = live ? (int)min((long long)seg_pixels, (long long)npix - p0) : 0;
+  const uint32_t* off = segoff + (size_t)img * (maxseg + 1);
+  const uint32_t begin = live ? min(pay + off[seg], size) : 0u;
+  const uint32_t end = live ? min(pay + off[seg + 1], size) : 0u;
+  const uint8_t* f = files + (size_t)img * (size_t)stride;
+  uint32_t ptr = begin;
+  auto next = [&]() -> uint32_t {
+    const uint32_t b = ptr < end ? (uint32_t)f[ptr] : 0u;
+    ++ptr;  // counts reads past end too: the segment then fails ptr == end
+    return b;
+  };
+  uint32_t x = 0;
+  if (live) {
+    x = next() << 24;
+    x |= next() << 16;
+    x |= next() << 8;
+    x |= next();
+  }
+  uint8_t* dst = z + ((size_t)img * npix + (size_t)p0) * kCh;
+  int maxpix = mypix;  // wave-uniform trip count
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) maxpix = max(maxpix, __shfl_xor(maxpix, o, 64));
+  uint32_t prev[24];
+#pragma unroll
+  for (int i = 0; i < 24; ++i) prev[i] = 0;
+  for (int p = 0; p < maxpix; ++p) {
+    const bool on = p < mypix;
+    for (int q = 0; q < 6; ++q) {
+      uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int b = 0; b < 16; ++b) {
+        const uint32_t left = (prev[b >> 2] >> (8 * (b & 3))) & 255u;
+        const uint32_t k = p > 0 ? ctx_of(left, anchor[16 * q + b]) : 0u;  // k <= 2: the row is one of the image's 288
+        const uint16_t* row = start + ((16 * q + b) * kCtx + k) * kCtxRow;
+        const uint32_t slot = x & (kProbScale - 1);
+        // largest s with row[s] <= slot: row[0] = 0 <= slot < 4096 = row[256]
+        uint32_t s = 0;
+#pragma unroll
+        for (uint32_t step = 128; step > 0; step >>= 1)
+          if (row[s + step] <= slot) s += step;
+        const uint32_t lo = row[s], freq = row[s + 1] - lo;
+        if (on) {  // a lane past its last pixel keeps its final state
+          x = freq * (x >> kProbBits) + slot - lo;
+          if (x < kRansL) {
+            x = (x << 8) | next();
+            if (x < kRansL) x = (x << 8) | next();
+          }
+        }
+        w[b >> 2] |= s << (8 * (b & 3));
+      }
+      if (on) *(uint4*)(dst + (size_t)p * kCh + 16 * q) = make_uint4(w[0], w[1], w[2], w[3]);
+#pragma unroll
+      for (int i = 0; i < 20; ++i) prev[i] = prev[i + 4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) prev[20 + i] = w[i];
+    }
+  }
+  if (live && !(x == kRansL && ptr == end)) atomicOr(&status[img], 1);
+}
+
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
@@ -713,7 +1056,7 @@ bool rans_shape_ok(int h8, int w8) {
   return h8 > 0 && w8 > 0 && (long long)h8 * w8 <= (1ll << 23);
 }
 
-void rans_plan(int n, int h8, int w8, int seg_pixels, bool decode, RansPlan* pl, bool v2) {
+void rans_plan(int n, int h8, int w8, int seg_pixels, bool decode, RansPlan* pl, int ver) {
   const size_t npix = (size_t)h8 * w8, N = (size_t)n;
   const int S = decode ? 1 : seg_pixels;  // decode sizes its offsets for the smallest segments
   pl->nseg = (int)((npix + S - 1) / S);
@@ -726,12 +1069,12 @@ void rans_plan(int n, int h8, int w8, int seg_pixels, bool decode, RansPlan* pl,
     o += align256(bytes);
     return at;
   };
-  pl->counts = take(decode ? 0 : N * kCh * 256 * 4);
-  pl->cum = take(N * kCumWords * 2);
+  pl->counts = take(decode ? 0 : N * kCh * 256 * 4 * (ver == 3 ? kCtx : 1));
+  pl->cum = take(N * (ver == 3 ? kCtxWords : kCumWords) * 2);
   pl->tab = take(decode ? 0 : N * kCh * kTabRow);
   pl->tablen = take(decode ? 0 : N * kCh * 4);
   pl->taboff = take(decode ? 0 : N * (kCh + 1) * 4);
-  pl->keep = take(decode || !v2 ? 0 : N * kCh * 4);
+  pl->keep = take(decode || ver == 1 ? 0 : N * kCh * 4);
   pl->seglen = take(N * pl->nseg * 4);
   pl->segoff = take(N * ((size_t)pl->nseg + 1) * 4);
   pl->meta = take(decode ? N * 16 : 0);
@@ -781,6 +1124,66 @@ hipError_t launch_rans_prior_count(const uint8_t* z, int n, int h8, int w8, unsi
 
 hipError_t launch_rans_prior_build(const unsigned long long* counts, uint16_t* freqs, hipStream_t st) {
   rans_prior_normalise<<<dim3(kCh), 64, 0, st>>>(counts, freqs);
+  return hipGetLastError();
+}
+
+hipError_t launch_rans_cprior_count(const uint8_t* z, int n, int h8, int w8, int seg_pixels, const uint8_t* anchor,
+                                    unsigned long long* counts, hipStream_t st) {
+  const int npix = h8 * w8;
+  rans3_hist<unsigned long long><<<dim3((npix + 255) / 256, 6, n), 256, 0, st>>>(z, npix, seg_pixels, anchor, counts, 0);
+  return hipGetLastError();
+}
+
+hipError_t launch_rans_cprior_build(const unsigned long long* counts, uint16_t* freqs, hipStream_t st) {
+  rans_prior_normalise<<<dim3(kCh * kCtx), 64, 0, st>>>(counts, freqs);
+  return hipGetLastError();
+}
+
+size_t rans_cprior_bytes(size_t* cum_at, size_t* anchor_at, size_t* cost_at) {
+  *cum_at = (size_t)kCh * kCtx * 256 * 2;
+  *anchor_at = *cum_at + (size_t)kCtxWords * 2;
+  *cost_at = *anchor_at + kCh;  // a multiple of 4
+  return *cost_at + (kProbScale + 1) * 4;
+}
+
+int rans_cprior_row_pitch() { return kCtxRow; }
+
+hipError_t launch_rans3_encode(const uint8_t* z, int n, int h8, int w8, int H, int W, int seg_pixels, const RansCPrior& pr,
+                               char* ws, const RansPlan& pl, uint8_t* out, long long stride, long long* sizes, hipStream_t st) {
+  const int npix = h8 * w8, nseg = pl.nseg;
+  uint32_t* counts = (uint32_t*)(ws + pl.counts);
+  uint16_t* cum = (uint16_t*)(ws + pl.cum);
+  uint8_t* tab = (uint8_t*)(ws + pl.tab);
+  uint32_t* tablen = (uint32_t*)(ws + pl.tablen);
+  uint32_t* taboff = (uint32_t*)(ws + pl.taboff);
+  uint32_t* keep = (uint32_t*)(ws + pl.keep);
+  uint32_t* seglen = (uint32_t*)(ws + pl.seglen);
+  uint32_t* segoff = (uint32_t*)(ws + pl.segoff);
+  uint8_t* scratch = (uint8_t*)(ws + pl.scratch);
+  hipError_t e = hipMemsetAsync(counts, 0, (size_t)n * kCh * kCtx * 256 * 4, st);
+  if (e != hipSuccess) return e;
+  rans3_hist<uint32_t><<<dim3((npix + 255) / 256, 6, n), 256, 0, st>>>(z, npix, seg_pixels, pr.anchor, counts,
+                                                                       (size_t)kCh * kCtx * 256);
+  rans3_tables<<<dim3(kCh, n), 64, 0, st>>>(counts, npix, pr.freq, pr.cum, pr.cost16, cum, tab, tablen, keep);
+  rans3_encode_segments<<<dim3((nseg + 63) / 64, n), 64, 0, st>>>(z, npix, seg_pixels, nseg, cum, pr.anchor, scratch, pl.cap,
+                                                                  seglen);
+  rans_layout<3><<<dim3(n), 256, 0, st>>>(tablen, taboff, seglen, segoff, nseg, sizes);
+  rans_assemble<3><<<dim3((kCh + nseg + 3) / 4, n), 256, 0, st>>>(tab, tablen, taboff, scratch, pl.cap, seglen, segoff, nseg,
+                                                                 seg_pixels, h8, w8, out, stride, (uint32_t)H, (uint32_t)W,
+                                                                 pr.id, keep);
+  return hipGetLastError();
+}
+
+hipError_t launch_rans3_decode(const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8,
+                               const RansCPrior& pr, char* ws, const RansPlan& pl, uint8_t* z, int* status, hipStream_t st) {
+  const int npix = h8 * w8, maxseg = pl.nseg;
+  uint16_t* cum = (uint16_t*)(ws + pl.cum);
+  uint32_t* seglen = (uint32_t*)(ws + pl.seglen);
+  uint32_t* segoff = (uint32_t*)(ws + pl.segoff);
+  uint32_t* meta = (uint32_t*)(ws + pl.meta);
+  rans3_parse<<<dim3(n), 256, 0, st>>>(files, stride, sizes, h8, w8, pr.cum, pr.id, cum, seglen, segoff, maxseg, meta, status);
+  rans3_decode_segments<<<dim3((maxseg + 63) / 64, n), 64, 0, st>>>(files, stride, npix, cum, pr.anchor, segoff, maxseg, meta, z,
+                                                                    status);
   return hipGetLastError();
 }
 
@@ -935,50 +1338,59 @@ int nic_rans2_bound(int h8, int w8, int seg_pixels, int64_t* bytes) {
   return rc;
 }
 
-int nic_rans2_inspect(const uint8_t* f, int64_t size, int* h8, int* w8, int* seg_pixels, int* H, int* W, uint32_t* prior_id) {
-  char msg[160];
+}  // extern "C"
+
+// nic_rans_inspect's checks on a file with the 40-byte header (version 2 or 3: tables of the masked
+// channels only) plus the H / W relation; every output nullable
+static int inspect_prior_file(const char* fn, int ver, const uint8_t* f, int64_t size, int* h8, int* w8, int* seg_pixels, int* H, int* W,
+                              uint32_t* prior_id) {
+  char msg[200], text[160];
   auto corrupt = [&](const char* what, long long a = 0, long long b = 0) {
-    snprintf(msg, sizeof(msg), what, a, b);
+    snprintf(text, sizeof(text), what, a, b);
+    snprintf(msg, sizeof(msg), "%s: %s", fn, text);
     return nic::set_error(NIC_ECORRUPT, msg);
   };
-  if (!f) return nic::set_error(NIC_EINVAL, "nic_rans2_inspect: file is NULL");
-  if (size < nic::kHeader) return corrupt("nic_rans2_inspect: %lld bytes are less than the 40-byte header", size);
-  if (std::memcmp(f, "NICR", 4) != 0) return corrupt("nic_rans2_inspect: bad magic");
-  if (f[4] != 2) return corrupt("nic_rans2_inspect: version %lld, expected 2", f[4]);
-  if (size < nic::kHeader2) return corrupt("nic_rans2_inspect: %lld bytes are less than the 40-byte header", size);
-  if (f[5] != nic::kProbBits) return corrupt("nic_rans2_inspect: %lld probability bits, expected 12", f[5]);
+  if (!f) {
+    snprintf(msg, sizeof(msg), "%s: file is NULL", fn);
+    return nic::set_error(NIC_EINVAL, msg);
+  }
+  if (size < nic::kHeader) return corrupt("%lld bytes are less than the 40-byte header", size);
+  if (std::memcmp(f, "NICR", 4) != 0) return corrupt("bad magic");
+  if (f[4] != ver) return corrupt("version %lld, expected %lld", f[4], ver);
+  if (size < nic::kHeader2) return corrupt("%lld bytes are less than the 40-byte header", size);
+  if (f[5] != nic::kProbBits) return corrupt("%lld probability bits, expected 12", f[5]);
   auto u32 = [&](int64_t at) { return (uint32_t)f[at] | ((uint32_t)f[at + 1] << 8) | ((uint32_t)f[at + 2] << 16) | ((uint32_t)f[at + 3] << 24); };
   const uint32_t S = (uint32_t)f[6] | ((uint32_t)f[7] << 8), fh = u32(8), fw = u32(12), ih = u32(16), iw = u32(20);
-  if (S == 0) return corrupt("nic_rans2_inspect: seg_pixels is 0");
+  if (S == 0) return corrupt("seg_pixels is 0");
   if (fh == 0 || fw == 0 || fh > (1u << 23) || fw > (1u << 23) || !nic::rans_shape_ok((int)fh, (int)fw))
-    return corrupt("nic_rans2_inspect: latent size %lld x %lld out of range", fh, fw);
-  if ((ih >> 3) + ((ih & 7u) != 0u) != fh) return corrupt("nic_rans2_inspect: image height %lld does not give h8 = %lld", ih, fh);
-  if ((iw >> 3) + ((iw & 7u) != 0u) != fw) return corrupt("nic_rans2_inspect: image width %lld does not give w8 = %lld", iw, fw);
+    return corrupt("latent size %lld x %lld out of range", fh, fw);
+  if ((ih >> 3) + ((ih & 7u) != 0u) != fh) return corrupt("image height %lld does not give h8 = %lld", ih, fh);
+  if ((iw >> 3) + ((iw & 7u) != 0u) != fw) return corrupt("image width %lld does not give w8 = %lld", iw, fw);
   int64_t at = nic::kHeader2;
   for (int c = 0; c < nic::kCh; ++c) {
-    if (!((f[28 + (c >> 3)] >> (c & 7)) & 1)) continue;  // the prior's row
-    if (at >= size) return corrupt("nic_rans2_inspect: truncated in the table of channel %lld", c);
+    if (!((f[28 + (c >> 3)] >> (c & 7)) & 1)) continue;  // the prior's row(s)
+    if (at >= size) return corrupt("truncated in the table of channel %lld", c);
     const int nsym = f[at] + 1;
-    if (at + 1 + 3 * nsym > size) return corrupt("nic_rans2_inspect: truncated in the table of channel %lld", c);
+    if (at + 1 + 3 * nsym > size) return corrupt("truncated in the table of channel %lld", c);
     int prev = -1;
     uint32_t sum = 0;
     for (int e = 0; e < nsym; ++e) {
       const int s = f[at + 1 + 3 * e];
       const uint32_t fr = (uint32_t)f[at + 2 + 3 * e] | ((uint32_t)f[at + 3 + 3 * e] << 8);
-      if (s <= prev) return corrupt("nic_rans2_inspect: channel %lld: symbols not strictly ascending", c);
-      if (fr < 1 || fr > nic::kProbScale) return corrupt("nic_rans2_inspect: channel %lld: freq %lld not in 1..4096", c, fr);
+      if (s <= prev) return corrupt("channel %lld: symbols not strictly ascending", c);
+      if (fr < 1 || fr > nic::kProbScale) return corrupt("channel %lld: freq %lld not in 1..4096", c, fr);
       prev = s;
       sum += fr;
     }
-    if (sum != nic::kProbScale) return corrupt("nic_rans2_inspect: channel %lld: freqs sum to %lld, not 4096", c, sum);
+    if (sum != nic::kProbScale) return corrupt("channel %lld: freqs sum to %lld, not 4096", c, sum);
     at += 1 + 3 * nsym;
   }
   const int64_t npix = (int64_t)fh * fw, nseg = (npix + S - 1) / S;
-  if (at + 4 * nseg > size) return corrupt("nic_rans2_inspect: truncated in the segment table");
+  if (at + 4 * nseg > size) return corrupt("truncated in the segment table");
   int64_t pay = 0;
   for (int64_t k = 0; k < nseg; ++k) pay += u32(at + 4 * k);
   if (at + 4 * nseg + pay != size)
-    return corrupt("nic_rans2_inspect: header, tables and segments need %lld bytes, the file has %lld", at + 4 * nseg + pay, size);
+    return corrupt("header, tables and segments need %lld bytes, the file has %lld", at + 4 * nseg + pay, size);
   if (h8) *h8 = (int)fh;
   if (w8) *w8 = (int)fw;
   if (seg_pixels) *seg_pixels = (int)S;
@@ -986,6 +1398,55 @@ int nic_rans2_inspect(const uint8_t* f, int64_t size, int* h8, int* w8, int* seg
   if (W) *W = (int)iw;
   if (prior_id) *prior_id = u32(24);
   return NIC_OK;
+}
+
+
+extern "C" {
+
+int nic_rans2_inspect(const uint8_t* f, int64_t size, int* h8, int* w8, int* seg_pixels, int* H, int* W, uint32_t* prior_id) {
+  return inspect_prior_file("nic_rans2_inspect", 2, f, size, h8, w8, seg_pixels, H, W, prior_id);
+}
+
+int nic_rans_cprior_check(const uint8_t* anchors, const uint16_t* freqs, uint32_t* id) {
+  char msg[160];
+  if (!anchors || !freqs) return nic::set_error(NIC_EINVAL, "nic_rans_cprior_check: anchors or freqs is NULL");
+  for (int c = 0; c < nic::kCh; ++c)
+    for (int k = 0; k < nic::kCtx; ++k) {
+      const uint16_t* row = freqs + ((size_t)c * nic::kCtx + k) * 256;
+      uint32_t sum = 0;
+      for (int s = 0; s < 256; ++s) {
+        const uint32_t fr = row[s];
+        if (fr < 1 || fr > nic::kProbScale) {
+          snprintf(msg, sizeof(msg), "nic_rans_cprior_check: channel %d context %d: freq %u of symbol %d not in 1..4096", c, k, fr, s);
+          return nic::set_error(NIC_ECORRUPT, msg);
+        }
+        sum += fr;
+      }
+      if (sum != nic::kProbScale) {
+        snprintf(msg, sizeof(msg), "nic_rans_cprior_check: channel %d context %d: freqs sum to %u, not 4096", c, k, sum);
+        return nic::set_error(NIC_ECORRUPT, msg);
+      }
+    }
+  if (id) {  // CRC-32 of the anchors, then the freqs as little-endian u16: channel-major, then context, then symbol
+    uint8_t le[512];
+    uLong crc = crc32(0L, Z_NULL, 0);
+    crc = crc32(crc, anchors, nic::kCh);
+    for (int r = 0; r < nic::kCh * nic::kCtx; ++r) {
+      for (int s = 0; s < 256; ++s) {
+        le[2 * s] = (uint8_t)(freqs[r * 256 + s] & 255u);
+        le[2 * s + 1] = (uint8_t)(freqs[r * 256 + s] >> 8);
+      }
+      crc = crc32(crc, le, sizeof(le));
+    }
+    *id = (uint32_t)crc;
+  }
+  return NIC_OK;
+}
+
+int nic_rans3_bound(int h8, int w8, int seg_pixels, int64_t* bytes) { return nic_rans2_bound(h8, w8, seg_pixels, bytes); }
+
+int nic_rans3_inspect(const uint8_t* f, int64_t size, int* h8, int* w8, int* seg_pixels, int* H, int* W, uint32_t* prior_id) {
+  return inspect_prior_file("nic_rans3_inspect", 3, f, size, h8, w8, seg_pixels, H, W, prior_id);
 }
 
 }  // extern "C"
