@@ -358,6 +358,53 @@ int nic_rans3_decode(nic_ctx* ctx, const uint8_t* files, int64_t stride, const i
 int nic_rans3_inspect(const uint8_t* host_file, int64_t size, int* h8, int* w8, int* seg_pixels, int* H, int* W,
                       uint32_t* prior_id);
 
+/* ---- Region decode: a pixel box out of a .nic file (every container version) --------------------
+ * A file's segment table is a random-access index: segment k holds the latent pixels [k S, (k+1) S)
+ * of the row-major order (S = seg_pixels), so a window of the latent needs only the segments that
+ * hold one of its pixels, and the decoder needs only a window of the latent ("Region
+ * decode").
+ *
+ * NIC_DECODE_HALO: the decoder's receptive field, in latent pixels on each side of the latent pixels
+ *     a box touches.  Output pixel o of a stride-2 transposed 5x5 layer (dconv1, dconv7, dconv8) reads
+ *     its input within floor(o/2) +- 1; dconv5 and dconv6 (3x3, stride 1, at twice the latent's
+ *     resolution) read +- 1 each.  So image pixel o reads the 4x level within floor(o/2) +- 1, the 2x
+ *     level within floor(o/4) +- 2 behind dconv7 and +- 4 behind dconv6 and dconv5, and the latent
+ *     within floor(o/8) +- 3.  With 3 the decode of the window, cut at the box, equals the crop of the
+ *     whole decode exactly (a window edge short of 3 is the latent's own edge, with the same zero
+ *     padding behind it); with 2 it does not.
+ * nic_region_plan: HOST only (no GPU, no ctx).  For the box [y, y + bh) x [x, x + bw) of an H x W
+ *     image (0 <= y, bh >= 1, y + bh <= H, likewise x; NIC_ESHAPE otherwise) with h8 = ceil(H/8),
+ *     w8 = ceil(W/8):  ry0 = y / 8, ry1 = (y + bh - 1) / 8 + 1, r0 = max(0, ry0 - 3), r1 = min(h8,
+ *     ry1 + 3), likewise c0, c1.  win4 = {r0, c0, r1 - r0, c1 - c0}: the latent window with its halo,
+ *     clamped to the latent; off2 = {y - 8 r0, x - 8 c0}: where the box starts in the window's
+ *     reconstruction (8 rows x 8 cols pixels).  NIC_EINVAL for a NULL output.
+ * nic_rans_window_segments: HOST only.  The number of distinct segments that hold a latent pixel of
+ *     the window (r0, c0, rows, cols) of an (h8, w8) latent under seg_pixels: the segment state
+ *     machines a window decode runs (a segment may cross row ends).  The window must lie inside the
+ *     latent (NIC_ESHAPE); count NULL: NIC_EINVAL.
+ * nic_rans_decode_window / nic_rans2_decode_window / nic_rans3_decode_window: as nic_rans_decode /
+ *     nic_rans2_decode / nic_rans3_decode -- n whole files of one (h8, w8), the same parse on the
+ *     device, the same workspace (nic_rans*_reserve of (n, h8, w8) covers it), `stream`, no host
+ *     synchronisation -- but only the segments that hold a pixel of the window r0, c0 >= 0, rows,
+ *     cols >= 1, r0 + rows <= h8, c0 + cols <= w8 (NIC_ESHAPE otherwise) are decoded, each from its
+ *     first pixel to its last, and latent_win (n, rows, cols, 96) u8 (16-byte aligned) receives the
+ *     window: latent_win[i][a][b] = latent[i][r0 + a][c0 + b].  status[i]: bits 1, 2 and 3 as in the
+ *     full decode (an image refused with bit 1 or bit 3 leaves its latent_win unwritten); bit 0
+ *     covers only the segments that were decoded -- damage in a segment outside the window is
+ *     neither seen nor reported.  File reads are clamped to the segment, lookups resolve inside the
+ *     4096 slots, and a lane stores only its own segment's pixels that lie inside the window.
+ * Arguments are validated before any HIP call: shape (the window included), empty batch (OK), NULL,
+ * then the prior (NIC_ENOPRIOR, versions 2 and 3). */
+#define NIC_DECODE_HALO 3
+int nic_region_plan(int H, int W, int y, int x, int bh, int bw, int* win4, int* off2);
+int nic_rans_window_segments(int h8, int w8, int seg_pixels, int r0, int c0, int rows, int cols, int64_t* count);
+int nic_rans_decode_window(nic_ctx* ctx, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, int h8, int w8,
+                           int r0, int c0, int rows, int cols, uint8_t* latent_win, int32_t* status, void* stream);
+int nic_rans2_decode_window(nic_ctx* ctx, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, int h8, int w8,
+                            int r0, int c0, int rows, int cols, uint8_t* latent_win, int32_t* status, void* stream);
+int nic_rans3_decode_window(nic_ctx* ctx, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, int h8, int w8,
+                            int r0, int c0, int rows, int cols, uint8_t* latent_win, int32_t* status, void* stream);
+
 /* ---- The device PNG writer: complete PNG files written on the device --------------------------
  * An optional writer for reconstructions (Pillow's optimize=True file, nic_png_encode, stays the
  * default and the bitstream's format).  Format: DESIGN.md, "The device PNG writer":

@@ -204,10 +204,10 @@ def nic_files(codec, z, seg_pixels: int = NIC_SEG_PIXELS, size=None) -> List[byt
     return [host[i, :sizes[i]].tobytes() for i in range(host.shape[0])]
 
 
-def _inspect_any(codec, i: int, data: bytes):
+def _inspect_any(codec, i: int, data: bytes, who: str = "read_nic"):
     """The decode group and the image size of file i: byte 4 says which version's checks apply.
     A version-2 file also needs the codec's prior to be the one it was written under, a version-3
-    file the codec's context prior."""
+    file the codec's context prior.  who: the caller named in the ValueError."""
     try:
         if len(data) > 4 and data[4] in (2, 3):
             ver = data[4]
@@ -220,7 +220,7 @@ def _inspect_any(codec, i: int, data: bytes):
         h8, w8, sp = nic_inspect(data)
         return (1, h8, w8, sp), (8 * h8, 8 * w8)
     except ValueError as e:
-        raise ValueError(f"read_nic: file {i}: {e}") from None
+        raise ValueError(f"{who}: file {i}: {e}") from None
 
 
 def read_nic_sizes(codec, files: Sequence[bytes]) -> List[Tuple[int, int]]:
@@ -260,6 +260,101 @@ def read_nic(codec, files: Sequence[bytes], sizes: bool = False) -> list:
         for r, i in enumerate(idx):
             out[i] = z[r]
     return (out, hw) if sizes else out
+
+
+def _upload_files(codec, files: Sequence[bytes]):
+    """The files as one zero-padded (N, stride) u8 device tensor and their (N,) int64 sizes."""
+    import torch
+
+    stride = max(len(d) for d in files)
+    host = np.zeros((len(files), stride), np.uint8)
+    for r, d in enumerate(files):
+        host[r, :len(d)] = np.frombuffer(d, np.uint8)
+    lens = torch.tensor([len(d) for d in files], dtype=torch.int64)
+    dev = f"cuda:{codec.device}"
+    return torch.from_numpy(host).to(dev), lens.to(dev)
+
+
+def _group_text(key) -> str:
+    return f"version {key[0]}, latent {key[1]}x{key[2]}" + (f", seg_pixels {key[3]}" if key[0] == 1 else "")
+
+
+def read_nic_window(codec, files: Sequence[bytes], window, sizes: bool = False):
+    """The window = (r0, c0, rows, cols) of the latents of .nic files: one (N,rows,cols,96) u8 tensor
+    on the codec's device, read_nic's latents cut to [r0:r0+rows, c0:c0+cols] -- but only the segments
+    that hold a pixel of the window are entropy-decoded (Codec.rans*_decode_window).  The host checks
+    are read_nic's (ValueError naming the file's index).  The files are one device batch: they must
+    share the version and (h8, w8), version-1 files also seg_pixels, as read_nic groups them
+    (ValueError naming the first file that differs from file 0).  Whole files are uploaded.
+    sizes=True: also the files' image sizes, (window latents, [(H, W)])."""
+    import torch
+
+    r0, c0, rows, cols = (int(v) for v in window)
+    keys, hw = [], []
+    for i, data in enumerate(files):
+        key, size = _inspect_any(codec, i, data, "read_nic_window")
+        if keys and key != keys[0]:
+            raise ValueError(f"read_nic_window: file {i}: {_group_text(key)}, but file 0 is {_group_text(keys[0])}: "
+                             "the files of one call must decode as one batch")
+        keys.append(key)
+        hw.append(size)
+    if not files:
+        z = torch.empty((0, max(rows, 0), max(cols, 0), 96), dtype=torch.uint8, device=f"cuda:{codec.device}")
+        return (z, hw) if sizes else z
+    ver, h8, w8 = keys[0][:3]
+    buf, lens = _upload_files(codec, files)
+    try:
+        decode = {1: codec.rans_decode_window, 2: codec.rans2_decode_window, 3: codec.rans3_decode_window}[ver]
+        z = decode(buf, lens, h8, w8, (r0, c0, rows, cols))
+    except ValueError as e:
+        raise ValueError(f"read_nic_window: {e}") from None
+    return (z, hw) if sizes else z
+
+
+def _fits(box, size) -> bool:
+    y, x, h, w = box
+    return y >= 0 and x >= 0 and h >= 1 and w >= 1 and y + h <= size[0] and x + w <= size[1]
+
+
+def _region_of_batch(decoder, files: Sequence[bytes], size, box):
+    """decode_region's device part for files that decode as one batch and whose images hold the box."""
+    codec = decoder.codec
+    window, (oy, ox) = codec.region_plan(size[0], size[1], box)
+    rec = codec.decode(read_nic_window(codec, files, window))
+    return rec[:, oy:oy + box[2], ox:ox + box[3]].contiguous()
+
+
+def decode_region(decoder, files: Sequence, box):
+    """The pixel box = (y, x, h, w) of the images of .nic files (bytes, or paths to read): an (N,h,w,3)
+    u8 tensor on the decoder's device, equal to the box cut out of the whole reconstructions.  The box
+    is checked against every file's recorded H x W (8 h8 x 8 w8 for a version-1 file; ValueError
+    naming the file when it does not fit), Codec.region_plan gives the latent window that holds every
+    latent pixel the box depends on (NIC_DECODE_HALO), read_nic_window entropy-decodes only that
+    window's segments, the decoder runs on the window, and the box is cut on the device.  The files
+    must decode as one batch (read_nic_window)."""
+    import torch
+
+    box = tuple(int(v) for v in box)
+    if len(box) != 4:
+        raise ValueError(f"decode_region: box must be (y, x, h, w), got {box!r}")
+    datas, names = [], []
+    for i, f in enumerate(files):
+        is_path = isinstance(f, (str, os.PathLike))
+        datas.append(_read_bytes(os.fspath(f)) if is_path else bytes(f))
+        names.append(os.fspath(f) if is_path else f"file {i}")
+    hw = []
+    for i, data in enumerate(datas):
+        try:
+            size = _inspect_any(decoder.codec, i, data, "decode_region")[1]
+        except ValueError as e:
+            raise ValueError(f"{names[i]}: {e}") from None
+        if not _fits(box, size):
+            raise ValueError(f"decode_region: {names[i]}: box (y {box[0]}, x {box[1]}, {box[2]} x {box[3]}) does not lie "
+                             f"inside its {size[0]} x {size[1]} image")
+        hw.append(size)
+    if not datas:
+        return torch.empty((0, max(box[2], 0), max(box[3], 0), 3), dtype=torch.uint8, device=f"cuda:{decoder.codec.device}")
+    return _region_of_batch(decoder, datas, hw[0], box)
 
 
 PNG_WRITERS = ("pillow", "device")
@@ -390,7 +485,7 @@ def _set_any_prior(codec, prior) -> None:
 
 def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, in_cshape: int,
               batch_size: int = 64, workers=None, container: str = "png", png_writer: str = "pillow",
-              prior=None) -> None:
+              prior=None, region=None) -> None:
     """utils.py:46-62: every colour image of ``dataset_path`` (sorted; read_dataset's filter)
     through the codec into ``output_dir``, one PNG per image named after its source.
 
@@ -417,17 +512,25 @@ def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, i
     files, which carry each image's true H x W; the decoder side reads directories that mix both
     versions and crops the reconstructions of version-2 files to H x W.  A prior.ContextPrior or
     a ``.nicc`` path does the same with version 3 (a context prior takes precedence on the encoder
-    side when the codec has both).  Without it everything behaves and writes as before."""
+    side when the codec has both).  Without it everything behaves and writes as before.
+
+    ``region`` (a pixel box (y, x, h, w); the decoder side of ``container="nic"`` only, ValueError
+    otherwise: a packed PNG has no index to read a part of): every file is decoded to that box only
+    (use_model_nic_in)."""
     if container not in CONTAINERS:
         raise ValueError(f"container must be one of {CONTAINERS}, got {container!r}")
     _check_png_writer(png_writer, decoder_side=in_cshape == 96)
+    if region is not None and not (container == "nic" and in_cshape == 96):
+        raise ValueError('region applies to the decoder side of container="nic" only: a packed PNG has no index, '
+                         "so a part of it cannot be decoded on its own")
     if prior is not None:
         if container != "nic":
             raise ValueError('prior applies to container="nic" only: the PNG container has no entropy model')
         _set_any_prior(model.codec, prior)
     if container == "nic" and in_cshape == 96:
+        more = {"region": region} if region is not None else {}
         return use_model_nic_in(model, dataset_path, checkpoint_path, output_dir, batch_size=batch_size, workers=workers,
-                                png_writer=png_writer)
+                                png_writer=png_writer, **more)
     extra = {"container": container} if container != "png" else {}
     if png_writer != "pillow":
         extra["png_writer"] = png_writer
@@ -483,7 +586,7 @@ def _read_bytes(path: str) -> bytes:
 
 
 def use_model_nic_in(model, dataset_path: str, checkpoint_path: str, output_dir: str, batch_size: int = 64,
-                     workers=None, png_writer: str = "pillow", prior=None) -> None:
+                     workers=None, png_writer: str = "pillow", prior=None, region=None) -> None:
     """The decoder side of ``container="nic"``: every ``.nic`` file of ``dataset_path`` (sorted)
     -> ``<stem>.png`` reconstructions in ``output_dir``, the same files the PNG route writes.
     The files are read by a pool, checked on the host (nic_rans_inspect) and decoded on the device
@@ -492,11 +595,19 @@ def use_model_nic_in(model, dataset_path: str, checkpoint_path: str, output_dir:
     ``png_writer="device"``: the PNG files are made on the device (png_files_device) and the writer
     thread only writes them.  ``prior``: set on the model's codec first; version-2 files need the
     prior they were written under (ValueError naming the file and both ids otherwise), and their
-    reconstructions are cropped on the device to the H x W they record, before either PNG writer."""
+    reconstructions are cropped on the device to the H x W they record, before either PNG writer.
+    ``region`` (a pixel box (y, x, h, w)): every file is decoded to that box of its image only
+    (decode_region: the segments and the latent window the box needs, not the whole frame) and
+    ``<stem>.png`` holds the box, by either PNG writer; a file whose recorded H x W does not hold the
+    box raises ValueError naming it.  Whole files are still read and uploaded."""
     import torch
     from concurrent.futures import ThreadPoolExecutor
 
     _check_png_writer(png_writer, decoder_side=True)
+    if region is not None:
+        region = tuple(int(v) for v in region)
+        if len(region) != 4:
+            raise ValueError(f"region must be a pixel box (y, x, h, w), got {region!r}")
     if prior is not None:
         _set_any_prior(model.codec, prior)
     os.makedirs(output_dir, exist_ok=True)
@@ -509,6 +620,26 @@ def use_model_nic_in(model, dataset_path: str, checkpoint_path: str, output_dir:
     step = max(1, batch_size)
     with ThreadPoolExecutor(max_workers=min(8, threads)) as readers, ThreadPoolExecutor(max_workers=1) as writer:
         futures = []
+
+        def emit(rec, stems):
+            """The PNG files of the reconstructions rec, a device tensor, by the chosen writer."""
+            if png_writer == "device":
+                pngs = png_files_device(codec, rec)
+                while len(futures) >= WRITES_IN_FLIGHT:
+                    futures.pop(0).result()
+                if serial:
+                    _write_files(pngs, output_dir, stems, ".png")
+                else:
+                    futures.append(writer.submit(_write_files, pngs, output_dir, stems, ".png"))
+                return
+            rec = rec.cpu().numpy()
+            while len(futures) >= WRITES_IN_FLIGHT:
+                futures.pop(0).result()
+            if serial:
+                save_imgs(rec, output_dir, stems, threads=1)
+            else:
+                futures.append(writer.submit(save_imgs, rec, output_dir, stems, png_threads))
+
         chunks = [files[i:i + step] for i in range(0, len(files), step)]
         pending = [readers.map(_read_bytes, [os.path.join(dataset_path, fn) for fn in ch]) for ch in chunks[:2]]
         for k, ch in enumerate(chunks):
@@ -516,32 +647,37 @@ def use_model_nic_in(model, dataset_path: str, checkpoint_path: str, output_dir:
             pending[k] = None
             if k + 2 < len(chunks):  # two chunks of reads in flight ahead of the device
                 pending.append(readers.map(_read_bytes, [os.path.join(dataset_path, fn) for fn in chunks[k + 2]]))
+            names = [fn[:-4] for fn in ch]
+            if region is not None:
+                keys = []
+                for i, data in enumerate(datas):
+                    try:
+                        key, size = _inspect_any(codec, i, data)
+                    except ValueError as e:
+                        raise ValueError(f"{dataset_path}: {ch[i]}: {e}") from None
+                    if not _fits(region, size):
+                        raise ValueError(f"{dataset_path}: {ch[i]}: region (y {region[0]}, x {region[1]}, {region[2]} x "
+                                         f"{region[3]}) does not lie inside its {size[0]} x {size[1]} image")
+                    keys.append(key)
+                for i, j in _batches(keys, step):  # consecutive files that decode as one batch: one plan, one window
+                    try:
+                        rec = _region_of_batch(model, datas[i:j], (8 * keys[i][1], 8 * keys[i][2]), region)
+                    except ValueError as e:  # the device refused an image of the batch: name its file
+                        m = re.search(r"(?:file|image) (\d+)", str(e))
+                        which = ch[i + int(m.group(1))] if m and i + int(m.group(1)) < j else f"files {ch[i]}..{ch[j - 1]}"
+                        raise ValueError(f"{dataset_path}: {which}: {e}") from None
+                    emit(rec, names[i:j])
+                continue
             try:
                 latents, hw = read_nic(codec, datas, sizes=True)
             except ValueError as e:
                 m = re.match(r"read_nic: file (\d+): ", str(e))
                 which = ch[int(m.group(1))] if m else f"files {ch[0]}..{ch[-1]}"
                 raise ValueError(f"{dataset_path}: {which}: {e}") from None
-            names = [fn[:-4] for fn in ch]
             for i, j in _batches([(tuple(z.shape), size) for z, size in zip(latents, hw)], step):
                 rec = model._device_call(torch.stack(latents[i:j]))
                 if hw[i] != tuple(rec.shape[1:3]):  # a version-2 file's own size: the top-left corner
                     rec = rec[:, :hw[i][0], :hw[i][1]].contiguous()
-                if png_writer == "device":
-                    datas = png_files_device(codec, rec)
-                    while len(futures) >= WRITES_IN_FLIGHT:
-                        futures.pop(0).result()
-                    if serial:
-                        _write_files(datas, output_dir, names[i:j], ".png")
-                    else:
-                        futures.append(writer.submit(_write_files, datas, output_dir, names[i:j], ".png"))
-                    continue
-                rec = rec.cpu().numpy()
-                while len(futures) >= WRITES_IN_FLIGHT:
-                    futures.pop(0).result()
-                if serial:
-                    save_imgs(rec, output_dir, names[i:j], threads=1)
-                else:
-                    futures.append(writer.submit(save_imgs, rec, output_dir, names[i:j], png_threads))
+                emit(rec, names[i:j])
         for f in futures:
             f.result()  # re-raise any write error

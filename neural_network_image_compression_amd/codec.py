@@ -565,6 +565,87 @@ class Codec:
             raise ValueError(f"rans3_decode: image {i} is corrupt (status {int(st[i])}; corrupt images: {bad.tolist()})")
         return z
 
+    # -- region decode: a latent window out of .nic files (nic_region_plan, nic_rans*_decode_window) --
+    @staticmethod
+    def region_plan(H: int, W: int, box):
+        """The latent window and the cut for box = (y, x, h, w) of an H x W image (nic_region_plan;
+        host only): ((r0, c0, rows, cols), (off_y, off_x)) -- the window holds every latent pixel
+        the box's pixels depend on, and the box is [off_y : off_y + h, off_x : off_x + w] of the
+        window's reconstruction.  ValueError for a box that does not lie inside the image."""
+        y, x, bh, bw = (int(v) for v in box)
+        win, off = (ctypes.c_int * 4)(), (ctypes.c_int * 2)()
+        _lib.check(_lib.lib().nic_region_plan(int(H), int(W), y, x, bh, bw, win, off), "nic_region_plan")
+        return tuple(win), tuple(off)
+
+    def _decode_window_status(self, ver: int, buf, sizes, h8: int, w8: int, window, out=None):
+        torch = _torch()
+        name = {1: "rans_decode_window", 2: "rans2_decode_window", 3: "rans3_decode_window"}[ver]
+        if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.device.type != "cuda" or buf.ndim != 2:
+            raise TypeError(f"{name}: expected an (N, stride) cuda torch.uint8 tensor of files")
+        if not isinstance(sizes, torch.Tensor) or sizes.dtype != torch.int64 or sizes.shape != (buf.shape[0],):
+            raise TypeError(f"{name}: expected an (N,) torch.int64 tensor of sizes")
+        if buf.device.index != self.device or sizes.device != buf.device:
+            raise ValueError(f"{name}: tensors must be on cuda:{self.device}")
+        r0, c0, rows, cols = (int(v) for v in window)
+        buf, sizes = buf.contiguous(), sizes.contiguous()
+        n, stride = buf.shape
+        if out is None:
+            out = torch.empty((n, max(rows, 0), max(cols, 0), 96), dtype=torch.uint8, device=buf.device)
+        elif (out.dtype != torch.uint8 or tuple(out.shape) != (n, rows, cols, 96) or out.device != buf.device
+              or not out.is_contiguous()):
+            raise TypeError(f"{name}: out must be a contiguous (N,rows,cols,96) torch.uint8 tensor on the codec's device")
+        status = torch.zeros((n,), dtype=torch.int32, device=buf.device)
+        fn = getattr(self._L, "nic_" + name)
+        _lib.check(fn(self._h, buf.data_ptr(), stride, sizes.data_ptr(), n, int(h8), int(w8), r0, c0, rows, cols,
+                      out.data_ptr(), status.data_ptr(), _stream_ptr(torch, self.device)), "nic_" + name)
+        return out, status
+
+    def _decode_window(self, ver: int, buf, sizes, h8: int, w8: int, window):
+        z, status = self._decode_window_status(ver, buf, sizes, h8, w8, window)
+        st = status.cpu().numpy()
+        bad = np.nonzero(st)[0]
+        if bad.size:
+            i = int(bad[0])
+            name = {1: "rans_decode_window", 2: "rans2_decode_window", 3: "rans3_decode_window"}[ver]
+            if st[i] & 8:
+                pid = int.from_bytes(bytes(buf[i, 24:28].cpu().numpy().tolist()), "little")
+                mine = self.prior if ver == 2 else self.context_prior
+                raise ValueError(f"{name}: image {i} was written under prior {pid:08x}, the codec's prior is "
+                                 f"{mine.id:08x} (status {int(st[i])}; refused images: {bad.tolist()})")
+            raise ValueError(f"{name}: image {i} is corrupt (status {int(st[i])}; corrupt images: {bad.tolist()})")
+        return z
+
+    def rans_decode_window_status(self, buf, sizes, h8: int, w8: int, window, out=None):
+        """rans_decode_window without the check: (window latent, status (N,) int32 device tensor).
+        out: the (N,rows,cols,96) u8 tensor to decode into (default: a new one)."""
+        return self._decode_window_status(1, buf, sizes, h8, w8, window, out)
+
+    def rans_decode_window(self, buf, sizes, h8: int, w8: int, window):
+        """The window = (r0, c0, rows, cols) of the (h8, w8) latents of version-1 .nic files
+        buf[i, :sizes[i]] -> (N,rows,cols,96) u8, the slice [:, r0:r0+rows, c0:c0+cols] of rans_decode's
+        result; only the segments that hold a pixel of the window are decoded
+        (nic_rans_decode_window).  Reads the statuses back (synchronises) and raises ValueError naming
+        the first image that did not decode cleanly; damage outside those segments is not seen."""
+        return self._decode_window(1, buf, sizes, h8, w8, window)
+
+    def rans2_decode_window_status(self, buf, sizes, h8: int, w8: int, window, out=None):
+        """rans2_decode_window without the check (as rans_decode_window_status)."""
+        return self._decode_window_status(2, buf, sizes, h8, w8, window, out)
+
+    def rans2_decode_window(self, buf, sizes, h8: int, w8: int, window):
+        """rans_decode_window for version-2 files, under the codec's prior (NicError(NIC_ENOPRIOR)
+        without one; a file written under another prior is reported with both ids)."""
+        return self._decode_window(2, buf, sizes, h8, w8, window)
+
+    def rans3_decode_window_status(self, buf, sizes, h8: int, w8: int, window, out=None):
+        """rans3_decode_window without the check (as rans_decode_window_status)."""
+        return self._decode_window_status(3, buf, sizes, h8, w8, window, out)
+
+    def rans3_decode_window(self, buf, sizes, h8: int, w8: int, window):
+        """rans_decode_window for version-3 files, under the codec's context prior
+        (NicError(NIC_ENOPRIOR) without one)."""
+        return self._decode_window(3, buf, sizes, h8, w8, window)
+
     # -- device PNG writer (nic_png_device_*) -------------------------------------------------
     def png_reserve(self, n: int, h: int, w: int, channels: int = 3) -> None:
         """Grow the workspace so png_encode of n (h, w, channels) images allocates nothing."""
@@ -700,8 +781,16 @@ class Decoder(ProClass):
             raise ValueError(f"Decoder: expected shape (N,h,w,96), got {a.shape}")
         return self.codec.decode_host(a, self.host_chunks)
 
+    def decode_region(self, files, box):
+        """The pixel box = (y, x, h, w) of the images of .nic files (bytes or paths, one latent shape)
+        -> (N,h,w,3) u8 device tensor, equal to that box of the whole reconstructions: only the
+        segments and the latent window the box needs are decoded (bitstream.decode_region)."""
+        from .bitstream import decode_region
+
+        return decode_region(self, files, box)
+
     def uncompress(self, dataset_path: str, checkpoint_path: str, batch_size: int = 64, workers=None,
-                   container: str = "png", png_writer: str = "pillow", prior=None) -> None:
+                   container: str = "png", png_writer: str = "pillow", prior=None, region=None) -> None:
         """decoder.py:50-52: packed PNGs in ``dataset_path`` -> ``dataset_path.replace('compressed','uncompressed')``.
         Pipelined as compress (``workers=0, batch_size=4``: the reference's serial loop).
         ``container="nic"`` reads the directory's ``.nic`` files instead (same reconstructions).
@@ -709,9 +798,12 @@ class Decoder(ProClass):
         pixels in files of its own format) instead of Pillow's optimize=True bytes.
         ``prior`` (``container="nic"`` only): the prior the directory's version-2 files were written
         under (a prior.ContextPrior or a ``.nicc`` path for version-3 files); their reconstructions
-        are cropped to the recorded H x W.  Version-1 files are read as before."""
+        are cropped to the recorded H x W.  Version-1 files are read as before.
+        ``region`` (a pixel box (y, x, h, w); ``container="nic"`` only, ValueError otherwise: a packed
+        PNG has no index): every file is decoded to that box only and ``<stem>.png`` holds the box."""
         from .bitstream import use_model
 
+        more = {"region": region} if region is not None else {}
         use_model(self, dataset_path, checkpoint_path, dataset_path.replace("compressed", "uncompressed"),
                   in_cshape=96, batch_size=batch_size, workers=workers, container=container, png_writer=png_writer,
-                  prior=prior)
+                  prior=prior, **more)

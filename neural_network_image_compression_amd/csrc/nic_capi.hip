@@ -465,7 +465,7 @@ bool models_ready(const nic_ctx* c, int m0) {
 
 extern "C" {
 
-int nic_version(void) { return 600; }
+int nic_version(void) { return 700; }
 
 int nic_constants(float* ycbcr9, float* ycbcr_inv9, float* off3) {
   // host copy of what nic_create uploads; lets tests compare with np.linalg.inv (utils.py:8)
@@ -1681,6 +1681,60 @@ int nic_rans3_decode(nic_ctx* c, const uint8_t* files, int64_t stride, const int
   HIP_TRY(launch_rans3_decode(files, stride, (const long long*)sizes, n, h8, w8, ctx_cprior(c), c->ws, pl, latent, status,
                               (hipStream_t)stream));
   return NIC_OK;
+}
+
+// ---- region decode: a latent window out of .nic files (nic_rans.hip; nic_region_plan and
+// nic_rans_window_segments are host-only there) ----
+// ver 1, 2 or 3: the full decode's checks in its order (shape, with the window; empty batch; NULL;
+// the prior), its parse and workspace, then the window's segments only.
+static int rans_decode_window(const char* fn, int ver, nic_ctx* c, const uint8_t* files, int64_t stride, const int64_t* sizes,
+                              int n, int h8, int w8, int r0, int c0, int rows, int cols, uint8_t* latent_win, int32_t* status,
+                              void* stream) {
+  int rc = rans_check(fn, n, h8, w8, 1);
+  if (rc) return rc;
+  if (r0 < 0 || c0 < 0 || rows < 1 || cols < 1 || (long long)r0 + rows > h8 || (long long)c0 + cols > w8)
+    return fail(NIC_ESHAPE, "%s: window (r0 %d, c0 %d, %d x %d) does not lie inside the %dx%d latent", fn, r0, c0, rows, cols,
+                h8, w8);
+  if (n == 0) return NIC_OK;
+  if (!c) return fail(NIC_EINVAL, "%s: NULL ctx", fn);
+  if (!files || !sizes || !latent_win || !status) return fail(NIC_EINVAL, "%s: NULL buffer", fn);
+  if ((uintptr_t)latent_win % 16) return fail(NIC_EINVAL, "%s: latent_win must be 16-byte aligned", fn);
+  const int header = ver == 1 ? 16 : 40;
+  if (stride < header) return fail(NIC_ESHAPE, "%s: stride %lld is below the %d-byte header", fn, (long long)stride, header);
+  if (ver == 2 && !c->have_prior) return fail(NIC_ENOPRIOR, "%s: no prior is set (nic_rans_prior_set)", fn);
+  if (ver == 3 && !c->have_cprior) return fail(NIC_ENOPRIOR, "%s: no context prior is set (nic_rans_cprior_set)", fn);
+  DeviceGuard guard(c->device);
+  RansPlan pl;
+  rans_plan(n, h8, w8, 1, true, &pl, ver);
+  if ((rc = ensure_ws(c, pl.bytes))) return rc;
+  if (ver == 3) {
+    HIP_TRY(launch_rans3_decode_window(files, stride, (const long long*)sizes, n, h8, w8, r0, c0, rows, cols, ctx_cprior(c),
+                                       c->ws, pl, latent_win, status, (hipStream_t)stream));
+  } else {
+    RansPrior pr{};
+    if (ver == 2) pr = ctx_prior(c);
+    HIP_TRY(launch_rans_decode_window(files, stride, (const long long*)sizes, n, h8, w8, r0, c0, rows, cols,
+                                      ver == 2 ? &pr : nullptr, c->ws, pl, latent_win, status, (hipStream_t)stream));
+  }
+  return NIC_OK;
+}
+
+int nic_rans_decode_window(nic_ctx* c, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, int h8, int w8,
+                           int r0, int c0, int rows, int cols, uint8_t* latent_win, int32_t* status, void* stream) {
+  return rans_decode_window("nic_rans_decode_window", 1, c, files, stride, sizes, n, h8, w8, r0, c0, rows, cols, latent_win,
+                            status, stream);
+}
+
+int nic_rans2_decode_window(nic_ctx* c, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, int h8, int w8,
+                            int r0, int c0, int rows, int cols, uint8_t* latent_win, int32_t* status, void* stream) {
+  return rans_decode_window("nic_rans2_decode_window", 2, c, files, stride, sizes, n, h8, w8, r0, c0, rows, cols, latent_win,
+                            status, stream);
+}
+
+int nic_rans3_decode_window(nic_ctx* c, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, int h8, int w8,
+                            int r0, int c0, int rows, int cols, uint8_t* latent_win, int32_t* status, void* stream) {
+  return rans_decode_window("nic_rans3_decode_window", 3, c, files, stride, sizes, n, h8, w8, r0, c0, rows, cols, latent_win,
+                            status, stream);
 }
 
 // ---- device PNG writer (nic_png_dev.hip; nic_png_device_block_bytes and nic_png_device_bound are host-only there) ----

@@ -215,6 +215,14 @@ hipError_t launch_rans3_encode(const uint8_t* z, int n, int h8, int w8, int H, i
                                char* ws, const RansPlan& plan, uint8_t* out, long long stride, long long* sizes, hipStream_t st);
 hipError_t launch_rans3_decode(const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8,
                                const RansCPrior& prior, char* ws, const RansPlan& plan, uint8_t* z, int* status, hipStream_t st);
+// Window decode: the latent pixels (r0 + i, c0 + x), i < rows, x < cols, of every file into zwin
+// (n, rows, cols, 96); plan: the decode plan of (n, h8, w8).  prior NULL: version 1, else version 2.
+hipError_t launch_rans_decode_window(const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8,
+                                     int r0, int c0, int rows, int cols, const RansPrior* prior, char* ws, const RansPlan& plan,
+                                     uint8_t* zwin, int* status, hipStream_t st);
+hipError_t launch_rans3_decode_window(const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8,
+                                      int r0, int c0, int rows, int cols, const RansCPrior& prior, char* ws, const RansPlan& plan,
+                                      uint8_t* zwin, int* status, hipStream_t st);
 
 // --- device PNG writer (nic_png_dev.hip) ------------------------------------------------------
 // Byte offsets of one call's scratch inside the ctx workspace (256-B aligned), from png_dev_plan:

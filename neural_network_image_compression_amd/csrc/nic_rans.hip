@@ -1047,6 +1047,196 @@ __global__ __launch_bounds__(64) void rans3_decode_segments(const uint8_t* __res
   if (live && !(x == kRansL && ptr == end)) atomicOr(&status[img], 1);
 }
 
+// ==== window decode: only the segments that hold a pixel of a latent window ("Region
+// decode") ====
+// The window is the latent pixels (r0 + i, c0 + x), i < rows, x < cols.  Its row i is the run
+// [a_i, a_i + cols) of the row-major pixel order, a_i = (r0 + i) w8 + c0, and lies in the segments
+// first_i = a_i / S .. last_i = (a_i + cols - 1) / S: at most J = (cols + S - 2) / S + 1 of them.
+// Slot (i, j), j < J, stands for segment first_i + j; it is live iff that segment is <= last_i and,
+// for i > 0, > last_(i-1) -- a segment that spans several window rows belongs to the first of them.
+// A live lane decodes its whole segment (rANS is serial, and the end check needs the last byte) and
+// stores only the pixels inside the window, at their place in the compact (n, rows, cols, 96) output.
+struct RansWindow {
+  int w8, r0, c0, rows, cols;
+};
+
+// the segment of `slot` under segments of S pixels, or -1 for a slot that is not live
+__device__ __forceinline__ int window_segment(const RansWindow& w, int S, int slot) {
+  const int J = (w.cols + S - 2) / S + 1;
+  const int i = slot / J, j = slot - i * J;
+  if (i >= w.rows) return -1;
+  const int a = (w.r0 + i) * w.w8 + w.c0;  // < h8 w8 <= 2^23
+  const int k = a / S + j;
+  if (k > (a + w.cols - 1) / S) return -1;
+  if (i > 0 && k <= (a - w.w8 + w.cols - 1) / S) return -1;
+  return k;
+}
+
+// where the pixel at (gy, gx) of the latent goes in image img's window, or nullptr outside it
+__device__ __forceinline__ uint8_t* window_pixel(const RansWindow& w, uint8_t* __restrict__ zwin, int img, int gy, int gx) {
+  const uint32_t i = (uint32_t)(gy - w.r0), x = (uint32_t)(gx - w.c0);
+  if (i >= (uint32_t)w.rows || x >= (uint32_t)w.cols) return nullptr;
+  return zwin + (((size_t)img * w.rows + i) * w.cols + x) * kCh;
+}
+
+// One lane's reader of its segment's bytes [ptr, end): a read past end gives 0 and still counts, so
+// the segment then fails the end check.
+struct SegmentReader {
+  const uint8_t* __restrict__ f;
+  uint32_t ptr, end;
+  __device__ __forceinline__ uint32_t next() {
+    const uint32_t b = ptr < end ? (uint32_t)f[ptr] : 0u;
+    ++ptr;
+    return b;
+  }
+  __device__ __forceinline__ uint32_t state() {  // the segment's leading big-endian final state
+    uint32_t x = next() << 24;
+    x |= next() << 16;
+    x |= next() << 8;
+    return x | next();
+  }
+};
+
+// One symbol of the window kernels, the step of rans_decode_segments: the largest s with
+// row[s] <= slot (row[0] = 0 <= slot < 4096 = row[256]), then, for a lane that is on, the state
+// update and up to two bytes of renormalisation.  A lane past its last pixel keeps its final state.
+__device__ __forceinline__ uint32_t window_symbol(const uint16_t* row, uint32_t& x, bool on, SegmentReader& in) {
+  const uint32_t slot = x & (kProbScale - 1);
+  uint32_t s = 0;
+#pragma unroll
+  for (uint32_t step = 128; step > 0; step >>= 1)
+    if (row[s + step] <= slot) s += step;
+  const uint32_t lo = row[s], freq = row[s + 1] - lo;
+  if (on) {
+    x = freq * (x >> kProbBits) + slot - lo;
+    if (x < kRansL) {
+      x = (x << 8) | in.next();
+      if (x < kRansL) x = (x << 8) | in.next();
+    }
+  }
+  return s;
+}
+
+// The lane of a window kernel: its segment (or none), its reader and where its pixels lie.
+struct WindowLane {
+  bool live;
+  int mypix, maxpix, gy, gx;  // maxpix: the wave-uniform trip count; (gy, gx): the latent position of pixel p
+  SegmentReader in;
+  uint32_t x;
+};
+
+// seg: window_segment's result.  A live seg is < nseg (it holds a pixel below npix), so off[seg + 1] exists.
+__device__ __forceinline__ WindowLane window_lane(int seg, int seg_pixels, int npix, int w8, const uint8_t* __restrict__ file,
+                                                  const uint32_t* __restrict__ off, uint32_t pay, uint32_t size) {
+  WindowLane l;
+  l.live = seg >= 0;
+  const int p0 = l.live ? seg * seg_pixels : 0;  // < npix
+  l.mypix = l.live ? min(seg_pixels, npix - p0) : 0;
+  l.in.f = file;
+  l.in.ptr = l.live ? min(pay + off[seg], size) : 0u;
+  l.in.end = l.live ? min(pay + off[seg + 1], size) : 0u;
+  l.x = l.live ? l.in.state() : 0u;
+  l.gy = p0 / w8;
+  l.gx = p0 - l.gy * w8;
+  l.maxpix = l.mypix;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) l.maxpix = max(l.maxpix, __shfl_xor(l.maxpix, o, 64));
+  return l;
+}
+
+// the block's first slot lies past the window's rows x J slots (block-uniform, before any per-lane work)
+__device__ __forceinline__ bool window_block_dead(const RansWindow& w, int S, int first_slot) {
+  return first_slot >= w.rows * ((w.cols + S - 2) / S + 1);
+}
+
+// ---- window decode 2 (versions 1 and 2): rans_decode_segments over the window's slots ---------
+// grid (ceil(rows cols / 64), n), block 64: the grid covers seg_pixels = 1 (J = cols).  A block is
+// one wave; one without a live lane (every block of a refused image: nseg = 0) exits before the
+// tables are staged.  File reads and lookups are bounded as in rans_decode_segments; a lane stores
+// only the pixels of its own segment that window_pixel places inside image img's output.
+__global__ __launch_bounds__(64) void rans_decode_window_segments(const uint8_t* __restrict__ files, long long stride, int npix,
+                                                                   const uint16_t* __restrict__ cum,
+                                                                   const uint32_t* __restrict__ segoff, int maxseg,
+                                                                   const uint32_t* __restrict__ meta, RansWindow win,
+                                                                   uint8_t* __restrict__ zwin, int* __restrict__ status) {
+  __shared__ uint16_t start[kCumWords];
+  const int lane = threadIdx.x, img = blockIdx.y;
+  const int nseg = (int)meta[4 * img + 0];
+  if (nseg == 0) return;  // block-uniform
+  const int seg_pixels = (int)meta[4 * img + 1];
+  if (window_block_dead(win, seg_pixels, (int)blockIdx.x * 64)) return;
+  const int seg = window_segment(win, seg_pixels, (int)blockIdx.x * 64 + lane);
+  if (__ballot(seg >= 0) == 0) return;  // block-uniform: the block is this wave
+  load_cum(start, cum + (size_t)img * kCumWords, lane, 64);
+  __syncthreads();
+  WindowLane l = window_lane(seg, seg_pixels, npix, win.w8, files + (size_t)img * (size_t)stride,
+                             segoff + (size_t)img * (maxseg + 1), meta[4 * img + 2], meta[4 * img + 3]);
+  for (int p = 0; p < l.maxpix; ++p) {
+    const bool on = p < l.mypix;
+    uint8_t* dst = on ? window_pixel(win, zwin, img, l.gy, l.gx) : nullptr;
+    for (int q = 0; q < 6; ++q) {
+      uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int b = 0; b < 16; ++b) w[b >> 2] |= window_symbol(start + (16 * q + b) * kCumRow, l.x, on, l.in) << (8 * (b & 3));
+      if (dst) *(uint4*)(dst + 16 * q) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    if (++l.gx == win.w8) {
+      l.gx = 0;
+      ++l.gy;
+    }
+  }
+  if (l.live && !(l.x == kRansL && l.in.ptr == l.in.end)) atomicOr(&status[img], 1);
+}
+
+// ---- window decode 2 (version 3): rans3_decode_segments over the window's slots ----------------
+// The context never leaves a segment and the lane decodes its segment from the first pixel, so the
+// left-pixel registers work as in rans3_decode_segments.
+__global__ __launch_bounds__(64) void rans3_decode_window_segments(const uint8_t* __restrict__ files, long long stride, int npix,
+                                                                    const uint16_t* __restrict__ cum,
+                                                                    const uint8_t* __restrict__ anchor,
+                                                                    const uint32_t* __restrict__ segoff, int maxseg,
+                                                                    const uint32_t* __restrict__ meta, RansWindow win,
+                                                                    uint8_t* __restrict__ zwin, int* __restrict__ status) {
+  __shared__ uint16_t start[kCtxWords];
+  const int lane = threadIdx.x, img = blockIdx.y;
+  const int nseg = (int)meta[4 * img + 0];
+  if (nseg == 0) return;  // block-uniform
+  const int seg_pixels = (int)meta[4 * img + 1];
+  if (window_block_dead(win, seg_pixels, (int)blockIdx.x * 64)) return;
+  const int seg = window_segment(win, seg_pixels, (int)blockIdx.x * 64 + lane);
+  if (__ballot(seg >= 0) == 0) return;  // block-uniform: the block is this wave
+  load_ctx_rows(start, cum + (size_t)img * kCtxWords, lane, 64);
+  __syncthreads();
+  WindowLane l = window_lane(seg, seg_pixels, npix, win.w8, files + (size_t)img * (size_t)stride,
+                             segoff + (size_t)img * (maxseg + 1), meta[4 * img + 2], meta[4 * img + 3]);
+  uint32_t prev[24];
+#pragma unroll
+  for (int i = 0; i < 24; ++i) prev[i] = 0;
+  for (int p = 0; p < l.maxpix; ++p) {
+    const bool on = p < l.mypix;
+    uint8_t* dst = on ? window_pixel(win, zwin, img, l.gy, l.gx) : nullptr;
+    for (int q = 0; q < 6; ++q) {
+      uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int b = 0; b < 16; ++b) {
+        const uint32_t left = (prev[b >> 2] >> (8 * (b & 3))) & 255u;
+        const uint32_t k = p > 0 ? ctx_of(left, anchor[16 * q + b]) : 0u;  // k <= 2: the row is one of the image's 288
+        w[b >> 2] |= window_symbol(start + ((16 * q + b) * kCtx + k) * kCtxRow, l.x, on, l.in) << (8 * (b & 3));
+      }
+      if (dst) *(uint4*)(dst + 16 * q) = make_uint4(w[0], w[1], w[2], w[3]);
+#pragma unroll
+      for (int i = 0; i < 20; ++i) prev[i] = prev[i + 4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) prev[20 + i] = w[i];
+    }
+    if (++l.gx == win.w8) {
+      l.gx = 0;
+      ++l.gy;
+    }
+  }
+  if (l.live && !(l.x == kRansL && l.in.ptr == l.in.end)) atomicOr(&status[img], 1);
+}
+
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
@@ -1229,6 +1419,40 @@ hipError_t launch_rans2_decode(const uint8_t* files, long long stride, const lon
   return hipGetLastError();
 }
 
+// ---- window decode: the full decode's parse, then the window's slots (pl: the decode plan of (n, h8, w8)) ----
+hipError_t launch_rans_decode_window(const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8,
+                                     int r0, int c0, int rows, int cols, const RansPrior* pr, char* ws, const RansPlan& pl,
+                                     uint8_t* zwin, int* status, hipStream_t st) {
+  const int npix = h8 * w8, maxseg = pl.nseg;
+  uint16_t* cum = (uint16_t*)(ws + pl.cum);
+  uint32_t* seglen = (uint32_t*)(ws + pl.seglen);
+  uint32_t* segoff = (uint32_t*)(ws + pl.segoff);
+  uint32_t* meta = (uint32_t*)(ws + pl.meta);
+  const RansWindow win = {w8, r0, c0, rows, cols};
+  if (pr)
+    rans2_parse<<<dim3(n), 256, 0, st>>>(files, stride, sizes, h8, w8, pr->cum, pr->id, cum, seglen, segoff, maxseg, meta, status);
+  else
+    rans_parse<<<dim3(n), 256, 0, st>>>(files, stride, sizes, h8, w8, cum, seglen, segoff, maxseg, meta, status);
+  rans_decode_window_segments<<<dim3((rows * cols + 63) / 64, n), 64, 0, st>>>(files, stride, npix, cum, segoff, maxseg, meta, win,
+                                                                              zwin, status);
+  return hipGetLastError();
+}
+
+hipError_t launch_rans3_decode_window(const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8,
+                                      int r0, int c0, int rows, int cols, const RansCPrior& pr, char* ws, const RansPlan& pl,
+                                      uint8_t* zwin, int* status, hipStream_t st) {
+  const int npix = h8 * w8, maxseg = pl.nseg;
+  uint16_t* cum = (uint16_t*)(ws + pl.cum);
+  uint32_t* seglen = (uint32_t*)(ws + pl.seglen);
+  uint32_t* segoff = (uint32_t*)(ws + pl.segoff);
+  uint32_t* meta = (uint32_t*)(ws + pl.meta);
+  const RansWindow win = {w8, r0, c0, rows, cols};
+  rans3_parse<<<dim3(n), 256, 0, st>>>(files, stride, sizes, h8, w8, pr.cum, pr.id, cum, seglen, segoff, maxseg, meta, status);
+  rans3_decode_window_segments<<<dim3((rows * cols + 63) / 64, n), 64, 0, st>>>(files, stride, npix, cum, pr.anchor, segoff,
+                                                                               maxseg, meta, win, zwin, status);
+  return hipGetLastError();
+}
+
 }  // namespace nic
 
 // ---- host-only entry points ------------------------------------------------------------------
@@ -1336,6 +1560,46 @@ int nic_rans2_bound(int h8, int w8, int seg_pixels, int64_t* bytes) {
   const int rc = nic_rans_bound(h8, w8, seg_pixels, bytes);
   if (rc == NIC_OK) *bytes += nic::kHeader2 - nic::kHeader;
   return rc;
+}
+
+int nic_region_plan(int H, int W, int y, int x, int bh, int bw, int* win4, int* off2) {
+  if (!win4 || !off2) return nic::set_error(NIC_EINVAL, "nic_region_plan: win4 or off2 is NULL");
+  if (H < 1 || W < 1 || y < 0 || x < 0 || bh < 1 || bw < 1 || (long long)y + bh > H || (long long)x + bw > W) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "nic_region_plan: box (y %d, x %d, %d x %d) does not lie inside a %d x %d image", y, x, bh, bw, H, W);
+    return nic::set_error(NIC_ESHAPE, msg);
+  }
+  const int h8 = (H >> 3) + ((H & 7) != 0), w8 = (W >> 3) + ((W & 7) != 0);
+  auto axis = [](int at, int len, int n8, int* lo, int* count) {
+    const int first = at / 8, last = (at + len - 1) / 8 + 1;  // the latent pixels the box touches: [first, last)
+    const int a = first - NIC_DECODE_HALO > 0 ? first - NIC_DECODE_HALO : 0;
+    const int b = last + NIC_DECODE_HALO < n8 ? last + NIC_DECODE_HALO : n8;
+    *lo = a;
+    *count = b - a;
+  };
+  axis(y, bh, h8, &win4[0], &win4[2]);
+  axis(x, bw, w8, &win4[1], &win4[3]);
+  off2[0] = y - 8 * win4[0];
+  off2[1] = x - 8 * win4[1];
+  return NIC_OK;
+}
+
+int nic_rans_window_segments(int h8, int w8, int seg_pixels, int r0, int c0, int rows, int cols, int64_t* count) {
+  if (!count) return nic::set_error(NIC_EINVAL, "nic_rans_window_segments: count is NULL");
+  if (!nic::rans_shape_ok(h8, w8)) return nic::set_error(NIC_ESHAPE, "nic_rans_window_segments: latent size out of range");
+  if (seg_pixels < 1 || seg_pixels > 65535)
+    return nic::set_error(NIC_ESHAPE, "nic_rans_window_segments: seg_pixels not in 1..65535");
+  if (r0 < 0 || c0 < 0 || rows < 1 || cols < 1 || (long long)r0 + rows > h8 || (long long)c0 + cols > w8)
+    return nic::set_error(NIC_ESHAPE, "nic_rans_window_segments: the window does not lie inside the latent");
+  int64_t total = 0, seen = -1;  // seen: the last segment counted so far
+  for (int i = 0; i < rows; ++i) {
+    const int64_t a = (int64_t)(r0 + i) * w8 + c0, first = a / seg_pixels, last = (a + cols - 1) / seg_pixels;
+    const int64_t from = first > seen ? first : seen + 1;
+    if (last >= from) total += last - from + 1;
+    seen = last;
+  }
+  *count = total;
+  return NIC_OK;
 }
 
 }  // extern "C"
