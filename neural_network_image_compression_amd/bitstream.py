@@ -116,10 +116,13 @@ def save_imgs(imgs: np.ndarray, output_dir: str, filenames: Sequence[str], threa
     ``threads`` native host threads (nic_png_encode, byte-identical to Pillow), then written."""
     imgs = np.asarray(imgs)
     assert (np.round(imgs) - imgs).sum() == 0  # utils.py:86
-    files = png_encode(imgs.astype(np.uint8), threads=threads)
+    return _write_files(png_encode(imgs.astype(np.uint8), threads=threads), output_dir, filenames, ".png")
+
+
+def _write_files(datas: Sequence[bytes], output_dir: str, filenames: Sequence[str], ext: str) -> List[str]:
     paths = []
-    for data, name in zip(files, filenames):
-        path = os.path.join(output_dir, name + ".png")
+    for data, name in zip(datas, filenames):
+        path = os.path.join(output_dir, name + ext)
         with open(path, "wb") as f:
             f.write(data)
         paths.append(path)
@@ -135,54 +138,49 @@ CONTAINERS = ("png", "nic")
 NIC_SEG_PIXELS = 32  # latent pixels per rANS segment (one device lane each) of the files written here
 
 
-def nic_inspect(data: bytes) -> Tuple[int, int, int]:
-    """(h8, w8, seg_pixels) of a well-formed .nic file; ValueError (nic_rans_inspect's text)
-    otherwise.  Host only."""
+def _inspect(ver: int, data: bytes) -> tuple:
+    """nic_rans_inspect (ver 1: three ints) or nic_rans2_inspect / nic_rans3_inspect (five ints and
+    the prior id) on data: the values, or ValueError with the call's text."""
     import ctypes
 
     from . import _lib
 
     a = np.frombuffer(data, np.uint8)
-    h8, w8, sp = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    rc = _lib.lib().nic_rans_inspect(a.ctypes.data_as(ctypes.c_void_p), len(data), ctypes.byref(h8), ctypes.byref(w8),
-                                     ctypes.byref(sp))
+    v = [ctypes.c_int() for _ in range(3 if ver == 1 else 5)]
+    pid = ctypes.c_uint32()
+    fn = getattr(_lib.lib(), {1: "nic_rans_inspect", 2: "nic_rans2_inspect", 3: "nic_rans3_inspect"}[ver])
+    rc = fn(a.ctypes.data_as(ctypes.c_void_p), len(data), *[ctypes.byref(t) for t in v],
+            *([] if ver == 1 else [ctypes.byref(pid)]))
     if rc != _lib.NIC_OK:
         raise ValueError(f"[{rc}] {_lib.last_error()}")
-    return h8.value, w8.value, sp.value
+    return tuple(t.value for t in v) + (() if ver == 1 else (int(pid.value),))
+
+
+def nic_inspect(data: bytes) -> Tuple[int, int, int]:
+    """(h8, w8, seg_pixels) of a well-formed .nic file; ValueError (nic_rans_inspect's text)
+    otherwise.  Host only."""
+    return _inspect(1, data)
 
 
 def nic2_inspect(data: bytes) -> Tuple[int, int, int, int, int, int]:
     """(h8, w8, seg_pixels, H, W, prior_id) of a well-formed version-2 .nic file; ValueError
     (nic_rans2_inspect's text) otherwise.  Host only."""
-    import ctypes
-
-    from . import _lib
-
-    a = np.frombuffer(data, np.uint8)
-    v = [ctypes.c_int() for _ in range(5)]
-    pid = ctypes.c_uint32()
-    rc = _lib.lib().nic_rans2_inspect(a.ctypes.data_as(ctypes.c_void_p), len(data), *[ctypes.byref(t) for t in v],
-                                      ctypes.byref(pid))
-    if rc != _lib.NIC_OK:
-        raise ValueError(f"[{rc}] {_lib.last_error()}")
-    return tuple(t.value for t in v) + (int(pid.value),)
+    return _inspect(2, data)
 
 
 def nic3_inspect(data: bytes) -> Tuple[int, int, int, int, int, int]:
     """(h8, w8, seg_pixels, H, W, prior_id) of a well-formed version-3 .nic file; ValueError
     (nic_rans3_inspect's text) otherwise.  Host only."""
-    import ctypes
+    return _inspect(3, data)
 
-    from . import _lib
 
-    a = np.frombuffer(data, np.uint8)
-    v = [ctypes.c_int() for _ in range(5)]
-    pid = ctypes.c_uint32()
-    rc = _lib.lib().nic_rans3_inspect(a.ctypes.data_as(ctypes.c_void_p), len(data), *[ctypes.byref(t) for t in v],
-                                      ctypes.byref(pid))
-    if rc != _lib.NIC_OK:
-        raise ValueError(f"[{rc}] {_lib.last_error()}")
-    return tuple(t.value for t in v) + (int(pid.value),)
+def _download_files(buf, sizes) -> List[bytes]:
+    """Files buf[i, :sizes[i]] of an (N, stride) u8 device tensor as bytes, in one copy to the host."""
+    if buf.shape[0] == 0:
+        return []
+    sizes = sizes.cpu().numpy()
+    host = buf[:, :int(sizes.max())].contiguous().cpu().numpy()
+    return [host[i, :sizes[i]].tobytes() for i in range(host.shape[0])]
 
 
 def nic_files(codec, z, seg_pixels: int = NIC_SEG_PIXELS, size=None) -> List[bytes]:
@@ -197,11 +195,7 @@ def nic_files(codec, z, seg_pixels: int = NIC_SEG_PIXELS, size=None) -> List[byt
         buf, sizes = codec.rans2_encode(z, seg_pixels, size)
     else:
         buf, sizes = codec.rans_encode(z, seg_pixels)
-    if buf.shape[0] == 0:
-        return []
-    sizes = sizes.cpu().numpy()
-    host = buf[:, :int(sizes.max())].contiguous().cpu().numpy()
-    return [host[i, :sizes[i]].tobytes() for i in range(host.shape[0])]
+    return _download_files(buf, sizes)
 
 
 def _inspect_any(codec, i: int, data: bytes, who: str = "read_nic"):
@@ -236,8 +230,6 @@ def read_nic(codec, files: Sequence[bytes], sizes: bool = False) -> list:
     files of equal (h8, w8, seg_pixels) and version-2 or version-3 files of equal (h8, w8) are
     decoded as one device batch each.
     sizes=True: also the files' image sizes, (latents, [(H, W)])."""
-    import torch
-
     groups, hw = {}, []
     for i, data in enumerate(files):
         key, size = _inspect_any(codec, i, data)
@@ -245,16 +237,10 @@ def read_nic(codec, files: Sequence[bytes], sizes: bool = False) -> list:
         hw.append(size)
     out = [None] * len(files)
     for key, idx in groups.items():
-        h8, w8 = key[1], key[2]
-        stride = max(len(files[i]) for i in idx)
-        host = np.zeros((len(idx), stride), np.uint8)
-        for r, i in enumerate(idx):
-            host[r, :len(files[i])] = np.frombuffer(files[i], np.uint8)
-        lens = torch.tensor([len(files[i]) for i in idx], dtype=torch.int64)
-        dev = f"cuda:{codec.device}"
+        buf, lens = _upload_files(codec, [files[i] for i in idx])
         try:
             decode = {1: codec.rans_decode, 2: codec.rans2_decode, 3: codec.rans3_decode}[key[0]]
-            z = decode(torch.from_numpy(host).to(dev), lens.to(dev), h8, w8)
+            z = decode(buf, lens, key[1], key[2])
         except ValueError as e:
             raise ValueError(f"read_nic: files {idx}: {e}") from None
         for r, i in enumerate(idx):
@@ -371,22 +357,7 @@ def _check_png_writer(png_writer: str, decoder_side: bool) -> None:
 def png_files_device(codec, x, filter="adaptive") -> List[bytes]:
     """The PNG file of every image of x (N,H,W,3) or (N,H,W,1), a u8 tensor on the codec's device:
     filtered, coded and framed there (Codec.png_encode), then one copy of the files to the host."""
-    buf, sizes = codec.png_encode(x, filter)
-    if buf.shape[0] == 0:
-        return []
-    sizes = sizes.cpu().numpy()
-    host = buf[:, :int(sizes.max())].contiguous().cpu().numpy()
-    return [host[i, :sizes[i]].tobytes() for i in range(host.shape[0])]
-
-
-def _write_files(datas: Sequence[bytes], output_dir: str, filenames: Sequence[str], ext: str) -> List[str]:
-    paths = []
-    for data, name in zip(datas, filenames):
-        path = os.path.join(output_dir, name + ext)
-        with open(path, "wb") as f:
-            f.write(data)
-        paths.append(path)
-    return paths
+    return _download_files(*codec.png_encode(x, filter))
 
 
 def _batches(shapes: Sequence[tuple], batch_size: int):
@@ -624,21 +595,15 @@ def use_model_nic_in(model, dataset_path: str, checkpoint_path: str, output_dir:
         def emit(rec, stems):
             """The PNG files of the reconstructions rec, a device tensor, by the chosen writer."""
             if png_writer == "device":
-                pngs = png_files_device(codec, rec)
-                while len(futures) >= WRITES_IN_FLIGHT:
-                    futures.pop(0).result()
-                if serial:
-                    _write_files(pngs, output_dir, stems, ".png")
-                else:
-                    futures.append(writer.submit(_write_files, pngs, output_dir, stems, ".png"))
-                return
-            rec = rec.cpu().numpy()
+                write, *args = _write_files, png_files_device(codec, rec), output_dir, stems, ".png"
+            else:
+                write, *args = save_imgs, rec.cpu().numpy(), output_dir, stems, png_threads  # serial: 1 thread
             while len(futures) >= WRITES_IN_FLIGHT:
                 futures.pop(0).result()
             if serial:
-                save_imgs(rec, output_dir, stems, threads=1)
+                write(*args)
             else:
-                futures.append(writer.submit(save_imgs, rec, output_dir, stems, png_threads))
+                futures.append(writer.submit(write, *args))
 
         chunks = [files[i:i + step] for i in range(0, len(files), step)]
         pending = [readers.map(_read_bytes, [os.path.join(dataset_path, fn) for fn in ch]) for ch in chunks[:2]]

@@ -303,51 +303,89 @@ class Codec:
         """Grow the workspace so rans_encode / rans_decode of (n, h8, w8) latents allocate nothing."""
         _lib.check(self._L.nic_rans_reserve(self._h, n, h8, w8, seg_pixels), "nic_rans_reserve")
 
-    def rans_encode(self, z, seg_pixels: int = 32):
-        """(N,h,w,96) u8 latent -> (buf (N, stride) u8, sizes (N,) int64), device tensors: image
-        i's complete .nic file is buf[i, :sizes[i]] (nic_rans_encode; no host synchronisation)."""
+    # One body per call for the three container versions: ver picks nic_rans_*, nic_rans2_* or
+    # nic_rans3_*, and the public method's name in the error texts.
+    _RANS = {1: "rans", 2: "rans2", 3: "rans3"}
+
+    def _rans_encode(self, ver: int, z, seg_pixels, size=None):
         torch = _torch()
-        z = self._check_dev(z, 4, 96, "rans_encode")
+        name = self._RANS[ver] + "_encode"
+        z = self._check_dev(z, 4, 96, name)
         n, h8, w8, _ = z.shape
         if z.data_ptr() % 16:  # a view at an odd offset: the kernels read 16-byte words
             z = z.clone()
+        hw = ()  # version 1 does not record the image size
+        if ver != 1:
+            hw = (8 * h8, 8 * w8) if size is None else (int(size[0]), int(size[1]))
         stride = ctypes.c_int64()
-        _lib.check(self._L.nic_rans_bound(h8, w8, int(seg_pixels), ctypes.byref(stride)), "nic_rans_bound")
+        bound = f"nic_{self._RANS[ver]}_bound"
+        _lib.check(getattr(self._L, bound)(h8, w8, int(seg_pixels), ctypes.byref(stride)), bound)
         buf = torch.empty((n, stride.value), dtype=torch.uint8, device=z.device)
         sizes = torch.zeros((n,), dtype=torch.int64, device=z.device)
-        _lib.check(self._L.nic_rans_encode(self._h, z.data_ptr(), n, h8, w8, int(seg_pixels), buf.data_ptr(), stride.value,
-                                           sizes.data_ptr(), _stream_ptr(torch, self.device)), "nic_rans_encode")
+        _lib.check(getattr(self._L, "nic_" + name)(self._h, z.data_ptr(), n, h8, w8, *hw, int(seg_pixels), buf.data_ptr(),
+                                                   stride.value, sizes.data_ptr(), _stream_ptr(torch, self.device)),
+                   "nic_" + name)
         return buf, sizes
+
+    def _rans_decode_status(self, ver: int, buf, sizes, h8: int, w8: int, out=None, window=None):
+        """window None: the whole (N,h8,w8,96) latents; else (r0, c0, rows, cols): that window of them."""
+        torch = _torch()
+        name = self._RANS[ver] + ("_decode" if window is None else "_decode_window")
+        if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.device.type != "cuda" or buf.ndim != 2:
+            raise TypeError(f"{name}: expected an (N, stride) cuda torch.uint8 tensor of files")
+        if not isinstance(sizes, torch.Tensor) or sizes.dtype != torch.int64 or sizes.shape != (buf.shape[0],):
+            raise TypeError(f"{name}: expected an (N,) torch.int64 tensor of sizes")
+        if buf.device.index != self.device or sizes.device != buf.device:
+            raise ValueError(f"{name}: tensors must be on cuda:{self.device}")
+        buf, sizes = buf.contiguous(), sizes.contiguous()
+        n, stride = buf.shape
+        if window is None:
+            win, shape, text = (), (n, h8, w8, 96), "(N,h8,w8,96)"
+        else:
+            win = tuple(int(v) for v in window)
+            shape, text = (n, win[2], win[3], 96), "(N,rows,cols,96)"
+        if out is None:
+            if window is not None:  # a bad window is nic_rans*_decode_window's to report
+                shape = (n, max(win[2], 0), max(win[3], 0), 96)
+            out = torch.empty(shape, dtype=torch.uint8, device=buf.device)
+        elif out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != buf.device or not out.is_contiguous():
+            raise TypeError(f"{name}: out must be a contiguous {text} torch.uint8 tensor on the codec's device")
+        status = torch.zeros((n,), dtype=torch.int32, device=buf.device)
+        _lib.check(getattr(self._L, "nic_" + name)(self._h, buf.data_ptr(), stride, sizes.data_ptr(), n, int(h8), int(w8), *win,
+                                                   out.data_ptr(), status.data_ptr(), _stream_ptr(torch, self.device)),
+                   "nic_" + name)
+        return out, status
+
+    def _rans_decode(self, ver: int, buf, sizes, h8: int, w8: int, window=None):
+        z, status = self._rans_decode_status(ver, buf, sizes, h8, w8, window=window)
+        st = status.cpu().numpy()
+        bad = np.nonzero(st)[0]
+        if bad.size:
+            i = int(bad[0])
+            name = self._RANS[ver] + ("_decode" if window is None else "_decode_window")
+            if ver != 1 and st[i] & 8:
+                pid = int.from_bytes(bytes(buf[i, 24:28].cpu().numpy().tolist()), "little")
+                mine = self.prior if ver == 2 else self.context_prior
+                raise ValueError(f"{name}: image {i} was written under prior {pid:08x}, the codec's prior is "
+                                 f"{mine.id:08x} (status {int(st[i])}; refused images: {bad.tolist()})")
+            raise ValueError(f"{name}: image {i} is corrupt (status {int(st[i])}; corrupt images: {bad.tolist()})")
+        return z
+
+    def rans_encode(self, z, seg_pixels: int = 32):
+        """(N,h,w,96) u8 latent -> (buf (N, stride) u8, sizes (N,) int64), device tensors: image
+        i's complete .nic file is buf[i, :sizes[i]] (nic_rans_encode; no host synchronisation)."""
+        return self._rans_encode(1, z, seg_pixels)
 
     def rans_decode_status(self, buf, sizes, h8: int, w8: int):
         """rans_decode without the check: (latent, status (N,) int32 device tensor; nic.h)."""
-        torch = _torch()
-        if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.device.type != "cuda" or buf.ndim != 2:
-            raise TypeError("rans_decode: expected an (N, stride) cuda torch.uint8 tensor of files")
-        if not isinstance(sizes, torch.Tensor) or sizes.dtype != torch.int64 or sizes.shape != (buf.shape[0],):
-            raise TypeError("rans_decode: expected an (N,) torch.int64 tensor of sizes")
-        if buf.device.index != self.device or sizes.device != buf.device:
-            raise ValueError(f"rans_decode: tensors must be on cuda:{self.device}")
-        buf, sizes = buf.contiguous(), sizes.contiguous()
-        n, stride = buf.shape
-        z = torch.empty((n, h8, w8, 96), dtype=torch.uint8, device=buf.device)
-        status = torch.zeros((n,), dtype=torch.int32, device=buf.device)
-        _lib.check(self._L.nic_rans_decode(self._h, buf.data_ptr(), stride, sizes.data_ptr(), n, int(h8), int(w8),
-                                           z.data_ptr(), status.data_ptr(), _stream_ptr(torch, self.device)),
-                   "nic_rans_decode")
-        return z, status
+        return self._rans_decode_status(1, buf, sizes, h8, w8)
 
     def rans_decode(self, buf, sizes, h8: int, w8: int):
         """.nic files buf[i, :sizes[i]] (device tensors, as rans_encode returns) of (h8, w8)
         latents -> (N,h8,w8,96) u8.  Reads the statuses back (synchronises) and raises ValueError
         naming the first image whose file did not decode cleanly."""
-        z, status = self.rans_decode_status(buf, sizes, h8, w8)
-        st = status.cpu().numpy()
-        bad = np.nonzero(st)[0]
-        if bad.size:
-            raise ValueError(f"rans_decode: image {int(bad[0])} is corrupt (status {int(st[bad[0]])}; "
-                             f"corrupt images: {bad.tolist()})")
-        return z
+        return self._rans_decode(1, buf, sizes, h8, w8)
+
 
     # -- .nic version 2: the codec-level prior (nic_rans_prior_*, nic_rans2_*) -----------------
     #: the Prior set by set_prior (None: version-1 files only)
@@ -401,59 +439,19 @@ class Codec:
         """rans_encode with the codec's prior: version-2 files, which store a table only for the
         channels where it pays and record the images' own size=(H, W) (default 8 h x 8 w).
         NicError(NIC_ENOPRIOR) without a prior."""
-        torch = _torch()
-        z = self._check_dev(z, 4, 96, "rans2_encode")
-        n, h8, w8, _ = z.shape
-        H, W = (8 * h8, 8 * w8) if size is None else (int(size[0]), int(size[1]))
-        if z.data_ptr() % 16:  # a view at an odd offset: the kernels read 16-byte words
-            z = z.clone()
-        stride = ctypes.c_int64()
-        _lib.check(self._L.nic_rans2_bound(h8, w8, int(seg_pixels), ctypes.byref(stride)), "nic_rans2_bound")
-        buf = torch.empty((n, stride.value), dtype=torch.uint8, device=z.device)
-        sizes = torch.zeros((n,), dtype=torch.int64, device=z.device)
-        _lib.check(self._L.nic_rans2_encode(self._h, z.data_ptr(), n, h8, w8, H, W, int(seg_pixels), buf.data_ptr(),
-                                            stride.value, sizes.data_ptr(), _stream_ptr(torch, self.device)),
-                   "nic_rans2_encode")
-        return buf, sizes
+        return self._rans_encode(2, z, seg_pixels, size)
 
     def rans2_decode_status(self, buf, sizes, h8: int, w8: int, out=None):
         """rans2_decode without the check: (latent, status (N,) int32 device tensor; nic.h).
         out: the (N,h8,w8,96) u8 tensor to decode into (default: a new one)."""
-        torch = _torch()
-        if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.device.type != "cuda" or buf.ndim != 2:
-            raise TypeError("rans2_decode: expected an (N, stride) cuda torch.uint8 tensor of files")
-        if not isinstance(sizes, torch.Tensor) or sizes.dtype != torch.int64 or sizes.shape != (buf.shape[0],):
-            raise TypeError("rans2_decode: expected an (N,) torch.int64 tensor of sizes")
-        if buf.device.index != self.device or sizes.device != buf.device:
-            raise ValueError(f"rans2_decode: tensors must be on cuda:{self.device}")
-        buf, sizes = buf.contiguous(), sizes.contiguous()
-        n, stride = buf.shape
-        if out is None:
-            out = torch.empty((n, h8, w8, 96), dtype=torch.uint8, device=buf.device)
-        elif (out.dtype != torch.uint8 or tuple(out.shape) != (n, h8, w8, 96) or out.device != buf.device
-              or not out.is_contiguous()):
-            raise TypeError("rans2_decode: out must be a contiguous (N,h8,w8,96) torch.uint8 tensor on the codec's device")
-        status = torch.zeros((n,), dtype=torch.int32, device=buf.device)
-        _lib.check(self._L.nic_rans2_decode(self._h, buf.data_ptr(), stride, sizes.data_ptr(), n, int(h8), int(w8),
-                                            out.data_ptr(), status.data_ptr(), _stream_ptr(torch, self.device)),
-                   "nic_rans2_decode")
-        return out, status
+        return self._rans_decode_status(2, buf, sizes, h8, w8, out)
 
     def rans2_decode(self, buf, sizes, h8: int, w8: int):
         """Version-2 .nic files buf[i, :sizes[i]] of (h8, w8) latents -> (N,h8,w8,96) u8.  Reads the
         statuses back (synchronises) and raises ValueError naming the first image whose file did
         not decode cleanly; a file written under another prior is reported with both ids."""
-        z, status = self.rans2_decode_status(buf, sizes, h8, w8)
-        st = status.cpu().numpy()
-        bad = np.nonzero(st)[0]
-        if bad.size:
-            i = int(bad[0])
-            if st[i] & 8:
-                pid = int.from_bytes(bytes(buf[i, 24:28].cpu().numpy().tolist()), "little")
-                raise ValueError(f"rans2_decode: image {i} was written under prior {pid:08x}, the codec's prior is "
-                                 f"{self.prior.id:08x} (status {int(st[i])}; refused images: {bad.tolist()})")
-            raise ValueError(f"rans2_decode: image {i} is corrupt (status {int(st[i])}; corrupt images: {bad.tolist()})")
-        return z
+        return self._rans_decode(2, buf, sizes, h8, w8)
+
 
     # -- .nic version 3: the context prior (nic_rans_cprior_*, nic_rans3_*) ---------------------
     #: the ContextPrior set by set_context_prior (None: no version-3 files)
@@ -511,59 +509,19 @@ class Codec:
     def rans3_encode(self, z, seg_pixels: int = 32, size=None):
         """rans2_encode with the codec's context prior: version-3 files, whose symbols are coded
         under the row their left neighbour selects.  NicError(NIC_ENOPRIOR) without a context prior."""
-        torch = _torch()
-        z = self._check_dev(z, 4, 96, "rans3_encode")
-        n, h8, w8, _ = z.shape
-        H, W = (8 * h8, 8 * w8) if size is None else (int(size[0]), int(size[1]))
-        if z.data_ptr() % 16:  # a view at an odd offset: the kernels read 16-byte words
-            z = z.clone()
-        stride = ctypes.c_int64()
-        _lib.check(self._L.nic_rans3_bound(h8, w8, int(seg_pixels), ctypes.byref(stride)), "nic_rans3_bound")
-        buf = torch.empty((n, stride.value), dtype=torch.uint8, device=z.device)
-        sizes = torch.zeros((n,), dtype=torch.int64, device=z.device)
-        _lib.check(self._L.nic_rans3_encode(self._h, z.data_ptr(), n, h8, w8, H, W, int(seg_pixels), buf.data_ptr(),
-                                            stride.value, sizes.data_ptr(), _stream_ptr(torch, self.device)),
-                   "nic_rans3_encode")
-        return buf, sizes
+        return self._rans_encode(3, z, seg_pixels, size)
 
     def rans3_decode_status(self, buf, sizes, h8: int, w8: int, out=None):
         """rans3_decode without the check: (latent, status (N,) int32 device tensor; nic.h).
         out: the (N,h8,w8,96) u8 tensor to decode into (default: a new one)."""
-        torch = _torch()
-        if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.device.type != "cuda" or buf.ndim != 2:
-            raise TypeError("rans3_decode: expected an (N, stride) cuda torch.uint8 tensor of files")
-        if not isinstance(sizes, torch.Tensor) or sizes.dtype != torch.int64 or sizes.shape != (buf.shape[0],):
-            raise TypeError("rans3_decode: expected an (N,) torch.int64 tensor of sizes")
-        if buf.device.index != self.device or sizes.device != buf.device:
-            raise ValueError(f"rans3_decode: tensors must be on cuda:{self.device}")
-        buf, sizes = buf.contiguous(), sizes.contiguous()
-        n, stride = buf.shape
-        if out is None:
-            out = torch.empty((n, h8, w8, 96), dtype=torch.uint8, device=buf.device)
-        elif (out.dtype != torch.uint8 or tuple(out.shape) != (n, h8, w8, 96) or out.device != buf.device
-              or not out.is_contiguous()):
-            raise TypeError("rans3_decode: out must be a contiguous (N,h8,w8,96) torch.uint8 tensor on the codec's device")
-        status = torch.zeros((n,), dtype=torch.int32, device=buf.device)
-        _lib.check(self._L.nic_rans3_decode(self._h, buf.data_ptr(), stride, sizes.data_ptr(), n, int(h8), int(w8),
-                                            out.data_ptr(), status.data_ptr(), _stream_ptr(torch, self.device)),
-                   "nic_rans3_decode")
-        return out, status
+        return self._rans_decode_status(3, buf, sizes, h8, w8, out)
 
     def rans3_decode(self, buf, sizes, h8: int, w8: int):
         """Version-3 .nic files buf[i, :sizes[i]] of (h8, w8) latents -> (N,h8,w8,96) u8.  Reads the
         statuses back (synchronises) and raises ValueError naming the first image whose file did
         not decode cleanly; a file written under another context prior is reported with both ids."""
-        z, status = self.rans3_decode_status(buf, sizes, h8, w8)
-        st = status.cpu().numpy()
-        bad = np.nonzero(st)[0]
-        if bad.size:
-            i = int(bad[0])
-            if st[i] & 8:
-                pid = int.from_bytes(bytes(buf[i, 24:28].cpu().numpy().tolist()), "little")
-                raise ValueError(f"rans3_decode: image {i} was written under prior {pid:08x}, the codec's prior is "
-                                 f"{self.context_prior.id:08x} (status {int(st[i])}; refused images: {bad.tolist()})")
-            raise ValueError(f"rans3_decode: image {i} is corrupt (status {int(st[i])}; corrupt images: {bad.tolist()})")
-        return z
+        return self._rans_decode(3, buf, sizes, h8, w8)
+
 
     # -- region decode: a latent window out of .nic files (nic_region_plan, nic_rans*_decode_window) --
     @staticmethod
@@ -577,48 +535,10 @@ class Codec:
         _lib.check(_lib.lib().nic_region_plan(int(H), int(W), y, x, bh, bw, win, off), "nic_region_plan")
         return tuple(win), tuple(off)
 
-    def _decode_window_status(self, ver: int, buf, sizes, h8: int, w8: int, window, out=None):
-        torch = _torch()
-        name = {1: "rans_decode_window", 2: "rans2_decode_window", 3: "rans3_decode_window"}[ver]
-        if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.device.type != "cuda" or buf.ndim != 2:
-            raise TypeError(f"{name}: expected an (N, stride) cuda torch.uint8 tensor of files")
-        if not isinstance(sizes, torch.Tensor) or sizes.dtype != torch.int64 or sizes.shape != (buf.shape[0],):
-            raise TypeError(f"{name}: expected an (N,) torch.int64 tensor of sizes")
-        if buf.device.index != self.device or sizes.device != buf.device:
-            raise ValueError(f"{name}: tensors must be on cuda:{self.device}")
-        r0, c0, rows, cols = (int(v) for v in window)
-        buf, sizes = buf.contiguous(), sizes.contiguous()
-        n, stride = buf.shape
-        if out is None:
-            out = torch.empty((n, max(rows, 0), max(cols, 0), 96), dtype=torch.uint8, device=buf.device)
-        elif (out.dtype != torch.uint8 or tuple(out.shape) != (n, rows, cols, 96) or out.device != buf.device
-              or not out.is_contiguous()):
-            raise TypeError(f"{name}: out must be a contiguous (N,rows,cols,96) torch.uint8 tensor on the codec's device")
-        status = torch.zeros((n,), dtype=torch.int32, device=buf.device)
-        fn = getattr(self._L, "nic_" + name)
-        _lib.check(fn(self._h, buf.data_ptr(), stride, sizes.data_ptr(), n, int(h8), int(w8), r0, c0, rows, cols,
-                      out.data_ptr(), status.data_ptr(), _stream_ptr(torch, self.device)), "nic_" + name)
-        return out, status
-
-    def _decode_window(self, ver: int, buf, sizes, h8: int, w8: int, window):
-        z, status = self._decode_window_status(ver, buf, sizes, h8, w8, window)
-        st = status.cpu().numpy()
-        bad = np.nonzero(st)[0]
-        if bad.size:
-            i = int(bad[0])
-            name = {1: "rans_decode_window", 2: "rans2_decode_window", 3: "rans3_decode_window"}[ver]
-            if st[i] & 8:
-                pid = int.from_bytes(bytes(buf[i, 24:28].cpu().numpy().tolist()), "little")
-                mine = self.prior if ver == 2 else self.context_prior
-                raise ValueError(f"{name}: image {i} was written under prior {pid:08x}, the codec's prior is "
-                                 f"{mine.id:08x} (status {int(st[i])}; refused images: {bad.tolist()})")
-            raise ValueError(f"{name}: image {i} is corrupt (status {int(st[i])}; corrupt images: {bad.tolist()})")
-        return z
-
     def rans_decode_window_status(self, buf, sizes, h8: int, w8: int, window, out=None):
         """rans_decode_window without the check: (window latent, status (N,) int32 device tensor).
         out: the (N,rows,cols,96) u8 tensor to decode into (default: a new one)."""
-        return self._decode_window_status(1, buf, sizes, h8, w8, window, out)
+        return self._rans_decode_status(1, buf, sizes, h8, w8, out, window)
 
     def rans_decode_window(self, buf, sizes, h8: int, w8: int, window):
         """The window = (r0, c0, rows, cols) of the (h8, w8) latents of version-1 .nic files
@@ -626,25 +546,25 @@ class Codec:
         result; only the segments that hold a pixel of the window are decoded
         (nic_rans_decode_window).  Reads the statuses back (synchronises) and raises ValueError naming
         the first image that did not decode cleanly; damage outside those segments is not seen."""
-        return self._decode_window(1, buf, sizes, h8, w8, window)
+        return self._rans_decode(1, buf, sizes, h8, w8, window)
 
     def rans2_decode_window_status(self, buf, sizes, h8: int, w8: int, window, out=None):
         """rans2_decode_window without the check (as rans_decode_window_status)."""
-        return self._decode_window_status(2, buf, sizes, h8, w8, window, out)
+        return self._rans_decode_status(2, buf, sizes, h8, w8, out, window)
 
     def rans2_decode_window(self, buf, sizes, h8: int, w8: int, window):
         """rans_decode_window for version-2 files, under the codec's prior (NicError(NIC_ENOPRIOR)
         without one; a file written under another prior is reported with both ids)."""
-        return self._decode_window(2, buf, sizes, h8, w8, window)
+        return self._rans_decode(2, buf, sizes, h8, w8, window)
 
     def rans3_decode_window_status(self, buf, sizes, h8: int, w8: int, window, out=None):
         """rans3_decode_window without the check (as rans_decode_window_status)."""
-        return self._decode_window_status(3, buf, sizes, h8, w8, window, out)
+        return self._rans_decode_status(3, buf, sizes, h8, w8, out, window)
 
     def rans3_decode_window(self, buf, sizes, h8: int, w8: int, window):
         """rans_decode_window for version-3 files, under the codec's context prior
         (NicError(NIC_ENOPRIOR) without one)."""
-        return self._decode_window(3, buf, sizes, h8, w8, window)
+        return self._rans_decode(3, buf, sizes, h8, w8, window)
 
     # -- device PNG writer (nic_png_device_*) -------------------------------------------------
     def png_reserve(self, n: int, h: int, w: int, channels: int = 3) -> None:

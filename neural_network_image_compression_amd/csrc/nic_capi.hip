@@ -294,14 +294,13 @@ struct nic_ctx {
   uint32_t* fold_part = nullptr;
   uint32_t* fold_acc = nullptr;
   size_t fold_acc_bytes = 0;
-  // the .nic version-2 prior (nic_rans_prior_set): freqs, cumulative rows and the cost table
-  char* prior = nullptr;
-  uint32_t prior_id = 0;
-  bool have_prior = false;
-  // the .nic version-3 context prior (nic_rans_cprior_set): freqs, cumulative rows, anchors and the cost table
-  char* cprior = nullptr;
-  uint32_t cprior_id = 0;
-  bool have_cprior = false;
+  // the .nic priors on the device (rans_prior_pack's allocation): [0] the version-2 prior
+  // (nic_rans_prior_set), [1] the version-3 context prior (nic_rans_cprior_set)
+  struct {
+    char* dev = nullptr;
+    uint32_t id = 0;
+    bool have = false;
+  } prior[2];
   char* qs = nullptr;  // MS-SSIM scratch (pooled scales + tile sums), grown on demand
   size_t qs_bytes = 0;
   // optional per-layer HIP-event timing (nic_set_timing): one event pair per layer and
@@ -562,8 +561,8 @@ int nic_destroy(nic_ctx* c) {
   if (c->counts) (void)hipFree(c->counts);
   if (c->fold_acc) (void)hipFree(c->fold_acc);
   if (c->qs) (void)hipFree(c->qs);
-  if (c->prior) (void)hipFree(c->prior);
-  if (c->cprior) (void)hipFree(c->cprior);
+  for (auto& p : c->prior)
+    if (p.dev) (void)hipFree(p.dev);
   if (c->zero16) (void)hipFree(c->zero16);
   if (c->wproj) (void)hipFree(c->wproj);
   if (c->range) (void)hipFree(c->range);
@@ -1382,7 +1381,11 @@ int nic_unpack_latent(const uint8_t* packed, int n, int h8, int w8, uint8_t* lat
   return NIC_OK;
 }
 
-// ---- .nic container (nic_rans.hip; nic_rans_bound and nic_rans_inspect are host-only there) ----
+// ---- .nic container, versions 1 to 3, and region decode (nic_rans.hip; the nic_rans*_bound,
+// nic_rans*_inspect, nic_rans_cost_table, nic_rans_*prior_check, nic_region_plan and
+// nic_rans_window_segments are host-only there) ----
+// Each entry point is one call of a body shared by the versions; fn is the entry point's name in
+// the error texts, ver the container version.
 static int rans_check(const char* fn, int n, int h8, int w8, int seg_pixels) {
   if (n < 0 || h8 <= 0 || w8 <= 0) return fail(NIC_ESHAPE, "%s: bad latent shape (%d,%d,%d,96)", fn, n, h8, w8);
   if (!rans_shape_ok(h8, w8)) return fail(NIC_ESHAPE, "%s: latent %dx%d exceeds 2^23 pixels", fn, h8, w8);
@@ -1391,351 +1394,209 @@ static int rans_check(const char* fn, int n, int h8, int w8, int seg_pixels) {
   return NIC_OK;
 }
 
-int nic_rans_reserve(nic_ctx* c, int n, int h8, int w8, int seg_pixels) {
-  int rc = rans_check("nic_rans_reserve", n, h8, w8, seg_pixels);
+// versions 2 and 3 code under the ctx's prior / context prior
+static int rans_need_prior(const char* fn, int ver, const nic_ctx* c) {
+  if (ver == 2 && !c->prior[0].have) return fail(NIC_ENOPRIOR, "%s: no prior is set (nic_rans_prior_set)", fn);
+  if (ver == 3 && !c->prior[1].have) return fail(NIC_ENOPRIOR, "%s: no context prior is set (nic_rans_cprior_set)", fn);
+  return NIC_OK;
+}
+
+static RansPrior ctx_prior(const nic_ctx* c, int ver) {
+  if (ver == 1) return RansPrior{};
+  return rans_prior_view(ver == 3, c->prior[ver - 2].dev, c->prior[ver - 2].id);
+}
+
+static int rans_reserve(const char* fn, int ver, nic_ctx* c, int n, int h8, int w8, int seg_pixels) {
+  int rc = rans_check(fn, n, h8, w8, seg_pixels);
   if (rc || n == 0) return rc;
-  if (!c) return fail(NIC_EINVAL, "nic_rans_reserve: NULL ctx");
+  if (!c) return fail(NIC_EINVAL, "%s: NULL ctx", fn);
   DeviceGuard guard(c->device);
   RansPlan enc, dec;
-  rans_plan(n, h8, w8, seg_pixels, false, &enc);
-  rans_plan(n, h8, w8, seg_pixels, true, &dec);
+  rans_plan(n, h8, w8, seg_pixels, false, &enc, ver);
+  rans_plan(n, h8, w8, seg_pixels, true, &dec, ver);
   return ensure_ws(c, std::max(enc.bytes, dec.bytes));
 }
 
-int nic_rans_encode(nic_ctx* c, const uint8_t* latent, int n, int h8, int w8, int seg_pixels, uint8_t* out, int64_t stride,
-                    int64_t* sizes, void* stream) {
-  int rc = rans_check("nic_rans_encode", n, h8, w8, seg_pixels);
-  if (rc || n == 0) return rc;
-  if (!c) return fail(NIC_EINVAL, "nic_rans_encode: NULL ctx");
-  if (!latent || !out || !sizes) return fail(NIC_EINVAL, "nic_rans_encode: NULL buffer");
-  if ((uintptr_t)latent % 16) return fail(NIC_EINVAL, "nic_rans_encode: latent must be 16-byte aligned");
-  int64_t bound = 0;
-  nic_rans_bound(h8, w8, seg_pixels, &bound);
-  if (stride < bound)
-    return fail(NIC_ESHAPE, "nic_rans_encode: stride %lld is below nic_rans_bound = %lld", (long long)stride, (long long)bound);
-  DeviceGuard guard(c->device);
-  RansPlan pl;
-  rans_plan(n, h8, w8, seg_pixels, false, &pl);
-  if ((rc = ensure_ws(c, pl.bytes))) return rc;
-  HIP_TRY(launch_rans_encode(latent, n, h8, w8, seg_pixels, c->ws, pl, out, stride, (long long*)sizes, (hipStream_t)stream));
-  return NIC_OK;
-}
-
-int nic_rans_decode(nic_ctx* c, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, int h8, int w8,
-                    uint8_t* latent, int32_t* status, void* stream) {
-  int rc = rans_check("nic_rans_decode", n, h8, w8, 1);
-  if (rc || n == 0) return rc;
-  if (!c) return fail(NIC_EINVAL, "nic_rans_decode: NULL ctx");
-  if (!files || !sizes || !latent || !status) return fail(NIC_EINVAL, "nic_rans_decode: NULL buffer");
-  if ((uintptr_t)latent % 16) return fail(NIC_EINVAL, "nic_rans_decode: latent must be 16-byte aligned");
-  if (stride < 16) return fail(NIC_ESHAPE, "nic_rans_decode: stride %lld is below the 16-byte header", (long long)stride);
-  DeviceGuard guard(c->device);
-  RansPlan pl;
-  rans_plan(n, h8, w8, 1, true, &pl);
-  if ((rc = ensure_ws(c, pl.bytes))) return rc;
-  HIP_TRY(launch_rans_decode(files, stride, (const long long*)sizes, n, h8, w8, c->ws, pl, latent, status, (hipStream_t)stream));
-  return NIC_OK;
-}
-
-// ---- .nic version 2: the codec-level prior (nic_rans.hip; nic_rans_cost_table, nic_rans_prior_check,
-// nic_rans2_bound and nic_rans2_inspect are host-only there) ----
-static RansPrior ctx_prior(const nic_ctx* c) {
-  size_t cum_at, cost_at;
-  rans_prior_bytes(&cum_at, &cost_at);
-  return {(const uint16_t*)c->prior, (const uint16_t*)(c->prior + cum_at), (const uint32_t*)(c->prior + cost_at), c->prior_id};
-}
-
-int nic_rans_prior_set(nic_ctx* c, const uint16_t* freqs, uint32_t* id) {
-  if (!c) return fail(NIC_EINVAL, "nic_rans_prior_set: NULL ctx");
-  if (!freqs) {  // back to no prior
-    c->have_prior = false;
-    return NIC_OK;
-  }
-  uint32_t pid = 0;
-  int rc = nic_rans_prior_check(freqs, &pid);
+// version 1 takes no H / W (0 here) and skips their check
+static int rans_encode(const char* fn, int ver, nic_ctx* c, const uint8_t* latent, int n, int h8, int w8, int H, int W,
+                       int seg_pixels, uint8_t* out, int64_t stride, int64_t* sizes, void* stream) {
+  int rc = rans_check(fn, n, h8, w8, seg_pixels);
   if (rc) return rc;
-  size_t cum_at, cost_at;
-  const size_t bytes = rans_prior_bytes(&cum_at, &cost_at);
-  std::vector<char> host(bytes);
-  std::memcpy(host.data(), freqs, cum_at);
-  uint16_t* cum = (uint16_t*)(host.data() + cum_at);
-  for (int ch = 0; ch < 96; ++ch) {
-    uint32_t run = 0;
-    for (int s = 0; s < 256; ++s) {
-      cum[ch * 257 + s] = (uint16_t)run;
-      run += freqs[ch * 256 + s];
-    }
-    cum[ch * 257 + 256] = (uint16_t)run;  // 4096
-  }
-  nic_rans_cost_table((uint32_t*)(host.data() + cost_at));
-  DeviceGuard guard(c->device);
-  c->have_prior = false;
-  if (!c->prior && hipMalloc(&c->prior, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    c->prior = nullptr;
-    return fail(NIC_ENOMEM, "nic_rans_prior_set: allocation of %zu bytes failed", bytes);
-  }
-  HIP_TRY(hipDeviceSynchronize());  // queued coding may still read the previous prior
-  HIP_TRY(hipMemcpy(c->prior, host.data(), bytes, hipMemcpyHostToDevice));
-  c->prior_id = pid;
-  c->have_prior = true;
-  if (id) *id = pid;
-  return NIC_OK;
-}
-
-int nic_rans_prior_count(nic_ctx* c, const uint8_t* latent, int n, int h8, int w8, uint64_t* counts, void* stream) {
-  int rc = rans_check("nic_rans_prior_count", n, h8, w8, 1);
-  if (rc || n == 0) return rc;
-  if (!c) return fail(NIC_EINVAL, "nic_rans_prior_count: NULL ctx");
-  if (!latent || !counts) return fail(NIC_EINVAL, "nic_rans_prior_count: NULL buffer");
-  if ((uintptr_t)latent % 16 || (uintptr_t)counts % 8)
-    return fail(NIC_EINVAL, "nic_rans_prior_count: latent must be 16-byte and counts 8-byte aligned");
-  DeviceGuard guard(c->device);
-  HIP_TRY(launch_rans_prior_count(latent, n, h8, w8, (unsigned long long*)counts, (hipStream_t)stream));
-  return NIC_OK;
-}
-
-int nic_rans_prior_build(nic_ctx* c, const uint64_t* counts, uint16_t* freqs, void* stream) {
-  if (!c) return fail(NIC_EINVAL, "nic_rans_prior_build: NULL ctx");
-  if (!counts || !freqs) return fail(NIC_EINVAL, "nic_rans_prior_build: NULL buffer");
-  if ((uintptr_t)counts % 8 || (uintptr_t)freqs % 2)
-    return fail(NIC_EINVAL, "nic_rans_prior_build: counts must be 8-byte and freqs 2-byte aligned");
-  DeviceGuard guard(c->device);
-  HIP_TRY(launch_rans_prior_build((const unsigned long long*)counts, freqs, (hipStream_t)stream));
-  return NIC_OK;
-}
-
-int nic_rans2_reserve(nic_ctx* c, int n, int h8, int w8, int seg_pixels) {
-  int rc = rans_check("nic_rans2_reserve", n, h8, w8, seg_pixels);
-  if (rc || n == 0) return rc;
-  if (!c) return fail(NIC_EINVAL, "nic_rans2_reserve: NULL ctx");
-  DeviceGuard guard(c->device);
-  RansPlan enc, dec;
-  rans_plan(n, h8, w8, seg_pixels, false, &enc, 2);
-  rans_plan(n, h8, w8, seg_pixels, true, &dec, 2);
-  return ensure_ws(c, std::max(enc.bytes, dec.bytes));
-}
-
-int nic_rans2_encode(nic_ctx* c, const uint8_t* latent, int n, int h8, int w8, int H, int W, int seg_pixels, uint8_t* out,
-                     int64_t stride, int64_t* sizes, void* stream) {
-  int rc = rans_check("nic_rans2_encode", n, h8, w8, seg_pixels);
-  if (rc) return rc;
-  if (H <= 0 || W <= 0 || (H + 7) / 8 != h8 || (W + 7) / 8 != w8)
-    return fail(NIC_ESHAPE, "nic_rans2_encode: a %dx%d image does not have a %dx%d latent", H, W, h8, w8);
-  if (n == 0) return NIC_OK;
-  if (!c) return fail(NIC_EINVAL, "nic_rans2_encode: NULL ctx");
-  if (!latent || !out || !sizes) return fail(NIC_EINVAL, "nic_rans2_encode: NULL buffer");
-  if ((uintptr_t)latent % 16) return fail(NIC_EINVAL, "nic_rans2_encode: latent must be 16-byte aligned");
-  int64_t bound = 0;
-  nic_rans2_bound(h8, w8, seg_pixels, &bound);
-  if (stride < bound)
-    return fail(NIC_ESHAPE, "nic_rans2_encode: stride %lld is below nic_rans2_bound = %lld", (long long)stride, (long long)bound);
-  if (!c->have_prior) return fail(NIC_ENOPRIOR, "nic_rans2_encode: no prior is set (nic_rans_prior_set)");
-  DeviceGuard guard(c->device);
-  RansPlan pl;
-  rans_plan(n, h8, w8, seg_pixels, false, &pl, 2);
-  if ((rc = ensure_ws(c, pl.bytes))) return rc;
-  HIP_TRY(launch_rans2_encode(latent, n, h8, w8, H, W, seg_pixels, ctx_prior(c), c->ws, pl, out, stride, (long long*)sizes,
-                              (hipStream_t)stream));
-  return NIC_OK;
-}
-
-int nic_rans2_decode(nic_ctx* c, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, int h8, int w8,
-                     uint8_t* latent, int32_t* status, void* stream) {
-  int rc = rans_check("nic_rans2_decode", n, h8, w8, 1);
-  if (rc || n == 0) return rc;
-  if (!c) return fail(NIC_EINVAL, "nic_rans2_decode: NULL ctx");
-  if (!files || !sizes || !latent || !status) return fail(NIC_EINVAL, "nic_rans2_decode: NULL buffer");
-  if ((uintptr_t)latent % 16) return fail(NIC_EINVAL, "nic_rans2_decode: latent must be 16-byte aligned");
-  if (stride < 40) return fail(NIC_ESHAPE, "nic_rans2_decode: stride %lld is below the 40-byte header", (long long)stride);
-  if (!c->have_prior) return fail(NIC_ENOPRIOR, "nic_rans2_decode: no prior is set (nic_rans_prior_set)");
-  DeviceGuard guard(c->device);
-  RansPlan pl;
-  rans_plan(n, h8, w8, 1, true, &pl, 2);
-  if ((rc = ensure_ws(c, pl.bytes))) return rc;
-  HIP_TRY(launch_rans2_decode(files, stride, (const long long*)sizes, n, h8, w8, ctx_prior(c), c->ws, pl, latent, status,
-                              (hipStream_t)stream));
-  return NIC_OK;
-}
-
-// ---- .nic version 3: the context prior (nic_rans.hip; nic_rans_cprior_check, nic_rans3_bound and
-// nic_rans3_inspect are host-only there) ----
-static RansCPrior ctx_cprior(const nic_ctx* c) {
-  size_t cum_at, anchor_at, cost_at;
-  rans_cprior_bytes(&cum_at, &anchor_at, &cost_at);
-  return {(const uint16_t*)c->cprior, (const uint16_t*)(c->cprior + cum_at), (const uint8_t*)(c->cprior + anchor_at),
-          (const uint32_t*)(c->cprior + cost_at), c->cprior_id};
-}
-
-int nic_rans_cprior_set(nic_ctx* c, const uint8_t* anchors, const uint16_t* freqs, uint32_t* id) {
-  if (!c) return fail(NIC_EINVAL, "nic_rans_cprior_set: NULL ctx");
-  if (!anchors && !freqs) {  // back to no context prior
-    c->have_cprior = false;
-    return NIC_OK;
-  }
-  uint32_t pid = 0;
-  int rc = nic_rans_cprior_check(anchors, freqs, &pid);
-  if (rc) return rc;
-  size_t cum_at, anchor_at, cost_at;
-  const size_t bytes = rans_cprior_bytes(&cum_at, &anchor_at, &cost_at);
-  const int pitch = rans_cprior_row_pitch();
-  std::vector<char> host(bytes, 0);
-  std::memcpy(host.data(), freqs, cum_at);
-  uint16_t* cum = (uint16_t*)(host.data() + cum_at);
-  for (int row = 0; row < 96 * 3; ++row) {
-    uint32_t run = 0;
-    for (int s = 0; s < 256; ++s) {
-      cum[row * pitch + s] = (uint16_t)run;
-      run += freqs[row * 256 + s];
-    }
-    cum[row * pitch + 256] = (uint16_t)run;  // 4096
-  }
-  std::memcpy(host.data() + anchor_at, anchors, 96);
-  nic_rans_cost_table((uint32_t*)(host.data() + cost_at));
-  DeviceGuard guard(c->device);
-  c->have_cprior = false;
-  if (!c->cprior && hipMalloc(&c->cprior, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    c->cprior = nullptr;
-    return fail(NIC_ENOMEM, "nic_rans_cprior_set: allocation of %zu bytes failed", bytes);
-  }
-  HIP_TRY(hipDeviceSynchronize());  // queued coding may still read the previous prior
-  HIP_TRY(hipMemcpy(c->cprior, host.data(), bytes, hipMemcpyHostToDevice));
-  c->cprior_id = pid;
-  c->have_cprior = true;
-  if (id) *id = pid;
-  return NIC_OK;
-}
-
-int nic_rans_cprior_count(nic_ctx* c, const uint8_t* latent, int n, int h8, int w8, int seg_pixels, const uint8_t* anchors,
-                          uint64_t* counts, void* stream) {
-  int rc = rans_check("nic_rans_cprior_count", n, h8, w8, seg_pixels);
-  if (rc || n == 0) return rc;
-  if (!c) return fail(NIC_EINVAL, "nic_rans_cprior_count: NULL ctx");
-  if (!latent || !anchors || !counts) return fail(NIC_EINVAL, "nic_rans_cprior_count: NULL buffer");
-  if ((uintptr_t)latent % 16 || (uintptr_t)counts % 8)
-    return fail(NIC_EINVAL, "nic_rans_cprior_count: latent must be 16-byte and counts 8-byte aligned");
-  DeviceGuard guard(c->device);
-  HIP_TRY(launch_rans_cprior_count(latent, n, h8, w8, seg_pixels, anchors, (unsigned long long*)counts, (hipStream_t)stream));
-  return NIC_OK;
-}
-
-int nic_rans_cprior_build(nic_ctx* c, const uint64_t* counts, uint16_t* freqs, void* stream) {
-  if (!c) return fail(NIC_EINVAL, "nic_rans_cprior_build: NULL ctx");
-  if (!counts || !freqs) return fail(NIC_EINVAL, "nic_rans_cprior_build: NULL buffer");
-  if ((uintptr_t)counts % 8 || (uintptr_t)freqs % 2)
-    return fail(NIC_EINVAL, "nic_rans_cprior_build: counts must be 8-byte and freqs 2-byte aligned");
-  DeviceGuard guard(c->device);
-  HIP_TRY(launch_rans_cprior_build((const unsigned long long*)counts, freqs, (hipStream_t)stream));
-  return NIC_OK;
-}
-
-int nic_rans3_reserve(nic_ctx* c, int n, int h8, int w8, int seg_pixels) {
-  int rc = rans_check("nic_rans3_reserve", n, h8, w8, seg_pixels);
-  if (rc || n == 0) return rc;
-  if (!c) return fail(NIC_EINVAL, "nic_rans3_reserve: NULL ctx");
-  DeviceGuard guard(c->device);
-  RansPlan enc, dec;
-  rans_plan(n, h8, w8, seg_pixels, false, &enc, 3);
-  rans_plan(n, h8, w8, seg_pixels, true, &dec, 3);
-  return ensure_ws(c, std::max(enc.bytes, dec.bytes));
-}
-
-int nic_rans3_encode(nic_ctx* c, const uint8_t* latent, int n, int h8, int w8, int H, int W, int seg_pixels, uint8_t* out,
-                     int64_t stride, int64_t* sizes, void* stream) {
-  int rc = rans_check("nic_rans3_encode", n, h8, w8, seg_pixels);
-  if (rc) return rc;
-  if (H <= 0 || W <= 0 || (H + 7) / 8 != h8 || (W + 7) / 8 != w8)
-    return fail(NIC_ESHAPE, "nic_rans3_encode: a %dx%d image does not have a %dx%d latent", H, W, h8, w8);
-  if (n == 0) return NIC_OK;
-  if (!c) return fail(NIC_EINVAL, "nic_rans3_encode: NULL ctx");
-  if (!latent || !out || !sizes) return fail(NIC_EINVAL, "nic_rans3_encode: NULL buffer");
-  if ((uintptr_t)latent % 16) return fail(NIC_EINVAL, "nic_rans3_encode: latent must be 16-byte aligned");
-  int64_t bound = 0;
-  nic_rans3_bound(h8, w8, seg_pixels, &bound);
-  if (stride < bound)
-    return fail(NIC_ESHAPE, "nic_rans3_encode: stride %lld is below nic_rans3_bound = %lld", (long long)stride, (long long)bound);
-  if (!c->have_cprior) return fail(NIC_ENOPRIOR, "nic_rans3_encode: no context prior is set (nic_rans_cprior_set)");
-  DeviceGuard guard(c->device);
-  RansPlan pl;
-  rans_plan(n, h8, w8, seg_pixels, false, &pl, 3);
-  if ((rc = ensure_ws(c, pl.bytes))) return rc;
-  HIP_TRY(launch_rans3_encode(latent, n, h8, w8, H, W, seg_pixels, ctx_cprior(c), c->ws, pl, out, stride, (long long*)sizes,
-                              (hipStream_t)stream));
-  return NIC_OK;
-}
-
-int nic_rans3_decode(nic_ctx* c, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, int h8, int w8,
-                     uint8_t* latent, int32_t* status, void* stream) {
-  int rc = rans_check("nic_rans3_decode", n, h8, w8, 1);
-  if (rc || n == 0) return rc;
-  if (!c) return fail(NIC_EINVAL, "nic_rans3_decode: NULL ctx");
-  if (!files || !sizes || !latent || !status) return fail(NIC_EINVAL, "nic_rans3_decode: NULL buffer");
-  if ((uintptr_t)latent % 16) return fail(NIC_EINVAL, "nic_rans3_decode: latent must be 16-byte aligned");
-  if (stride < 40) return fail(NIC_ESHAPE, "nic_rans3_decode: stride %lld is below the 40-byte header", (long long)stride);
-  if (!c->have_cprior) return fail(NIC_ENOPRIOR, "nic_rans3_decode: no context prior is set (nic_rans_cprior_set)");
-  DeviceGuard guard(c->device);
-  RansPlan pl;
-  rans_plan(n, h8, w8, 1, true, &pl, 3);
-  if ((rc = ensure_ws(c, pl.bytes))) return rc;
-  HIP_TRY(launch_rans3_decode(files, stride, (const long long*)sizes, n, h8, w8, ctx_cprior(c), c->ws, pl, latent, status,
-                              (hipStream_t)stream));
-  return NIC_OK;
-}
-
-// ---- region decode: a latent window out of .nic files (nic_rans.hip; nic_region_plan and
-// nic_rans_window_segments are host-only there) ----
-// ver 1, 2 or 3: the full decode's checks in its order (shape, with the window; empty batch; NULL;
-// the prior), its parse and workspace, then the window's segments only.
-static int rans_decode_window(const char* fn, int ver, nic_ctx* c, const uint8_t* files, int64_t stride, const int64_t* sizes,
-                              int n, int h8, int w8, int r0, int c0, int rows, int cols, uint8_t* latent_win, int32_t* status,
-                              void* stream) {
-  int rc = rans_check(fn, n, h8, w8, 1);
-  if (rc) return rc;
-  if (r0 < 0 || c0 < 0 || rows < 1 || cols < 1 || (long long)r0 + rows > h8 || (long long)c0 + cols > w8)
-    return fail(NIC_ESHAPE, "%s: window (r0 %d, c0 %d, %d x %d) does not lie inside the %dx%d latent", fn, r0, c0, rows, cols,
-                h8, w8);
+  if (ver != 1 && (H <= 0 || W <= 0 || (H + 7) / 8 != h8 || (W + 7) / 8 != w8))
+    return fail(NIC_ESHAPE, "%s: a %dx%d image does not have a %dx%d latent", fn, H, W, h8, w8);
   if (n == 0) return NIC_OK;
   if (!c) return fail(NIC_EINVAL, "%s: NULL ctx", fn);
-  if (!files || !sizes || !latent_win || !status) return fail(NIC_EINVAL, "%s: NULL buffer", fn);
-  if ((uintptr_t)latent_win % 16) return fail(NIC_EINVAL, "%s: latent_win must be 16-byte aligned", fn);
+  if (!latent || !out || !sizes) return fail(NIC_EINVAL, "%s: NULL buffer", fn);
+  if ((uintptr_t)latent % 16) return fail(NIC_EINVAL, "%s: latent must be 16-byte aligned", fn);
+  int64_t bound = 0;
+  (ver == 1 ? nic_rans_bound : nic_rans2_bound)(h8, w8, seg_pixels, &bound);  // nic_rans3_bound is nic_rans2_bound
+  if (stride < bound) {
+    const char* bound_fn[] = {"nic_rans_bound", "nic_rans2_bound", "nic_rans3_bound"};
+    return fail(NIC_ESHAPE, "%s: stride %lld is below %s = %lld", fn, (long long)stride, bound_fn[ver - 1], (long long)bound);
+  }
+  if ((rc = rans_need_prior(fn, ver, c))) return rc;
+  DeviceGuard guard(c->device);
+  RansPlan pl;
+  rans_plan(n, h8, w8, seg_pixels, false, &pl, ver);
+  if ((rc = ensure_ws(c, pl.bytes))) return rc;
+  HIP_TRY(launch_rans_encode(ver, latent, n, h8, w8, H, W, seg_pixels, ctx_prior(c, ver), c->ws, pl, out, stride,
+                             (long long*)sizes, (hipStream_t)stream));
+  return NIC_OK;
+}
+
+// window NULL: the whole latents; else {r0, c0, rows, cols}, and latent is the window's (n, rows, cols, 96).
+// The checks in order: shape, with the window; empty batch; NULL; the stride; the prior.
+static int rans_decode(const char* fn, int ver, nic_ctx* c, const uint8_t* files, int64_t stride, const int64_t* sizes, int n,
+                       int h8, int w8, const int* window, uint8_t* latent, int32_t* status, void* stream) {
+  int rc = rans_check(fn, n, h8, w8, 1);
+  if (rc) return rc;
+  RansWindow win{};
+  if (window) {
+    win = {w8, window[0], window[1], window[2], window[3]};
+    if (win.r0 < 0 || win.c0 < 0 || win.rows < 1 || win.cols < 1 || (long long)win.r0 + win.rows > h8 ||
+        (long long)win.c0 + win.cols > w8)
+      return fail(NIC_ESHAPE, "%s: window (r0 %d, c0 %d, %d x %d) does not lie inside the %dx%d latent", fn, win.r0, win.c0,
+                  win.rows, win.cols, h8, w8);
+  }
+  if (n == 0) return NIC_OK;
+  if (!c) return fail(NIC_EINVAL, "%s: NULL ctx", fn);
+  if (!files || !sizes || !latent || !status) return fail(NIC_EINVAL, "%s: NULL buffer", fn);
+  if ((uintptr_t)latent % 16) return fail(NIC_EINVAL, "%s: %s must be 16-byte aligned", fn, window ? "latent_win" : "latent");
   const int header = ver == 1 ? 16 : 40;
   if (stride < header) return fail(NIC_ESHAPE, "%s: stride %lld is below the %d-byte header", fn, (long long)stride, header);
-  if (ver == 2 && !c->have_prior) return fail(NIC_ENOPRIOR, "%s: no prior is set (nic_rans_prior_set)", fn);
-  if (ver == 3 && !c->have_cprior) return fail(NIC_ENOPRIOR, "%s: no context prior is set (nic_rans_cprior_set)", fn);
+  if ((rc = rans_need_prior(fn, ver, c))) return rc;
   DeviceGuard guard(c->device);
   RansPlan pl;
   rans_plan(n, h8, w8, 1, true, &pl, ver);
   if ((rc = ensure_ws(c, pl.bytes))) return rc;
-  if (ver == 3) {
-    HIP_TRY(launch_rans3_decode_window(files, stride, (const long long*)sizes, n, h8, w8, r0, c0, rows, cols, ctx_cprior(c),
-                                       c->ws, pl, latent_win, status, (hipStream_t)stream));
-  } else {
-    RansPrior pr{};
-    if (ver == 2) pr = ctx_prior(c);
-    HIP_TRY(launch_rans_decode_window(files, stride, (const long long*)sizes, n, h8, w8, r0, c0, rows, cols,
-                                      ver == 2 ? &pr : nullptr, c->ws, pl, latent_win, status, (hipStream_t)stream));
-  }
+  HIP_TRY(launch_rans_decode(ver, files, stride, (const long long*)sizes, n, h8, w8, window ? &win : nullptr, ctx_prior(c, ver),
+                             c->ws, pl, latent, status, (hipStream_t)stream));
   return NIC_OK;
+}
+
+// context: the context prior (anchors and freqs), else the static prior (anchors NULL)
+static int rans_prior_set(const char* fn, bool context, nic_ctx* c, const uint8_t* anchors, const uint16_t* freqs, uint32_t* id) {
+  if (!c) return fail(NIC_EINVAL, "%s: NULL ctx", fn);
+  auto& slot = c->prior[context ? 1 : 0];
+  if (!anchors && !freqs) {  // back to no prior
+    slot.have = false;
+    return NIC_OK;
+  }
+  uint32_t pid = 0;
+  int rc = context ? nic_rans_cprior_check(anchors, freqs, &pid) : nic_rans_prior_check(freqs, &pid);
+  if (rc) return rc;
+  const std::vector<char> host = rans_prior_pack(anchors, freqs);
+  DeviceGuard guard(c->device);
+  slot.have = false;
+  if (!slot.dev && hipMalloc(&slot.dev, host.size()) != hipSuccess) {
+    (void)hipGetLastError();
+    slot.dev = nullptr;
+    return fail(NIC_ENOMEM, "%s: allocation of %zu bytes failed", fn, host.size());
+  }
+  HIP_TRY(hipDeviceSynchronize());  // queued coding may still read the previous prior
+  HIP_TRY(hipMemcpy(slot.dev, host.data(), host.size(), hipMemcpyHostToDevice));
+  slot.id = pid;
+  slot.have = true;
+  if (id) *id = pid;
+  return NIC_OK;
+}
+
+static int rans_prior_count(const char* fn, bool context, nic_ctx* c, const uint8_t* latent, int n, int h8, int w8, int seg_pixels,
+                            const uint8_t* anchors, uint64_t* counts, void* stream) {
+  int rc = rans_check(fn, n, h8, w8, seg_pixels);
+  if (rc || n == 0) return rc;
+  if (!c) return fail(NIC_EINVAL, "%s: NULL ctx", fn);
+  if (!latent || (context && !anchors) || !counts) return fail(NIC_EINVAL, "%s: NULL buffer", fn);
+  if ((uintptr_t)latent % 16 || (uintptr_t)counts % 8)
+    return fail(NIC_EINVAL, "%s: latent must be 16-byte and counts 8-byte aligned", fn);
+  DeviceGuard guard(c->device);
+  HIP_TRY(launch_rans_prior_count(latent, n, h8, w8, seg_pixels, anchors, (unsigned long long*)counts, (hipStream_t)stream));
+  return NIC_OK;
+}
+
+static int rans_prior_build(const char* fn, bool context, nic_ctx* c, const uint64_t* counts, uint16_t* freqs, void* stream) {
+  if (!c) return fail(NIC_EINVAL, "%s: NULL ctx", fn);
+  if (!counts || !freqs) return fail(NIC_EINVAL, "%s: NULL buffer", fn);
+  if ((uintptr_t)counts % 8 || (uintptr_t)freqs % 2) return fail(NIC_EINVAL, "%s: counts must be 8-byte and freqs 2-byte aligned", fn);
+  DeviceGuard guard(c->device);
+  HIP_TRY(launch_rans_prior_build(context, (const unsigned long long*)counts, freqs, (hipStream_t)stream));
+  return NIC_OK;
+}
+
+int nic_rans_reserve(nic_ctx* c, int n, int h8, int w8, int seg_pixels) {
+  return rans_reserve("nic_rans_reserve", 1, c, n, h8, w8, seg_pixels);
+}
+int nic_rans2_reserve(nic_ctx* c, int n, int h8, int w8, int seg_pixels) {
+  return rans_reserve("nic_rans2_reserve", 2, c, n, h8, w8, seg_pixels);
+}
+int nic_rans3_reserve(nic_ctx* c, int n, int h8, int w8, int seg_pixels) {
+  return rans_reserve("nic_rans3_reserve", 3, c, n, h8, w8, seg_pixels);
+}
+
+int nic_rans_encode(nic_ctx* c, const uint8_t* latent, int n, int h8, int w8, int seg_pixels, uint8_t* out, int64_t stride,
+                    int64_t* sizes, void* stream) {
+  return rans_encode("nic_rans_encode", 1, c, latent, n, h8, w8, 0, 0, seg_pixels, out, stride, sizes, stream);
+}
+int nic_rans2_encode(nic_ctx* c, const uint8_t* latent, int n, int h8, int w8, int H, int W, int seg_pixels, uint8_t* out,
+                     int64_t stride, int64_t* sizes, void* stream) {
+  return rans_encode("nic_rans2_encode", 2, c, latent, n, h8, w8, H, W, seg_pixels, out, stride, sizes, stream);
+}
+int nic_rans3_encode(nic_ctx* c, const uint8_t* latent, int n, int h8, int w8, int H, int W, int seg_pixels, uint8_t* out,
+                     int64_t stride, int64_t* sizes, void* stream) {
+  return rans_encode("nic_rans3_encode", 3, c, latent, n, h8, w8, H, W, seg_pixels, out, stride, sizes, stream);
+}
+
+int nic_rans_decode(nic_ctx* c, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, int h8, int w8,
+                    uint8_t* latent, int32_t* status, void* stream) {
+  return rans_decode("nic_rans_decode", 1, c, files, stride, sizes, n, h8, w8, nullptr, latent, status, stream);
+}
+int nic_rans2_decode(nic_ctx* c, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, int h8, int w8,
+                     uint8_t* latent, int32_t* status, void* stream) {
+  return rans_decode("nic_rans2_decode", 2, c, files, stride, sizes, n, h8, w8, nullptr, latent, status, stream);
+}
+int nic_rans3_decode(nic_ctx* c, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, int h8, int w8,
+                     uint8_t* latent, int32_t* status, void* stream) {
+  return rans_decode("nic_rans3_decode", 3, c, files, stride, sizes, n, h8, w8, nullptr, latent, status, stream);
 }
 
 int nic_rans_decode_window(nic_ctx* c, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, int h8, int w8,
                            int r0, int c0, int rows, int cols, uint8_t* latent_win, int32_t* status, void* stream) {
-  return rans_decode_window("nic_rans_decode_window", 1, c, files, stride, sizes, n, h8, w8, r0, c0, rows, cols, latent_win,
-                            status, stream);
+  const int window[4] = {r0, c0, rows, cols};
+  return rans_decode("nic_rans_decode_window", 1, c, files, stride, sizes, n, h8, w8, window, latent_win, status, stream);
 }
-
 int nic_rans2_decode_window(nic_ctx* c, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, int h8, int w8,
                             int r0, int c0, int rows, int cols, uint8_t* latent_win, int32_t* status, void* stream) {
-  return rans_decode_window("nic_rans2_decode_window", 2, c, files, stride, sizes, n, h8, w8, r0, c0, rows, cols, latent_win,
-                            status, stream);
+  const int window[4] = {r0, c0, rows, cols};
+  return rans_decode("nic_rans2_decode_window", 2, c, files, stride, sizes, n, h8, w8, window, latent_win, status, stream);
 }
-
 int nic_rans3_decode_window(nic_ctx* c, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, int h8, int w8,
                             int r0, int c0, int rows, int cols, uint8_t* latent_win, int32_t* status, void* stream) {
-  return rans_decode_window("nic_rans3_decode_window", 3, c, files, stride, sizes, n, h8, w8, r0, c0, rows, cols, latent_win,
-                            status, stream);
+  const int window[4] = {r0, c0, rows, cols};
+  return rans_decode("nic_rans3_decode_window", 3, c, files, stride, sizes, n, h8, w8, window, latent_win, status, stream);
 }
+
+int nic_rans_prior_set(nic_ctx* c, const uint16_t* freqs, uint32_t* id) {
+  return rans_prior_set("nic_rans_prior_set", false, c, nullptr, freqs, id);
+}
+int nic_rans_cprior_set(nic_ctx* c, const uint8_t* anchors, const uint16_t* freqs, uint32_t* id) {
+  return rans_prior_set("nic_rans_cprior_set", true, c, anchors, freqs, id);
+}
+
+int nic_rans_prior_count(nic_ctx* c, const uint8_t* latent, int n, int h8, int w8, uint64_t* counts, void* stream) {
+  return rans_prior_count("nic_rans_prior_count", false, c, latent, n, h8, w8, 1, nullptr, counts, stream);
+}
+int nic_rans_cprior_count(nic_ctx* c, const uint8_t* latent, int n, int h8, int w8, int seg_pixels, const uint8_t* anchors,
+                          uint64_t* counts, void* stream) {
+  return rans_prior_count("nic_rans_cprior_count", true, c, latent, n, h8, w8, seg_pixels, anchors, counts, stream);
+}
+
+int nic_rans_prior_build(nic_ctx* c, const uint64_t* counts, uint16_t* freqs, void* stream) {
+  return rans_prior_build("nic_rans_prior_build", false, c, counts, freqs, stream);
+}
+int nic_rans_cprior_build(nic_ctx* c, const uint64_t* counts, uint16_t* freqs, void* stream) {
+  return rans_prior_build("nic_rans_cprior_build", true, c, counts, freqs, stream);
+}
+
 
 // ---- device PNG writer (nic_png_dev.hip; nic_png_device_block_bytes and nic_png_device_bound are host-only there) ----
 static int png_dev_check(const char* fn, int n, int h, int w, int channels, int filter) {

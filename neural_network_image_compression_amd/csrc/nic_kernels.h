@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 namespace nic {
 
 int set_error(int code, const char* msg);  // nic_last_error() text of this thread (nic_capi.hip)
@@ -174,55 +176,42 @@ struct RansPlan {
   uint32_t cap;  // encode: bytes of one segment's worst-case region
   size_t counts, cum, tab, tablen, taboff, keep, seglen, segoff, meta, scratch, bytes;
 };
-// The ctx's prior on the device (version 2): 96 x 256 freqs, their 96 x 257 cumulative rows and
-// the 4,097-entry cost table, in one allocation of rans_prior_bytes() bytes.
+// A prior of the ctx on the device, one allocation: the static prior (version 2: 96 x 256 freqs,
+// their 96 x 257 cumulative rows, the cost table) or the context prior (version 3: 96 x 3 x 256
+// freqs, their cumulative rows at the segment kernels' row pitch, the 96 anchors, the cost table).
+// anchor is NULL without contexts; all of it is NULL / 0 for version 1.
 struct RansPrior {
-  const uint16_t* freq;
-  const uint16_t* cum;
-  const uint32_t* cost16;
-  uint32_t id;
-};
-bool rans_shape_ok(int h8, int w8);
-// ver: the container version; 2 and 3: + keep[96] per image; 3: three rows and three histograms per channel
-void rans_plan(int n, int h8, int w8, int seg_pixels, bool decode, RansPlan* plan, int ver = 1);
-hipError_t launch_rans_encode(const uint8_t* z, int n, int h8, int w8, int seg_pixels, char* ws, const RansPlan& plan,
-                              uint8_t* out, long long stride, long long* sizes, hipStream_t st);
-hipError_t launch_rans_decode(const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8, char* ws,
-                              const RansPlan& plan, uint8_t* z, int* status, hipStream_t st);
-size_t rans_prior_bytes(size_t* cum_at, size_t* cost_at);
-hipError_t launch_rans_prior_count(const uint8_t* z, int n, int h8, int w8, unsigned long long* counts, hipStream_t st);
-hipError_t launch_rans_prior_build(const unsigned long long* counts, uint16_t* freqs, hipStream_t st);
-hipError_t launch_rans2_encode(const uint8_t* z, int n, int h8, int w8, int H, int W, int seg_pixels, const RansPrior& prior,
-                               char* ws, const RansPlan& plan, uint8_t* out, long long stride, long long* sizes, hipStream_t st);
-hipError_t launch_rans2_decode(const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8,
-                               const RansPrior& prior, char* ws, const RansPlan& plan, uint8_t* z, int* status, hipStream_t st);
-// The ctx's context prior on the device (version 3): 96 x 3 x 256 freqs, their cumulative rows at
-// the segment kernels' row pitch (rans_cprior_row_pitch() u16 per row), the 96 anchors and the cost
-// table, in one allocation of rans_cprior_bytes() bytes.
-struct RansCPrior {
   const uint16_t* freq;
   const uint16_t* cum;
   const uint8_t* anchor;
   const uint32_t* cost16;
   uint32_t id;
 };
-size_t rans_cprior_bytes(size_t* cum_at, size_t* anchor_at, size_t* cost_at);
-int rans_cprior_row_pitch();
-hipError_t launch_rans_cprior_count(const uint8_t* z, int n, int h8, int w8, int seg_pixels, const uint8_t* anchor,
-                                    unsigned long long* counts, hipStream_t st);
-hipError_t launch_rans_cprior_build(const unsigned long long* counts, uint16_t* freqs, hipStream_t st);
-hipError_t launch_rans3_encode(const uint8_t* z, int n, int h8, int w8, int H, int W, int seg_pixels, const RansCPrior& prior,
-                               char* ws, const RansPlan& plan, uint8_t* out, long long stride, long long* sizes, hipStream_t st);
-hipError_t launch_rans3_decode(const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8,
-                               const RansCPrior& prior, char* ws, const RansPlan& plan, uint8_t* z, int* status, hipStream_t st);
-// Window decode: the latent pixels (r0 + i, c0 + x), i < rows, x < cols, of every file into zwin
-// (n, rows, cols, 96); plan: the decode plan of (n, h8, w8).  prior NULL: version 1, else version 2.
-hipError_t launch_rans_decode_window(const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8,
-                                     int r0, int c0, int rows, int cols, const RansPrior* prior, char* ws, const RansPlan& plan,
-                                     uint8_t* zwin, int* status, hipStream_t st);
-hipError_t launch_rans3_decode_window(const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8,
-                                      int r0, int c0, int rows, int cols, const RansCPrior& prior, char* ws, const RansPlan& plan,
-                                      uint8_t* zwin, int* status, hipStream_t st);
+// the host image of a prior's allocation from checked freqs (anchors NULL: the static prior), and the
+// pointers into its device copy
+std::vector<char> rans_prior_pack(const uint8_t* anchors, const uint16_t* freqs);
+RansPrior rans_prior_view(bool context, const char* dev, uint32_t id);
+// counts of a batch's latents into one u64 accumulator: [96][256], or [96][3][256] under anchor (the
+// context prior, segments of seg_pixels); and an accumulator's 96 or 96 x 3 rows -> freqs
+hipError_t launch_rans_prior_count(const uint8_t* z, int n, int h8, int w8, int seg_pixels, const uint8_t* anchor,
+                                   unsigned long long* counts, hipStream_t st);
+hipError_t launch_rans_prior_build(bool context, const unsigned long long* counts, uint16_t* freqs, hipStream_t st);
+// A latent window: the pixels (r0 + i, c0 + x), i < rows, x < cols, of a latent w8 wide.
+struct RansWindow {
+  int w8, r0, c0, rows, cols;
+};
+bool rans_shape_ok(int h8, int w8);
+// ver: the container version; 2 and 3: + keep[96] per image; 3: three rows and three histograms per channel
+void rans_plan(int n, int h8, int w8, int seg_pixels, bool decode, RansPlan* plan, int ver);
+// Files of version ver from latents / latents from files; prior: the version's (RansPrior{} for
+// version 1, which also ignores H and W).  win NULL: the whole latents into z (n, h8, w8, 96); else
+// only the window's pixels, into z (n, rows, cols, 96).  plan: rans_plan's for (n, h8, w8) and ver.
+hipError_t launch_rans_encode(int ver, const uint8_t* z, int n, int h8, int w8, int H, int W, int seg_pixels,
+                              const RansPrior& prior, char* ws, const RansPlan& plan, uint8_t* out, long long stride,
+                              long long* sizes, hipStream_t st);
+hipError_t launch_rans_decode(int ver, const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8,
+                              const RansWindow* win, const RansPrior& prior, char* ws, const RansPlan& plan, uint8_t* z,
+                              int* status, hipStream_t st);
 
 // --- device PNG writer (nic_png_dev.hip) ------------------------------------------------------
 // Byte offsets of one call's scratch inside the ctx workspace (256-B aligned), from png_dev_plan:

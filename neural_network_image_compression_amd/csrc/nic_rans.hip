@@ -13,6 +13,11 @@
 // table and payload into out + i * stride).
 // Decode: rans_parse (header check, tables -> cumulative rows, segment offsets; all on the
 // device) -> rans_decode_segments (binary search of the LDS cumulative row per slot).
+//
+// Versions 2 (a codec-level prior) and 3 (a context prior: three rows per channel, chosen by the
+// left neighbour) run the same kernels: every kernel that differs between versions is one template,
+// over the version (rans_parse, rans_layout, rans_assemble) or over the rows of an image (Rows<>:
+// rans_tables, rans_encode_segments, rans_decode_segments), instantiated per case.
 
 #include <hip/hip_runtime.h>
 
@@ -37,7 +42,36 @@ constexpr int kCumRow = 257;             // start[0..256] of one channel
 constexpr int kCumWords = kCh * kCumRow; // u16 per image (49,344 B: the LDS table)
 constexpr int kTabRow = 772;             // >= 1 + 3 * 256 file bytes of one channel's table
 constexpr int kHeader = 16;
-constexpr int kHeader2 = 40;             // version 2: + u32 H, u32 W, u32 prior_id, 12-byte channel mask
+constexpr int kHeader2 = 40;             // versions 2 and 3: + u32 H, u32 W, u32 prior_id, 12-byte channel mask
+
+// Version 3's row pitch in LDS: all 64 lanes are at one channel, spread over its three rows, and most
+// of them at symbols near the anchor.  At 257 u16 (128.5 dwords) the same symbol of the three rows
+// falls onto one or two neighbouring banks; at 278 u16 (139 dwords = 4 x 32 + 11) the rows sit 11
+// and 22 banks apart.  288 rows x 556 B = 160,128 B of the 163,840.
+constexpr int kCtx = 3;
+constexpr int kCtxRow = 278;
+constexpr int kCtxWords = kCh * kCtx * kCtxRow;  // u16 per image
+static_assert(kCtxRow % 2 == 0 && kCtxRow >= kCumRow && kCtxWords * 2 + 64 <= 160 * 1024, "the rows must fit the LDS");
+
+// The cumulative rows of one image, u16[96][kPerCh][kPitch] in global memory and in LDS alike:
+// one row per channel (versions 1 and 2) or one per (channel, context) (version 3).
+template <bool kContext>
+struct Rows {
+  static constexpr int kPerCh = kContext ? kCtx : 1;
+  static constexpr int kPitch = kContext ? kCtxRow : kCumRow;
+  static constexpr int kWords = kContext ? kCtxWords : kCumWords;
+  // channel ch's row of context k (k = 0 without contexts)
+  __device__ static const uint16_t* row(const uint16_t* rows, int ch, uint32_t k) { return rows + (ch * kPerCh + k) * kPitch; }
+};
+
+// the image's rows into LDS as dwords (kWords is even and every image's rows start 4-B aligned; the
+// pad of a version-3 row is copied, never read)
+template <class R>
+__device__ __forceinline__ void load_rows(uint16_t* lds, const uint16_t* __restrict__ src, int tid, int nthreads) {
+  const uint32_t* s = (const uint32_t*)src;
+  uint32_t* d = (uint32_t*)lds;
+  for (int i = tid; i < R::kWords / 2; i += nthreads) d[i] = s[i];
+}
 
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 #pragma unroll
@@ -66,7 +100,12 @@ __device__ __forceinline__ uint32_t wave_excl(uint32_t v, int lane) {
 // ---- encode 1: per-image, per-channel counts ----------------------------------------------
 // grid (ceil(npix / 256), 3, n), block 256: thread = pixel, blockIdx.y = a third of the channels
 // (32 LDS histograms = 32 KB); each thread reads its pixel's 32 bytes as two 16-B loads.
-__global__ __launch_bounds__(256) void rans_hist(const uint8_t* __restrict__ z, int npix, uint32_t* __restrict__ counts) {
+// T = uint32_t: per-image counts [n][96][256] (img_stride = 96 * 256); T = unsigned long long: the
+// prior's one accumulator [96][256] (img_stride = 0), added into with 64-bit integer atomics, so the
+// totals do not depend on the order and accumulate across calls.
+template <typename T>
+__global__ __launch_bounds__(256) void rans_hist(const uint8_t* __restrict__ z, int npix, T* __restrict__ counts,
+                                                  size_t img_stride) {
   __shared__ uint32_t h[32 * 256];
   const int tid = threadIdx.x, third = blockIdx.y, img = blockIdx.z;
   for (int i = tid; i < 32 * 256; i += 256) h[i] = 0;
@@ -83,9 +122,9 @@ __global__ __launch_bounds__(256) void rans_hist(const uint8_t* __restrict__ z, 
     }
   }
   __syncthreads();
-  uint32_t* dst = counts + ((size_t)img * kCh + 32 * third) * 256;
+  T* dst = counts + (size_t)img * img_stride + (size_t)(32 * third) * 256;
   for (int i = tid; i < 32 * 256; i += 256)
-    if (h[i]) atomicAdd(&dst[i], h[i]);
+    if (h[i]) atomicAdd(&dst[i], (T)h[i]);
 }
 
 // ---- encode 2: 12-bit tables ---------------------------------------------------------------
@@ -94,7 +133,7 @@ __global__ __launch_bounds__(256) void rans_hist(const uint8_t* __restrict__ z, 
 //   a surplus (at most 255, from the floor-to-zero bumps) is taken one at a time from the
 //   currently largest entry (lowest symbol on ties), which never takes an entry below 1.
 // Writes the channel's cumulative row start[0..256], its file bytes and their count.
-// The steps are device functions of the whole wave, shared with the version-2 tables kernel.
+// The steps are device functions of the whole wave, shared with rans_tables.
 
 // lane l's four counts -> its four freqs (0 for an unused symbol) and how many it uses
 __device__ __forceinline__ void normalise_own(const uint32_t cnt[4], int npix, int lane, uint32_t f[4], uint32_t& used) {
@@ -183,11 +222,85 @@ __global__ __launch_bounds__(64) void rans_normalise(const uint32_t* __restrict_
   write_table(f, used, lane, tab + row * kTabRow, tablen + row);
 }
 
-// the image's 96 cumulative rows into LDS (kCumWords u16 = 24,672 dwords)
-__device__ __forceinline__ void load_cum(uint16_t* lds, const uint16_t* __restrict__ src, int tid, int nthreads) {
-  const uint32_t* s = (const uint32_t*)src;  // kCumWords is even and every image's rows start 4-B aligned
-  uint32_t* d = (uint32_t*)lds;
-  for (int i = tid; i < kCumWords / 2; i += nthreads) d[i] = s[i];
+__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint32_t lo = __shfl_xor((uint32_t)v, o, 64), hi = __shfl_xor((uint32_t)(v >> 32), o, 64);
+    v += ((unsigned long long)hi << 32) | lo;
+  }
+  return v;
+}
+
+// ---- encode 2, versions 2 and 3: tables and the per-channel choice.  grid (96, n), block 64 -----
+// The prior is 96 x kPerCh x 256 freqs in 1..4096, every row summing to 4096, fitted once over a
+// corpus and shared by every file.  A file stores a table only for the channels whose own table
+// pays for itself; the others are coded with the prior's row(s).
+// counts: the image's [96][kPerCh][256]; their sum over the contexts is version 1's histogram and
+// is normalised by version 1's rule.  With cost16[f] = round((12 - log2 f) 2^16):
+//   own = sum c cost16[f_own] + (8 (1 + 3 n) << 16),  prior = sum over rows k of c_k cost16[f_prior[k]]   (u64)
+// The channel keeps its own table iff own < prior.  Writes the channel's kPerCh cumulative rows (the
+// prior's, or its own row in every context), the table's file bytes and their length (0 for a prior
+// channel) and keep[].
+template <bool kContext>
+__global__ __launch_bounds__(64) void rans_tables(const uint32_t* __restrict__ counts, int npix,
+                                                   const uint16_t* __restrict__ prior_freq,
+                                                   const uint16_t* __restrict__ prior_cum, const uint32_t* __restrict__ cost16,
+                                                   uint16_t* __restrict__ cum, uint8_t* __restrict__ tab,
+                                                   uint32_t* __restrict__ tablen, uint32_t* __restrict__ keep) {
+  using R = Rows<kContext>;
+  const int lane = threadIdx.x, c = blockIdx.x, img = blockIdx.y;
+  const size_t row = (size_t)img * kCh + c;
+  uint32_t cnt[4] = {0, 0, 0, 0};
+  unsigned long long pri = 0;
+#pragma unroll
+  for (int k = 0; k < R::kPerCh; ++k) {
+    const uint4 cv = ((const uint4*)(counts + (row * R::kPerCh + k) * 256))[lane];
+    const uint32_t ck[4] = {cv.x, cv.y, cv.z, cv.w};
+    const uint2 pv = ((const uint2*)(prior_freq + ((size_t)c * R::kPerCh + k) * 256))[lane];  // each in 1..4096 (checked on upload)
+    const uint32_t pf[4] = {pv.x & 0xffffu, pv.x >> 16, pv.y & 0xffffu, pv.y >> 16};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      cnt[j] += ck[j];
+      pri += (unsigned long long)ck[j] * cost16[min(pf[j], kProbScale)];
+    }
+  }
+  uint32_t f[4], used;
+  normalise_own(cnt, npix, lane, f, used);
+  unsigned long long own = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) own += (unsigned long long)cnt[j] * cost16[f[j]];  // f <= 4096; cost16[0] = 0 (and c = 0 there)
+  const uint32_t nsym = wave_sum(used);
+  own = wave_sum64(own) + ((unsigned long long)(8u * (1u + 3u * nsym)) << 16);
+  pri = wave_sum64(pri);
+  uint16_t* crow = cum + (size_t)img * R::kWords + (size_t)c * R::kPerCh * R::kPitch;
+  if (own < pri) {  // wave-uniform
+#pragma unroll
+    for (int k = 0; k < R::kPerCh; ++k) write_cum(f, lane, crow + k * R::kPitch);
+    write_table(f, used, lane, tab + row * kTabRow, tablen + row);
+    if (lane == 0) keep[row] = 1u;
+  } else {
+    const uint16_t* prow = prior_cum + (size_t)c * R::kPerCh * R::kPitch;
+#pragma unroll
+    for (int k = 0; k < R::kPerCh; ++k) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) crow[k * R::kPitch + 4 * lane + j] = prow[k * R::kPitch + 4 * lane + j];
+      if (lane == 63) crow[k * R::kPitch + 256] = prow[k * R::kPitch + 256];
+    }
+    if (lane == 0) {
+      tablen[row] = 0u;
+      keep[row] = 0u;
+    }
+  }
+}
+
+// Version 3's context of a byte: the byte at segment-relative offset j (channel c = j % 96) is coded
+// under row (c, k), k = 0 for the segment's first pixel, else min(2, |z[j - 96] - anchor[c]|).  A
+// channel that keeps its own table is coded under it in every context, so the segment kernels always
+// see three rows per channel.
+__device__ __forceinline__ uint32_t ctx_of(uint32_t left, uint32_t anchor) {
+  const int d = (int)left - (int)anchor;
+  const uint32_t a = (uint32_t)(d < 0 ? -d : d);
+  return a < 2u ? a : 2u;
 }
 
 // ---- encode 3: segment coding, one lane per segment -----------------------------------------
@@ -195,12 +308,18 @@ __device__ __forceinline__ void load_cum(uint16_t* lds, const uint16_t* __restri
 // last to the first as six per-lane-contiguous 16-B loads (a segment starts at a multiple of
 // 96 B); bytes are written backwards from the end of the lane's region of `cap` bytes, so the
 // finished segment is region[cap - len, cap).
+// kContext: the row is chosen per symbol, so beside the 16 bytes of pixel p the lane loads the same
+// 16 bytes of pixel p - 1 (its first pixel has none: context 0); the lanes of the wave are at one
+// channel, in up to three rows.  anchor is not read without contexts.
+template <bool kContext>
 __global__ __launch_bounds__(64) void rans_encode_segments(const uint8_t* __restrict__ z, int npix, int seg_pixels, int nseg,
-                                                            const uint16_t* __restrict__ cum, uint8_t* __restrict__ scratch,
+                                                            const uint16_t* __restrict__ cum,
+                                                            const uint8_t* __restrict__ anchor, uint8_t* __restrict__ scratch,
                                                             uint32_t cap, uint32_t* __restrict__ seglen) {
-  __shared__ uint16_t start[kCumWords];
+  using R = Rows<kContext>;
+  __shared__ uint16_t start[R::kWords];
   const int lane = threadIdx.x, img = blockIdx.y;
-  load_cum(start, cum + (size_t)img * kCumWords, lane, 64);
+  load_rows<R>(start, cum + (size_t)img * R::kWords, lane, 64);
   __syncthreads();
   const int seg = blockIdx.x * 64 + lane;
   const bool live = seg < nseg;
@@ -218,15 +337,19 @@ __global__ __launch_bounds__(64) void rans_encode_segments(const uint8_t* __rest
   for (int p = maxpix - 1; p >= 0; --p) {
     const bool on = p < mypix;
     for (int q = 5; q >= 0; --q) {
-      uint4 v = make_uint4(0, 0, 0, 0);
+      uint4 v = make_uint4(0, 0, 0, 0), u = make_uint4(0, 0, 0, 0);
       if (on) v = *(const uint4*)(src + (size_t)p * kCh + 16 * q);
-      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+      if constexpr (kContext)
+        if (on && p > 0) u = *(const uint4*)(src + (size_t)(p - 1) * kCh + 16 * q);
+      const uint32_t w[4] = {v.x, v.y, v.z, v.w}, l[4] = {u.x, u.y, u.z, u.w};
 #pragma unroll
       for (int b = 15; b >= 0; --b) {
         const uint32_t s = (w[b >> 2] >> (8 * (b & 3))) & 255u;
-        const uint16_t* row = start + (16 * q + b) * kCumRow;
+        uint32_t k = 0;
+        if constexpr (kContext) k = p > 0 ? ctx_of((l[b >> 2] >> (8 * (b & 3))) & 255u, anchor[16 * q + b]) : 0u;
+        const uint16_t* row = R::row(start, 16 * q + b, k);
         const uint32_t lo = row[s], freq = row[s + 1] - lo;
-        // freq == 4096: the channel's only symbol, x is unchanged and nothing is emitted
+        // freq == 4096: the row's only symbol, x is unchanged and nothing is emitted
         if (on && freq != kProbScale) {
           const uint32_t xmax = freq << 19;
           if (x >= xmax) {
@@ -347,18 +470,29 @@ __global__ __launch_bounds__(256) void rans_assemble(const uint8_t* __restrict__
     if (at + i < (size_t)stride) file[at + i] = src[i];
 }
 
-// ---- decode 1: parse.  grid (n), block 256 ---------------------------------------------------
+// ---- decode 1: parse, one instantiation per version.  grid (n), block 256 ---------------------
 // Every read of a file byte is clamped to [0, size).  meta[img] = {nseg, seg_pixels, payload
-// begin, size}; a header that does not describe an (h8, w8) version-1 file leaves nseg = 0 and
-// status 2 (nothing of that image is decoded); a table that breaks the invariants sets status
-// bit 4 and still yields cumulative rows that resolve every slot (start[0] = 0, non-decreasing,
-// start[256] = 4096).
+// begin, size}.  A header that does not describe an (h8, w8) file of version kVer leaves nseg = 0
+// and status 2 (nothing of that image is decoded); versions 2 and 3 (the 40-byte header) must also
+// describe an H x W image with h8 = ceil(H / 8), w8 = ceil(W / 8), and their prior_id must be the
+// ctx's, else status 8 and nseg = 0 likewise.  A table that breaks the invariants sets status bit 4
+// and still yields cumulative rows that resolve every slot (start[0] = 0, non-decreasing,
+// start[256] = 4096).  Version 1 stores every channel's table; versions 2 and 3 those of the masked
+// channels only, and the other channels' rows are copies of the prior's.  A table is walked once and
+// stored into each of the channel's rows (three in version 3).
+template <int kVer>
 __global__ __launch_bounds__(256) void rans_parse(const uint8_t* __restrict__ files, long long stride,
-                                                   const long long* __restrict__ sizes, int h8, int w8, uint16_t* __restrict__ cum,
-                                                   uint32_t* __restrict__ seglen, uint32_t* __restrict__ segoff, int maxseg,
-                                                   uint32_t* __restrict__ meta, int* __restrict__ status) {
+                                                   const long long* __restrict__ sizes, int h8, int w8,
+                                                   const uint16_t* __restrict__ prior_cum, uint32_t prior_id,
+                                                   uint16_t* __restrict__ cum, uint32_t* __restrict__ seglen,
+                                                   uint32_t* __restrict__ segoff, int maxseg, uint32_t* __restrict__ meta,
+                                                   int* __restrict__ status) {
+  using R = Rows<kVer == 3>;
+  constexpr bool kPrior = kVer != 1;
+  constexpr uint32_t kHdr = kPrior ? kHeader2 : kHeader;
   __shared__ uint32_t sh[257];
   __shared__ uint32_t choff[kCh + 1];
+  __shared__ uint32_t own[kCh];  // versions 2 and 3: the channel stores its table (version 1: all do, own is not used)
   __shared__ int s_bad, s_nseg;
   const int tid = threadIdx.x, img = blockIdx.x;
   const uint8_t* f = files + (size_t)img * (size_t)stride;
@@ -367,22 +501,32 @@ __global__ __launch_bounds__(256) void rans_parse(const uint8_t* __restrict__ fi
   sz = sz > 0x7fffffffll ? 0x7fffffffll : sz;
   const uint32_t size = (uint32_t)sz;
   auto rd = [&](uint32_t i) -> uint32_t { return i < size ? (uint32_t)f[i] : 0u; };
+  auto rd32 = [&](uint32_t i) -> uint32_t { return rd(i) | (rd(i + 1) << 8) | (rd(i + 2) << 16) | (rd(i + 3) << 24); };
+  auto owns = [&](int c) -> bool {
+    if constexpr (kPrior) return own[c] != 0u;
+    return true;
+  };
   const int npix = h8 * w8;
   if (tid == 0) {
-    const uint32_t S = rd(6) | (rd(7) << 8);
-    const uint32_t fh = rd(8) | (rd(9) << 8) | (rd(10) << 16) | (rd(11) << 24);
-    const uint32_t fw = rd(12) | (rd(13) << 8) | (rd(14) << 16) | (rd(15) << 24);
-    const bool ok = size >= (uint32_t)kHeader && rd(0) == 'N' && rd(1) == 'I' && rd(2) == 'C' && rd(3) == 'R' && rd(4) == 1 &&
-                    rd(5) == (uint32_t)kProbBits && S >= 1 && fh == (uint32_t)h8 && fw == (uint32_t)w8;
-    const int nseg = ok ? (int)(((uint32_t)npix + S - 1) / S) : 0;  // <= npix = maxseg
-    uint32_t off = kHeader;
+    const uint32_t S = rd(6) | (rd(7) << 8), fh = rd32(8), fw = rd32(12);
+    bool ok = size >= kHdr && rd(0) == 'N' && rd(1) == 'I' && rd(2) == 'C' && rd(3) == 'R' && rd(4) == (uint32_t)kVer &&
+              rd(5) == (uint32_t)kProbBits && S >= 1 && fh == (uint32_t)h8 && fw == (uint32_t)w8;
+    bool mine = true;
+    if constexpr (kPrior) {
+      const uint32_t H = rd32(16), W = rd32(20);
+      ok = ok && (H >> 3) + ((H & 7u) != 0u) == fh && (W >> 3) + ((W & 7u) != 0u) == fw;
+      mine = rd32(24) == prior_id;
+    }
+    const int nseg = ok && mine ? (int)(((uint32_t)npix + S - 1) / S) : 0;  // <= npix = maxseg
+    uint32_t off = kHdr;
     for (int c = 0; c < kCh; ++c) {
       choff[c] = off;
-      off += 1 + 3 * (rd(off) + 1);
+      if constexpr (kPrior) own[c] = (rd(28 + (c >> 3)) >> (c & 7)) & 1u;
+      if (owns(c)) off += 1 + 3 * (rd(off) + 1);  // <= 40 + 96 * 769
     }
     choff[kCh] = off;
     s_nseg = nseg;
-    s_bad = ok ? 0 : 2;
+    s_bad = !ok ? 2 : (mine ? 0 : 8);
     meta[4 * img + 0] = (uint32_t)nseg;
     meta[4 * img + 1] = ok ? S : 1u;
     meta[4 * img + 2] = min(off + 4u * (uint32_t)nseg, size);
@@ -390,12 +534,14 @@ __global__ __launch_bounds__(256) void rans_parse(const uint8_t* __restrict__ fi
   }
   __syncthreads();
   const int nseg = s_nseg;
-  if (nseg > 0 && tid < kCh) {
-    uint16_t* row = cum + ((size_t)img * kCh + tid) * kCumRow;
+  uint16_t* rows = cum + (size_t)img * R::kWords;
+  if (nseg > 0 && tid < kCh && owns(tid)) {
+    uint16_t* row = rows + tid * R::kPerCh * R::kPitch;
     const uint32_t base = choff[tid], nsym = rd(base) + 1;
     uint32_t e = 0, run = 0, es = rd(base + 1), ef = rd(base + 2) | (rd(base + 3) << 8);
     for (uint32_t s = 0; s < 256; ++s) {
-      row[s] = (uint16_t)run;
+#pragma unroll
+      for (int k = 0; k < R::kPerCh; ++k) row[k * R::kPitch + s] = (uint16_t)run;
       if (e < nsym && es == s) {
         run = min(run + ef, kProbScale);
         ++e;
@@ -403,134 +549,27 @@ __global__ __launch_bounds__(256) void rans_parse(const uint8_t* __restrict__ fi
         ef = rd(base + 2 + 3 * e) | (rd(base + 3 + 3 * e) << 8);
       }
     }
-    row[256] = (uint16_t)kProbScale;
+#pragma unroll
+    for (int k = 0; k < R::kPerCh; ++k) row[k * R::kPitch + 256] = (uint16_t)kProbScale;
     if (e != nsym || run != kProbScale) atomicOr(&s_bad, 4);
+  }
+  if constexpr (kPrior) {
+    if (nseg > 0)  // the prior's rows (start[0] = 0, non-decreasing, start[256] = 4096 by construction), without a row's pad
+      for (int i = tid; i < R::kWords; i += 256)
+        if (!own[i / (R::kPerCh * R::kPitch)] && (R::kPitch == kCumRow || i % R::kPitch < kCumRow)) rows[i] = prior_cum[i];
   }
   // the segment table -> clamped lengths -> offsets
   const uint32_t segtab = choff[kCh];
   uint32_t* len = seglen + (size_t)img * maxseg;
-  for (int k = tid; k < nseg; k += 256) {
-    const uint32_t a = segtab + 4u * (uint32_t)k;  // < 2^31 + 2^27: no wrap
-    len[k] = rd(a) | (rd(a + 1) << 8) | (rd(a + 2) << 16) | (rd(a + 3) << 24);
-  }
+  for (int k = tid; k < nseg; k += 256) len[k] = rd32(segtab + 4u * (uint32_t)k);  // < 2^31 + 2^27: no wrap
   __syncthreads();
   block_offsets(len, nseg, segoff + (size_t)img * (maxseg + 1), size, sh);
   __syncthreads();
   if (tid == 0) status[img] = s_bad;
 }
 
-// ---- decode 2: segments, one lane per segment -----------------------------------------------
-// grid (ceil(maxseg / 64), n), block 64; the grid covers seg_pixels = 1, blocks past the file's
-// own nseg exit.  Lane reads only file bytes of its segment [begin, end) (a read past end gives
-// 0), looks symbols up in rows that resolve every slot, and writes only its own latent bytes.
-__global__ __launch_bounds__(64) void rans_decode_segments(const uint8_t* __restrict__ files, long long stride, int npix,
-                                                            const uint16_t* __restrict__ cum, const uint32_t* __restrict__ segoff,
-                                                            int maxseg, const uint32_t* __restrict__ meta, uint8_t* __restrict__ z,
-                                                            int* __restrict__ status) {
-  __shared__ uint16_t start[kCumWords];
-  const int lane = threadIdx.x, img = blockIdx.y;
-  const int nseg = (int)meta[4 * img + 0];
-  if ((int)blockIdx.x * 64 >= nseg) return;  // block-uniform
-  const int seg_pixels = (int)meta[4 * img + 1];
-  const uint32_t pay = meta[4 * img + 2], size = meta[4 * img + 3];
-  load_cum(start, cum + (size_t)img * kCumWords, lane, 64);
-  __syncthreads();
-  const int seg = blockIdx.x * 64 + lane;
-  const bool live = seg < nseg;
-  const long long p0 = live ? (long long)seg * seg_pixels : 0;  // < npix: seg < nseg = ceil(npix / seg_pixels)
-  const int mypix = live ? (int)min((long long)seg_pixels, (long long)npix - p0) : 0;
-  const uint32_t* off = segoff + (size_t)img * (maxseg + 1);
-  const uint32_t begin = live ? min(pay + off[seg], size) : 0u;
-  const uint32_t end = live ? min(pay + off[seg + 1], size) : 0u;
-  const uint8_t* f = files + (size_t)img * (size_t)stride;
-  uint32_t ptr = begin;
-  auto next = [&]() -> uint32_t {
-    const uint32_t b = ptr < end ? (uint32_t)f[ptr] : 0u;
-    ++ptr;  // counts reads past end too: the segment then fails ptr == end
-    return b;
-  };
-  uint32_t x = 0;
-  if (live) {
-    x = next() << 24;
-    x |= next() << 16;
-    x |= next() << 8;
-    x |= next();
-  }
-  uint8_t* dst = z + ((size_t)img * npix + (size_t)p0) * kCh;
-  int maxpix = mypix;  // wave-uniform trip count
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) maxpix = max(maxpix, __shfl_xor(maxpix, o, 64));
-  for (int p = 0; p < maxpix; ++p) {
-    const bool on = p < mypix;
-    for (int q = 0; q < 6; ++q) {
-      uint32_t w[4] = {0, 0, 0, 0};
-#pragma unroll
-      for (int b = 0; b < 16; ++b) {
-        const uint16_t* row = start + (16 * q + b) * kCumRow;
-        const uint32_t slot = x & (kProbScale - 1);
-        // largest s with row[s] <= slot: row[0] = 0 <= slot < 4096 = row[256]
-        uint32_t s = 0;
-#pragma unroll
-        for (uint32_t step = 128; step > 0; step >>= 1)
-          if (row[s + step] <= slot) s += step;
-        const uint32_t lo = row[s], freq = row[s + 1] - lo;
-        if (on) {  // a lane past its last pixel keeps its final state
-          x = freq * (x >> kProbBits) + slot - lo;
-          if (x < kRansL) {
-            x = (x << 8) | next();
-            if (x < kRansL) x = (x << 8) | next();
-          }
-        }
-        w[b >> 2] |= s << (8 * (b & 3));
-      }
-      if (on) *(uint4*)(dst + (size_t)p * kCh + 16 * q) = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-  }
-  if (live && !(x == kRansL && ptr == end)) atomicOr(&status[img], 1);
-}
-
-// ==== version 2: a codec-level prior ("The .nic container, version 2") =============
-// The prior is 96 x 256 freqs in 1..4096, every channel summing to 4096, fitted once over a
-// corpus and shared by every file.  A version-2 file stores a table only for the channels whose
-// own table pays for itself; the others are coded with the prior's row.  The segment coder and
-// decoder above run unchanged on the per-image cumulative rows.
-
-__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t lo = __shfl_xor((uint32_t)v, o, 64), hi = __shfl_xor((uint32_t)(v >> 32), o, 64);
-    v += ((unsigned long long)hi << 32) | lo;
-  }
-  return v;
-}
-
-// ---- prior 1: counts of a batch's latents into one accumulator ------------------------------
-// rans_hist's grid and LDS histograms; the flush adds into the caller's uint64[96][256] with
-// 64-bit integer atomics, so the totals do not depend on the order and accumulate across calls.
-__global__ __launch_bounds__(256) void rans_prior_count(const uint8_t* __restrict__ z, int npix,
-                                                         unsigned long long* __restrict__ counts) {
-  __shared__ uint32_t h[32 * 256];
-  const int tid = threadIdx.x, third = blockIdx.y, img = blockIdx.z;
-  for (int i = tid; i < 32 * 256; i += 256) h[i] = 0;
-  __syncthreads();
-  const int p = blockIdx.x * 256 + tid;
-  if (p < npix) {
-    const uint4* src = (const uint4*)(z + ((size_t)img * npix + p) * kCh + 32 * third);
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const uint4 v = src[q];
-      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int b = 0; b < 16; ++b) atomicAdd(&h[(16 * q + b) * 256 + ((w[b >> 2] >> (8 * (b & 3))) & 255u)], 1u);
-    }
-  }
-  __syncthreads();
-  unsigned long long* dst = counts + (size_t)(32 * third) * 256;
-  for (int i = tid; i < 32 * 256; i += 256)
-    if (h[i]) atomicAdd(&dst[i], (unsigned long long)h[i]);
-}
-
-// ---- prior 2: counts -> freqs.  grid (rows), block 64: one wave per row of 256 counts -----------
+// ---- fitting a prior: counts (rans_hist / rans3_hist into one u64 accumulator) -> freqs ---------
+// grid (rows), block 64: one wave per row of 256 counts
 // (96 channels of the static prior; 96 x 3 (channel, context) rows of the context prior)
 // Version 1's rule with all 256 symbols "used": f = max(1, floor(c 4096 / N)); a deficit goes onto
 // the largest entry; a surplus (at most 255) is taken one at a time from the currently largest
@@ -583,151 +622,6 @@ __global__ __launch_bounds__(64) void rans_prior_normalise(const unsigned long l
   for (int k = 0; k < 4; ++k) freqs[(size_t)c * 256 + 4 * lane + k] = (uint16_t)f[k];
 }
 
-// ---- version-2 encode 2: tables and the per-channel choice.  grid (96, n), block 64 ------------
-// Version 1's normalisation of the image's counts, then with cost16[f] = round((12 - log2 f) 2^16):
-//   own = sum c cost16[f_own] + (8 (1 + 3 n) << 16),  prior = sum c cost16[f_prior]   (u64)
-// The channel keeps its own table iff own < prior.  Writes the channel's cumulative row (its own
-// or the prior's), the table's file bytes and their length (0 for a prior channel) and keep[].
-__global__ __launch_bounds__(64) void rans2_tables(const uint32_t* __restrict__ counts, int npix,
-                                                    const uint16_t* __restrict__ prior_freq,
-                                                    const uint16_t* __restrict__ prior_cum, const uint32_t* __restrict__ cost16,
-                                                    uint16_t* __restrict__ cum, uint8_t* __restrict__ tab,
-                                                    uint32_t* __restrict__ tablen, uint32_t* __restrict__ keep) {
-  const int lane = threadIdx.x, c = blockIdx.x, img = blockIdx.y;
-  const size_t row = (size_t)img * kCh + c;
-  const uint4 cv = ((const uint4*)(counts + row * 256))[lane];
-  const uint32_t cnt[4] = {cv.x, cv.y, cv.z, cv.w};
-  uint32_t f[4], used;
-  normalise_own(cnt, npix, lane, f, used);
-  const uint2 pv = ((const uint2*)(prior_freq + (size_t)c * 256))[lane];  // four u16 freqs, each in 1..4096 (checked on upload)
-  const uint32_t pf[4] = {pv.x & 0xffffu, pv.x >> 16, pv.y & 0xffffu, pv.y >> 16};
-  unsigned long long own = 0, pri = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    own += (unsigned long long)cnt[k] * cost16[f[k]];  // f <= 4096; cost16[0] = 0 (and c = 0 there)
-    pri += (unsigned long long)cnt[k] * cost16[min(pf[k], kProbScale)];
-  }
-  const uint32_t nsym = wave_sum(used);
-  own = wave_sum64(own) + ((unsigned long long)(8u * (1u + 3u * nsym)) << 16);
-  pri = wave_sum64(pri);
-  uint16_t* crow = cum + row * kCumRow;
-  if (own < pri) {  // wave-uniform
-    write_cum(f, lane, crow);
-    write_table(f, used, lane, tab + row * kTabRow, tablen + row);
-    if (lane == 0) keep[row] = 1u;
-  } else {
-    const uint16_t* prow = prior_cum + (size_t)c * kCumRow;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) crow[4 * lane + k] = prow[4 * lane + k];
-    if (lane == 63) crow[256] = prow[256];
-    if (lane == 0) {
-      tablen[row] = 0u;
-      keep[row] = 0u;
-    }
-  }
-}
-
-// ---- version-2 decode 1: parse.  grid (n), block 256 ------------------------------------------
-// As rans_parse, with the 40-byte header: the file must describe an (h8, w8) latent of an H x W
-// image (h8 = ceil(H / 8), w8 = ceil(W / 8)), else status 2; its prior_id must be the ctx's, else
-// status 8; either way nseg = 0 and nothing of that image is decoded.  Tables are walked for the
-// masked channels only; the other rows are copies of the prior's cumulative rows.
-__global__ __launch_bounds__(256) void rans2_parse(const uint8_t* __restrict__ files, long long stride,
-                                                    const long long* __restrict__ sizes, int h8, int w8,
-                                                    const uint16_t* __restrict__ prior_cum, uint32_t prior_id,
-                                                    uint16_t* __restrict__ cum, uint32_t* __restrict__ seglen,
-                                                    uint32_t* __restrict__ segoff, int maxseg, uint32_t* __restrict__ meta,
-                                                    int* __restrict__ status) {
-  __shared__ uint32_t sh[257];
-  __shared__ uint32_t choff[kCh + 1];
-  __shared__ uint32_t own[kCh];
-  __shared__ int s_bad, s_nseg;
-  const int tid = threadIdx.x, img = blockIdx.x;
-  const uint8_t* f = files + (size_t)img * (size_t)stride;
-  long long sz = sizes[img];
-  sz = sz < 0 ? 0 : (sz > stride ? stride : sz);
-  sz = sz > 0x7fffffffll ? 0x7fffffffll : sz;
-  const uint32_t size = (uint32_t)sz;
-  auto rd = [&](uint32_t i) -> uint32_t { return i < size ? (uint32_t)f[i] : 0u; };
-  auto rd32 = [&](uint32_t i) -> uint32_t { return rd(i) | (rd(i + 1) << 8) | (rd(i + 2) << 16) | (rd(i + 3) << 24); };
-  const int npix = h8 * w8;
-  if (tid == 0) {
-    const uint32_t S = rd(6) | (rd(7) << 8);
-    const uint32_t fh = rd32(8), fw = rd32(12), H = rd32(16), W = rd32(20), pid = rd32(24);
-    const bool ok = size >= (uint32_t)kHeader2 && rd(0) == 'N' && rd(1) == 'I' && rd(2) == 'C' && rd(3) == 'R' && rd(4) == 2 &&
-                    rd(5) == (uint32_t)kProbBits && S >= 1 && fh == (uint32_t)h8 && fw == (uint32_t)w8 &&
-                    (H >> 3) + ((H & 7u) != 0u) == fh && (W >> 3) + ((W & 7u) != 0u) == fw;
-    const bool mine = pid == prior_id;
-    const int nseg = ok && mine ? (int)(((uint32_t)npix + S - 1) / S) : 0;  // <= npix = maxseg
-    uint32_t off = kHeader2;
-    for (int c = 0; c < kCh; ++c) {
-      choff[c] = off;
-      own[c] = (rd(28 + (c >> 3)) >> (c & 7)) & 1u;
-      if (own[c]) off += 1 + 3 * (rd(off) + 1);  // <= 40 + 96 * 769
-    }
-    choff[kCh] = off;
-    s_nseg = nseg;
-    s_bad = !ok ? 2 : (mine ? 0 : 8);
-    meta[4 * img + 0] = (uint32_t)nseg;
-    meta[4 * img + 1] = ok ? S : 1u;
-    meta[4 * img + 2] = min(off + 4u * (uint32_t)nseg, size);
-    meta[4 * img + 3] = size;
-  }
-  __syncthreads();
-  const int nseg = s_nseg;
-  uint16_t* rows = cum + (size_t)img * kCumWords;
-  if (nseg > 0 && tid < kCh && own[tid]) {
-    uint16_t* row = rows + tid * kCumRow;
-    const uint32_t base = choff[tid], nsym = rd(base) + 1;
-    uint32_t e = 0, run = 0, es = rd(base + 1), ef = rd(base + 2) | (rd(base + 3) << 8);
-    for (uint32_t s = 0; s < 256; ++s) {
-      row[s] = (uint16_t)run;
-      if (e < nsym && es == s) {
-        run = min(run + ef, kProbScale);
-        ++e;
-        es = rd(base + 1 + 3 * e);
-        ef = rd(base + 2 + 3 * e) | (rd(base + 3 + 3 * e) << 8);
-      }
-    }
-    row[256] = (uint16_t)kProbScale;
-    if (e != nsym || run != kProbScale) atomicOr(&s_bad, 4);
-  }
-  if (nseg > 0)  // the prior's rows (start[0] = 0, non-decreasing, start[256] = 4096 by construction)
-    for (int i = tid; i < kCumWords; i += 256)
-      if (!own[i / kCumRow]) rows[i] = prior_cum[i];
-  // the segment table -> clamped lengths -> offsets
-  const uint32_t segtab = choff[kCh];
-  uint32_t* len = seglen + (size_t)img * maxseg;
-  for (int k = tid; k < nseg; k += 256) len[k] = rd32(segtab + 4u * (uint32_t)k);  // < 2^31 + 2^27: no wrap
-  __syncthreads();
-  block_offsets(len, nseg, segoff + (size_t)img * (maxseg + 1), size, sh);
-  __syncthreads();
-  if (tid == 0) status[img] = s_bad;
-}
-
-// ==== version 3: a context prior conditioned on the left neighbour ("The .nic container,
-// version 3") ====
-// The context prior is 96 anchors and 96 x 3 x 256 freqs.  The byte at segment-relative offset j
-// (channel c = j % 96, pixel q = j / 96) is coded under row (c, k): k = 0 for the segment's first
-// pixel, else min(2, |z[j - 96] - anchor[c]|).  A channel that keeps its own table is coded under
-// it in every context, so the segment kernels always see three rows per channel.  The rows of one
-// image are u16[96][3][kCtxRow] in global memory and in LDS alike (copied as dwords).
-
-// The row pitch in LDS: all 64 lanes are at one channel, spread over its three rows, and most of
-// them at symbols near the anchor.  At 257 u16 (128.5 dwords) the same symbol of the three rows
-// falls onto one or two neighbouring banks; at 278 u16 (139 dwords = 4 x 32 + 11) the rows sit 11
-// and 22 banks apart.  288 rows x 556 B = 160,128 B of the 163,840.
-constexpr int kCtx = 3;
-constexpr int kCtxRow = 278;
-constexpr int kCtxWords = kCh * kCtx * kCtxRow;  // u16 per image
-static_assert(kCtxRow % 2 == 0 && kCtxRow >= kCumRow && kCtxWords * 2 + 64 <= 160 * 1024, "the rows must fit the LDS");
-
-__device__ __forceinline__ uint32_t ctx_of(uint32_t left, uint32_t anchor) {
-  const int d = (int)left - (int)anchor;
-  const uint32_t a = (uint32_t)(d < 0 ? -d : d);
-  return a < 2u ? a : 2u;
-}
-
 // ---- context counts ---------------------------------------------------------------------------
 // grid (ceil(npix / 256), 6, n), block 256: rans_hist's structure with a sixth of the channels per
 // block (16 x 3 LDS histograms = 48 KB); a thread reads its pixel's 16 bytes and, unless the pixel
@@ -763,290 +657,6 @@ __global__ __launch_bounds__(256) void rans3_hist(const uint8_t* __restrict__ z,
     if (h[i]) atomicAdd(&dst[i], (T)h[i]);
 }
 
-// ---- version-3 encode 2: tables and the per-channel choice.  grid (96, n), block 64 ------------
-// counts: the image's [96][3][256]; their sum over the contexts is version 1's histogram.  own as
-// in rans2_tables; prior = sum over the contexts of c_k cost16[f[c][k]].  Writes the channel's three
-// cumulative rows: the context prior's, or its own row three times.
-__global__ __launch_bounds__(64) void rans3_tables(const uint32_t* __restrict__ counts, int npix,
-                                                    const uint16_t* __restrict__ prior_freq,
-                                                    const uint16_t* __restrict__ prior_cum, const uint32_t* __restrict__ cost16,
-                                                    uint16_t* __restrict__ cum, uint8_t* __restrict__ tab,
-                                                    uint32_t* __restrict__ tablen, uint32_t* __restrict__ keep) {
-  const int lane = threadIdx.x, c = blockIdx.x, img = blockIdx.y;
-  const size_t row = (size_t)img * kCh + c;
-  uint32_t cnt[4] = {0, 0, 0, 0};
-  unsigned long long pri = 0;
-#pragma unroll
-  for (int k = 0; k < kCtx; ++k) {
-    const uint4 cv = ((const uint4*)(counts + (row * kCtx + k) * 256))[lane];
-    const uint32_t ck[4] = {cv.x, cv.y, cv.z, cv.w};
-    const uint2 pv = ((const uint2*)(prior_freq + ((size_t)c * kCtx + k) * 256))[lane];  // each in 1..4096 (checked on upload)
-    const uint32_t pf[4] = {pv.x & 0xffffu, pv.x >> 16, pv.y & 0xffffu, pv.y >> 16};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      cnt[j] += ck[j];
-      pri += (unsigned long long)ck[j] * cost16[min(pf[j], kProbScale)];
-    }
-  }
-  uint32_t f[4], used;
-  normalise_own(cnt, npix, lane, f, used);
-  unsigned long long own = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) own += (unsigned long long)cnt[j] * cost16[f[j]];  // f <= 4096; cost16[0] = 0 (and c = 0 there)
-  const uint32_t nsym = wave_sum(used);
-  own = wave_sum64(own) + ((unsigned long long)(8u * (1u + 3u * nsym)) << 16);
-  pri = wave_sum64(pri);
-  uint16_t* crow = cum + (size_t)img * kCtxWords + (size_t)c * kCtx * kCtxRow;
-  if (own < pri) {  // wave-uniform
-#pragma unroll
-    for (int k = 0; k < kCtx; ++k) write_cum(f, lane, crow + k * kCtxRow);
-    write_table(f, used, lane, tab + row * kTabRow, tablen + row);
-    if (lane == 0) keep[row] = 1u;
-  } else {
-    const uint16_t* prow = prior_cum + (size_t)c * kCtx * kCtxRow;
-#pragma unroll
-    for (int k = 0; k < kCtx; ++k) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) crow[k * kCtxRow + 4 * lane + j] = prow[k * kCtxRow + 4 * lane + j];
-      if (lane == 63) crow[k * kCtxRow + 256] = prow[k * kCtxRow + 256];
-    }
-    if (lane == 0) {
-      tablen[row] = 0u;
-      keep[row] = 0u;
-    }
-  }
-}
-
-// the image's 288 rows into LDS (kCtxWords u16 = 40,032 dwords; the pad of a row is copied, never read)
-__device__ __forceinline__ void load_ctx_rows(uint16_t* lds, const uint16_t* __restrict__ src, int tid, int nthreads) {
-  const uint32_t* s = (const uint32_t*)src;  // kCtxWords is even and every image's rows start 4-B aligned
-  uint32_t* d = (uint32_t*)lds;
-  for (int i = tid; i < kCtxWords / 2; i += nthreads) d[i] = s[i];
-}
-
-// ---- version-3 encode 3: segment coding, one lane per segment -----------------------------------
-// rans_encode_segments with the row chosen per symbol.  The lane walks from its last pixel to its
-// first, so beside the 16 bytes of pixel p it loads the same 16 bytes of pixel p - 1 (its first
-// pixel has none: context 0).  The lanes of the wave are at one channel, in up to three rows.
-__global__ __launch_bounds__(64) void rans3_encode_segments(const uint8_t* __restrict__ z, int npix, int seg_pixels, int nseg,
-                                                             const uint16_t* __restrict__ cum,
-                                                             const uint8_t* __restrict__ anchor, uint8_t* __restrict__ scratch,
-                                                             uint32_t cap, uint32_t* __restrict__ seglen) {
-  __shared__ uint16_t start[kCtxWords];
-  const int lane = threadIdx.x, img = blockIdx.y;
-  load_ctx_rows(start, cum + (size_t)img * kCtxWords, lane, 64);
-  __syncthreads();
-  const int seg = blockIdx.x * 64 + lane;
-  const bool live = seg < nseg;
-  const int p0 = live ? seg * seg_pixels : 0;
-  const int mypix = live ? min(seg_pixels, npix - p0) : 0;
-  const uint8_t* src = z + ((size_t)img * npix + p0) * kCh;
-  uint8_t* region = scratch + ((size_t)img * nseg + (live ? seg : 0)) * cap;
-  uint32_t pos = cap, x = kRansL;
-  auto emit = [&](uint32_t b) {
-    if (pos > 0) region[--pos] = (uint8_t)b;  // pos > 0 always holds: cap is the worst case
-  };
-  int maxpix = mypix;  // wave-uniform trip count
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) maxpix = max(maxpix, __shfl_xor(maxpix, o, 64));
-  for (int p = maxpix - 1; p >= 0; --p) {
-    const bool on = p < mypix;
-    for (int q = 5; q >= 0; --q) {
-      uint4 v = make_uint4(0, 0, 0, 0), u = make_uint4(0, 0, 0, 0);
-      if (on) v = *(const uint4*)(src + (size_t)p * kCh + 16 * q);
-      if (on && p > 0) u = *(const uint4*)(src + (size_t)(p - 1) * kCh + 16 * q);
-      const uint32_t w[4] = {v.x, v.y, v.z, v.w}, l[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-      for (int b = 15; b >= 0; --b) {
-        const uint32_t s = (w[b >> 2] >> (8 * (b & 3))) & 255u, left = (l[b >> 2] >> (8 * (b & 3))) & 255u;
-        const uint32_t k = p > 0 ? ctx_of(left, anchor[16 * q + b]) : 0u;
-        const uint16_t* row = start + ((16 * q + b) * kCtx + k) * kCtxRow;
-        const uint32_t lo = row[s], freq = row[s + 1] - lo;
-        // freq == 4096: the row's only symbol, x is unchanged and nothing is emitted
-        if (on && freq != kProbScale) {
-          const uint32_t xmax = freq << 19;
-          if (x >= xmax) {
-            emit(x & 255u);
-            x >>= 8;
-            if (x >= xmax) {
-              emit(x & 255u);
-              x >>= 8;
-            }
-          }
-          const uint32_t qd = x / freq;
-          x = (qd << kProbBits) + (x - qd * freq) + lo;
-        }
-      }
-    }
-  }
-  if (live) {
-    emit(x & 255u);
-    emit((x >> 8) & 255u);
-    emit((x >> 16) & 255u);
-    emit(x >> 24);
-    seglen[(size_t)img * nseg + seg] = cap - pos;
-  }
-}
-
-// ---- version-3 decode 1: parse.  grid (n), block 256 ------------------------------------------
-// rans2_parse's rules with version byte 3 and three rows per channel: a masked channel's table is
-// walked once and stored into all three, the other channels' rows are copies of the context prior's.
-__global__ __launch_bounds__(256) void rans3_parse(const uint8_t* __restrict__ files, long long stride,
-                                                    const long long* __restrict__ sizes, int h8, int w8,
-                                                    const uint16_t* __restrict__ prior_cum, uint32_t prior_id,
-                                                    uint16_t* __restrict__ cum, uint32_t* __restrict__ seglen,
-                                                    uint32_t* __restrict__ segoff, int maxseg, uint32_t* __restrict__ meta,
-                                                    int* __restrict__ status) {
-  __shared__ uint32_t sh[257];
-  __shared__ uint32_t choff[kCh + 1];
-  __shared__ uint32_t own[kCh];
-  __shared__ int s_bad, s_nseg;
-  const int tid = threadIdx.x, img = blockIdx.x;
-  const uint8_t* f = files + (size_t)img * (size_t)stride;
-  long long sz = sizes[img];
-  sz = sz < 0 ? 0 : (sz > stride ? stride : sz);
-  sz = sz > 0x7fffffffll ? 0x7fffffffll : sz;
-  const uint32_t size = (uint32_t)sz;
-  auto rd = [&](uint32_t i) -> uint32_t { return i < size ? (uint32_t)f[i] : 0u; };
-  auto rd32 = [&](uint32_t i) -> uint32_t { return rd(i) | (rd(i + 1) << 8) | (rd(i + 2) << 16) | (rd(i + 3) << 24); };
-  const int npix = h8 * w8;
-  if (tid == 0) {
-    const uint32_t S = rd(6) | (rd(7) << 8);
-    const uint32_t fh = rd32(8), fw = rd32(12), H = rd32(16), W = rd32(20), pid = rd32(24);
-    const bool ok = size >= (uint32_t)kHeader2 && rd(0) == 'N' && rd(1) == 'I' && rd(2) == 'C' && rd(3) == 'R' && rd(4) == 3 &&
-                    rd(5) == (uint32_t)kProbBits && S >= 1 && fh == (uint32_t)h8 && fw == (uint32_t)w8 &&
-                    (H >> 3) + ((H & 7u) != 0u) == fh && (W >> 3) + ((W & 7u) != 0u) == fw;
-    const bool mine = pid == prior_id;
-    const int nseg = ok && mine ? (int)(((uint32_t)npix + S - 1) / S) : 0;  // <= npix = maxseg
-    uint32_t off = kHeader2;
-    for (int c = 0; c < kCh; ++c) {
-      choff[c] = off;
-      own[c] = (rd(28 + (c >> 3)) >> (c & 7)) & 1u;
-      if (own[c]) off += 1 + 3 * (rd(off) + 1);  // <= 40 + 96 * 769
-    }
-    choff[kCh] = off;
-    s_nseg = nseg;
-    s_bad = !ok ? 2 : (mine ? 0 : 8);
-    meta[4 * img + 0] = (uint32_t)nseg;
-    meta[4 * img + 1] = ok ? S : 1u;
-    meta[4 * img + 2] = min(off + 4u * (uint32_t)nseg, size);
-    meta[4 * img + 3] = size;
-  }
-  __syncthreads();
-  const int nseg = s_nseg;
-  uint16_t* rows = cum + (size_t)img * kCtxWords;
-  if (nseg > 0 && tid < kCh && own[tid]) {
-    uint16_t* row = rows + tid * kCtx * kCtxRow;
-    const uint32_t base = choff[tid], nsym = rd(base) + 1;
-    uint32_t e = 0, run = 0, es = rd(base + 1), ef = rd(base + 2) | (rd(base + 3) << 8);
-    for (uint32_t s = 0; s < 256; ++s) {
-#pragma unroll
-      for (int k = 0; k < kCtx; ++k) row[k * kCtxRow + s] = (uint16_t)run;
-      if (e < nsym && es == s) {
-        run = min(run + ef, kProbScale);
-        ++e;
-        es = rd(base + 1 + 3 * e);
-        ef = rd(base + 2 + 3 * e) | (rd(base + 3 + 3 * e) << 8);
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < kCtx; ++k) row[k * kCtxRow + 256] = (uint16_t)kProbScale;
-    if (e != nsym || run != kProbScale) atomicOr(&s_bad, 4);
-  }
-  if (nseg > 0)  // the prior's rows (start[0] = 0, non-decreasing, start[256] = 4096 by construction)
-    for (int i = tid; i < kCtxWords; i += 256)
-      if (!own[i / (kCtx * kCtxRow)] && i % kCtxRow < kCumRow) rows[i] = prior_cum[i];
-  // the segment table -> clamped lengths -> offsets
-  const uint32_t segtab = choff[kCh];
-  uint32_t* len = seglen + (size_t)img * maxseg;
-  for (int k = tid; k < nseg; k += 256) len[k] = rd32(segtab + 4u * (uint32_t)k);  // < 2^31 + 2^27: no wrap
-  __syncthreads();
-  block_offsets(len, nseg, segoff + (size_t)img * (maxseg + 1), size, sh);
-  __syncthreads();
-  if (tid == 0) status[img] = s_bad;
-}
-
-// ---- version-3 decode 2: segments, one lane per segment -----------------------------------------
-// rans_decode_segments with the row chosen per symbol from the pixel decoded before.  That pixel's
-// 96 symbols stay in 24 registers: chunk q of the left pixel is prev[0..3] in every iteration, and
-// the array is rotated by one chunk after it, so every index is static and the q loop stays rolled.
-__global__ __launch_bounds__(64) void rans3_decode_segments(const uint8_t* __restrict__ files, long long stride, int npix,
-                                                             const uint16_t* __restrict__ cum,
-                                                             const uint8_t* __restrict__ anchor,
-                                                             const uint32_t* __restrict__ segoff, int maxseg,
-                                                             const uint32_t* __restrict__ meta, uint8_t* __restrict__ z,
-                                                             int* __restrict__ status) {
-  __shared__ uint16_t start[kCtxWords];
-  const int lane = threadIdx.x, img = blockIdx.y;
-  const int nseg = (int)meta[4 * img + 0];
-  if ((int)blockIdx.x * 64 >= nseg) return;  // block-uniform
-  const int seg_pixels = (int)meta[4 * img + 1];
-  const uint32_t pay = meta[4 * img + 2], size = meta[4 * img + 3];
-  load_ctx_rows(start, cum + (size_t)img * kCtxWords, lane, 64);
-  __syncthreads();
-  const int seg = blockIdx.x * 64 + lane;
-  const bool live = seg < nseg;
-  const long long p0 = live ? (long long)seg * seg_pixels : 0;  // < npix: seg < nseg = ceil(npix / seg_pixels)
-  const int mypix = live ? (int)min((long long)seg_pixels, (long long)npix - p0) : 0;
-  const uint32_t* off = segoff + (size_t)img * (maxseg + 1);
-  const uint32_t begin = live ? min(pay + off[seg], size) : 0u;
-  const uint32_t end = live ? min(pay + off[seg + 1], size) : 0u;
-  const uint8_t* f = files + (size_t)img * (size_t)stride;
-  uint32_t ptr = begin;
-  auto next = [&]() -> uint32_t {
-    const uint32_t b = ptr < end ? (uint32_t)f[ptr] : 0u;
-    ++ptr;  // counts reads past end too: the segment then fails ptr == end
-    return b;
-  };
-  uint32_t x = 0;
-  if (live) {
-    x = next() << 24;
-    x |= next() << 16;
-    x |= next() << 8;
-    x |= next();
-  }
-  uint8_t* dst = z + ((size_t)img * npix + (size_t)p0) * kCh;
-  int maxpix = mypix;  // wave-uniform trip count
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) maxpix = max(maxpix, __shfl_xor(maxpix, o, 64));
-  uint32_t prev[24];
-#pragma unroll
-  for (int i = 0; i < 24; ++i) prev[i] = 0;
-  for (int p = 0; p < maxpix; ++p) {
-    const bool on = p < mypix;
-    for (int q = 0; q < 6; ++q) {
-      uint32_t w[4] = {0, 0, 0, 0};
-#pragma unroll
-      for (int b = 0; b < 16; ++b) {
-        const uint32_t left = (prev[b >> 2] >> (8 * (b & 3))) & 255u;
-        const uint32_t k = p > 0 ? ctx_of(left, anchor[16 * q + b]) : 0u;  // k <= 2: the row is one of the image's 288
-        const uint16_t* row = start + ((16 * q + b) * kCtx + k) * kCtxRow;
-        const uint32_t slot = x & (kProbScale - 1);
-        // largest s with row[s] <= slot: row[0] = 0 <= slot < 4096 = row[256]
-        uint32_t s = 0;
-#pragma unroll
-        for (uint32_t step = 128; step > 0; step >>= 1)
-          if (row[s + step] <= slot) s += step;
-        const uint32_t lo = row[s], freq = row[s + 1] - lo;
-        if (on) {  // a lane past its last pixel keeps its final state
-          x = freq * (x >> kProbBits) + slot - lo;
-          if (x < kRansL) {
-            x = (x << 8) | next();
-            if (x < kRansL) x = (x << 8) | next();
-          }
-        }
-        w[b >> 2] |= s << (8 * (b & 3));
-      }
-      if (on) *(uint4*)(dst + (size_t)p * kCh + 16 * q) = make_uint4(w[0], w[1], w[2], w[3]);
-#pragma unroll
-      for (int i = 0; i < 20; ++i) prev[i] = prev[i + 4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) prev[20 + i] = w[i];
-    }
-  }
-  if (live && !(x == kRansL && ptr == end)) atomicOr(&status[img], 1);
-}
-
 // ==== window decode: only the segments that hold a pixel of a latent window ("Region
 // decode") ====
 // The window is the latent pixels (r0 + i, c0 + x), i < rows, x < cols.  Its row i is the run
@@ -1056,9 +666,7 @@ __global__ __launch_bounds__(64) void rans3_decode_segments(const uint8_t* __res
 // for i > 0, > last_(i-1) -- a segment that spans several window rows belongs to the first of them.
 // A live lane decodes its whole segment (rANS is serial, and the end check needs the last byte) and
 // stores only the pixels inside the window, at their place in the compact (n, rows, cols, 96) output.
-struct RansWindow {
-  int w8, r0, c0, rows, cols;
-};
+// (RansWindow: nic_kernels.h)
 
 // the segment of `slot` under segments of S pixels, or -1 for a slot that is not live
 __device__ __forceinline__ int window_segment(const RansWindow& w, int S, int slot) {
@@ -1097,10 +705,10 @@ struct SegmentReader {
   }
 };
 
-// One symbol of the window kernels, the step of rans_decode_segments: the largest s with
-// row[s] <= slot (row[0] = 0 <= slot < 4096 = row[256]), then, for a lane that is on, the state
-// update and up to two bytes of renormalisation.  A lane past its last pixel keeps its final state.
-__device__ __forceinline__ uint32_t window_symbol(const uint16_t* row, uint32_t& x, bool on, SegmentReader& in) {
+// One symbol of rans_decode_segments: the largest s with row[s] <= slot (row[0] = 0 <= slot < 4096
+// = row[256]), then, for a lane that is on, the state update and up to two bytes of renormalisation.
+// A lane past its last pixel keeps its final state.
+__device__ __forceinline__ uint32_t decode_symbol(const uint16_t* row, uint32_t& x, bool on, SegmentReader& in) {
   const uint32_t slot = x & (kProbScale - 1);
   uint32_t s = 0;
 #pragma unroll
@@ -1117,27 +725,26 @@ __device__ __forceinline__ uint32_t window_symbol(const uint16_t* row, uint32_t&
   return s;
 }
 
-// The lane of a window kernel: its segment (or none), its reader and where its pixels lie.
-struct WindowLane {
+// The lane of rans_decode_segments: its segment (or none), its reader and its pixels [p0, p0 + mypix).
+struct SegmentLane {
   bool live;
-  int mypix, maxpix, gy, gx;  // maxpix: the wave-uniform trip count; (gy, gx): the latent position of pixel p
+  int p0, mypix, maxpix;  // maxpix: the wave-uniform trip count
   SegmentReader in;
   uint32_t x;
 };
 
-// seg: window_segment's result.  A live seg is < nseg (it holds a pixel below npix), so off[seg + 1] exists.
-__device__ __forceinline__ WindowLane window_lane(int seg, int seg_pixels, int npix, int w8, const uint8_t* __restrict__ file,
-                                                  const uint32_t* __restrict__ off, uint32_t pay, uint32_t size) {
-  WindowLane l;
+// seg: the lane's segment, or -1 for none.  A live seg is < nseg = ceil(npix / seg_pixels), so
+// p0 < npix and off[seg + 1] exists.
+__device__ __forceinline__ SegmentLane segment_lane(int seg, int seg_pixels, int npix, const uint8_t* __restrict__ file,
+                                                    const uint32_t* __restrict__ off, uint32_t pay, uint32_t size) {
+  SegmentLane l;
   l.live = seg >= 0;
-  const int p0 = l.live ? seg * seg_pixels : 0;  // < npix
-  l.mypix = l.live ? min(seg_pixels, npix - p0) : 0;
+  l.p0 = l.live ? seg * seg_pixels : 0;
+  l.mypix = l.live ? min(seg_pixels, npix - l.p0) : 0;
   l.in.f = file;
   l.in.ptr = l.live ? min(pay + off[seg], size) : 0u;
   l.in.end = l.live ? min(pay + off[seg + 1], size) : 0u;
   l.x = l.live ? l.in.state() : 0u;
-  l.gy = p0 / w8;
-  l.gx = p0 - l.gy * w8;
   l.maxpix = l.mypix;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) l.maxpix = max(l.maxpix, __shfl_xor(l.maxpix, o, 64));
@@ -1149,89 +756,84 @@ __device__ __forceinline__ bool window_block_dead(const RansWindow& w, int S, in
   return first_slot >= w.rows * ((w.cols + S - 2) / S + 1);
 }
 
-// ---- window decode 2 (versions 1 and 2): rans_decode_segments over the window's slots ---------
-// grid (ceil(rows cols / 64), n), block 64: the grid covers seg_pixels = 1 (J = cols).  A block is
-// one wave; one without a live lane (every block of a refused image: nseg = 0) exits before the
-// tables are staged.  File reads and lookups are bounded as in rans_decode_segments; a lane stores
-// only the pixels of its own segment that window_pixel places inside image img's output.
-__global__ __launch_bounds__(64) void rans_decode_window_segments(const uint8_t* __restrict__ files, long long stride, int npix,
-                                                                   const uint16_t* __restrict__ cum,
-                                                                   const uint32_t* __restrict__ segoff, int maxseg,
-                                                                   const uint32_t* __restrict__ meta, RansWindow win,
-                                                                   uint8_t* __restrict__ zwin, int* __restrict__ status) {
-  __shared__ uint16_t start[kCumWords];
+// ---- decode 2: segments, one lane per segment -----------------------------------------------
+// block 64, one wave.  A lane reads only file bytes of its segment [begin, end) (a read past end
+// gives 0), looks symbols up in rows that resolve every slot, and writes only its own latent bytes.
+// Full frame (kWindow false): grid (ceil(maxseg / 64), n) covers seg_pixels = 1; lane = segment, blocks
+// past the file's own nseg exit; pixel p of the lane goes to z (n, h8, w8, 96) at p0 + p.
+// Window (kWindow true): grid (ceil(rows cols / 64), n) covers seg_pixels = 1 (J = cols); lane = slot,
+// and a block without a live lane (every block of a refused image: nseg = 0) exits; the lane stores
+// only the pixels of its segment that window_pixel places inside image img's (rows, cols, 96) of z.
+// Either way the rows are staged only behind those exits.
+// kContext: the row is chosen per symbol from the pixel decoded before (the context never leaves a
+// segment, and a lane decodes its segment from the first pixel).  That pixel's 96 symbols stay in 24
+// registers: chunk q of the left pixel is prev[0..3] in every iteration, and the array is rotated by
+// one chunk after it, so every index is static and the q loop stays rolled.  anchor is not read
+// without contexts, win not without a window.
+template <bool kContext, bool kWindow>
+__global__ __launch_bounds__(64) void rans_decode_segments(const uint8_t* __restrict__ files, long long stride, int npix,
+                                                            const uint16_t* __restrict__ cum,
+                                                            const uint8_t* __restrict__ anchor,
+                                                            const uint32_t* __restrict__ segoff, int maxseg,
+                                                            const uint32_t* __restrict__ meta, RansWindow win,
+                                                            uint8_t* __restrict__ z, int* __restrict__ status) {
+  using R = Rows<kContext>;
+  __shared__ uint16_t start[R::kWords];
   const int lane = threadIdx.x, img = blockIdx.y;
   const int nseg = (int)meta[4 * img + 0];
-  if (nseg == 0) return;  // block-uniform
   const int seg_pixels = (int)meta[4 * img + 1];
-  if (window_block_dead(win, seg_pixels, (int)blockIdx.x * 64)) return;
-  const int seg = window_segment(win, seg_pixels, (int)blockIdx.x * 64 + lane);
-  if (__ballot(seg >= 0) == 0) return;  // block-uniform: the block is this wave
-  load_cum(start, cum + (size_t)img * kCumWords, lane, 64);
-  __syncthreads();
-  WindowLane l = window_lane(seg, seg_pixels, npix, win.w8, files + (size_t)img * (size_t)stride,
-                             segoff + (size_t)img * (maxseg + 1), meta[4 * img + 2], meta[4 * img + 3]);
-  for (int p = 0; p < l.maxpix; ++p) {
-    const bool on = p < l.mypix;
-    uint8_t* dst = on ? window_pixel(win, zwin, img, l.gy, l.gx) : nullptr;
-    for (int q = 0; q < 6; ++q) {
-      uint32_t w[4] = {0, 0, 0, 0};
-#pragma unroll
-      for (int b = 0; b < 16; ++b) w[b >> 2] |= window_symbol(start + (16 * q + b) * kCumRow, l.x, on, l.in) << (8 * (b & 3));
-      if (dst) *(uint4*)(dst + 16 * q) = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-    if (++l.gx == win.w8) {
-      l.gx = 0;
-      ++l.gy;
-    }
+  int seg = (int)blockIdx.x * 64 + lane;
+  if constexpr (kWindow) {
+    if (nseg == 0) return;  // block-uniform
+    if (window_block_dead(win, seg_pixels, (int)blockIdx.x * 64)) return;
+    seg = window_segment(win, seg_pixels, seg);
+    if (__ballot(seg >= 0) == 0) return;  // block-uniform: the block is this wave
+  } else {
+    if ((int)blockIdx.x * 64 >= nseg) return;  // block-uniform
+    if (seg >= nseg) seg = -1;
   }
-  if (l.live && !(l.x == kRansL && l.in.ptr == l.in.end)) atomicOr(&status[img], 1);
-}
-
-// ---- window decode 2 (version 3): rans3_decode_segments over the window's slots ----------------
-// The context never leaves a segment and the lane decodes its segment from the first pixel, so the
-// left-pixel registers work as in rans3_decode_segments.
-__global__ __launch_bounds__(64) void rans3_decode_window_segments(const uint8_t* __restrict__ files, long long stride, int npix,
-                                                                    const uint16_t* __restrict__ cum,
-                                                                    const uint8_t* __restrict__ anchor,
-                                                                    const uint32_t* __restrict__ segoff, int maxseg,
-                                                                    const uint32_t* __restrict__ meta, RansWindow win,
-                                                                    uint8_t* __restrict__ zwin, int* __restrict__ status) {
-  __shared__ uint16_t start[kCtxWords];
-  const int lane = threadIdx.x, img = blockIdx.y;
-  const int nseg = (int)meta[4 * img + 0];
-  if (nseg == 0) return;  // block-uniform
-  const int seg_pixels = (int)meta[4 * img + 1];
-  if (window_block_dead(win, seg_pixels, (int)blockIdx.x * 64)) return;
-  const int seg = window_segment(win, seg_pixels, (int)blockIdx.x * 64 + lane);
-  if (__ballot(seg >= 0) == 0) return;  // block-uniform: the block is this wave
-  load_ctx_rows(start, cum + (size_t)img * kCtxWords, lane, 64);
+  load_rows<R>(start, cum + (size_t)img * R::kWords, lane, 64);
   __syncthreads();
-  WindowLane l = window_lane(seg, seg_pixels, npix, win.w8, files + (size_t)img * (size_t)stride,
-                             segoff + (size_t)img * (maxseg + 1), meta[4 * img + 2], meta[4 * img + 3]);
+  SegmentLane l = segment_lane(seg, seg_pixels, npix, files + (size_t)img * (size_t)stride,
+                               segoff + (size_t)img * (maxseg + 1), meta[4 * img + 2], meta[4 * img + 3]);
+  int gy = 0, gx = 0;  // window: the latent position of pixel p
+  if constexpr (kWindow) {
+    gy = l.p0 / win.w8;
+    gx = l.p0 - gy * win.w8;
+  }
+  uint8_t* mine = z + ((size_t)img * npix + (size_t)l.p0) * kCh;  // full frame: the lane's pixels
   uint32_t prev[24];
 #pragma unroll
   for (int i = 0; i < 24; ++i) prev[i] = 0;
   for (int p = 0; p < l.maxpix; ++p) {
     const bool on = p < l.mypix;
-    uint8_t* dst = on ? window_pixel(win, zwin, img, l.gy, l.gx) : nullptr;
+    uint8_t* dst = nullptr;
+    if constexpr (kWindow) {
+      if (on) dst = window_pixel(win, z, img, gy, gx);
+    } else {
+      if (on) dst = mine + (size_t)p * kCh;
+    }
     for (int q = 0; q < 6; ++q) {
       uint32_t w[4] = {0, 0, 0, 0};
 #pragma unroll
       for (int b = 0; b < 16; ++b) {
-        const uint32_t left = (prev[b >> 2] >> (8 * (b & 3))) & 255u;
-        const uint32_t k = p > 0 ? ctx_of(left, anchor[16 * q + b]) : 0u;  // k <= 2: the row is one of the image's 288
-        w[b >> 2] |= window_symbol(start + ((16 * q + b) * kCtx + k) * kCtxRow, l.x, on, l.in) << (8 * (b & 3));
+        uint32_t k = 0;  // k <= 2: the row is one of the image's
+        if constexpr (kContext) k = p > 0 ? ctx_of((prev[b >> 2] >> (8 * (b & 3))) & 255u, anchor[16 * q + b]) : 0u;
+        w[b >> 2] |= decode_symbol(R::row(start, 16 * q + b, k), l.x, on, l.in) << (8 * (b & 3));
       }
       if (dst) *(uint4*)(dst + 16 * q) = make_uint4(w[0], w[1], w[2], w[3]);
+      if constexpr (kContext) {
 #pragma unroll
-      for (int i = 0; i < 20; ++i) prev[i] = prev[i + 4];
+        for (int i = 0; i < 20; ++i) prev[i] = prev[i + 4];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) prev[20 + i] = w[i];
+        for (int i = 0; i < 4; ++i) prev[20 + i] = w[i];
+      }
     }
-    if (++l.gx == win.w8) {
-      l.gx = 0;
-      ++l.gy;
+    if constexpr (kWindow) {
+      if (++gx == win.w8) {
+        gx = 0;
+        ++gy;
+      }
     }
   }
   if (l.live && !(l.x == kRansL && l.in.ptr == l.in.end)) atomicOr(&status[img], 1);
@@ -1272,190 +874,252 @@ void rans_plan(int n, int h8, int w8, int seg_pixels, bool decode, RansPlan* pl,
   pl->bytes = o;
 }
 
-hipError_t launch_rans_encode(const uint8_t* z, int n, int h8, int w8, int seg_pixels, char* ws, const RansPlan& pl,
-                              uint8_t* out, long long stride, long long* sizes, hipStream_t st) {
+namespace {
+
+// a plan's offsets as typed pointers into the workspace
+struct RansBuffers {
+  uint32_t* counts;
+  uint16_t* cum;
+  uint8_t* tab;
+  uint32_t *tablen, *taboff, *keep, *seglen, *segoff, *meta;
+  uint8_t* scratch;
+};
+
+RansBuffers rans_buffers(char* ws, const RansPlan& pl) {
+  return {(uint32_t*)(ws + pl.counts), (uint16_t*)(ws + pl.cum),    (uint8_t*)(ws + pl.tab),     (uint32_t*)(ws + pl.tablen),
+          (uint32_t*)(ws + pl.taboff), (uint32_t*)(ws + pl.keep),   (uint32_t*)(ws + pl.seglen), (uint32_t*)(ws + pl.segoff),
+          (uint32_t*)(ws + pl.meta),   (uint8_t*)(ws + pl.scratch)};
+}
+
+template <int kVer>
+hipError_t rans_encode(const uint8_t* z, int n, int h8, int w8, int H, int W, int seg_pixels, const RansPrior& pr, char* ws,
+                       const RansPlan& pl, uint8_t* out, long long stride, long long* sizes, hipStream_t st) {
+  constexpr bool kContext = kVer == 3;
+  constexpr size_t kCounts = (size_t)kCh * Rows<kContext>::kPerCh * 256;  // per image
   const int npix = h8 * w8, nseg = pl.nseg;
-  uint32_t* counts = (uint32_t*)(ws + pl.counts);
-  uint16_t* cum = (uint16_t*)(ws + pl.cum);
-  uint8_t* tab = (uint8_t*)(ws + pl.tab);
-  uint32_t* tablen = (uint32_t*)(ws + pl.tablen);
-  uint32_t* taboff = (uint32_t*)(ws + pl.taboff);
-  uint32_t* seglen = (uint32_t*)(ws + pl.seglen);
-  uint32_t* segoff = (uint32_t*)(ws + pl.segoff);
-  uint8_t* scratch = (uint8_t*)(ws + pl.scratch);
-  hipError_t e = hipMemsetAsync(counts, 0, (size_t)n * kCh * 256 * 4, st);
+  const RansBuffers b = rans_buffers(ws, pl);
+  hipError_t e = hipMemsetAsync(b.counts, 0, (size_t)n * kCounts * 4, st);
   if (e != hipSuccess) return e;
-  rans_hist<<<dim3((npix + 255) / 256, 3, n), 256, 0, st>>>(z, npix, counts);
-  rans_normalise<<<dim3(kCh, n), 64, 0, st>>>(counts, npix, cum, tab, tablen);
-  rans_encode_segments<<<dim3((nseg + 63) / 64, n), 64, 0, st>>>(z, npix, seg_pixels, nseg, cum, scratch, pl.cap, seglen);
-  rans_layout<1><<<dim3(n), 256, 0, st>>>(tablen, taboff, seglen, segoff, nseg, sizes);
-  rans_assemble<1><<<dim3((kCh + nseg + 3) / 4, n), 256, 0, st>>>(tab, tablen, taboff, scratch, pl.cap, seglen, segoff, nseg,
-                                                                 seg_pixels, h8, w8, out, stride, 0u, 0u, 0u, nullptr);
-  return hipGetLastError();
-}
-
-hipError_t launch_rans_decode(const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8, char* ws,
-                              const RansPlan& pl, uint8_t* z, int* status, hipStream_t st) {
-  const int npix = h8 * w8, maxseg = pl.nseg;
-  uint16_t* cum = (uint16_t*)(ws + pl.cum);
-  uint32_t* seglen = (uint32_t*)(ws + pl.seglen);
-  uint32_t* segoff = (uint32_t*)(ws + pl.segoff);
-  uint32_t* meta = (uint32_t*)(ws + pl.meta);
-  rans_parse<<<dim3(n), 256, 0, st>>>(files, stride, sizes, h8, w8, cum, seglen, segoff, maxseg, meta, status);
-  rans_decode_segments<<<dim3((maxseg + 63) / 64, n), 64, 0, st>>>(files, stride, npix, cum, segoff, maxseg, meta, z, status);
-  return hipGetLastError();
-}
-
-hipError_t launch_rans_prior_count(const uint8_t* z, int n, int h8, int w8, unsigned long long* counts, hipStream_t st) {
-  const int npix = h8 * w8;
-  rans_prior_count<<<dim3((npix + 255) / 256, 3, n), 256, 0, st>>>(z, npix, counts);
-  return hipGetLastError();
-}
-
-hipError_t launch_rans_prior_build(const unsigned long long* counts, uint16_t* freqs, hipStream_t st) {
-  rans_prior_normalise<<<dim3(kCh), 64, 0, st>>>(counts, freqs);
-  return hipGetLastError();
-}
-
-hipError_t launch_rans_cprior_count(const uint8_t* z, int n, int h8, int w8, int seg_pixels, const uint8_t* anchor,
-                                    unsigned long long* counts, hipStream_t st) {
-  const int npix = h8 * w8;
-  rans3_hist<unsigned long long><<<dim3((npix + 255) / 256, 6, n), 256, 0, st>>>(z, npix, seg_pixels, anchor, counts, 0);
-  return hipGetLastError();
-}
-
-hipError_t launch_rans_cprior_build(const unsigned long long* counts, uint16_t* freqs, hipStream_t st) {
-  rans_prior_normalise<<<dim3(kCh * kCtx), 64, 0, st>>>(counts, freqs);
-  return hipGetLastError();
-}
-
-size_t rans_cprior_bytes(size_t* cum_at, size_t* anchor_at, size_t* cost_at) {
-  *cum_at = (size_t)kCh * kCtx * 256 * 2;
-  *anchor_at = *cum_at + (size_t)kCtxWords * 2;
-  *cost_at = *anchor_at + kCh;  // a multiple of 4
-  return *cost_at + (kProbScale + 1) * 4;
-}
-
-int rans_cprior_row_pitch() { return kCtxRow; }
-
-hipError_t launch_rans3_encode(const uint8_t* z, int n, int h8, int w8, int H, int W, int seg_pixels, const RansCPrior& pr,
-                               char* ws, const RansPlan& pl, uint8_t* out, long long stride, long long* sizes, hipStream_t st) {
-  const int npix = h8 * w8, nseg = pl.nseg;
-  uint32_t* counts = (uint32_t*)(ws + pl.counts);
-  uint16_t* cum = (uint16_t*)(ws + pl.cum);
-  uint8_t* tab = (uint8_t*)(ws + pl.tab);
-  uint32_t* tablen = (uint32_t*)(ws + pl.tablen);
-  uint32_t* taboff = (uint32_t*)(ws + pl.taboff);
-  uint32_t* keep = (uint32_t*)(ws + pl.keep);
-  uint32_t* seglen = (uint32_t*)(ws + pl.seglen);
-  uint32_t* segoff = (uint32_t*)(ws + pl.segoff);
-  uint8_t* scratch = (uint8_t*)(ws + pl.scratch);
-  hipError_t e = hipMemsetAsync(counts, 0, (size_t)n * kCh * kCtx * 256 * 4, st);
-  if (e != hipSuccess) return e;
-  rans3_hist<uint32_t><<<dim3((npix + 255) / 256, 6, n), 256, 0, st>>>(z, npix, seg_pixels, pr.anchor, counts,
-                                                                       (size_t)kCh * kCtx * 256);
-  rans3_tables<<<dim3(kCh, n), 64, 0, st>>>(counts, npix, pr.freq, pr.cum, pr.cost16, cum, tab, tablen, keep);
-  rans3_encode_segments<<<dim3((nseg + 63) / 64, n), 64, 0, st>>>(z, npix, seg_pixels, nseg, cum, pr.anchor, scratch, pl.cap,
-                                                                  seglen);
-  rans_layout<3><<<dim3(n), 256, 0, st>>>(tablen, taboff, seglen, segoff, nseg, sizes);
-  rans_assemble<3><<<dim3((kCh + nseg + 3) / 4, n), 256, 0, st>>>(tab, tablen, taboff, scratch, pl.cap, seglen, segoff, nseg,
-                                                                 seg_pixels, h8, w8, out, stride, (uint32_t)H, (uint32_t)W,
-                                                                 pr.id, keep);
-  return hipGetLastError();
-}
-
-hipError_t launch_rans3_decode(const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8,
-                               const RansCPrior& pr, char* ws, const RansPlan& pl, uint8_t* z, int* status, hipStream_t st) {
-  const int npix = h8 * w8, maxseg = pl.nseg;
-  uint16_t* cum = (uint16_t*)(ws + pl.cum);
-  uint32_t* seglen = (uint32_t*)(ws + pl.seglen);
-  uint32_t* segoff = (uint32_t*)(ws + pl.segoff);
-  uint32_t* meta = (uint32_t*)(ws + pl.meta);
-  rans3_parse<<<dim3(n), 256, 0, st>>>(files, stride, sizes, h8, w8, pr.cum, pr.id, cum, seglen, segoff, maxseg, meta, status);
-  rans3_decode_segments<<<dim3((maxseg + 63) / 64, n), 64, 0, st>>>(files, stride, npix, cum, pr.anchor, segoff, maxseg, meta, z,
-                                                                    status);
-  return hipGetLastError();
-}
-
-size_t rans_prior_bytes(size_t* cum_at, size_t* cost_at) {
-  *cum_at = (size_t)kCh * 256 * 2;
-  *cost_at = *cum_at + (size_t)kCumWords * 2;  // a multiple of 4
-  return *cost_at + (kProbScale + 1) * 4;
-}
-
-hipError_t launch_rans2_encode(const uint8_t* z, int n, int h8, int w8, int H, int W, int seg_pixels, const RansPrior& pr,
-                               char* ws, const RansPlan& pl, uint8_t* out, long long stride, long long* sizes, hipStream_t st) {
-  const int npix = h8 * w8, nseg = pl.nseg;
-  uint32_t* counts = (uint32_t*)(ws + pl.counts);
-  uint16_t* cum = (uint16_t*)(ws + pl.cum);
-  uint8_t* tab = (uint8_t*)(ws + pl.tab);
-  uint32_t* tablen = (uint32_t*)(ws + pl.tablen);
-  uint32_t* taboff = (uint32_t*)(ws + pl.taboff);
-  uint32_t* keep = (uint32_t*)(ws + pl.keep);
-  uint32_t* seglen = (uint32_t*)(ws + pl.seglen);
-  uint32_t* segoff = (uint32_t*)(ws + pl.segoff);
-  uint8_t* scratch = (uint8_t*)(ws + pl.scratch);
-  hipError_t e = hipMemsetAsync(counts, 0, (size_t)n * kCh * 256 * 4, st);
-  if (e != hipSuccess) return e;
-  rans_hist<<<dim3((npix + 255) / 256, 3, n), 256, 0, st>>>(z, npix, counts);
-  rans2_tables<<<dim3(kCh, n), 64, 0, st>>>(counts, npix, pr.freq, pr.cum, pr.cost16, cum, tab, tablen, keep);
-  rans_encode_segments<<<dim3((nseg + 63) / 64, n), 64, 0, st>>>(z, npix, seg_pixels, nseg, cum, scratch, pl.cap, seglen);
-  rans_layout<2><<<dim3(n), 256, 0, st>>>(tablen, taboff, seglen, segoff, nseg, sizes);
-  rans_assemble<2><<<dim3((kCh + nseg + 3) / 4, n), 256, 0, st>>>(tab, tablen, taboff, scratch, pl.cap, seglen, segoff, nseg,
-                                                                 seg_pixels, h8, w8, out, stride, (uint32_t)H, (uint32_t)W,
-                                                                 pr.id, keep);
-  return hipGetLastError();
-}
-
-hipError_t launch_rans2_decode(const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8,
-                               const RansPrior& pr, char* ws, const RansPlan& pl, uint8_t* z, int* status, hipStream_t st) {
-  const int npix = h8 * w8, maxseg = pl.nseg;
-  uint16_t* cum = (uint16_t*)(ws + pl.cum);
-  uint32_t* seglen = (uint32_t*)(ws + pl.seglen);
-  uint32_t* segoff = (uint32_t*)(ws + pl.segoff);
-  uint32_t* meta = (uint32_t*)(ws + pl.meta);
-  rans2_parse<<<dim3(n), 256, 0, st>>>(files, stride, sizes, h8, w8, pr.cum, pr.id, cum, seglen, segoff, maxseg, meta, status);
-  rans_decode_segments<<<dim3((maxseg + 63) / 64, n), 64, 0, st>>>(files, stride, npix, cum, segoff, maxseg, meta, z, status);
-  return hipGetLastError();
-}
-
-// ---- window decode: the full decode's parse, then the window's slots (pl: the decode plan of (n, h8, w8)) ----
-hipError_t launch_rans_decode_window(const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8,
-                                     int r0, int c0, int rows, int cols, const RansPrior* pr, char* ws, const RansPlan& pl,
-                                     uint8_t* zwin, int* status, hipStream_t st) {
-  const int npix = h8 * w8, maxseg = pl.nseg;
-  uint16_t* cum = (uint16_t*)(ws + pl.cum);
-  uint32_t* seglen = (uint32_t*)(ws + pl.seglen);
-  uint32_t* segoff = (uint32_t*)(ws + pl.segoff);
-  uint32_t* meta = (uint32_t*)(ws + pl.meta);
-  const RansWindow win = {w8, r0, c0, rows, cols};
-  if (pr)
-    rans2_parse<<<dim3(n), 256, 0, st>>>(files, stride, sizes, h8, w8, pr->cum, pr->id, cum, seglen, segoff, maxseg, meta, status);
+  if constexpr (kContext)
+    rans3_hist<uint32_t><<<dim3((npix + 255) / 256, 6, n), 256, 0, st>>>(z, npix, seg_pixels, pr.anchor, b.counts, kCounts);
   else
-    rans_parse<<<dim3(n), 256, 0, st>>>(files, stride, sizes, h8, w8, cum, seglen, segoff, maxseg, meta, status);
-  rans_decode_window_segments<<<dim3((rows * cols + 63) / 64, n), 64, 0, st>>>(files, stride, npix, cum, segoff, maxseg, meta, win,
-                                                                              zwin, status);
+    rans_hist<uint32_t><<<dim3((npix + 255) / 256, 3, n), 256, 0, st>>>(z, npix, b.counts, kCounts);
+  if constexpr (kVer == 1)
+    rans_normalise<<<dim3(kCh, n), 64, 0, st>>>(b.counts, npix, b.cum, b.tab, b.tablen);
+  else
+    rans_tables<kContext><<<dim3(kCh, n), 64, 0, st>>>(b.counts, npix, pr.freq, pr.cum, pr.cost16, b.cum, b.tab, b.tablen, b.keep);
+  rans_encode_segments<kContext><<<dim3((nseg + 63) / 64, n), 64, 0, st>>>(z, npix, seg_pixels, nseg, b.cum, pr.anchor, b.scratch,
+                                                                           pl.cap, b.seglen);
+  rans_layout<kVer><<<dim3(n), 256, 0, st>>>(b.tablen, b.taboff, b.seglen, b.segoff, nseg, sizes);
+  // version 1 writes neither H, W, the id nor the mask: its header ends before them
+  rans_assemble<kVer><<<dim3((kCh + nseg + 3) / 4, n), 256, 0, st>>>(b.tab, b.tablen, b.taboff, b.scratch, pl.cap, b.seglen, b.segoff,
+                                                                    nseg, seg_pixels, h8, w8, out, stride, (uint32_t)H, (uint32_t)W,
+                                                                    pr.id, b.keep);
   return hipGetLastError();
 }
 
-hipError_t launch_rans3_decode_window(const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8,
-                                      int r0, int c0, int rows, int cols, const RansCPrior& pr, char* ws, const RansPlan& pl,
-                                      uint8_t* zwin, int* status, hipStream_t st) {
+// the parse, then every segment (win NULL) or the window's slots
+template <int kVer>
+hipError_t rans_decode(const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8, const RansWindow* win,
+                       const RansPrior& pr, char* ws, const RansPlan& pl, uint8_t* z, int* status, hipStream_t st) {
+  constexpr bool kContext = kVer == 3;
   const int npix = h8 * w8, maxseg = pl.nseg;
-  uint16_t* cum = (uint16_t*)(ws + pl.cum);
-  uint32_t* seglen = (uint32_t*)(ws + pl.seglen);
-  uint32_t* segoff = (uint32_t*)(ws + pl.segoff);
-  uint32_t* meta = (uint32_t*)(ws + pl.meta);
-  const RansWindow win = {w8, r0, c0, rows, cols};
-  rans3_parse<<<dim3(n), 256, 0, st>>>(files, stride, sizes, h8, w8, pr.cum, pr.id, cum, seglen, segoff, maxseg, meta, status);
-  rans3_decode_window_segments<<<dim3((rows * cols + 63) / 64, n), 64, 0, st>>>(files, stride, npix, cum, pr.anchor, segoff,
-                                                                               maxseg, meta, win, zwin, status);
+  const RansBuffers b = rans_buffers(ws, pl);
+  rans_parse<kVer><<<dim3(n), 256, 0, st>>>(files, stride, sizes, h8, w8, pr.cum, pr.id, b.cum, b.seglen, b.segoff, maxseg, b.meta,
+                                            status);
+  if (win)
+    rans_decode_segments<kContext, true><<<dim3((win->rows * win->cols + 63) / 64, n), 64, 0, st>>>(
+        files, stride, npix, b.cum, pr.anchor, b.segoff, maxseg, b.meta, *win, z, status);
+  else
+    rans_decode_segments<kContext, false><<<dim3((maxseg + 63) / 64, n), 64, 0, st>>>(files, stride, npix, b.cum, pr.anchor, b.segoff,
+                                                                                      maxseg, b.meta, RansWindow{}, z, status);
   return hipGetLastError();
 }
+
+// The device allocation of a prior: freqs | cumulative rows at the segment kernels' pitch | the 96
+// anchors (a context prior only) | the cost table.  Every part starts at a multiple of 4.
+size_t prior_layout(bool context, size_t* cum_at, size_t* anchor_at, size_t* cost_at) {
+  *cum_at = (size_t)kCh * (context ? kCtx : 1) * 256 * 2;
+  *anchor_at = *cum_at + (size_t)(context ? kCtxWords : kCumWords) * 2;
+  *cost_at = *anchor_at + (context ? kCh : 0);
+  return *cost_at + (kProbScale + 1) * 4;
+}
+
+}  // namespace
+
+hipError_t launch_rans_encode(int ver, const uint8_t* z, int n, int h8, int w8, int H, int W, int seg_pixels, const RansPrior& pr,
+                              char* ws, const RansPlan& pl, uint8_t* out, long long stride, long long* sizes, hipStream_t st) {
+  switch (ver) {
+    case 1: return rans_encode<1>(z, n, h8, w8, H, W, seg_pixels, pr, ws, pl, out, stride, sizes, st);
+    case 2: return rans_encode<2>(z, n, h8, w8, H, W, seg_pixels, pr, ws, pl, out, stride, sizes, st);
+    case 3: return rans_encode<3>(z, n, h8, w8, H, W, seg_pixels, pr, ws, pl, out, stride, sizes, st);
+  }
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_rans_decode(int ver, const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8,
+                              const RansWindow* win, const RansPrior& pr, char* ws, const RansPlan& pl, uint8_t* z, int* status,
+                              hipStream_t st) {
+  switch (ver) {
+    case 1: return rans_decode<1>(files, stride, sizes, n, h8, w8, win, pr, ws, pl, z, status, st);
+    case 2: return rans_decode<2>(files, stride, sizes, n, h8, w8, win, pr, ws, pl, z, status, st);
+    case 3: return rans_decode<3>(files, stride, sizes, n, h8, w8, win, pr, ws, pl, z, status, st);
+  }
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_rans_prior_count(const uint8_t* z, int n, int h8, int w8, int seg_pixels, const uint8_t* anchor,
+                                   unsigned long long* counts, hipStream_t st) {
+  const int npix = h8 * w8;
+  if (anchor)
+    rans3_hist<unsigned long long><<<dim3((npix + 255) / 256, 6, n), 256, 0, st>>>(z, npix, seg_pixels, anchor, counts, 0);
+  else
+    rans_hist<unsigned long long><<<dim3((npix + 255) / 256, 3, n), 256, 0, st>>>(z, npix, counts, 0);
+  return hipGetLastError();
+}
+
+hipError_t launch_rans_prior_build(bool context, const unsigned long long* counts, uint16_t* freqs, hipStream_t st) {
+  rans_prior_normalise<<<dim3(kCh * (context ? kCtx : 1)), 64, 0, st>>>(counts, freqs);
+  return hipGetLastError();
+}
+
+std::vector<char> rans_prior_pack(const uint8_t* anchors, const uint16_t* freqs) {
+  const bool context = anchors != nullptr;
+  const int rows = kCh * (context ? kCtx : 1), pitch = context ? kCtxRow : kCumRow;
+  size_t cum_at, anchor_at, cost_at;
+  std::vector<char> host(prior_layout(context, &cum_at, &anchor_at, &cost_at), 0);
+  std::memcpy(host.data(), freqs, cum_at);
+  uint16_t* cum = (uint16_t*)(host.data() + cum_at);
+  for (int row = 0; row < rows; ++row) {
+    uint32_t run = 0;
+    for (int s = 0; s < 256; ++s) {
+      cum[row * pitch + s] = (uint16_t)run;
+      run += freqs[row * 256 + s];
+    }
+    cum[row * pitch + 256] = (uint16_t)run;  // 4096
+  }
+  if (context) std::memcpy(host.data() + anchor_at, anchors, kCh);
+  nic_rans_cost_table((uint32_t*)(host.data() + cost_at));
+  return host;
+}
+
+RansPrior rans_prior_view(bool context, const char* dev, uint32_t id) {
+  size_t cum_at, anchor_at, cost_at;
+  prior_layout(context, &cum_at, &anchor_at, &cost_at);
+  return {(const uint16_t*)dev, (const uint16_t*)(dev + cum_at), context ? (const uint8_t*)(dev + anchor_at) : nullptr,
+          (const uint32_t*)(dev + cost_at), id};
+}
+
 
 }  // namespace nic
 
-// ---- host-only entry points ------------------------------------------------------------------
+// ---- host-only checks and entry points ---------------------------------------------------------
+
+// Every check of a version-`ver` file, for the nic_rans*_inspect named fn: the header (16 bytes in
+// version 1; 40 in versions 2 and 3, which also relate H / W to the latent), the tables (all 96 in
+// version 1, the masked channels' in versions 2 and 3), the segment table and the size.  Every
+// output is nullable; H, W and prior_id are written for versions 2 and 3 only.
+static int inspect_file(const char* fn, int ver, const uint8_t* f, int64_t size, int* h8, int* w8, int* seg_pixels, int* H, int* W,
+                        uint32_t* prior_id) {
+  char msg[200], text[160];
+  auto corrupt = [&](const char* what, long long a = 0, long long b = 0) {
+    snprintf(text, sizeof(text), what, a, b);
+    snprintf(msg, sizeof(msg), "%s: %s", fn, text);
+    return nic::set_error(NIC_ECORRUPT, msg);
+  };
+  if (!f) {
+    snprintf(msg, sizeof(msg), "%s: file is NULL", fn);
+    return nic::set_error(NIC_EINVAL, msg);
+  }
+  const int header = ver == 1 ? nic::kHeader : nic::kHeader2;
+  if (size < nic::kHeader) return corrupt("%lld bytes are less than the %lld-byte header", size, header);
+  if (std::memcmp(f, "NICR", 4) != 0) return corrupt("bad magic");
+  if (f[4] != ver) return corrupt("version %lld, expected %lld", f[4], ver);
+  if (size < header) return corrupt("%lld bytes are less than the %lld-byte header", size, header);
+  if (f[5] != nic::kProbBits) return corrupt("%lld probability bits, expected 12", f[5]);
+  auto u32 = [&](int64_t at) { return (uint32_t)f[at] | ((uint32_t)f[at + 1] << 8) | ((uint32_t)f[at + 2] << 16) | ((uint32_t)f[at + 3] << 24); };
+  const uint32_t S = (uint32_t)f[6] | ((uint32_t)f[7] << 8), fh = u32(8), fw = u32(12);
+  if (S == 0) return corrupt("seg_pixels is 0");
+  if (fh == 0 || fw == 0 || fh > (1u << 23) || fw > (1u << 23) || !nic::rans_shape_ok((int)fh, (int)fw))
+    return corrupt("latent size %lld x %lld out of range", fh, fw);
+  const uint32_t ih = ver == 1 ? 0u : u32(16), iw = ver == 1 ? 0u : u32(20);
+  if (ver != 1) {
+    if ((ih >> 3) + ((ih & 7u) != 0u) != fh) return corrupt("image height %lld does not give h8 = %lld", ih, fh);
+    if ((iw >> 3) + ((iw & 7u) != 0u) != fw) return corrupt("image width %lld does not give w8 = %lld", iw, fw);
+  }
+  int64_t at = header;
+  for (int c = 0; c < nic::kCh; ++c) {
+    if (ver != 1 && !((f[28 + (c >> 3)] >> (c & 7)) & 1)) continue;  // the prior's row(s)
+    if (at >= size) return corrupt("truncated in the table of channel %lld", c);
+    const int nsym = f[at] + 1;
+    if (at + 1 + 3 * nsym > size) return corrupt("truncated in the table of channel %lld", c);
+    int prev = -1;
+    uint32_t sum = 0;
+    for (int e = 0; e < nsym; ++e) {
+      const int s = f[at + 1 + 3 * e];
+      const uint32_t fr = (uint32_t)f[at + 2 + 3 * e] | ((uint32_t)f[at + 3 + 3 * e] << 8);
+      if (s <= prev) return corrupt("channel %lld: symbols not strictly ascending", c);
+      if (fr < 1 || fr > nic::kProbScale) return corrupt("channel %lld: freq %lld not in 1..4096", c, fr);
+      prev = s;
+      sum += fr;
+    }
+    if (sum != nic::kProbScale) return corrupt("channel %lld: freqs sum to %lld, not 4096", c, sum);
+    at += 1 + 3 * nsym;
+  }
+  const int64_t npix = (int64_t)fh * fw, nseg = (npix + S - 1) / S;
+  if (at + 4 * nseg > size) return corrupt("truncated in the segment table");
+  int64_t pay = 0;
+  for (int64_t k = 0; k < nseg; ++k) pay += u32(at + 4 * k);
+  if (at + 4 * nseg + pay != size)
+    return corrupt("header, tables and segments need %lld bytes, the file has %lld", at + 4 * nseg + pay, size);
+  if (h8) *h8 = (int)fh;
+  if (w8) *w8 = (int)fw;
+  if (seg_pixels) *seg_pixels = (int)S;
+  if (ver != 1) {
+    if (H) *H = (int)ih;
+    if (W) *W = (int)iw;
+    if (prior_id) *prior_id = u32(24);
+  }
+  return NIC_OK;
+}
+
+// A prior's freqs, 96 x per_ch rows of 256 (per_ch 1: the static prior; 3: the context prior): each
+// in 1..4096, every row summing to 4096.  id: the CRC-32 of the anchors (a context prior only), then
+// the freqs as little-endian u16, channel-major, then context, then symbol.
+static int check_freq_rows(const char* fn, const uint8_t* anchors, const uint16_t* freqs, int per_ch, uint32_t* id) {
+  char msg[160], where[40];
+  for (int r = 0; r < nic::kCh * per_ch; ++r) {
+    if (per_ch == 1) snprintf(where, sizeof(where), "channel %d", r);
+    else snprintf(where, sizeof(where), "channel %d context %d", r / per_ch, r % per_ch);
+    uint32_t sum = 0;
+    for (int s = 0; s < 256; ++s) {
+      const uint32_t fr = freqs[r * 256 + s];
+      if (fr < 1 || fr > nic::kProbScale) {
+        snprintf(msg, sizeof(msg), "%s: %s: freq %u of symbol %d not in 1..4096", fn, where, fr, s);
+        return nic::set_error(NIC_ECORRUPT, msg);
+      }
+      sum += fr;
+    }
+    if (sum != nic::kProbScale) {
+      snprintf(msg, sizeof(msg), "%s: %s: freqs sum to %u, not 4096", fn, where, sum);
+      return nic::set_error(NIC_ECORRUPT, msg);
+    }
+  }
+  if (id) {
+    uint8_t le[512];
+    uLong crc = crc32(0L, Z_NULL, 0);
+    if (anchors) crc = crc32(crc, anchors, nic::kCh);
+    for (int r = 0; r < nic::kCh * per_ch; ++r) {
+      for (int s = 0; s < 256; ++s) {
+        le[2 * s] = (uint8_t)(freqs[r * 256 + s] & 255u);
+        le[2 * s + 1] = (uint8_t)(freqs[r * 256 + s] >> 8);
+      }
+      crc = crc32(crc, le, sizeof(le));
+    }
+    *id = (uint32_t)crc;
+  }
+  return NIC_OK;
+}
 
 extern "C" {
 
@@ -1470,49 +1134,15 @@ int nic_rans_bound(int h8, int w8, int seg_pixels, int64_t* bytes) {
 }
 
 int nic_rans_inspect(const uint8_t* f, int64_t size, int* h8, int* w8, int* seg_pixels) {
-  char msg[160];
-  auto corrupt = [&](const char* what, long long a = 0, long long b = 0) {
-    snprintf(msg, sizeof(msg), what, a, b);
-    return nic::set_error(NIC_ECORRUPT, msg);
-  };
-  if (!f) return nic::set_error(NIC_EINVAL, "nic_rans_inspect: file is NULL");
-  if (size < nic::kHeader) return corrupt("nic_rans_inspect: %lld bytes are less than the 16-byte header", size);
-  if (std::memcmp(f, "NICR", 4) != 0) return corrupt("nic_rans_inspect: bad magic");
-  if (f[4] != 1) return corrupt("nic_rans_inspect: version %lld, expected 1", f[4]);
-  if (f[5] != nic::kProbBits) return corrupt("nic_rans_inspect: %lld probability bits, expected 12", f[5]);
-  auto u32 = [&](int64_t at) { return (uint32_t)f[at] | ((uint32_t)f[at + 1] << 8) | ((uint32_t)f[at + 2] << 16) | ((uint32_t)f[at + 3] << 24); };
-  const uint32_t S = (uint32_t)f[6] | ((uint32_t)f[7] << 8), fh = u32(8), fw = u32(12);
-  if (S == 0) return corrupt("nic_rans_inspect: seg_pixels is 0");
-  if (fh == 0 || fw == 0 || fh > (1u << 23) || fw > (1u << 23) || !nic::rans_shape_ok((int)fh, (int)fw))
-    return corrupt("nic_rans_inspect: latent size %lld x %lld out of range", fh, fw);
-  int64_t at = nic::kHeader;
-  for (int c = 0; c < nic::kCh; ++c) {
-    if (at >= size) return corrupt("nic_rans_inspect: truncated in the table of channel %lld", c);
-    const int nsym = f[at] + 1;
-    if (at + 1 + 3 * nsym > size) return corrupt("nic_rans_inspect: truncated in the table of channel %lld", c);
-    int prev = -1;
-    uint32_t sum = 0;
-    for (int e = 0; e < nsym; ++e) {
-      const int s = f[at + 1 + 3 * e];
-      const uint32_t fr = (uint32_t)f[at + 2 + 3 * e] | ((uint32_t)f[at + 3 + 3 * e] << 8);
-      if (s <= prev) return corrupt("nic_rans_inspect: channel %lld: symbols not strictly ascending", c);
-      if (fr < 1 || fr > nic::kProbScale) return corrupt("nic_rans_inspect: channel %lld: freq %lld not in 1..4096", c, fr);
-      prev = s;
-      sum += fr;
-    }
-    if (sum != nic::kProbScale) return corrupt("nic_rans_inspect: channel %lld: freqs sum to %lld, not 4096", c, sum);
-    at += 1 + 3 * nsym;
-  }
-  const int64_t npix = (int64_t)fh * fw, nseg = (npix + S - 1) / S;
-  if (at + 4 * nseg > size) return corrupt("nic_rans_inspect: truncated in the segment table");
-  int64_t pay = 0;
-  for (int64_t k = 0; k < nseg; ++k) pay += u32(at + 4 * k);
-  if (at + 4 * nseg + pay != size)
-    return corrupt("nic_rans_inspect: header, tables and segments need %lld bytes, the file has %lld", at + 4 * nseg + pay, size);
-  if (h8) *h8 = (int)fh;
-  if (w8) *w8 = (int)fw;
-  if (seg_pixels) *seg_pixels = (int)S;
-  return NIC_OK;
+  return inspect_file("nic_rans_inspect", 1, f, size, h8, w8, seg_pixels, nullptr, nullptr, nullptr);
+}
+
+int nic_rans2_inspect(const uint8_t* f, int64_t size, int* h8, int* w8, int* seg_pixels, int* H, int* W, uint32_t* prior_id) {
+  return inspect_file("nic_rans2_inspect", 2, f, size, h8, w8, seg_pixels, H, W, prior_id);
+}
+
+int nic_rans3_inspect(const uint8_t* f, int64_t size, int* h8, int* w8, int* seg_pixels, int* H, int* W, uint32_t* prior_id) {
+  return inspect_file("nic_rans3_inspect", 3, f, size, h8, w8, seg_pixels, H, W, prior_id);
 }
 
 int nic_rans_cost_table(uint32_t* out4097) {
@@ -1524,36 +1154,13 @@ int nic_rans_cost_table(uint32_t* out4097) {
 }
 
 int nic_rans_prior_check(const uint16_t* freqs, uint32_t* id) {
-  char msg[160];
   if (!freqs) return nic::set_error(NIC_EINVAL, "nic_rans_prior_check: freqs is NULL");
-  for (int c = 0; c < nic::kCh; ++c) {
-    uint32_t sum = 0;
-    for (int s = 0; s < 256; ++s) {
-      const uint32_t fr = freqs[c * 256 + s];
-      if (fr < 1 || fr > nic::kProbScale) {
-        snprintf(msg, sizeof(msg), "nic_rans_prior_check: channel %d: freq %u of symbol %d not in 1..4096", c, fr, s);
-        return nic::set_error(NIC_ECORRUPT, msg);
-      }
-      sum += fr;
-    }
-    if (sum != nic::kProbScale) {
-      snprintf(msg, sizeof(msg), "nic_rans_prior_check: channel %d: freqs sum to %u, not 4096", c, sum);
-      return nic::set_error(NIC_ECORRUPT, msg);
-    }
-  }
-  if (id) {  // CRC-32 of the freqs as little-endian u16, channel-major
-    uint8_t le[512];
-    uLong crc = crc32(0L, Z_NULL, 0);
-    for (int c = 0; c < nic::kCh; ++c) {
-      for (int s = 0; s < 256; ++s) {
-        le[2 * s] = (uint8_t)(freqs[c * 256 + s] & 255u);
-        le[2 * s + 1] = (uint8_t)(freqs[c * 256 + s] >> 8);
-      }
-      crc = crc32(crc, le, sizeof(le));
-    }
-    *id = (uint32_t)crc;
-  }
-  return NIC_OK;
+  return check_freq_rows("nic_rans_prior_check", nullptr, freqs, 1, id);
+}
+
+int nic_rans_cprior_check(const uint8_t* anchors, const uint16_t* freqs, uint32_t* id) {
+  if (!anchors || !freqs) return nic::set_error(NIC_EINVAL, "nic_rans_cprior_check: anchors or freqs is NULL");
+  return check_freq_rows("nic_rans_cprior_check", anchors, freqs, nic::kCtx, id);
 }
 
 int nic_rans2_bound(int h8, int w8, int seg_pixels, int64_t* bytes) {
@@ -1602,115 +1209,6 @@ int nic_rans_window_segments(int h8, int w8, int seg_pixels, int r0, int c0, int
   return NIC_OK;
 }
 
-}  // extern "C"
-
-// nic_rans_inspect's checks on a file with the 40-byte header (version 2 or 3: tables of the masked
-// channels only) plus the H / W relation; every output nullable
-static int inspect_prior_file(const char* fn, int ver, const uint8_t* f, int64_t size, int* h8, int* w8, int* seg_pixels, int* H, int* W,
-                              uint32_t* prior_id) {
-  char msg[200], text[160];
-  auto corrupt = [&](const char* what, long long a = 0, long long b = 0) {
-    snprintf(text, sizeof(text), what, a, b);
-    snprintf(msg, sizeof(msg), "%s: %s", fn, text);
-    return nic::set_error(NIC_ECORRUPT, msg);
-  };
-  if (!f) {
-    snprintf(msg, sizeof(msg), "%s: file is NULL", fn);
-    return nic::set_error(NIC_EINVAL, msg);
-  }
-  if (size < nic::kHeader) return corrupt("%lld bytes are less than the 40-byte header", size);
-  if (std::memcmp(f, "NICR", 4) != 0) return corrupt("bad magic");
-  if (f[4] != ver) return corrupt("version %lld, expected %lld", f[4], ver);
-  if (size < nic::kHeader2) return corrupt("%lld bytes are less than the 40-byte header", size);
-  if (f[5] != nic::kProbBits) return corrupt("%lld probability bits, expected 12", f[5]);
-  auto u32 = [&](int64_t at) { return (uint32_t)f[at] | ((uint32_t)f[at + 1] << 8) | ((uint32_t)f[at + 2] << 16) | ((uint32_t)f[at + 3] << 24); };
-  const uint32_t S = (uint32_t)f[6] | ((uint32_t)f[7] << 8), fh = u32(8), fw = u32(12), ih = u32(16), iw = u32(20);
-  if (S == 0) return corrupt("seg_pixels is 0");
-  if (fh == 0 || fw == 0 || fh > (1u << 23) || fw > (1u << 23) || !nic::rans_shape_ok((int)fh, (int)fw))
-    return corrupt("latent size %lld x %lld out of range", fh, fw);
-  if ((ih >> 3) + ((ih & 7u) != 0u) != fh) return corrupt("image height %lld does not give h8 = %lld", ih, fh);
-  if ((iw >> 3) + ((iw & 7u) != 0u) != fw) return corrupt("image width %lld does not give w8 = %lld", iw, fw);
-  int64_t at = nic::kHeader2;
-  for (int c = 0; c < nic::kCh; ++c) {
-    if (!((f[28 + (c >> 3)] >> (c & 7)) & 1)) continue;  // the prior's row(s)
-    if (at >= size) return corrupt("truncated in the table of channel %lld", c);
-    const int nsym = f[at] + 1;
-    if (at + 1 + 3 * nsym > size) return corrupt("truncated in the table of channel %lld", c);
-    int prev = -1;
-    uint32_t sum = 0;
-    for (int e = 0; e < nsym; ++e) {
-      const int s = f[at + 1 + 3 * e];
-      const uint32_t fr = (uint32_t)f[at + 2 + 3 * e] | ((uint32_t)f[at + 3 + 3 * e] << 8);
-      if (s <= prev) return corrupt("channel %lld: symbols not strictly ascending", c);
-      if (fr < 1 || fr > nic::kProbScale) return corrupt("channel %lld: freq %lld not in 1..4096", c, fr);
-      prev = s;
-      sum += fr;
-    }
-    if (sum != nic::kProbScale) return corrupt("channel %lld: freqs sum to %lld, not 4096", c, sum);
-    at += 1 + 3 * nsym;
-  }
-  const int64_t npix = (int64_t)fh * fw, nseg = (npix + S - 1) / S;
-  if (at + 4 * nseg > size) return corrupt("truncated in the segment table");
-  int64_t pay = 0;
-  for (int64_t k = 0; k < nseg; ++k) pay += u32(at + 4 * k);
-  if (at + 4 * nseg + pay != size)
-    return corrupt("header, tables and segments need %lld bytes, the file has %lld", at + 4 * nseg + pay, size);
-  if (h8) *h8 = (int)fh;
-  if (w8) *w8 = (int)fw;
-  if (seg_pixels) *seg_pixels = (int)S;
-  if (H) *H = (int)ih;
-  if (W) *W = (int)iw;
-  if (prior_id) *prior_id = u32(24);
-  return NIC_OK;
-}
-
-
-extern "C" {
-
-int nic_rans2_inspect(const uint8_t* f, int64_t size, int* h8, int* w8, int* seg_pixels, int* H, int* W, uint32_t* prior_id) {
-  return inspect_prior_file("nic_rans2_inspect", 2, f, size, h8, w8, seg_pixels, H, W, prior_id);
-}
-
-int nic_rans_cprior_check(const uint8_t* anchors, const uint16_t* freqs, uint32_t* id) {
-  char msg[160];
-  if (!anchors || !freqs) return nic::set_error(NIC_EINVAL, "nic_rans_cprior_check: anchors or freqs is NULL");
-  for (int c = 0; c < nic::kCh; ++c)
-    for (int k = 0; k < nic::kCtx; ++k) {
-      const uint16_t* row = freqs + ((size_t)c * nic::kCtx + k) * 256;
-      uint32_t sum = 0;
-      for (int s = 0; s < 256; ++s) {
-        const uint32_t fr = row[s];
-        if (fr < 1 || fr > nic::kProbScale) {
-          snprintf(msg, sizeof(msg), "nic_rans_cprior_check: channel %d context %d: freq %u of symbol %d not in 1..4096", c, k, fr, s);
-          return nic::set_error(NIC_ECORRUPT, msg);
-        }
-        sum += fr;
-      }
-      if (sum != nic::kProbScale) {
-        snprintf(msg, sizeof(msg), "nic_rans_cprior_check: channel %d context %d: freqs sum to %u, not 4096", c, k, sum);
-        return nic::set_error(NIC_ECORRUPT, msg);
-      }
-    }
-  if (id) {  // CRC-32 of the anchors, then the freqs as little-endian u16: channel-major, then context, then symbol
-    uint8_t le[512];
-    uLong crc = crc32(0L, Z_NULL, 0);
-    crc = crc32(crc, anchors, nic::kCh);
-    for (int r = 0; r < nic::kCh * nic::kCtx; ++r) {
-      for (int s = 0; s < 256; ++s) {
-        le[2 * s] = (uint8_t)(freqs[r * 256 + s] & 255u);
-        le[2 * s + 1] = (uint8_t)(freqs[r * 256 + s] >> 8);
-      }
-      crc = crc32(crc, le, sizeof(le));
-    }
-    *id = (uint32_t)crc;
-  }
-  return NIC_OK;
-}
-
 int nic_rans3_bound(int h8, int w8, int seg_pixels, int64_t* bytes) { return nic_rans2_bound(h8, w8, seg_pixels, bytes); }
-
-int nic_rans3_inspect(const uint8_t* f, int64_t size, int* h8, int* w8, int* seg_pixels, int* H, int* W, uint32_t* prior_id) {
-  return inspect_prior_file("nic_rans3_inspect", 3, f, size, h8, w8, seg_pixels, H, W, prior_id);
-}
 
 }  // extern "C"

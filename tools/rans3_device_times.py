@@ -1,5 +1,5 @@
 """Device time and file sizes of the .nic container's version 3 beside versions 1 and 2, in one
-process: Codec.rans2_encode / rans2_decode and rans3_encode / rans3_decode on the two batches of
+process: Codec.rans_encode / rans_decode, rans2_encode / rans2_decode and rans3_encode / rans3_decode on the two batches of
 DESIGN.md section 10 (64 latents of 256^2 kodim21 tiles and one 270x480 latent of a 2160x3840
 frame, trained coef-0.01 codec), hipEvents on the current stream, the median of `--iters` calls after
 `--warmup`, the two versions alternating (`--rounds` medians each, all reported); workspaces are
@@ -59,12 +59,17 @@ def main():
     for name, img in (("64x256x256", np.stack(tiles(64))), ("1x2160x3840", frame[None])):
         lat = c.encode(torch.from_numpy(np.ascontiguousarray(img)).cuda())
         n, h8, w8, _ = lat.shape
+        c.rans_reserve(n, h8, w8)
         c.rans2_reserve(n, h8, w8)
         c.rans3_reserve(n, h8, w8)
+        b1, s1 = c.rans_encode(lat)
         b2, s2 = c.rans2_encode(lat)
         b3, s3 = c.rans3_encode(lat)
+        assert bool((c.rans_decode(b1, s1, h8, w8) == lat).all())
         assert bool((c.rans2_decode(b2, s2, h8, w8) == lat).all()) and bool((c.rans3_decode(b3, s3, h8, w8) == lat).all())
-        calls = {"rans2_encode_ms": lambda: c.rans2_encode(lat), "rans3_encode_ms": lambda: c.rans3_encode(lat),
+        calls = {"rans_encode_ms": lambda: c.rans_encode(lat), "rans2_encode_ms": lambda: c.rans2_encode(lat),
+                 "rans3_encode_ms": lambda: c.rans3_encode(lat),
+                 "rans_decode_ms": lambda: c.rans_decode_status(b1, s1, h8, w8),
                  "rans2_decode_ms": lambda: c.rans2_decode_status(b2, s2, h8, w8),
                  "rans3_decode_ms": lambda: c.rans3_decode_status(b3, s3, h8, w8)}
         times = {k: [] for k in calls}
