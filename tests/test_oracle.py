@@ -194,6 +194,38 @@ def test_power_of_two_weight_scaling_is_exact(golden, weights_spread):
     np.testing.assert_array_equal(O.decode(w, g["latent"]), g["recon"])
 
 
+def test_float_decoder_check_sees_what_the_u8_check_cannot(weights_spread):
+    """tests/test_gpu_parity.py check_recon_f32 on known inputs: one image column 1e-3 off (a
+    quarter of a u8 step: a shifted halo column or strip seam) passes check_recon's |delta u8|
+    <= 1 and 50 dB and fails the float comparison; the oracle's own fp32-accumulation output,
+    the rounding noise a correct fp32 kernel has, passes it."""
+    from tests.test_gpu_parity import SHARE_SPREAD, check_recon, check_recon_f32
+    z = np.random.default_rng(96).integers(0, 256, (1, 3, 20, 96), dtype=np.uint8)
+    rf = O.decode_f32(weights_spread, z)
+    assert rf.shape == (1, 24, 160, 3)
+    col = 77
+    inside = (rf[:, :, col] > 0) & (rf[:, :, col] < 1 - 2e-3)  # the shifted value stays unclipped
+    assert inside.mean() >= 0.5
+    bad = rf.copy()
+    bad[:, :, col][inside] += np.float32(1e-3)
+    assert np.abs(bad - rf).max() == pytest.approx(1e-3, rel=1e-3)
+    check_recon(O.quantise_u8(bad), O.quantise_u8(rf))
+    with pytest.raises(AssertionError, match=f"col {col} "):
+        check_recon_f32(bad, O.quantise_u8(bad), rf)
+    rf32 = O.decode_f32(weights_spread, z, acc=np.float32)
+    worst, share = check_recon_f32(rf32, O.quantise_u8(rf32), rf)
+    assert 0 < worst <= 2e-6 and share >= SHARE_SPREAD
+    # the u8 output is held to the device's own floats, and to the oracle's away from a .5 boundary
+    r = O.quantise_u8(rf)
+    flip = r.copy()
+    v = rf.astype(np.float64) * 255
+    far = (np.abs(v - np.floor(v) - 0.5) > 0.1) & (r < 255)
+    at = tuple(np.argwhere(far)[0])
+    flip[at] += 1
+    with pytest.raises(AssertionError, match="away from a rounding boundary"):
+        check_recon_f32(rf, flip, rf)
+
+
 def test_tile_patches_roundtrip():
     from neural_network_image_compression_amd.rd import tile_patches, untile_patches
     x = np.random.default_rng(0).integers(0, 256, (2, 512, 768, 3), dtype=np.uint8)
