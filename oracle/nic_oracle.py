@@ -153,28 +153,44 @@ def _layer(x, params: Dict[str, np.ndarray], name: str, stride: int, transposed:
     return leaky(z + b)  # Keras: conv -> BiasAdd -> activation, fp32
 
 
+ENCODER_LAYERS = ("conv1", "conv2", "conv3", "conv4", "conv8")
+DECODER_LAYERS = ("dconv1", "dconv5", "dconv6", "dconv7", "dconv8")
+
+
+def encoder_layers(params: Dict[str, np.ndarray], x: np.ndarray, acc=np.float64) -> Dict[str, np.ndarray]:
+    """BaseEncoder.call (encoder.py:19-32) layer by layer: every layer's post-activation output,
+    conv4's after the residual add, conv8's before the clip.  params keyed '<layer>/<kernel|bias>'."""
+    out = {}
+    out["conv1"] = x = _layer(x, params, "conv1", 2, False, acc)
+    out["conv2"] = res = x = _layer(x, params, "conv2", 2, False, acc)
+    out["conv3"] = x = _layer(x, params, "conv3", 1, False, acc)
+    x = _layer(x, params, "conv4", 1, False, acc)
+    out["conv4"] = x = x + res
+    out["conv8"] = _layer(x, params, "conv8", 2, False, acc)
+    return out
+
+
+def decoder_layers(params: Dict[str, np.ndarray], x: np.ndarray, acc=np.float64) -> Dict[str, np.ndarray]:
+    """BaseDecoder.call (decoder.py:19-32) layer by layer: every layer's post-activation output,
+    dconv6's after the residual add, dconv8's before the clip."""
+    out = {}
+    out["dconv1"] = res = x = _layer(x, params, "dconv1", 2, True, acc)
+    out["dconv5"] = x = _layer(x, params, "dconv5", 1, True, acc)
+    x = _layer(x, params, "dconv6", 1, True, acc)
+    out["dconv6"] = x = x + res
+    out["dconv7"] = x = _layer(x, params, "dconv7", 2, True, acc)
+    out["dconv8"] = _layer(x, params, "dconv8", 2, True, acc)
+    return out
+
+
 def base_encoder(params: Dict[str, np.ndarray], x: np.ndarray, acc=np.float64) -> np.ndarray:
     """BaseEncoder.call (encoder.py:19-32).  params keyed '<layer>/<kernel|bias>'."""
-    x = _layer(x, params, "conv1", 2, False, acc)
-    x = _layer(x, params, "conv2", 2, False, acc)
-    res = x
-    x = _layer(x, params, "conv3", 1, False, acc)
-    x = _layer(x, params, "conv4", 1, False, acc)
-    x = x + res
-    x = _layer(x, params, "conv8", 2, False, acc)
-    return np.clip(x, F32(0), F32(1))
+    return np.clip(encoder_layers(params, x, acc)["conv8"], F32(0), F32(1))
 
 
 def base_decoder(params: Dict[str, np.ndarray], x: np.ndarray, acc=np.float64) -> np.ndarray:
     """BaseDecoder.call (decoder.py:19-32)."""
-    x = _layer(x, params, "dconv1", 2, True, acc)
-    res = x
-    x = _layer(x, params, "dconv5", 1, True, acc)
-    x = _layer(x, params, "dconv6", 1, True, acc)
-    x = x + res
-    x = _layer(x, params, "dconv7", 2, True, acc)
-    x = _layer(x, params, "dconv8", 2, True, acc)
-    return np.clip(x, F32(0), F32(1))
+    return np.clip(decoder_layers(params, x, acc)["dconv8"], F32(0), F32(1))
 
 
 def _model_params(weights: Dict[str, np.ndarray], model: str) -> Dict[str, np.ndarray]:
@@ -190,11 +206,39 @@ def run_model(weights, kind: str, planes: Sequence[np.ndarray], acc=np.float64) 
     return [fn(py, planes[0], acc), fn(pc, planes[1], acc), fn(pc, planes[2], acc)]
 
 
+def _encoder_planes(x_u8: np.ndarray) -> List[np.ndarray]:
+    assert x_u8.dtype == np.uint8 and x_u8.ndim == 4 and x_u8.shape[3] == 3
+    return convert_to_colourspace(normalise_u8(x_u8))
+
+
+def _decoder_planes(z_u8: np.ndarray) -> List[np.ndarray]:
+    assert z_u8.dtype == np.uint8 and z_u8.ndim == 4 and z_u8.shape[3] == 96
+    zn = normalise_u8(z_u8)
+    return [zn[..., 32 * i:32 * (i + 1)] for i in range(3)]  # tf.split(., 3, axis=3)
+
+
+def _activations(weights, kind: str, planes: Sequence[np.ndarray], acc) -> List[Dict[str, np.ndarray]]:
+    fn = encoder_layers if kind == "encoder" else decoder_layers
+    py = _model_params(weights, kind + "Y")
+    pc = _model_params(weights, kind + "CbCr")
+    return [fn(py, planes[0], acc), fn(pc, planes[1], acc), fn(pc, planes[2], acc)]
+
+
+def encoder_activations(weights, x_u8: np.ndarray, acc=np.float64) -> List[Dict[str, np.ndarray]]:
+    """Every encoder layer's post-activation output (encoder_layers) per model plane: [Y, Cb, Cr],
+    each a dict layer -> (N,h,w,C) fp32, by the code encode_f32 runs."""
+    return _activations(weights, "encoder", _encoder_planes(x_u8), acc)
+
+
+def decoder_activations(weights, z_u8: np.ndarray, acc=np.float64) -> List[Dict[str, np.ndarray]]:
+    """The same for the decoder (decoder_layers): dconv8's entries are the Y, Cb, Cr planes
+    before the clip and the colour conversion."""
+    return _activations(weights, "decoder", _decoder_planes(z_u8), acc)
+
+
 def encode_f32(weights, x_u8: np.ndarray, acc=np.float64) -> np.ndarray:
     """Encoder.__call__ up to the quantiser (encoder.py:38-45): (N,H,W,3) u8 -> (N,h,w,96) fp32 in [0,1]."""
-    assert x_u8.dtype == np.uint8 and x_u8.ndim == 4 and x_u8.shape[3] == 3
-    planes = convert_to_colourspace(normalise_u8(x_u8))
-    return np.concatenate(run_model(weights, "encoder", planes, acc), axis=3)
+    return np.concatenate(run_model(weights, "encoder", _encoder_planes(x_u8), acc), axis=3)
 
 
 def encode(weights, x_u8: np.ndarray, acc=np.float64) -> np.ndarray:
@@ -204,10 +248,7 @@ def encode(weights, x_u8: np.ndarray, acc=np.float64) -> np.ndarray:
 
 def decode_f32(weights, z_u8: np.ndarray, acc=np.float64) -> np.ndarray:
     """Decoder.__call__ up to the output quantiser (decoder.py:39-46): clipped fp32 RGB."""
-    assert z_u8.dtype == np.uint8 and z_u8.ndim == 4 and z_u8.shape[3] == 96
-    zn = normalise_u8(z_u8)
-    planes = [zn[..., 32 * i:32 * (i + 1)] for i in range(3)]  # tf.split(., 3, axis=3)
-    y, cb, cr = run_model(weights, "decoder", planes, acc)
+    y, cb, cr = run_model(weights, "decoder", _decoder_planes(z_u8), acc)
     return np.clip(convert_to_rgb(y, cb, cr), F32(0), F32(1))
 
 
