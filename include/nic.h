@@ -405,6 +405,50 @@ int nic_rans2_decode_window(nic_ctx* ctx, const uint8_t* files, int64_t stride, 
 int nic_rans3_decode_window(nic_ctx* ctx, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, int h8, int w8,
                             int r0, int c0, int rows, int cols, uint8_t* latent_win, int32_t* status, void* stream);
 
+/* ---- Batched region decode: a box per file, files of different frame sizes, one call -------------
+ * Boxes of one size out of files of any sizes need latent windows of one shape, so the windows of a
+ * whole batch decode, and the decoder runs, as one (n, rows, cols, 96) tensor ("Batched
+ * region decode").
+ *
+ * nic_region_plan_fixed: HOST only, beside nic_region_plan (the same boxes are valid, the same error
+ *     codes).  The window's shape depends on the box's size and on the latent's only where the latent
+ *     is smaller: per axis T = (bh + 6) / 8 + 1 (the most latent rows bh pixel rows touch), R = T +
+ *     2 NIC_DECODE_HALO, rows = min(h8, R), r0 = clamp(y / 8 - NIC_DECODE_HALO, 0, h8 - rows);
+ *     columns likewise from bw, x and w8.  win4 = {r0, c0, rows, cols}, off2 = {y - 8 r0, x - 8 c0}.
+ *     The window holds nic_region_plan's; each of its edges lies on the latent's edge or at least
+ *     NIC_DECODE_HALO latent pixels beyond the box's, so the window's reconstruction cut at off2 is the
+ *     crop of the whole one, exactly as for nic_region_plan.
+ * nic_rans_decode_windows / nic_rans2_decode_windows / nic_rans3_decode_windows: as
+ *     nic_rans*_decode_window -- n whole files at one stride, `stream`, no host synchronisation -- but
+ *     file i has its own latent size and window place, row i of table, int32[n][4] = {h8, w8, r0, c0}
+ *     on the DEVICE (4-byte aligned), and the call has one window shape rows x cols; latent_win
+ *     (n, rows, cols, 96) u8, 16-byte aligned: latent_win[i][a][b] = latent_i[r0_i + a][c0_i + b].
+ *     max_pixels: the caller's bound on h8 w8 of any row, 1..2^23; it sizes the workspace
+ *     (nic_rans*_reserve of n latents of at least max_pixels pixels covers it), because the table is
+ *     never read on the host.  The device checks row i before it acts on it: h8, w8 >= 1, h8 w8 <=
+ *     max_pixels, r0, c0 >= 0, r0 + rows <= h8, c0 + cols <= w8, and the file's header must describe
+ *     an (h8, w8) latent; otherwise status[i] has bit 1 (the header bit), nothing of file i is decoded
+ *     or written, and the other files are not affected.  The other status bits mean, per file, what
+ *     they mean in nic_rans*_decode_window, and the same bounds hold: clamped file reads, lookups
+ *     inside the 4096 slots, stores only inside latent_win[i].
+ *     Validated before any HIP call: n in 0..65535, max_pixels, 1 <= rows, cols, rows cols <=
+ *     max_pixels (NIC_ESHAPE); empty batch (OK); NULL; alignment; stride; the prior (NIC_ENOPRIOR).
+ * nic_cut_boxes: boxes (n, bh, bw, 3) u8 = the bh x bw box at offsets[i] = {oy, ox} of image i of
+ *     images (n, Hs, Ws, 3) u8; offsets is int32[n][2] on the DEVICE; boxes and offsets 4-byte aligned;
+ *     one launch on `stream`, no host synchronisation.  1 <= bh <= Hs, 1 <= bw <= Ws, Hs Ws <= 2^29,
+ *     n bh bw 3 < 2^40 (NIC_ESHAPE).  Whoever fills the table checks 0 <= oy <= Hs - bh, 0 <= ox <=
+ *     Ws - bw on the host (Codec.cut_boxes does, before the upload); the kernel does not trust it: a
+ *     source byte outside its image reads as 0 and no byte outside images is touched. */
+int nic_region_plan_fixed(int H, int W, int y, int x, int bh, int bw, int* win4, int* off2);
+int nic_rans_decode_windows(nic_ctx* ctx, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, const int32_t* table,
+                            int max_pixels, int rows, int cols, uint8_t* latent_win, int32_t* status, void* stream);
+int nic_rans2_decode_windows(nic_ctx* ctx, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, const int32_t* table,
+                             int max_pixels, int rows, int cols, uint8_t* latent_win, int32_t* status, void* stream);
+int nic_rans3_decode_windows(nic_ctx* ctx, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, const int32_t* table,
+                             int max_pixels, int rows, int cols, uint8_t* latent_win, int32_t* status, void* stream);
+int nic_cut_boxes(nic_ctx* ctx, const uint8_t* images, int n, int Hs, int Ws, const int32_t* offsets, int bh, int bw, uint8_t* boxes,
+                  void* stream);
+
 /* ---- The device PNG writer: complete PNG files written on the device --------------------------
  * An optional writer for reconstructions (Pillow's optimize=True file, nic_png_encode, stays the
  * default and the bitstream's format).  Format: DESIGN.md, "The device PNG writer":

@@ -116,6 +116,15 @@ _SIGNATURES = {
     "nic_rans_decode_window": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp] + [ctypes.c_int] * 7 + [c_vp, c_vp, c_vp]),
     "nic_rans2_decode_window": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp] + [ctypes.c_int] * 7 + [c_vp, c_vp, c_vp]),
     "nic_rans3_decode_window": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp] + [ctypes.c_int] * 7 + [c_vp, c_vp, c_vp]),
+    # batched region decode: a window per file, one shape per call (nic_rans.hip)
+    "nic_region_plan_fixed": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_int)] * 2),
+    "nic_rans_decode_windows": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp, ctypes.c_int, c_vp] + [ctypes.c_int] * 3
+                                + [c_vp] * 3),
+    "nic_rans2_decode_windows": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp, ctypes.c_int, c_vp] + [ctypes.c_int] * 3
+                                 + [c_vp] * 3),
+    "nic_rans3_decode_windows": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp, ctypes.c_int, c_vp] + [ctypes.c_int] * 3
+                                 + [c_vp] * 3),
+    "nic_cut_boxes": (ctypes.c_int, [c_vp, c_vp] + [ctypes.c_int] * 3 + [c_vp] + [ctypes.c_int] * 2 + [c_vp, c_vp]),
     # device PNG writer (nic_png_dev.hip)
     "nic_png_device_block_bytes": (ctypes.c_int, []),
     "nic_png_device_bound": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int64)]),

@@ -302,6 +302,16 @@ def _fits(box, size) -> bool:
     return y >= 0 and x >= 0 and h >= 1 and w >= 1 and y + h <= size[0] and x + w <= size[1]
 
 
+def _files_and_names(files: Sequence):
+    """The bytes of files given as bytes or as paths to read, and what an error calls each: its path, or "file i"."""
+    datas, names = [], []
+    for i, f in enumerate(files):
+        is_path = isinstance(f, (str, os.PathLike))
+        datas.append(_read_bytes(os.fspath(f)) if is_path else bytes(f))
+        names.append(os.fspath(f) if is_path else f"file {i}")
+    return datas, names
+
+
 def _region_of_batch(decoder, files: Sequence[bytes], size, box):
     """decode_region's device part for files that decode as one batch and whose images hold the box."""
     codec = decoder.codec
@@ -323,11 +333,7 @@ def decode_region(decoder, files: Sequence, box):
     box = tuple(int(v) for v in box)
     if len(box) != 4:
         raise ValueError(f"decode_region: box must be (y, x, h, w), got {box!r}")
-    datas, names = [], []
-    for i, f in enumerate(files):
-        is_path = isinstance(f, (str, os.PathLike))
-        datas.append(_read_bytes(os.fspath(f)) if is_path else bytes(f))
-        names.append(os.fspath(f) if is_path else f"file {i}")
+    datas, names = _files_and_names(files)
     hw = []
     for i, data in enumerate(datas):
         try:
@@ -341,6 +347,100 @@ def decode_region(decoder, files: Sequence, box):
     if not datas:
         return torch.empty((0, max(box[2], 0), max(box[3], 0), 3), dtype=torch.uint8, device=f"cuda:{decoder.codec.device}")
     return _region_of_batch(decoder, datas, hw[0], box)
+
+
+def _window_groups(codec, files: Sequence[bytes], boxes, who: str, names: Sequence[str]):
+    """The host part of read_nic_windows and decode_regions: every check, then the plans.  Returns the
+    boxes' (h, w) and the groups as {(rows, cols): [(file index, (h8, w8, r0, c0), (off_y, off_x))]},
+    in the order the window shapes first appear."""
+    boxes = [tuple(int(v) for v in b) for b in boxes]
+    if len(boxes) != len(files):
+        raise ValueError(f"{who}: {len(boxes)} boxes for {len(files)} files: one box (y, x, h, w) per file")
+    for i, b in enumerate(boxes):
+        if len(b) != 4:
+            raise ValueError(f"{who}: {names[i]}: box must be (y, x, h, w), got {b!r}")
+        if b[2:] != boxes[0][2:]:
+            raise ValueError(f"{who}: {names[i]}: box size {b[2]} x {b[3]}, but the first box is {boxes[0][2]} x "
+                             f"{boxes[0][3]}: the boxes of one call must share one size")
+    groups, ver0 = {}, None
+    for i, data in enumerate(files):
+        try:
+            key, size = _inspect_any(codec, i, data, who)
+        except ValueError as e:
+            raise ValueError(f"{names[i]}: {e}") from None
+        if ver0 is None:
+            ver0 = key[0]
+        if key[0] != ver0:
+            raise ValueError(f"{who}: {names[i]}: version {key[0]}, but {names[0]} is version {ver0}: the files of one "
+                             "call must share the container version")
+        b = boxes[i]
+        if not _fits(b, size):
+            raise ValueError(f"{who}: {names[i]}: box (y {b[0]}, x {b[1]}, {b[2]} x {b[3]}) does not lie inside its "
+                             f"{size[0]} x {size[1]} image")
+        win, off = codec.region_plan_fixed(size[0], size[1], b)
+        groups.setdefault(win[2:], []).append((i, (key[1], key[2], win[0], win[1]), off))
+    return (boxes[0][2:] if boxes else (0, 0)), ver0, groups
+
+
+def _read_window_groups(codec, files: Sequence[bytes], ver: int, groups, who: str, names: Sequence[str]):
+    """One upload and one Codec.rans*_decode_windows per group: [(file indices, (n,rows,cols,96) latents, offsets)]."""
+    decode = {1: codec.rans_decode_windows, 2: codec.rans2_decode_windows, 3: codec.rans3_decode_windows}.get(ver)
+    out = []
+    for shape, members in groups.items():
+        idx = [m[0] for m in members]
+        buf, lens = _upload_files(codec, [files[i] for i in idx])
+        try:
+            z = decode(buf, lens, [m[1] for m in members], shape)
+        except ValueError as e:  # the device refused a file of the group: "image k" counts inside the group
+            m = re.search(r"image (\d+)", str(e))
+            which = names[idx[int(m.group(1))]] if m and int(m.group(1)) < len(idx) else f"files {idx}"
+            raise ValueError(f"{who}: {which}: {e}") from None
+        out.append((idx, z, [m[2] for m in members]))
+    return out
+
+
+def read_nic_windows(codec, files: Sequence[bytes], boxes):
+    """The latent windows that pixel boxes need, one box (y, x, h, w) per .nic file, all boxes of one
+    (h, w); the files may hold images of different sizes.  Codec.region_plan_fixed gives every file a
+    window whose shape depends on the box size alone -- unless the file's latent is smaller than that
+    in a dimension, which gives it another shape -- so the files are grouped by window shape and each
+    group is uploaded and entropy-decoded as one device batch (Codec.rans*_decode_windows: only the
+    segments that hold a pixel of a file's window).  Returns one entry per group, in the order the
+    shapes first appear: (the files' indices, their (n,rows,cols,96) u8 window latents on the codec's
+    device, their [(off_y, off_x)]: where each box starts in its window's reconstruction).
+    The host checks are read_nic's (ValueError naming the file's index); the files must share the
+    container version, every box must lie inside its file's recorded H x W (8 h8 x 8 w8 for a
+    version-1 file), and the boxes must share their size (ValueError naming the file).  Whole files
+    are uploaded."""
+    names = [f"file {i}" for i in range(len(files))]
+    _, ver, groups = _window_groups(codec, files, boxes, "read_nic_windows", names)
+    return _read_window_groups(codec, files, ver, groups, "read_nic_windows", names)
+
+
+def decode_regions(decoder, files: Sequence, boxes):
+    """One pixel box (y, x, h, w) per .nic file (bytes, or paths to read), all boxes of one (h, w), out
+    of files whose images may differ in size: an (N,h,w,3) u8 tensor on the decoder's device, in the
+    files' order, each the box cut out of that file's whole reconstruction.  read_nic_windows' checks
+    and groups (ValueError naming the file, by its path where it was given as one); per group the
+    window entropy decode, the decoder on the (n,rows,cols,96) windows and Codec.cut_boxes, all on the
+    device.  Files no smaller than the fixed window -- every file, for a directory of images larger
+    than the crop -- are one group, so one batch, whatever their sizes."""
+    import torch
+
+    datas, names = _files_and_names(files)
+    codec = decoder.codec
+    (h, w), ver, groups = _window_groups(codec, datas, boxes, "decode_regions", names)
+    out = None
+    for idx, z, offs in _read_window_groups(codec, datas, ver, groups, "decode_regions", names):
+        cut = codec.cut_boxes(codec.decode(z), offs, h, w)
+        if len(idx) == len(datas):  # one group: its order is the files'
+            return cut
+        if out is None:
+            out = torch.empty((len(datas), h, w, 3), dtype=torch.uint8, device=cut.device)
+        out[torch.tensor(idx, device=cut.device)] = cut
+    if out is None:
+        out = torch.empty((0, max(h, 0), max(w, 0), 3), dtype=torch.uint8, device=f"cuda:{codec.device}")
+    return out
 
 
 PNG_WRITERS = ("pillow", "device")

@@ -358,18 +358,21 @@ class Codec:
 
     def _rans_decode(self, ver: int, buf, sizes, h8: int, w8: int, window=None):
         z, status = self._rans_decode_status(ver, buf, sizes, h8, w8, window=window)
+        self._rans_raise(self._RANS[ver] + ("_decode" if window is None else "_decode_window"), ver, buf, status)
+        return z
+
+    def _rans_raise(self, name: str, ver: int, buf, status) -> None:
+        """Reads the statuses back (synchronises); ValueError naming the first image with one set."""
         st = status.cpu().numpy()
         bad = np.nonzero(st)[0]
         if bad.size:
             i = int(bad[0])
-            name = self._RANS[ver] + ("_decode" if window is None else "_decode_window")
             if ver != 1 and st[i] & 8:
                 pid = int.from_bytes(bytes(buf[i, 24:28].cpu().numpy().tolist()), "little")
                 mine = self.prior if ver == 2 else self.context_prior
                 raise ValueError(f"{name}: image {i} was written under prior {pid:08x}, the codec's prior is "
                                  f"{mine.id:08x} (status {int(st[i])}; refused images: {bad.tolist()})")
             raise ValueError(f"{name}: image {i} is corrupt (status {int(st[i])}; corrupt images: {bad.tolist()})")
-        return z
 
     def rans_encode(self, z, seg_pixels: int = 32):
         """(N,h,w,96) u8 latent -> (buf (N, stride) u8, sizes (N,) int64), device tensors: image
@@ -566,6 +569,128 @@ class Codec:
         (NicError(NIC_ENOPRIOR) without one)."""
         return self._rans_decode(3, buf, sizes, h8, w8, window)
 
+    # -- batched region decode: a window per file, one shape per call (nic_region_plan_fixed,
+    # nic_rans*_decode_windows, nic_cut_boxes) --
+    @staticmethod
+    def region_plan_fixed(H: int, W: int, box):
+        """region_plan with a window whose shape depends on the box's size alone, unless the latent is
+        smaller (nic_region_plan_fixed; host only): ((r0, c0, rows, cols), (off_y, off_x)) with rows =
+        min(h8, (h + 6) // 8 + 1 + 2 NIC_DECODE_HALO), likewise cols, so boxes of one size out of images
+        of any sizes give windows of one shape.  The window holds region_plan's; the cut is as exact."""
+        y, x, bh, bw = (int(v) for v in box)
+        win, off = (ctypes.c_int * 4)(), (ctypes.c_int * 2)()
+        _lib.check(_lib.lib().nic_region_plan_fixed(int(H), int(W), y, x, bh, bw, win, off), "nic_region_plan_fixed")
+        return tuple(win), tuple(off)
+
+    def _device_table(self, table, cols: int, name: str, what: str):
+        """An (N, cols) int32 table for the device: a contiguous tensor there, or host values uploaded.
+        Returns (device tensor, host array or None)."""
+        torch = _torch()
+        if isinstance(table, torch.Tensor) and table.device.type == "cuda":
+            if table.dtype != torch.int32 or table.ndim != 2 or table.shape[1] != cols or table.device.index != self.device:
+                raise TypeError(f"{name}: {what} must be an (N,{cols}) torch.int32 tensor on cuda:{self.device}")
+            return table.contiguous(), None
+        host = np.ascontiguousarray(np.asarray(table.cpu() if isinstance(table, torch.Tensor) else table, dtype=np.int64))
+        if host.size == 0:
+            host = host.reshape(0, cols)
+        if host.ndim != 2 or host.shape[1] != cols or (host.size and np.abs(host).max() >= 2 ** 31):
+            raise ValueError(f"{name}: {what} must be N rows of {cols} 32-bit integers")
+        return torch.from_numpy(host.astype(np.int32)).to(f"cuda:{self.device}"), host
+
+    def _rans_decode_windows_status(self, ver: int, buf, sizes, table, shape, max_pixels=None, out=None):
+        torch = _torch()
+        name = self._RANS[ver] + "_decode_windows"
+        if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.device.type != "cuda" or buf.ndim != 2:
+            raise TypeError(f"{name}: expected an (N, stride) cuda torch.uint8 tensor of files")
+        if not isinstance(sizes, torch.Tensor) or sizes.dtype != torch.int64 or sizes.shape != (buf.shape[0],):
+            raise TypeError(f"{name}: expected an (N,) torch.int64 tensor of sizes")
+        if buf.device.index != self.device or sizes.device != buf.device:
+            raise ValueError(f"{name}: tensors must be on cuda:{self.device}")
+        buf, sizes = buf.contiguous(), sizes.contiguous()
+        n, stride = buf.shape
+        rows, cols = (int(v) for v in shape)
+        tab, host = self._device_table(table, 4, name, "table")
+        if tab.shape[0] != n:
+            raise ValueError(f"{name}: {tab.shape[0]} table rows for {n} files")
+        if max_pixels is None:
+            if host is None:
+                raise ValueError(f"{name}: a table on the device needs max_pixels, the bound on h8 * w8 of its rows")
+            # the largest latent a row names; rows that name none, or too large a one, are the device's to refuse
+            pixels = [a * b for a, b in host[:, :2].tolist() if a > 0 and b > 0 and a * b <= 1 << 23]
+            max_pixels = min(max(pixels + [rows * cols, 1]), 1 << 23)
+        if out is None:
+            out = torch.empty((n, max(rows, 0), max(cols, 0), 96), dtype=torch.uint8, device=buf.device)
+        elif out.dtype != torch.uint8 or tuple(out.shape) != (n, rows, cols, 96) or out.device != buf.device or not out.is_contiguous():
+            raise TypeError(f"{name}: out must be a contiguous (N,rows,cols,96) torch.uint8 tensor on the codec's device")
+        status = torch.zeros((n,), dtype=torch.int32, device=buf.device)
+        _lib.check(getattr(self._L, "nic_" + name)(self._h, buf.data_ptr(), stride, sizes.data_ptr(), n, tab.data_ptr(),
+                                                   int(max_pixels), rows, cols, out.data_ptr(), status.data_ptr(),
+                                                   _stream_ptr(torch, self.device)), "nic_" + name)
+        return out, status
+
+    def _rans_decode_windows(self, ver: int, buf, sizes, table, shape, max_pixels=None):
+        z, status = self._rans_decode_windows_status(ver, buf, sizes, table, shape, max_pixels)
+        self._rans_raise(self._RANS[ver] + "_decode_windows", ver, buf, status)
+        return z
+
+    def rans_decode_windows_status(self, buf, sizes, table, shape, max_pixels=None, out=None):
+        """rans_decode_windows without the check: (window latents, status (N,) int32 device tensor).
+        out: the (N,rows,cols,96) u8 tensor to decode into (default: a new one)."""
+        return self._rans_decode_windows_status(1, buf, sizes, table, shape, max_pixels, out)
+
+    def rans_decode_windows(self, buf, sizes, table, shape, max_pixels=None):
+        """A window of shape = (rows, cols) out of each of the version-1 .nic files buf[i, :sizes[i]],
+        which may hold latents of different sizes: row i of table is file i's (h8, w8, r0, c0), and the
+        result (N,rows,cols,96) u8 holds [r0:r0+rows, c0:c0+cols] of file i's latent
+        (nic_rans_decode_windows).  table: N rows of host integers, uploaded here, or an (N,4) int32
+        tensor on the device, which then needs max_pixels, a bound on h8 * w8 of every row (it sizes
+        the workspace; from host rows it is computed).  A row that does not match its file's header,
+        exceeds the bound, or whose window does not fit its latent is refused on the device with the
+        header bit (status 2).  Reads the statuses back (synchronises) and raises ValueError naming the
+        first image that was refused or did not decode cleanly."""
+        return self._rans_decode_windows(1, buf, sizes, table, shape, max_pixels)
+
+    def rans2_decode_windows_status(self, buf, sizes, table, shape, max_pixels=None, out=None):
+        """rans2_decode_windows without the check (as rans_decode_windows_status)."""
+        return self._rans_decode_windows_status(2, buf, sizes, table, shape, max_pixels, out)
+
+    def rans2_decode_windows(self, buf, sizes, table, shape, max_pixels=None):
+        """rans_decode_windows for version-2 files, under the codec's prior."""
+        return self._rans_decode_windows(2, buf, sizes, table, shape, max_pixels)
+
+    def rans3_decode_windows_status(self, buf, sizes, table, shape, max_pixels=None, out=None):
+        """rans3_decode_windows without the check (as rans_decode_windows_status)."""
+        return self._rans_decode_windows_status(3, buf, sizes, table, shape, max_pixels, out)
+
+    def rans3_decode_windows(self, buf, sizes, table, shape, max_pixels=None):
+        """rans_decode_windows for version-3 files, under the codec's context prior."""
+        return self._rans_decode_windows(3, buf, sizes, table, shape, max_pixels)
+
+    def cut_boxes(self, x, offsets, h: int, w: int, out=None):
+        """The h x w box at offsets[i] = (oy, ox) of image i of x (N,Hs,Ws,3) u8 -> (N,h,w,3) u8, one
+        launch on the current stream (nic_cut_boxes).  offsets: N pairs of host integers, checked here
+        against the images (ValueError naming the row) and uploaded, or an (N,2) int32 tensor on the
+        device, which is not read back: there a source pixel outside its image reads as 0."""
+        torch = _torch()
+        x = self._check_dev(x, 4, 3, "cut_boxes")
+        n, Hs, Ws, _ = x.shape
+        h, w = int(h), int(w)
+        off, host = self._device_table(offsets, 2, "cut_boxes", "offsets")
+        if off.shape[0] != n:
+            raise ValueError(f"cut_boxes: {off.shape[0]} offsets for {n} images")
+        if host is not None:
+            for i, (oy, ox) in enumerate(host.tolist()):
+                if oy < 0 or ox < 0 or oy + h > Hs or ox + w > Ws:
+                    raise ValueError(f"cut_boxes: image {i}: a {h} x {w} box at ({oy}, {ox}) does not lie inside the "
+                                     f"{Hs} x {Ws} images")
+        if out is None:
+            out = torch.empty((n, max(h, 0), max(w, 0), 3), dtype=torch.uint8, device=x.device)
+        elif out.dtype != torch.uint8 or tuple(out.shape) != (n, h, w, 3) or out.device != x.device or not out.is_contiguous():
+            raise TypeError("cut_boxes: out must be a contiguous (N,h,w,3) torch.uint8 tensor on the codec's device")
+        _lib.check(self._L.nic_cut_boxes(self._h, x.data_ptr(), n, Hs, Ws, off.data_ptr(), h, w, out.data_ptr(),
+                                         _stream_ptr(torch, self.device)), "nic_cut_boxes")
+        return out
+
     # -- device PNG writer (nic_png_device_*) -------------------------------------------------
     def png_reserve(self, n: int, h: int, w: int, channels: int = 3) -> None:
         """Grow the workspace so png_encode of n (h, w, channels) images allocates nothing."""
@@ -708,6 +833,16 @@ class Decoder(ProClass):
         from .bitstream import decode_region
 
         return decode_region(self, files, box)
+
+    def decode_regions(self, files, boxes):
+        """One pixel box (y, x, h, w) per .nic file, all of one (h, w), out of files whose images may
+        differ in size: an (N,h,w,3) u8 tensor on this device, in the files' order, each equal to the
+        box cut out of that file's whole reconstruction.  The windows of one call have one shape, so
+        files of different frames are entropy-decoded and run through the decoder as one batch
+        (bitstream.decode_regions)."""
+        from .bitstream import decode_regions
+
+        return decode_regions(self, files, boxes)
 
     def uncompress(self, dataset_path: str, checkpoint_path: str, batch_size: int = 64, workers=None,
                    container: str = "png", png_writer: str = "pillow", prior=None, region=None) -> None:

@@ -464,7 +464,7 @@ bool models_ready(const nic_ctx* c, int m0) {
 
 extern "C" {
 
-int nic_version(void) { return 700; }
+int nic_version(void) { return 800; }
 
 int nic_constants(float* ycbcr9, float* ycbcr_inv9, float* off3) {
   // host copy of what nic_create uploads; lets tests compare with np.linalg.inv (utils.py:8)
@@ -1382,8 +1382,8 @@ int nic_unpack_latent(const uint8_t* packed, int n, int h8, int w8, uint8_t* lat
 }
 
 // ---- .nic container, versions 1 to 3, and region decode (nic_rans.hip; the nic_rans*_bound,
-// nic_rans*_inspect, nic_rans_cost_table, nic_rans_*prior_check, nic_region_plan and
-// nic_rans_window_segments are host-only there) ----
+// nic_rans*_inspect, nic_rans_cost_table, nic_rans_*prior_check, nic_region_plan, nic_region_plan_fixed
+// and nic_rans_window_segments are host-only there) ----
 // Each entry point is one call of a body shared by the versions; fn is the entry point's name in
 // the error texts, ver the container version.
 static int rans_check(const char* fn, int n, int h8, int w8, int seg_pixels) {
@@ -1469,8 +1469,37 @@ static int rans_decode(const char* fn, int ver, nic_ctx* c, const uint8_t* files
   RansPlan pl;
   rans_plan(n, h8, w8, 1, true, &pl, ver);
   if ((rc = ensure_ws(c, pl.bytes))) return rc;
-  HIP_TRY(launch_rans_decode(ver, files, stride, (const long long*)sizes, n, h8, w8, window ? &win : nullptr, ctx_prior(c, ver),
-                             c->ws, pl, latent, status, (hipStream_t)stream));
+  HIP_TRY(launch_rans_decode(ver, files, stride, (const long long*)sizes, n, h8, w8, window ? &win : nullptr, nullptr,
+                             ctx_prior(c, ver), c->ws, pl, latent, status, (hipStream_t)stream));
+  return NIC_OK;
+}
+
+// Per-file windows: table (h8, w8, r0, c0) per file on the device, one rows x cols for the call, and
+// max_pixels, the caller's bound on h8 w8 of any file, which sizes the workspace (the table is not read
+// on the host; a row above the bound is refused on the device).  The checks in order as rans_decode's.
+static int rans_decode_windows(const char* fn, int ver, nic_ctx* c, const uint8_t* files, int64_t stride, const int64_t* sizes,
+                               int n, const int32_t* table, int max_pixels, int rows, int cols, uint8_t* latent, int32_t* status,
+                               void* stream) {
+  if (n < 0 || n > 65535) return fail(NIC_ESHAPE, "%s: batch %d not in 0..65535", fn, n);
+  if (max_pixels < 1 || max_pixels > (1 << 23)) return fail(NIC_ESHAPE, "%s: max_pixels %d not in 1..2^23", fn, max_pixels);
+  if (rows < 1 || cols < 1 || (long long)rows * cols > max_pixels)
+    return fail(NIC_ESHAPE, "%s: a %d x %d window does not lie inside a latent of at most %d pixels", fn, rows, cols, max_pixels);
+  if (n == 0) return NIC_OK;
+  if (!c) return fail(NIC_EINVAL, "%s: NULL ctx", fn);
+  if (!files || !sizes || !table || !latent || !status) return fail(NIC_EINVAL, "%s: NULL buffer", fn);
+  if ((uintptr_t)latent % 16 || (uintptr_t)table % 4)
+    return fail(NIC_EINVAL, "%s: latent_win must be 16-byte and table 4-byte aligned", fn);
+  const int header = ver == 1 ? 16 : 40;
+  if (stride < header) return fail(NIC_ESHAPE, "%s: stride %lld is below the %d-byte header", fn, (long long)stride, header);
+  int rc = rans_need_prior(fn, ver, c);
+  if (rc) return rc;
+  DeviceGuard guard(c->device);
+  RansPlan pl;
+  rans_plan(n, 1, max_pixels, 1, true, &pl, ver);  // the decode plan depends on the latent's pixel count only
+  if ((rc = ensure_ws(c, pl.bytes))) return rc;
+  const RansWindow win{0, 0, 0, rows, cols};
+  HIP_TRY(launch_rans_decode(ver, files, stride, (const long long*)sizes, n, 0, 0, &win, table, ctx_prior(c, ver), c->ws, pl, latent,
+                             status, (hipStream_t)stream));
   return NIC_OK;
 }
 
@@ -1573,6 +1602,40 @@ int nic_rans3_decode_window(nic_ctx* c, const uint8_t* files, int64_t stride, co
                             int r0, int c0, int rows, int cols, uint8_t* latent_win, int32_t* status, void* stream) {
   const int window[4] = {r0, c0, rows, cols};
   return rans_decode("nic_rans3_decode_window", 3, c, files, stride, sizes, n, h8, w8, window, latent_win, status, stream);
+}
+
+int nic_rans_decode_windows(nic_ctx* c, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, const int32_t* table,
+                            int max_pixels, int rows, int cols, uint8_t* latent_win, int32_t* status, void* stream) {
+  return rans_decode_windows("nic_rans_decode_windows", 1, c, files, stride, sizes, n, table, max_pixels, rows, cols, latent_win,
+                             status, stream);
+}
+int nic_rans2_decode_windows(nic_ctx* c, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, const int32_t* table,
+                             int max_pixels, int rows, int cols, uint8_t* latent_win, int32_t* status, void* stream) {
+  return rans_decode_windows("nic_rans2_decode_windows", 2, c, files, stride, sizes, n, table, max_pixels, rows, cols, latent_win,
+                             status, stream);
+}
+int nic_rans3_decode_windows(nic_ctx* c, const uint8_t* files, int64_t stride, const int64_t* sizes, int n, const int32_t* table,
+                             int max_pixels, int rows, int cols, uint8_t* latent_win, int32_t* status, void* stream) {
+  return rans_decode_windows("nic_rans3_decode_windows", 3, c, files, stride, sizes, n, table, max_pixels, rows, cols, latent_win,
+                             status, stream);
+}
+
+int nic_cut_boxes(nic_ctx* c, const uint8_t* images, int n, int Hs, int Ws, const int32_t* offsets, int bh, int bw, uint8_t* boxes,
+                  void* stream) {
+  if (n < 0 || Hs < 1 || Ws < 1 || (long long)Hs * Ws > (1ll << 29))
+    return fail(NIC_ESHAPE, "nic_cut_boxes: bad image shape (%d,%d,%d,3)", n, Hs, Ws);
+  if (bh < 1 || bw < 1 || bh > Hs || bw > Ws)
+    return fail(NIC_ESHAPE, "nic_cut_boxes: a %d x %d box does not lie inside a %d x %d image", bh, bw, Hs, Ws);
+  if ((long long)n * bh * bw * 3 >= (1ll << 40))
+    return fail(NIC_ESHAPE, "nic_cut_boxes: %d boxes of %d x %d exceed 2^40 bytes", n, bh, bw);
+  if (n == 0) return NIC_OK;
+  if (!c) return fail(NIC_EINVAL, "nic_cut_boxes: NULL ctx");
+  if (!images || !offsets || !boxes) return fail(NIC_EINVAL, "nic_cut_boxes: NULL buffer");
+  if ((uintptr_t)boxes % 4 || (uintptr_t)offsets % 4)
+    return fail(NIC_EINVAL, "nic_cut_boxes: boxes and offsets must be 4-byte aligned");
+  DeviceGuard guard(c->device);
+  HIP_TRY(launch_cut_boxes(images, n, Hs, Ws, offsets, bh, bw, boxes, (hipStream_t)stream));
+  return NIC_OK;
 }
 
 int nic_rans_prior_set(nic_ctx* c, const uint16_t* freqs, uint32_t* id) {

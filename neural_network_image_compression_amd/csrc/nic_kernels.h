@@ -206,12 +206,20 @@ void rans_plan(int n, int h8, int w8, int seg_pixels, bool decode, RansPlan* pla
 // Files of version ver from latents / latents from files; prior: the version's (RansPrior{} for
 // version 1, which also ignores H and W).  win NULL: the whole latents into z (n, h8, w8, 96); else
 // only the window's pixels, into z (n, rows, cols, 96).  plan: rans_plan's for (n, h8, w8) and ver.
+// wintab (decode, with win; else NULL): int32[n][4] = (h8, w8, r0, c0) on the device, each file's own
+// latent size and the place of its win->rows x win->cols window; h8, w8 and win's other fields are then
+// not used, and plan is rans_plan's for n latents of as many pixels as the largest file may have
+// (a row above that, or whose window does not fit, is refused on the device with status 2).
 hipError_t launch_rans_encode(int ver, const uint8_t* z, int n, int h8, int w8, int H, int W, int seg_pixels,
                               const RansPrior& prior, char* ws, const RansPlan& plan, uint8_t* out, long long stride,
                               long long* sizes, hipStream_t st);
 hipError_t launch_rans_decode(int ver, const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8,
-                              const RansWindow* win, const RansPrior& prior, char* ws, const RansPlan& plan, uint8_t* z,
-                              int* status, hipStream_t st);
+                              const RansWindow* win, const int* wintab, const RansPrior& prior, char* ws, const RansPlan& plan,
+                              uint8_t* z, int* status, hipStream_t st);
+// dst (n, bh, bw, 3) = the box at off[i] = (oy, ox) (int32[n][2] on the device) of image i of src
+// (n, Hs, Ws, 3); dst 4-byte aligned, n bh bw 3 < 2^40.  A source byte outside its image reads as 0.
+hipError_t launch_cut_boxes(const uint8_t* src, int n, int Hs, int Ws, const int* off, int bh, int bw, uint8_t* dst,
+                            hipStream_t st);
 
 // --- device PNG writer (nic_png_dev.hip) ------------------------------------------------------
 // Byte offsets of one call's scratch inside the ctx workspace (256-B aligned), from png_dev_plan:

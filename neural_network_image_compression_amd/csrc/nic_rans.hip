@@ -18,6 +18,9 @@
 // left neighbour) run the same kernels: every kernel that differs between versions is one template,
 // over the version (rans_parse, rans_layout, rans_assemble) or over the rows of an image (Rows<>:
 // rans_tables, rans_encode_segments, rans_decode_segments), instantiated per case.
+// Region decode runs the same parse and segment kernel over a latent window: one window for every
+// file of the call, or (batched region decode) a window of one shape at each file's own place in its
+// own frame, from a per-file table on the device; cut_boxes then cuts each image's pixel box.
 
 #include <hip/hip_runtime.h>
 
@@ -480,9 +483,14 @@ __global__ __launch_bounds__(256) void rans_assemble(const uint8_t* __restrict__
 // start[256] = 4096).  Version 1 stores every channel's table; versions 2 and 3 those of the masked
 // channels only, and the other channels' rows are copies of the prior's.  A table is walked once and
 // stored into each of the channel's rows (three in version 3).
+// wintab (per-file windows, else NULL): row img = (h8, w8, r0, c0) replaces the call's (h8, w8), and
+// a row that is no latent of at most maxseg pixels, or whose win_rows x win_cols window at (r0, c0) does not
+// lie inside it, is refused like a header of another geometry (status 2, nseg = 0), so what the
+// segment kernel reads of a row it acts on has been checked here.
 template <int kVer>
 __global__ __launch_bounds__(256) void rans_parse(const uint8_t* __restrict__ files, long long stride,
                                                    const long long* __restrict__ sizes, int h8, int w8,
+                                                   const int* __restrict__ wintab, int win_rows, int win_cols,
                                                    const uint16_t* __restrict__ prior_cum, uint32_t prior_id,
                                                    uint16_t* __restrict__ cum, uint32_t* __restrict__ seglen,
                                                    uint32_t* __restrict__ segoff, int maxseg, uint32_t* __restrict__ meta,
@@ -506,10 +514,18 @@ __global__ __launch_bounds__(256) void rans_parse(const uint8_t* __restrict__ fi
     if constexpr (kPrior) return own[c] != 0u;
     return true;
   };
-  const int npix = h8 * w8;
+  bool fits = true;
+  if (wintab) {
+    const int* t = wintab + 4 * (size_t)img;
+    h8 = t[0];
+    w8 = t[1];
+    fits = h8 > 0 && w8 > 0 && (long long)h8 * w8 <= (long long)maxseg && t[2] >= 0 && t[3] >= 0 &&
+           (long long)t[2] + win_rows <= h8 && (long long)t[3] + win_cols <= w8;
+  }
+  const int npix = fits ? h8 * w8 : 0;
   if (tid == 0) {
     const uint32_t S = rd(6) | (rd(7) << 8), fh = rd32(8), fw = rd32(12);
-    bool ok = size >= kHdr && rd(0) == 'N' && rd(1) == 'I' && rd(2) == 'C' && rd(3) == 'R' && rd(4) == (uint32_t)kVer &&
+    bool ok = fits && size >= kHdr && rd(0) == 'N' && rd(1) == 'I' && rd(2) == 'C' && rd(3) == 'R' && rd(4) == (uint32_t)kVer &&
               rd(5) == (uint32_t)kProbBits && S >= 1 && fh == (uint32_t)h8 && fw == (uint32_t)w8;
     bool mine = true;
     if constexpr (kPrior) {
@@ -668,6 +684,10 @@ __global__ __launch_bounds__(256) void rans3_hist(const uint8_t* __restrict__ z,
 // stores only the pixels inside the window, at their place in the compact (n, rows, cols, 96) output.
 // (RansWindow: nic_kernels.h)
 
+// Which pixels rans_decode_segments keeps: the whole frame, the call's one window of every file, or a
+// window of the call's one shape at each file's own place in its own frame (the table of rans_parse).
+enum : int { kFrame = 0, kOneWindow = 1, kFileWindows = 2 };
+
 // the segment of `slot` under segments of S pixels, or -1 for a slot that is not live
 __device__ __forceinline__ int window_segment(const RansWindow& w, int S, int slot) {
   const int J = (w.cols + S - 2) / S + 1;
@@ -759,24 +779,28 @@ __device__ __forceinline__ bool window_block_dead(const RansWindow& w, int S, in
 // ---- decode 2: segments, one lane per segment -----------------------------------------------
 // block 64, one wave.  A lane reads only file bytes of its segment [begin, end) (a read past end
 // gives 0), looks symbols up in rows that resolve every slot, and writes only its own latent bytes.
-// Full frame (kWindow false): grid (ceil(maxseg / 64), n) covers seg_pixels = 1; lane = segment, blocks
+// Full frame (kWindow = kFrame): grid (ceil(maxseg / 64), n) covers seg_pixels = 1; lane = segment, blocks
 // past the file's own nseg exit; pixel p of the lane goes to z (n, h8, w8, 96) at p0 + p.
-// Window (kWindow true): grid (ceil(rows cols / 64), n) covers seg_pixels = 1 (J = cols); lane = slot,
+// Window (kOneWindow, kFileWindows): grid (ceil(rows cols / 64), n) covers seg_pixels = 1 (J = cols); lane = slot,
 // and a block without a live lane (every block of a refused image: nseg = 0) exits; the lane stores
 // only the pixels of its segment that window_pixel places inside image img's (rows, cols, 96) of z.
+// kFileWindows: win holds the call's rows and cols, and its w8, r0 and c0 -- and npix -- are image
+// img's own, from row img = (h8, w8, r0, c0) of wintab (block-uniform; read behind the nseg exit, so
+// only from a row the parse accepted: the window lies inside an h8 x w8 latent of that file).
 // Either way the rows are staged only behind those exits.
 // kContext: the row is chosen per symbol from the pixel decoded before (the context never leaves a
 // segment, and a lane decodes its segment from the first pixel).  That pixel's 96 symbols stay in 24
 // registers: chunk q of the left pixel is prev[0..3] in every iteration, and the array is rotated by
 // one chunk after it, so every index is static and the q loop stays rolled.  anchor is not read
-// without contexts, win not without a window.
-template <bool kContext, bool kWindow>
+// without contexts, win not without a window, wintab only with per-file windows.
+template <bool kContext, int kWindow>
 __global__ __launch_bounds__(64) void rans_decode_segments(const uint8_t* __restrict__ files, long long stride, int npix,
                                                             const uint16_t* __restrict__ cum,
                                                             const uint8_t* __restrict__ anchor,
                                                             const uint32_t* __restrict__ segoff, int maxseg,
                                                             const uint32_t* __restrict__ meta, RansWindow win,
-                                                            uint8_t* __restrict__ z, int* __restrict__ status) {
+                                                            const int* __restrict__ wintab, uint8_t* __restrict__ z,
+                                                            int* __restrict__ status) {
   using R = Rows<kContext>;
   __shared__ uint16_t start[R::kWords];
   const int lane = threadIdx.x, img = blockIdx.y;
@@ -785,6 +809,13 @@ __global__ __launch_bounds__(64) void rans_decode_segments(const uint8_t* __rest
   int seg = (int)blockIdx.x * 64 + lane;
   if constexpr (kWindow) {
     if (nseg == 0) return;  // block-uniform
+    if constexpr (kWindow == kFileWindows) {
+      const int* t = wintab + 4 * (size_t)img;
+      npix = t[0] * t[1];
+      win.w8 = t[1];
+      win.r0 = t[2];
+      win.c0 = t[3];
+    }
     if (window_block_dead(win, seg_pixels, (int)blockIdx.x * 64)) return;
     seg = window_segment(win, seg_pixels, seg);
     if (__ballot(seg >= 0) == 0) return;  // block-uniform: the block is this wave
@@ -918,22 +949,66 @@ hipError_t rans_encode(const uint8_t* z, int n, int h8, int w8, int H, int W, in
   return hipGetLastError();
 }
 
-// the parse, then every segment (win NULL) or the window's slots
+// the parse, then every segment (win NULL), the window's slots, or (wintab) the slots of each file's
+// own window of win's rows x cols: then h8, w8 and win's other fields are not used, and pl.nseg is the
+// call's bound on a file's latent pixels
 template <int kVer>
 hipError_t rans_decode(const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8, const RansWindow* win,
-                       const RansPrior& pr, char* ws, const RansPlan& pl, uint8_t* z, int* status, hipStream_t st) {
+                       const int* wintab, const RansPrior& pr, char* ws, const RansPlan& pl, uint8_t* z, int* status,
+                       hipStream_t st) {
   constexpr bool kContext = kVer == 3;
   const int npix = h8 * w8, maxseg = pl.nseg;
   const RansBuffers b = rans_buffers(ws, pl);
-  rans_parse<kVer><<<dim3(n), 256, 0, st>>>(files, stride, sizes, h8, w8, pr.cum, pr.id, b.cum, b.seglen, b.segoff, maxseg, b.meta,
-                                            status);
-  if (win)
-    rans_decode_segments<kContext, true><<<dim3((win->rows * win->cols + 63) / 64, n), 64, 0, st>>>(
-        files, stride, npix, b.cum, pr.anchor, b.segoff, maxseg, b.meta, *win, z, status);
+  rans_parse<kVer><<<dim3(n), 256, 0, st>>>(files, stride, sizes, h8, w8, wintab, win ? win->rows : 0, win ? win->cols : 0, pr.cum,
+                                            pr.id, b.cum, b.seglen, b.segoff, maxseg, b.meta, status);
+  if (wintab)
+    rans_decode_segments<kContext, kFileWindows><<<dim3((win->rows * win->cols + 63) / 64, n), 64, 0, st>>>(
+        files, stride, 0, b.cum, pr.anchor, b.segoff, maxseg, b.meta, *win, wintab, z, status);
+  else if (win)
+    rans_decode_segments<kContext, kOneWindow><<<dim3((win->rows * win->cols + 63) / 64, n), 64, 0, st>>>(
+        files, stride, npix, b.cum, pr.anchor, b.segoff, maxseg, b.meta, *win, nullptr, z, status);
   else
-    rans_decode_segments<kContext, false><<<dim3((maxseg + 63) / 64, n), 64, 0, st>>>(files, stride, npix, b.cum, pr.anchor, b.segoff,
-                                                                                      maxseg, b.meta, RansWindow{}, z, status);
+    rans_decode_segments<kContext, kFrame><<<dim3((maxseg + 63) / 64, n), 64, 0, st>>>(
+        files, stride, npix, b.cum, pr.anchor, b.segoff, maxseg, b.meta, RansWindow{}, nullptr, z, status);
   return hipGetLastError();
+}
+
+// ---- region decode's cut: dst (n, bh, bw, 3) = the bh x bw box at (off[img][0], off[img][1]) of
+// image img of src (n, Hs, Ws, 3).  grid (ceil(n bh bw 3 / 1024)), block 256: a thread makes four
+// consecutive bytes of dst (4-byte aligned) and stores them as one dword, so a wave writes 256
+// contiguous bytes and reads runs of a source row.  A source byte outside its image -- a table row
+// the caller did not check -- reads as 0 and nothing outside src is touched.
+__global__ __launch_bounds__(256) void cut_boxes(const uint8_t* __restrict__ src, int Hs, int Ws, const int* __restrict__ off,
+                                                  int bh, int bw, uint8_t* __restrict__ dst, size_t total) {
+  const size_t at = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (at >= total) return;
+  const uint32_t row_bytes = 3u * (uint32_t)bw;  // bw <= Ws: 3 Ws fits an int (checked on the host)
+  const size_t img_bytes = (size_t)row_bytes * (uint32_t)bh;
+  size_t img = at / img_bytes;
+  const size_t rem = at - img * img_bytes;
+  uint32_t y = (uint32_t)(rem / row_bytes), b = (uint32_t)(rem - (size_t)y * row_bytes);
+  uint32_t word = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (at + k < total) {
+      const long long sy = (long long)off[2 * img] + y, sb = 3ll * off[2 * img + 1] + b;
+      uint32_t v = 0;
+      if (sy >= 0 && sy < Hs && sb >= 0 && sb < 3ll * Ws) v = src[((size_t)img * Hs + (size_t)sy) * (3 * (size_t)Ws) + (size_t)sb];
+      word |= v << (8 * k);
+      if (++b == row_bytes) {
+        b = 0;
+        if (++y == (uint32_t)bh) {
+          y = 0;
+          ++img;
+        }
+      }
+    }
+  }
+  if (at + 4 <= total) {
+    *(uint32_t*)(dst + at) = word;
+  } else {
+    for (size_t k = 0; at + k < total; ++k) dst[at + k] = (uint8_t)(word >> (8 * k));
+  }
 }
 
 // The device allocation of a prior: freqs | cumulative rows at the segment kernels' pitch | the 96
@@ -958,14 +1033,20 @@ hipError_t launch_rans_encode(int ver, const uint8_t* z, int n, int h8, int w8, 
 }
 
 hipError_t launch_rans_decode(int ver, const uint8_t* files, long long stride, const long long* sizes, int n, int h8, int w8,
-                              const RansWindow* win, const RansPrior& pr, char* ws, const RansPlan& pl, uint8_t* z, int* status,
-                              hipStream_t st) {
+                              const RansWindow* win, const int* wintab, const RansPrior& pr, char* ws, const RansPlan& pl,
+                              uint8_t* z, int* status, hipStream_t st) {
   switch (ver) {
-    case 1: return rans_decode<1>(files, stride, sizes, n, h8, w8, win, pr, ws, pl, z, status, st);
-    case 2: return rans_decode<2>(files, stride, sizes, n, h8, w8, win, pr, ws, pl, z, status, st);
-    case 3: return rans_decode<3>(files, stride, sizes, n, h8, w8, win, pr, ws, pl, z, status, st);
+    case 1: return rans_decode<1>(files, stride, sizes, n, h8, w8, win, wintab, pr, ws, pl, z, status, st);
+    case 2: return rans_decode<2>(files, stride, sizes, n, h8, w8, win, wintab, pr, ws, pl, z, status, st);
+    case 3: return rans_decode<3>(files, stride, sizes, n, h8, w8, win, wintab, pr, ws, pl, z, status, st);
   }
   return hipErrorInvalidValue;
+}
+
+hipError_t launch_cut_boxes(const uint8_t* src, int n, int Hs, int Ws, const int* off, int bh, int bw, uint8_t* dst, hipStream_t st) {
+  const size_t total = (size_t)n * bh * bw * 3;
+  cut_boxes<<<dim3((unsigned)((total + 1023) / 1024)), 256, 0, st>>>(src, Hs, Ws, off, bh, bw, dst, total);
+  return hipGetLastError();
 }
 
 hipError_t launch_rans_prior_count(const uint8_t* z, int n, int h8, int w8, int seg_pixels, const uint8_t* anchor,
@@ -1183,6 +1264,29 @@ int nic_region_plan(int H, int W, int y, int x, int bh, int bw, int* win4, int* 
     const int b = last + NIC_DECODE_HALO < n8 ? last + NIC_DECODE_HALO : n8;
     *lo = a;
     *count = b - a;
+  };
+  axis(y, bh, h8, &win4[0], &win4[2]);
+  axis(x, bw, w8, &win4[1], &win4[3]);
+  off2[0] = y - 8 * win4[0];
+  off2[1] = x - 8 * win4[1];
+  return NIC_OK;
+}
+
+int nic_region_plan_fixed(int H, int W, int y, int x, int bh, int bw, int* win4, int* off2) {
+  if (!win4 || !off2) return nic::set_error(NIC_EINVAL, "nic_region_plan_fixed: win4 or off2 is NULL");
+  if (H < 1 || W < 1 || y < 0 || x < 0 || bh < 1 || bw < 1 || (long long)y + bh > H || (long long)x + bw > W) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "nic_region_plan_fixed: box (y %d, x %d, %d x %d) does not lie inside a %d x %d image", y, x, bh, bw,
+             H, W);
+    return nic::set_error(NIC_ESHAPE, msg);
+  }
+  const int h8 = (H >> 3) + ((H & 7) != 0), w8 = (W >> 3) + ((W & 7) != 0);
+  auto axis = [](int at, int len, int n8, int* lo, int* count) {
+    const int touched = (len + 6) / 8 + 1;  // the most latent pixels that len image pixels touch (len <= H: no overflow)
+    const int fixed = touched + 2 * NIC_DECODE_HALO;
+    *count = fixed < n8 ? fixed : n8;
+    const int want = at / 8 - NIC_DECODE_HALO, last = n8 - *count;
+    *lo = want < 0 ? 0 : (want > last ? last : want);
   };
   axis(y, bh, h8, &win4[0], &win4[2]);
   axis(x, bw, w8, &win4[1], &win4[3]);
