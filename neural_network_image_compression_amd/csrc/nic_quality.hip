@@ -2,17 +2,31 @@
 // tf2_0/tests/calc_ssim.py:13 with max_val=255) and per-image squared error (PSNR).
 //
 // MS-SSIM per scale k (5 scales): one block per (32x32 output tile, plane) stages the
-// 42x42 input window of both images in LDS (shifted by -0.5: covariances are
-// shift-invariant and the smaller magnitudes keep more fp32 bits), runs the separable
-// 11-tap Gaussian (sigma 1.5) horizontally into 4 LDS maps (x, y, x^2+y^2, x*y) and
-// vertically per output pixel, forms luminance * cs and cs and writes the tile's two sums
-// (fp64) -- no atomics, so the result is deterministic.  Between scales a 2x2 average
+// 42x42 input window of both images in LDS, each image minus a shift of its own (below),
+// runs the separable 11-tap Gaussian (sigma 1.5) horizontally into 4 LDS maps (x, y,
+// x^2+y^2, x*y) and vertically per output pixel, forms luminance * cs and cs and writes
+// the tile's two sums (fp64) -- no atomics, so the result is deterministic.
+//
+// The shift: cs = (2 cov + c2) / (var_x + var_y + c2) is formed from E[xy] - E[x]E[y] and
+// E[x^2 + y^2] - (E[x]^2 + E[y]^2) in fp32.  Both are invariant under a constant subtracted
+// from x and another from y, but their rounding error is not: it is about an fp32 ulp of
+// E[x^2 + y^2], i.e. 6e-8 d^2 for pixels at distance d from the shift, against c2 = 9e-4.  A
+// fixed 0.5 leaves d = 0.5 on near-black and near-white content (a relative error of order
+// 1e-4 in every flat pixel's cs, which does not average out: 3e-5 in MS-SSIM of 255 vs 254).
+// So each block subtracts, per image, the mean of its window's in-image pixels -- the
+// constant that minimises the window's sum of d^2 -- and adds it back for the luminance term.
+// What stays: a window that holds two flat regions far apart (half black, half white)
+// keeps d up to 0.5 on both, as before.  tests/ssim_f32_model.py restates this arithmetic.
+//
+// Between scales a 2x2 average
 // pool (odd sizes padded SYMMETRIC, i.e. the last row/column repeated) writes planar fp32
 // images for the next scale.  A final block per image reduces the tile sums to means,
 // relu's them and forms the weighted geometric mean over scales, averaged over channels.
 // HBM-bound and tiny next to the codec: scale 0 reads 2 x 3 B per pixel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "nic_kernels.h"
 
@@ -42,6 +56,7 @@ __global__ __launch_bounds__(256) void ssim_tile_kernel(SsimScaleArgs a) {
   __shared__ float sy[kSsimIn][kSsimIn + 1];
   __shared__ float hm[4][kSsimIn][kSsimTile];
   __shared__ float red[2][4];
+  __shared__ float shf[2][4];
   const int tid = threadIdx.x;
   const int p = blockIdx.y;
   const int tx = blockIdx.x % a.tiles_x, ty = blockIdx.x / a.tiles_x;
@@ -51,36 +66,64 @@ __global__ __launch_bounds__(256) void ssim_tile_kernel(SsimScaleArgs a) {
   // window load: every element's global load issued before any is used (one latency
   // round per block instead of one per 256 elements)
   constexpr int kLoads = (kSsimIn * kSsimIn + 255) / 256;
+  // Every load is unconditional, at an address clamped into the plane, so that none sits
+  // behind a branch with its own wait; what was read outside the window or image is dropped.
   float lx[kLoads], ly[kLoads];
+  typename std::conditional<U8, uint8_t, float>::type rx[kLoads], ry[kLoads];
 #pragma unroll
   for (int k = 0; k < kLoads; ++k) {
     const int i = tid + 256 * k;
-    const int r = i / kSsimIn, c = i % kSsimIn;
-    const int y = y0 + r, x = x0 + c;
-    lx[k] = 0.f;
-    ly[k] = 0.f;
-    if (i < kSsimIn * kSsimIn && y < a.H && x < a.W) {
-      if constexpr (U8) {
-        const int img = p / 3, ch = p % 3;
-        const size_t o = ((size_t)(img * a.H + y) * a.W + x) * 3 + ch;
-        lx[k] = (float)a.a8[o];
-        ly[k] = (float)a.b8[o];
-      } else {
-        const size_t o = ((size_t)p * a.H + y) * a.W + x;
-        lx[k] = a.af[o];
-        ly[k] = a.bf[o];
-      }
+    const int y = min(y0 + i / kSsimIn, a.H - 1), x = min(x0 + i % kSsimIn, a.W - 1);
+    if constexpr (U8) {
+      const int img = p / 3, ch = p % 3;
+      const size_t o = ((size_t)(img * a.H + y) * a.W + x) * 3 + ch;
+      rx[k] = a.a8[o];
+      ry[k] = a.b8[o];
+    } else {
+      const size_t o = ((size_t)p * a.H + y) * a.W + x;
+      rx[k] = a.af[o];
+      ry[k] = a.bf[o];
     }
   }
+#pragma unroll
+  for (int k = 0; k < kLoads; ++k) {
+    const int i = tid + 256 * k;
+    const bool in = i < kSsimIn * kSsimIn && y0 + i / kSsimIn < a.H && x0 + i % kSsimIn < a.W;
+    lx[k] = in ? (float)rx[k] : 0.f;
+    ly[k] = in ? (float)ry[k] : 0.f;
+  }
+  // the shift: per image, the mean of the window's in-image pixels (see the header).  Each
+  // thread adds its own elements, a wave is a butterfly, the four wave sums add in order.
+  float psx = 0.f, psy = 0.f;
+#pragma unroll
+  for (int k = 0; k < kLoads; ++k) {
+    // convert_image_dtype: u8 * (1/255) in fp32 (0 loaded outside the image)
+    if constexpr (U8) {
+      lx[k] *= 1.0f / 255.0f;
+      ly[k] *= 1.0f / 255.0f;
+    }
+    psx += lx[k];
+    psy += ly[k];
+  }
+  psx = wave_sum(psx);
+  psy = wave_sum(psy);
+  if ((tid & 63) == 0) {
+    shf[0][tid >> 6] = psx;
+    shf[1][tid >> 6] = psy;
+  }
+  __syncthreads();
+  const float inv_cnt = 1.0f / (float)(min(kSsimIn, a.H - y0) * min(kSsimIn, a.W - x0));
+  const float shx = (((shf[0][0] + shf[0][1]) + shf[0][2]) + shf[0][3]) * inv_cnt;
+  const float shy = (((shf[1][0] + shf[1][1]) + shf[1][2]) + shf[1][3]) * inv_cnt;
 #pragma unroll
   for (int k = 0; k < kLoads; ++k) {
     const int i = tid + 256 * k;
     if (i < kSsimIn * kSsimIn) {
       const int r = i / kSsimIn, c = i % kSsimIn;
       const bool in = y0 + r < a.H && x0 + c < a.W;
-      // convert_image_dtype: u8 * (1/255) in fp32; shifted by -0.5 (0 outside the image)
-      sx[r][c] = in ? (U8 ? lx[k] * (1.0f / 255.0f) : lx[k]) - 0.5f : 0.f;
-      sy[r][c] = in ? (U8 ? ly[k] * (1.0f / 255.0f) : ly[k]) - 0.5f : 0.f;
+      // outside the image: 0, read by no VALID output
+      sx[r][c] = in ? lx[k] - shx : 0.f;
+      sy[r][c] = in ? ly[k] - shy : 0.f;
     }
   }
   __syncthreads();
@@ -144,7 +187,7 @@ __global__ __launch_bounds__(256) void ssim_tile_kernel(SsimScaleArgs a) {
     for (int o = 0; o < kSeg; ++o) {
       if (y0 + r0 + o >= OH || x0 + c >= OW) continue;
       const float m0 = a01[o][0], m1 = a01[o][1], e2 = a23[o][0], e3 = a23[o][1];
-      const float mx = m0 + 0.5f, my = m1 + 0.5f;
+      const float mx = m0 + shx, my = m1 + shy;
       // v_rcp_f32 (1 ulp) instead of the IEEE division sequence
       const float lum = (2.f * mx * my + c1) * __builtin_amdgcn_rcpf(mx * mx + my * my + c1);
       const float cs = (2.f * (e3 - m0 * m1) + c2) * __builtin_amdgcn_rcpf(e2 - (m0 * m0 + m1 * m1) + c2);

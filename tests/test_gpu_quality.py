@@ -3,9 +3,36 @@
 Contract:
   * MS-SSIM (tf.image.ssim_multiscale, tf2_0/tests/calc_ssim.py:13): |GPU - oracle| <=
     MSSSIM_ATOL per image, and the per-scale mean SSIM / cs terms within TERM_ATOL.  The
-    GPU filters in fp32 (separable Gaussian, shifted by -0.5) and reduces in fp64; the
-    oracle is float64 throughout.  Parity vs TensorFlow itself is unpinned (no TF here).
+    GPU filters in fp32 (separable Gaussian, each tile's window minus its own mean per
+    image) and reduces in fp64; the oracle is float64 throughout.  Parity vs TensorFlow
+    itself is unpinned (no TF here).
   * squared error: bit-exact (integer), PSNR equal to the oracle's to 1e-9 dB.
+
+Measured on an MI355X, max |GPU - oracle| over the per-scale terms / over the result, for the
+cases of tests/ssim_cases.py.  "fixed 0.5" is the kernel as it was, subtracting 0.5 from every
+pixel; "window mean" is the kernel now:
+  case                      fixed 0.5            window mean
+  flat_254_noise1           5.7e-05 / 3.3e-06    1.3e-07 / 2.9e-08
+  bright_250_255_noise2     4.3e-05 / 3.2e-06    1.5e-07 / 1.8e-09
+  dark_0_5_noise2           2.6e-05 / 6.5e-07    1.2e-07 / 5.5e-09
+  const_255_vs_254          3.3e-05 / 3.3e-05    6.0e-08 / 4.4e-08
+  const_0_vs_1              6.0e-08 / 8.0e-08    6.0e-08 / 8.0e-08
+  const_255_identical       6.0e-08 / 6.0e-08    6.0e-08 / 6.0e-08
+  ramp_200_255_noise1       1.2e-05 / 2.0e-07    1.0e-07 / 1.8e-08
+  halves_0_255_noise1       1.2e-05 / 6.0e-06    1.1e-05 / 1.1e-06   (terms: own bound 2.2e-5, below)
+  batch_black_white_noise   4.0e-05 / 2.0e-05    1.2e-07 / 1.8e-08
+  tile_edge_168x172         1.8e-07 / 1.8e-08    1.8e-07 / 1.8e-08
+  tile_edge_172x168         1.2e-07 / 4.1e-08    1.2e-07 / 1.8e-08
+  wide_161x700              1.1e-07 / 2.0e-08    4.8e-08 / 2.0e-08
+  relu_inverted             1.5e-07 / 0          1.3e-07 / 0
+  cross_row37_col37         1.4e-07 / 5.7e-09    1.4e-07 / 5.7e-09   (relative check: 2.1e-07 to spare)
+halves_0_255_noise1 is the one case whose per-scale terms stay outside 2e-6: every window across
+the seam holds flat black and flat white, each 0.5 from the window's mean, so their flat pixels
+keep the cancellation of the fixed shift (the CPU model, tests/ssim_f32_model.py, gives the same
+1.1e-5).  Its terms alone are held to twice their measured figure; its result (1.1e-6) is held to
+MSSSIM_ATOL like every other, and the shared constants are unchanged.  Under 2.2e-5 the terms of
+this case would pass with the old kernel too (1.2e-5): on the device it is the result check
+(6.0e-6 before, 1.1e-6 now) that tells the two kernels apart for this case, not the terms.
 """
 import os
 
@@ -13,6 +40,7 @@ import numpy as np
 import pytest
 
 from oracle import nic_oracle as O
+from tests import ssim_cases as C
 
 pytestmark = pytest.mark.gpu
 
@@ -52,19 +80,33 @@ def _pairs():
 
 
 @pytest.mark.parametrize("case", ["noise_vs_noisy", "odd_177x203", "independent_noise", "identical",
-                                  "smallest_161x161"])
+                                  "smallest_161x161"] + sorted(C.all_pairs()))
 def test_ms_ssim_vs_oracle(case, codec):
-    a, b = _pairs()[case]
+    if case in C.all_pairs():  # flat / extreme content, tile geometry, relu, cross: tests/ssim_cases.py
+        a, b = C.all_pairs()[case]
+        ref, ref_terms = C.oracle_of(case)
+    else:
+        a, b = _pairs()[case]
+        ref_terms = O.ms_ssim_terms(a, b)
+        ref = O.ms_ssim(a, b)
     got, terms = codec.ms_ssim(_dev(a), _dev(b), per_scale=True)
     got, terms = got.cpu().numpy(), terms.cpu().numpy()
-    ref_terms = O.ms_ssim_terms(a, b)
-    ref = O.ms_ssim(a, b)
     print(f"{case}: ms_ssim gpu {got} oracle {ref} max|d| {np.abs(got - ref).max():.2e} "
           f"terms max|d| {np.abs(terms - ref_terms).max():.2e}")
-    np.testing.assert_allclose(terms, ref_terms, rtol=0, atol=TERM_ATOL)
+    # one case has its own bound on the per-scale terms (see the table above); the result of
+    # every case keeps MSSSIM_ATOL
+    np.testing.assert_allclose(terms, ref_terms, rtol=0, atol=C.OWN_TERM_ATOL.get(case, TERM_ATOL))
     np.testing.assert_allclose(got, ref, rtol=0, atol=MSSSIM_ATOL)
-    if case == "identical":
+    if case in ("identical", "const_255_identical"):
         np.testing.assert_allclose(got, 1.0, atol=1e-6)
+    if case == "relu_inverted":
+        assert (ref_terms[:, :, :4, 1] < 0).all()  # the mean cs of scales 0..3 is negative: the relu decides
+        np.testing.assert_array_equal(got, 0.0)
+    if case == "cross_row37_col37":
+        # outside the cross the images are identical, so 1 - term measures the band alone
+        excess = C.cross_excess(terms, ref_terms)
+        print(f"{case}: max of |(1-got)-(1-ref)| - ({C.CROSS_RTOL:g} (1-ref) + {C.CROSS_ATOL:g}) = {excess:.2e}")
+        assert excess <= 0.0
 
 
 def test_ms_ssim_codec_recon(codec, golden):

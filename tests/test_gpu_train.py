@@ -219,6 +219,40 @@ def test_ssim_gaussian_on_hip_matches_float64():
     assert _rel_err(xd.grad, xr.grad) <= 1e-4
 
 
+@pytest.mark.parametrize("level", [0.98, 0.02])
+def test_ssim_flat_patches_no_worse_than_fp32_reference(level):
+    # Near-white and near-black planes: local variance ~3e-5, far below c2 = 9e-4, so
+    # E[x^2 + y^2] - (E[x]^2 + E[y]^2) cancels.  T.ssim(hip=True) keeps TF's fp32 op order on
+    # unshifted values, so that cancellation is TF's own; what is held here is that the HIP
+    # kernels lose no more than the same formula in torch fp32 on the CPU does, against float64.
+    # The factor 2 covers fmaf in gauss1d_kernel against torch's accumulation order.
+    # Measured on the MI355X, max |error| vs float64 (HIP / torch fp32):
+    #   0.98: value 1.01e-5 / 1.02e-5, input gradient 6.42e-6 / 6.44e-6 (max |gradient| 5.2e-2)
+    #   0.02: value 3.86e-8 / 8.06e-8, input gradient 2.03e-8 / 1.94e-8 (max |gradient| 4.7e-2)
+    g = torch.Generator().manual_seed(int(level * 100))
+    x = level + 0.01 * (2 * torch.rand((3, 1, 40, 37), generator=g) - 1)
+    y = level + 0.01 * (2 * torch.rand((3, 1, 40, 37), generator=g) - 1)
+    xr = x.double().requires_grad_()
+    s_ref = T.ssim(xr, y.double())
+    s_ref.sum().backward()
+    xc = x.clone().requires_grad_()
+    s_cpu = T.ssim(xc, y)
+    s_cpu.sum().backward()
+    xd = x.cuda().requires_grad_()
+    s_hip = T.ssim(xd, y.cuda(), hip=True)
+    s_hip.sum().backward()
+
+    def err(a, ref):
+        return float((a.detach().double().cpu() - ref.detach()).abs().max())
+
+    ev_hip, ev_cpu = err(s_hip, s_ref), err(s_cpu, s_ref)
+    eg_hip, eg_cpu = err(xd.grad, xr.grad), err(xc.grad, xr.grad)
+    print(f"flat {level}: value max|d| hip {ev_hip:.2e} torch-fp32 {ev_cpu:.2e}; "
+          f"grad max|d| hip {eg_hip:.2e} torch-fp32 {eg_cpu:.2e} (max|grad| {float(xr.grad.abs().max()):.2e})")
+    assert ev_hip <= 2 * ev_cpu
+    assert eg_hip <= 2 * eg_cpu
+
+
 def test_ssim_map_fused_matches_float64_both_inputs():
     # the map's arithmetic and per-plane mean in one HIP pass (nic_ssim_map) and its backward
     # (nic_ssim_map_grad), weighted per plane, gradients to both images, a training-size plane
