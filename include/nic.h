@@ -58,7 +58,8 @@ enum {
   NIC_ENOMEM = -5,      /* device allocation failed                        */
   NIC_ERANGE = -6,      /* NIC_RANGE_ERROR: a split-f16 activation left the f16 range */
   NIC_ECORRUPT = -7,    /* nic_rans_inspect: not a well-formed .nic file              */
-  NIC_ENOPRIOR = -8     /* nic_rans2_encode / nic_rans2_decode before nic_rans_prior_set */
+  NIC_ENOPRIOR = -8,    /* nic_rans2_encode / nic_rans2_decode before nic_rans_prior_set */
+  NIC_EUNSUPPORTED = -9 /* nic_png_inspect: a well-formed PNG of a kind the device reader does not take */
 };
 
 /* model_id values for nic_set_weights (checkpoint names encoder{Y,CbCr}, decoder{Y,CbCr},
@@ -476,6 +477,50 @@ int nic_png_device_bound(int h, int w, int channels, int64_t* bytes);
 int nic_png_device_reserve(nic_ctx* ctx, int n, int h, int w, int channels);
 int nic_png_device_encode(nic_ctx* ctx, const uint8_t* images, int n, int h, int w, int channels, int filter,
                           uint8_t* out, int64_t stride, int64_t* sizes, void* stream);
+
+/* ---- The device PNG reader: PNG files inflated and unfiltered on the device ---------------------
+ * An optional reader for the directory drivers (Pillow stays the default).  The host cuts a file
+ * into its one zlib stream and checks the container; the device does the rest ("The device
+ * PNG reader"):
+ *   host    signature, chunk framing, every chunk's CRC-32, IHDR first, consecutive IDATs, IEND last
+ *   device  inflate (stored, fixed and dynamic blocks, LZ77 matches over the 32 KB window), the
+ *           Adler-32 of the inflated stream, the five PNG filters undone
+ *
+ * nic_png_inspect: HOST only (no GPU, no ctx).  One PNG file in host memory -> h, w, channels (each
+ *     nullable), the byte count of the concatenated IDAT payloads in *idat_bytes (nullable) and, when
+ *     idat is not NULL, those bytes copied to idat[0 .. *idat_bytes) (idat_capacity below that:
+ *     NIC_ESHAPE).  NIC_ECORRUPT for a broken file: bad signature, a truncated chunk, a wrong CRC-32,
+ *     IHDR missing, repeated or not 13 bytes, zero dimensions, IDATs split by another chunk, no IDAT,
+ *     no IEND, bytes after IEND.  NIC_EUNSUPPORTED for a well-formed file the device reader does not
+ *     take (nic_last_error says which): anything but 8-bit colour type 0 or 2, non-interlaced, no
+ *     tRNS, no unknown critical chunk, w * channels <= 16384 and T = h * (w * channels + 1) <= 2^30.
+ *     Ancillary chunks are skipped.  A broken file is NIC_ECORRUPT whatever its kind.
+ * nic_png_device_read_reserve: grow the workspace so nic_png_device_read of n such images allocates
+ *     nothing.  Synchronous.
+ * nic_png_device_read: zlib stream i at streams + i * stride (DEVICE) of sizes[i] bytes (DEVICE
+ *     int64[n]; a size outside 0..stride is clamped to it), every stream of an image of one (h, w,
+ *     channels) -> images (n,h,w,channels) u8 and status[i] (DEVICE int32[n]): 0 ok, else one of
+ *        1  bad zlib header: CM, CINFO, FCHECK, or FDICT set
+ *        2  invalid deflate data: block type 3; stored LEN / NLEN mismatch; a code-length set that is
+ *           over-subscribed or incomplete as zlib judges it; a repeat code with no previous length;
+ *           HLIT / HDIST out of range; no end-of-block code; a symbol with no code; a distance beyond
+ *           the bytes produced so far; input exhausted before the final block ends
+ *        4  the stream produces more or fewer than T bytes, or ends before its four Adler-32 bytes
+ *           (bytes after them are ignored, as zlib's decompress ignores them)
+ *        8  Adler-32 mismatch
+ *       16  a filter byte above 4 (that row is read as filter 0)
+ *     An image with a non-zero status may hold anything, but nothing outside its own h * w * channels
+ *     bytes is written; an image's result depends on its stream alone.  Everything runs on `stream`;
+ *     no host synchronisation.  No input bytes can take the kernels out of bounds or make them loop:
+ *     stream reads are clamped to sizes[i], table and window indices are masked, stores are checked
+ *     against the image's own T bytes, and the symbol loop ends once the bits consumed exceed the
+ *     stream's.  n <= 65535; stride in 1..2^31-1.
+ * Arguments are validated before any HIP call: shape, empty batch (OK), stride, NULL. */
+int nic_png_inspect(const uint8_t* host_file, int64_t size, int* h, int* w, int* channels, uint8_t* idat,
+                    int64_t idat_capacity, int64_t* idat_bytes);
+int nic_png_device_read_reserve(nic_ctx* ctx, int n, int h, int w, int channels);
+int nic_png_device_read(nic_ctx* ctx, const uint8_t* streams, int64_t stride, const int64_t* sizes, int n, int h, int w,
+                        int channels, uint8_t* images, int32_t* status, void* stream);
 
 /* ---- Training side path (tf2_0/src/training.py:74-151): the step's convolutions ------------
  * NHWC fp32 device tensors, split-f16x3 MFMA (fp32-class), kernels of Keras layouts, no ctx.

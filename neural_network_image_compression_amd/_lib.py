@@ -33,6 +33,7 @@ NIC_ENOMEM = -5
 NIC_ERANGE = -6
 NIC_ECORRUPT = -7
 NIC_ENOPRIOR = -8
+NIC_EUNSUPPORTED = -9
 
 RANGE_POLICIES = {"fallback": 0, "error": 1}  # nic.h NIC_RANGE_FALLBACK / NIC_RANGE_ERROR
 PNG_FILTER_ADAPTIVE = -1  # nic.h NIC_PNG_FILTER_ADAPTIVE
@@ -130,6 +131,11 @@ _SIGNATURES = {
     "nic_png_device_bound": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int64)]),
     "nic_png_device_reserve": (ctypes.c_int, [c_vp] + [ctypes.c_int] * 4),
     "nic_png_device_encode": (ctypes.c_int, [c_vp, c_vp] + [ctypes.c_int] * 5 + [c_vp, ctypes.c_int64, c_vp, c_vp]),
+    # device PNG reader (nic_png.cpp nic_png_inspect, nic_png_read.hip)
+    "nic_png_inspect": (ctypes.c_int, [c_vp, ctypes.c_int64] + [ctypes.POINTER(ctypes.c_int)] * 3
+                        + [c_vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
+    "nic_png_device_read_reserve": (ctypes.c_int, [c_vp] + [ctypes.c_int] * 4),
+    "nic_png_device_read": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp] + [ctypes.c_int] * 4 + [c_vp, c_vp, c_vp]),
     # training side path (nic_train.hip)
     "nic_conv_gather_work": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_int64)]),
     "nic_conv_gather": (ctypes.c_int, [c_vp] + [ctypes.c_int] * 4 + [c_vp] + [ctypes.c_int] * 7 + [c_vp] * 4

@@ -460,6 +460,127 @@ def png_files_device(codec, x, filter="adaptive") -> List[bytes]:
     return _download_files(*codec.png_encode(x, filter))
 
 
+PNG_READERS = ("pillow", "device")
+_PNG_SIGNATURE = bytes([137, 80, 78, 71, 13, 10, 26, 10])
+
+
+def _check_png_reader(png_reader: str, container: str, decoder_side: bool) -> None:
+    if png_reader not in PNG_READERS:
+        raise ValueError(f"png_reader must be one of {PNG_READERS}, got {png_reader!r}")
+    if png_reader == "device" and container == "nic" and decoder_side:
+        raise ValueError('png_reader="device" does not apply to the decoder side of container="nic": it reads .nic '
+                         "files, no PNG")
+
+
+class PngUnsupported(ValueError):
+    """nic_png_inspect: a well-formed PNG of a kind the device reader does not take (NIC_EUNSUPPORTED)."""
+
+
+def png_stream(data: bytes) -> Tuple[int, int, int, bytes]:
+    """(h, w, channels, zlib stream) of one PNG file's bytes: nic_png_inspect checks the signature, the
+    chunk framing and every CRC-32 on the host and cuts out the concatenated IDAT payload, which is
+    what Codec.png_read takes.  ValueError for a broken file (NIC_ECORRUPT), PngUnsupported for a
+    well-formed one the device reader does not take (interlaced, 16-bit, palette, alpha, tRNS, rows
+    over 16,384 bytes); both carry the call's text.  Host only."""
+    import ctypes
+
+    from . import _lib
+
+    a = np.frombuffer(data, np.uint8)
+    h, w, ch, n = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+    out = np.empty(max(len(data), 1), np.uint8)
+    rc = _lib.lib().nic_png_inspect(a.ctypes.data_as(ctypes.c_void_p), len(data), ctypes.byref(h), ctypes.byref(w),
+                                    ctypes.byref(ch), out.ctypes.data_as(ctypes.c_void_p), out.size, ctypes.byref(n))
+    if rc == _lib.NIC_EUNSUPPORTED:
+        raise PngUnsupported(f"[{rc}] {_lib.last_error()}")
+    if rc != _lib.NIC_OK:
+        raise ValueError(f"[{rc}] {_lib.last_error()}")
+    return h.value, w.value, ch.value, out[:n.value].tobytes()
+
+
+class _PngStream:
+    """One PNG file for the device reader; shape / ndim are those of the array Pillow would give."""
+
+    def __init__(self, h: int, w: int, channels: int, data: bytes):
+        self.hwc, self.data = (h, w, channels), data
+        self.shape = (h, w, channels) if channels != 1 else (h, w)
+        self.ndim = len(self.shape)
+
+
+def _png_item(data: bytes, name: str):
+    """A file's bytes -> a _PngStream when it is a PNG the device reader takes, else Pillow's array
+    (JPEGs and the other formats; unsupported PNGs).  ValueError naming the file for a corrupt PNG."""
+    from PIL import Image
+
+    if data[:8] == _PNG_SIGNATURE:
+        try:
+            return _PngStream(*png_stream(data))
+        except PngUnsupported:
+            pass
+        except ValueError as e:
+            raise ValueError(f"{name}: {e}") from None
+    with Image.open(io.BytesIO(data)) as im:
+        return np.array(im)
+
+
+def _read_item(path: str):
+    return _png_item(_read_bytes(path), path)
+
+
+def _stage_batch(codec, items: Sequence, names: Sequence[str]):
+    """Equal-shaped items (_PngStream or Pillow's arrays) -> one (N,h,w,c) u8 tensor on the codec's
+    device: the streams staged in one pinned buffer, copied in one transfer and read by
+    Codec.png_read; the arrays stacked and uploaded.  ValueError naming the file the device refuses."""
+    import torch
+
+    dev = f"cuda:{codec.device}"
+    zi = [k for k, it in enumerate(items) if isinstance(it, _PngStream)]
+    ai = [k for k, it in enumerate(items) if not isinstance(it, _PngStream)]
+    imgs = arr = None
+    if zi:
+        h, w, ch = items[zi[0]].hwc
+        stride = max(1, max(len(items[k].data) for k in zi))
+        host = torch.zeros((len(zi), stride), dtype=torch.uint8, pin_memory=True)
+        view = host.numpy()
+        for r, k in enumerate(zi):
+            view[r, :len(items[k].data)] = np.frombuffer(items[k].data, np.uint8)
+        lens = torch.tensor([len(items[k].data) for k in zi], dtype=torch.int64)
+        try:
+            imgs, _ = codec.png_read(host.to(dev, non_blocking=True), lens.to(dev), h, w, ch)
+        except ValueError as e:
+            m = re.search(r"image (\d+)", str(e))
+            which = names[zi[int(m.group(1))]] if m and int(m.group(1)) < len(zi) else f"files {list(names)}"
+            raise ValueError(f"{which}: {e}") from None
+        if not ai:
+            return imgs
+    if ai:
+        a = np.stack([np.asarray(items[k], np.uint8) for k in ai])
+        arr = torch.from_numpy(a.reshape(a.shape[0], a.shape[1], a.shape[2], -1)).to(dev)
+        if not zi:
+            return arr
+    out = torch.empty((len(items),) + tuple(imgs.shape[1:]), dtype=torch.uint8, device=dev)
+    out[torch.tensor(zi, device=dev)] = imgs
+    out[torch.tensor(ai, device=dev)] = arr
+    return out
+
+
+def read_png_device(codec, files: Sequence[bytes]) -> list:
+    """Image files' bytes -> their pixels on the codec's device, one tensor per shape group:
+    [(the files' indices, (n,h,w,c) u8 tensor)], in the order the shapes first appear (gray: c = 1).
+    PNG files go through png_stream and, group by group, through one pinned staging buffer, one
+    transfer and Codec.png_read; a file the inspector calls unsupported (and any other format) is
+    decoded by Pillow and joins the group of its shape.  ValueError naming the file ("file i") for a
+    corrupt PNG, on the host or on the device."""
+    groups = {}
+    items = []
+    for i, data in enumerate(files):
+        it = _png_item(bytes(data), f"file {i}")
+        items.append(it)
+        shape = tuple(it.shape) if len(it.shape) == 3 else tuple(it.shape) + (1,)
+        groups.setdefault(shape, []).append(i)
+    return [(idx, _stage_batch(codec, [items[i] for i in idx], [f"file {i}" for i in idx])) for idx in groups.values()]
+
+
 def _batches(shapes: Sequence[tuple], batch_size: int):
     """Consecutive runs of equal-shaped images, at most batch_size long (utils.py:53-62)."""
     i = 0
@@ -487,7 +608,8 @@ def feed_batch(model, x: np.ndarray, filenames: Sequence[str], output_dir: str, 
     import torch
 
     codec = model.codec
-    dev = torch.from_numpy(np.ascontiguousarray(x)).to(f"cuda:{codec.device}")
+    # a batch the device PNG reader made is on the device already
+    dev = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x)).to(f"cuda:{codec.device}")
     n, h, w, c = dev.shape
     if in_cshape == 96 and c == 3:
         dev = codec.unpack(dev)
@@ -556,7 +678,7 @@ def _set_any_prior(codec, prior) -> None:
 
 def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, in_cshape: int,
               batch_size: int = 64, workers=None, container: str = "png", png_writer: str = "pillow",
-              prior=None, region=None) -> None:
+              prior=None, region=None, png_reader: str = "pillow") -> None:
     """utils.py:46-62: every colour image of ``dataset_path`` (sorted; read_dataset's filter)
     through the codec into ``output_dir``, one PNG per image named after its source.
 
@@ -587,10 +709,17 @@ def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, i
 
     ``region`` (a pixel box (y, x, h, w); the decoder side of ``container="nic"`` only, ValueError
     otherwise: a packed PNG has no index to read a part of): every file is decoded to that box only
-    (use_model_nic_in)."""
+    (use_model_nic_in).
+
+    ``png_reader="device"`` (ValueError on the decoder side of ``container="nic"``, which reads no
+    PNG): the reader pool reads the files' bytes and runs nic_png_inspect on them (framing and every
+    CRC-32); the PNG files it takes go to the device as zlib streams and are inflated and unfiltered
+    there (Codec.png_read), JPEGs and the PNG kinds it does not take go through Pillow as before.
+    File order, batching and the files written are those of ``"pillow"``."""
     if container not in CONTAINERS:
         raise ValueError(f"container must be one of {CONTAINERS}, got {container!r}")
     _check_png_writer(png_writer, decoder_side=in_cshape == 96)
+    _check_png_reader(png_reader, container, decoder_side=in_cshape == 96)
     if region is not None and not (container == "nic" and in_cshape == 96):
         raise ValueError('region applies to the decoder side of container="nic" only: a packed PNG has no index, '
                          "so a part of it cannot be decoded on its own")
@@ -607,10 +736,16 @@ def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, i
         extra["png_writer"] = png_writer
     os.makedirs(output_dir, exist_ok=True)
     model.load(checkpoint_path)
+    device_reader = png_reader == "device"
     if workers is not None and workers <= 0:
-        imgs, names = read_dataset(dataset_path)
+        if device_reader:
+            pairs = [(_read_item(os.path.join(dataset_path, fn)), ".".join(fn.split(".")[:-1])) for fn in list_dataset(dataset_path)]
+            imgs, names = [a for a, _ in pairs if a.ndim == 3], [s for a, s in pairs if a.ndim == 3]
+        else:
+            imgs, names = read_dataset(dataset_path)
         for i, j in _batches([a.shape for a in imgs], batch_size):
-            feed_batch(model, np.stack(imgs[i:j]), names[i:j], output_dir, in_cshape, **extra)
+            x = _stage_batch(model.codec, imgs[i:j], names[i:j]) if device_reader else np.stack(imgs[i:j])
+            feed_batch(model, x, names[i:j], output_dir, in_cshape, **extra)
         return
     from concurrent.futures import ThreadPoolExecutor
 
@@ -619,7 +754,8 @@ def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, i
     files = list_dataset(dataset_path)
     with ThreadPoolExecutor(max_workers=min(8, threads)) as readers, ThreadPoolExecutor(max_workers=1) as writer:
         futures, batch, names, depth = [], [], [], 4 * max(1, batch_size)
-        pending = [readers.submit(_read_one, os.path.join(dataset_path, fn)) for fn in files[:depth]]
+        read = _read_item if device_reader else _read_one
+        pending = [readers.submit(read, os.path.join(dataset_path, fn)) for fn in files[:depth]]
 
         def flush():
             if batch:
@@ -627,7 +763,8 @@ def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, i
                 # (slower) PNG writer; the device pass of the next batch still overlaps them
                 while len(futures) >= WRITES_IN_FLIGHT:
                     futures.pop(0).result()  # re-raises a write error
-                futures.extend(feed_batch(model, np.stack(batch), list(names), output_dir, in_cshape, pool=writer,
+                x = _stage_batch(model.codec, batch, names) if device_reader else np.stack(batch)
+                futures.extend(feed_batch(model, x, list(names), output_dir, in_cshape, pool=writer,
                                           png_threads=png_threads, **extra))
                 batch.clear()
                 names.clear()
@@ -637,14 +774,14 @@ def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, i
         for k, fn in enumerate(files):
             a = pending[k].result()
             if k + depth < len(files):  # keep `depth` decodes in flight ahead of the device
-                pending.append(readers.submit(_read_one, os.path.join(dataset_path, files[k + depth])))
+                pending.append(readers.submit(read, os.path.join(dataset_path, files[k + depth])))
             pending[k] = None
             if a.ndim != 3:  # read_dataset keeps colour (3-D) images only
                 continue
             if batch and (a.shape != batch[0].shape or len(batch) >= batch_size
                           or (len(batch) + 1) * a.shape[0] * a.shape[1] > BATCH_PIXELS):
                 flush()
-            batch.append(a.astype(np.uint8, copy=False))
+            batch.append(a if isinstance(a, _PngStream) else a.astype(np.uint8, copy=False))
             names.append(".".join(fn.split(".")[:-1]))
         flush()
         for f in futures:

@@ -721,6 +721,47 @@ class Codec:
                                                  sizes.data_ptr(), _stream_ptr(torch, self.device)), "nic_png_device_encode")
         return buf, sizes
 
+    # -- device PNG reader (nic_png_device_read*) ---------------------------------------------
+    def png_read_reserve(self, n: int, h: int, w: int, channels: int = 3) -> None:
+        """Grow the workspace so png_read of n (h, w, channels) images allocates nothing."""
+        _lib.check(self._L.nic_png_device_read_reserve(self._h, n, h, w, channels), "nic_png_device_read_reserve")
+
+    def png_read_status(self, streams, sizes, h: int, w: int, channels: int = 3, out=None):
+        """png_read without the check: (images, status (N,) int32 device tensor; bits in nic.h)."""
+        torch = _torch()
+        if (not isinstance(streams, torch.Tensor) or streams.dtype != torch.uint8 or streams.device.type != "cuda"
+                or streams.ndim != 2):
+            raise TypeError("png_read: expected an (N, stride) cuda torch.uint8 tensor of zlib streams")
+        if not isinstance(sizes, torch.Tensor) or sizes.dtype != torch.int64 or sizes.shape != (streams.shape[0],):
+            raise TypeError("png_read: expected an (N,) torch.int64 tensor of sizes")
+        if streams.device.index != self.device or sizes.device != streams.device:
+            raise ValueError(f"png_read: tensors must be on cuda:{self.device}")
+        streams, sizes = streams.contiguous(), sizes.contiguous()
+        n, stride = streams.shape
+        shape = (n, int(h), int(w), int(channels))
+        if out is None:
+            out = torch.empty(tuple(max(v, 0) for v in shape), dtype=torch.uint8, device=streams.device)
+        elif out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != streams.device or not out.is_contiguous():
+            raise TypeError("png_read: out must be a contiguous (N,h,w,channels) torch.uint8 tensor on the codec's device")
+        status = torch.zeros((n,), dtype=torch.int32, device=streams.device)
+        _lib.check(self._L.nic_png_device_read(self._h, streams.data_ptr(), stride, sizes.data_ptr(), n, int(h), int(w),
+                                               int(channels), out.data_ptr(), status.data_ptr(),
+                                               _stream_ptr(torch, self.device)), "nic_png_device_read")
+        return out, status
+
+    def png_read(self, streams, sizes, h: int, w: int, channels: int = 3, out=None):
+        """The zlib streams streams[i, :sizes[i]] (device tensors: the IDAT payloads of PNG files of
+        one (h, w, channels), bitstream.png_stream) -> ((N,h,w,channels) u8 images, status): inflated,
+        Adler-checked and unfiltered on the device (nic_png_device_read).  Reads the statuses back
+        (synchronises) and raises ValueError naming the first image whose stream did not decode."""
+        images, status = self.png_read_status(streams, sizes, h, w, channels, out)
+        st = status.cpu().numpy()
+        bad = np.nonzero(st)[0]
+        if bad.size:
+            raise ValueError(f"png_read: image {int(bad[0])} is corrupt (status {int(st[bad[0]])}; corrupt images: "
+                             f"{bad.tolist()})")
+        return images, status
+
     def pack(self, z):
         """(N,h,w,96) -> (N,4h,8w,3) bitstream image (utils.py:39-40)."""
         torch = _torch()
@@ -798,7 +839,7 @@ class Encoder(ProClass):
         return self.codec.encode_host(a, self.host_chunks)
 
     def compress(self, dataset_path: str, checkpoint_path: str, batch_size: int = 64, workers=None,
-                 container: str = "png", prior=None) -> None:
+                 container: str = "png", prior=None, png_reader: str = "pillow") -> None:
         """encoder.py:49-51: every image in ``dataset_path`` -> ``dataset_path + '_compressed'``.
         Pipelined over the host cores in batches of ``batch_size`` (bitstream.use_model);
         ``workers=0, batch_size=4`` is the reference's serial loop (same files).
@@ -806,11 +847,14 @@ class Encoder(ProClass):
         the reference's packed PNGs (the default).  ``prior`` (a prior.Prior or a ``.nicp`` path;
         ``container="nic"`` only): version-2 files, coded against the prior and carrying each
         image's true H x W.  A prior.ContextPrior or a ``.nicc`` path: version-3 files, coded
-        against the context prior."""
+        against the context prior.
+        ``png_reader="device"``: the directory's PNG files are inflated and unfiltered on the device
+        (Codec.png_read) instead of by Pillow on the reader pool; the files written are the same."""
         from .bitstream import use_model
 
+        more = {"png_reader": png_reader} if png_reader != "pillow" else {}
         use_model(self, dataset_path, checkpoint_path, dataset_path + "_compressed", in_cshape=3,
-                  batch_size=batch_size, workers=workers, container=container, prior=prior)
+                  batch_size=batch_size, workers=workers, container=container, prior=prior, **more)
 
 
 class Decoder(ProClass):
@@ -845,7 +889,8 @@ class Decoder(ProClass):
         return decode_regions(self, files, boxes)
 
     def uncompress(self, dataset_path: str, checkpoint_path: str, batch_size: int = 64, workers=None,
-                   container: str = "png", png_writer: str = "pillow", prior=None, region=None) -> None:
+                   container: str = "png", png_writer: str = "pillow", prior=None, region=None,
+                   png_reader: str = "pillow") -> None:
         """decoder.py:50-52: packed PNGs in ``dataset_path`` -> ``dataset_path.replace('compressed','uncompressed')``.
         Pipelined as compress (``workers=0, batch_size=4``: the reference's serial loop).
         ``container="nic"`` reads the directory's ``.nic`` files instead (same reconstructions).
@@ -855,10 +900,14 @@ class Decoder(ProClass):
         under (a prior.ContextPrior or a ``.nicc`` path for version-3 files); their reconstructions
         are cropped to the recorded H x W.  Version-1 files are read as before.
         ``region`` (a pixel box (y, x, h, w); ``container="nic"`` only, ValueError otherwise: a packed
-        PNG has no index): every file is decoded to that box only and ``<stem>.png`` holds the box."""
+        PNG has no index): every file is decoded to that box only and ``<stem>.png`` holds the box.
+        ``png_reader="device"`` (``container="png"`` only, ValueError otherwise): the packed PNGs are
+        inflated and unfiltered on the device (Codec.png_read) and go straight into the unpack."""
         from .bitstream import use_model
 
         more = {"region": region} if region is not None else {}
+        if png_reader != "pillow":
+            more["png_reader"] = png_reader
         use_model(self, dataset_path, checkpoint_path, dataset_path.replace("compressed", "uncompressed"),
                   in_cshape=96, batch_size=batch_size, workers=workers, container=container, png_writer=png_writer,
                   prior=prior, **more)

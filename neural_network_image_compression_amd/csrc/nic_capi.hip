@@ -1702,6 +1702,39 @@ int nic_png_device_encode(nic_ctx* c, const uint8_t* images, int n, int h, int w
   return NIC_OK;
 }
 
+// ---- device PNG reader (nic_png_read.hip; nic_png_inspect is host-only in nic_png.cpp) ----
+static int png_read_check(const char* fn, int n, int h, int w, int channels) {
+  int rc = png_dev_check(fn, n, h, w, channels, NIC_PNG_FILTER_ADAPTIVE);
+  return rc;
+}
+
+int nic_png_device_read_reserve(nic_ctx* c, int n, int h, int w, int channels) {
+  int rc = png_read_check("nic_png_device_read_reserve", n, h, w, channels);
+  if (rc || n == 0) return rc;
+  if (!c) return fail(NIC_EINVAL, "nic_png_device_read_reserve: NULL ctx");
+  DeviceGuard guard(c->device);
+  PngReadPlan pl;
+  png_read_plan(n, h, w, channels, &pl);
+  return ensure_ws(c, pl.bytes);
+}
+
+int nic_png_device_read(nic_ctx* c, const uint8_t* streams, int64_t stride, const int64_t* sizes, int n, int h, int w,
+                        int channels, uint8_t* images, int32_t* status, void* stream) {
+  int rc = png_read_check("nic_png_device_read", n, h, w, channels);
+  if (rc || n == 0) return rc;
+  if (stride < 1 || stride > 0x7fffffffll)
+    return fail(NIC_ESHAPE, "nic_png_device_read: stride %lld not in 1..2^31-1", (long long)stride);
+  if (!c) return fail(NIC_EINVAL, "nic_png_device_read: NULL ctx");
+  if (!streams || !sizes || !images || !status) return fail(NIC_EINVAL, "nic_png_device_read: NULL buffer");
+  DeviceGuard guard(c->device);
+  PngReadPlan pl;
+  png_read_plan(n, h, w, channels, &pl);
+  if ((rc = ensure_ws(c, pl.bytes))) return rc;
+  HIP_TRY(launch_png_dev_read(streams, stride, (const long long*)sizes, n, h, w, channels, c->ws, pl, images, (int*)status,
+                              (hipStream_t)stream));
+  return NIC_OK;
+}
+
 // ---- training side path (nic_train.hip) ----------------------------------------------------
 static bool train_dims_ok(int c) { return c >= 1 && c <= 64; }
 

@@ -235,6 +235,17 @@ void png_dev_plan(int n, int h, int w, int channels, PngDevPlan* plan);
 hipError_t launch_png_dev_encode(const uint8_t* images, int n, int h, int w, int channels, int filter, char* ws,
                                  const PngDevPlan& plan, uint8_t* out, long long stride, long long* sizes, hipStream_t st);
 
+// --- device PNG reader (nic_png_read.hip) -----------------------------------------------------
+// Byte offsets of one call's scratch inside the ctx workspace: the inflated filtered streams (fstride
+// bytes per image) and per image its inflate status and the stream's Adler-32 field.
+struct PngReadPlan {
+  uint32_t total;  // filtered bytes per image: h * (w * channels + 1)
+  size_t fstride, filt, meta, bytes;
+};
+void png_read_plan(int n, int h, int w, int channels, PngReadPlan* plan);
+hipError_t launch_png_dev_read(const uint8_t* streams, long long stride, const long long* sizes, int n, int h, int w, int channels,
+                               char* ws, const PngReadPlan& plan, uint8_t* images, int* status, hipStream_t st);
+
 // --- quality metrics (nic_quality.hip) ---------------------------------------------------
 constexpr int kSsimScales = 5;  // tf.image.ssim_multiscale power_factors
 

@@ -274,3 +274,95 @@ extern "C" int nic_png_sizes(const uint8_t* images, int m, int h, int w, int cha
   if (e) return shape_error("nic_png_sizes", e);
   return nic_png_encode(images, m, h, w, channels, NIC_PNG_PILLOW, nullptr, 0, sizes, threads);
 }
+
+// ---- nic_png_inspect: the host half of the device PNG reader ------------------------------------
+namespace {
+
+int inspect_fail(int code, const char* what) {
+  static thread_local char msg[200];
+  std::snprintf(msg, sizeof(msg), "nic_png_inspect: %s", what);
+  return nic::set_error(code, msg);
+}
+
+uint32_t be32(const uint8_t* p) { return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | (uint32_t)p[3]; }
+
+}  // namespace
+
+extern "C" int nic_png_inspect(const uint8_t* host_file, int64_t size, int* h, int* w, int* channels, uint8_t* idat,
+                               int64_t idat_capacity, int64_t* idat_bytes) {
+  static const uint8_t kSig[8] = {137, 80, 78, 71, 13, 10, 26, 10};
+  if (!host_file || size < 0) return inspect_fail(NIC_EINVAL, "NULL file or negative size");
+  if (idat && idat_capacity < 0) return inspect_fail(NIC_EINVAL, "negative idat_capacity");
+  if (size < 8 || std::memcmp(host_file, kSig, 8) != 0) return inspect_fail(NIC_ECORRUPT, "not a PNG signature");
+  // pass 1: framing and every CRC; the IHDR fields; what else the file holds
+  int64_t at = 8, total = 0;
+  int nchunks = 0, state = 0;  // state 0: before the IDATs, 1: inside them, 2: after them
+  bool end = false, trns = false, critical = false;
+  uint32_t W = 0, H = 0;
+  int depth = 0, colour = 0, comp = 0, filt = 0, lace = 0;
+  while (!end) {
+    if (at + 12 > size) return inspect_fail(NIC_ECORRUPT, at == size ? "no IEND chunk" : "truncated chunk");
+    const uint32_t n = be32(host_file + at);
+    const uint8_t* typ = host_file + at + 4;
+    if (n > 0x7fffffffu || at + 12 + (int64_t)n > size) return inspect_fail(NIC_ECORRUPT, "truncated chunk data");
+    uint32_t crc = (uint32_t)crc32(0L, typ, 4);
+    for (int64_t o = 0; o < (int64_t)n; o += 1 << 30)
+      crc = (uint32_t)crc32(crc, typ + 4 + o, (uInt)std::min<int64_t>((int64_t)n - o, 1 << 30));
+    if (crc != be32(typ + 4 + n)) return inspect_fail(NIC_ECORRUPT, "a chunk's CRC-32 does not match");
+    const bool is_ihdr = !std::memcmp(typ, "IHDR", 4), is_idat = !std::memcmp(typ, "IDAT", 4), is_iend = !std::memcmp(typ, "IEND", 4);
+    if ((nchunks == 0) != is_ihdr) return inspect_fail(NIC_ECORRUPT, nchunks ? "a second IHDR" : "IHDR is not the first chunk");
+    if (is_ihdr) {
+      if (n != 13) return inspect_fail(NIC_ECORRUPT, "IHDR is not 13 bytes");
+      W = be32(typ + 4);
+      H = be32(typ + 8);
+      depth = typ[12], colour = typ[13], comp = typ[14], filt = typ[15], lace = typ[16];
+      if (W == 0 || H == 0 || W > 0x7fffffffu || H > 0x7fffffffu) return inspect_fail(NIC_ECORRUPT, "IHDR: zero or oversized dimensions");
+    } else if (is_idat) {
+      if (state == 2) return inspect_fail(NIC_ECORRUPT, "IDAT chunks are not consecutive");
+      state = 1;
+      total += n;
+    } else {
+      if (state == 1) state = 2;
+      if (is_iend) {
+        if (n != 0) return inspect_fail(NIC_ECORRUPT, "IEND carries data");
+        end = true;
+      } else if (!std::memcmp(typ, "tRNS", 4)) {
+        trns = true;
+      } else if (!(typ[0] & 32) && std::memcmp(typ, "PLTE", 4)) {
+        critical = true;
+      }
+    }
+    at += 12 + (int64_t)n;
+    ++nchunks;
+  }
+  if (at != size) return inspect_fail(NIC_ECORRUPT, "bytes after IEND");
+  if (state == 0) return inspect_fail(NIC_ECORRUPT, "no IDAT chunk");
+  // what the device reader takes
+  if (comp != 0 || filt != 0) return inspect_fail(NIC_EUNSUPPORTED, "unknown compression or filter method");
+  if (lace != 0) return inspect_fail(NIC_EUNSUPPORTED, "interlaced");
+  if (depth != 8) return inspect_fail(NIC_EUNSUPPORTED, "bit depth is not 8");
+  if (colour != 0 && colour != 2) return inspect_fail(NIC_EUNSUPPORTED, "colour type is not 0 (gray) or 2 (RGB)");
+  if (trns) return inspect_fail(NIC_EUNSUPPORTED, "a tRNS chunk adds transparency");
+  if (critical) return inspect_fail(NIC_EUNSUPPORTED, "an unknown critical chunk");
+  const int ch = colour == 2 ? 3 : 1;
+  if ((long long)W * ch > 16384 || (long long)H * ((long long)W * ch + 1) > (1LL << 30))
+    return inspect_fail(NIC_EUNSUPPORTED, "rows wider than 16384 bytes or images above 2^30 filtered bytes");
+  if (h) *h = (int)H;
+  if (w) *w = (int)W;
+  if (channels) *channels = ch;
+  if (idat_bytes) *idat_bytes = total;
+  if (idat) {
+    if (idat_capacity < total) return inspect_fail(NIC_ESHAPE, "idat_capacity is below the IDAT payload");
+    // pass 2: the payloads, in order
+    int64_t o = 0;
+    for (at = 8; at + 12 <= size;) {
+      const uint32_t n = be32(host_file + at);
+      if (!std::memcmp(host_file + at + 4, "IDAT", 4)) {
+        std::memcpy(idat + o, host_file + at + 8, n);
+        o += n;
+      }
+      at += 12 + (int64_t)n;
+    }
+  }
+  return NIC_OK;
+}

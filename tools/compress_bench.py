@@ -86,18 +86,22 @@ def recon_pixels(path):
         return np.array(im).tobytes()
 
 
-def run_containers(enc, dec, tmp, ds, ck, n, px, containers, repeat, writers=None):
+def run_containers(enc, dec, tmp, ds, ck, n, px, containers, repeat, writers=None, readers=None):
     """Best-of-`repeat` compress / uncompress wall time and mean file size per container (and per
-    reconstruction writer, when writers are named)."""
+    reconstruction writer and PNG reader, when they are named; both repeats of every figure are
+    listed then)."""
     res, recon = {}, {}
-    for cont, writer in [(c, w) for c in containers for w in (writers or [None])]:
-        best, runs = {}, []
+    for cont, writer, reader in [(c, w, r) for c in containers for w in (writers or [None]) for r in (readers or [None])]:
+        best, runs, cruns = {}, [], []
         ukw = {"png_writer": writer} if writer else {}
+        ckw = {"png_reader": reader} if reader else {}
+        if reader and cont == "png":
+            ukw["png_reader"] = reader  # the decoder side of "nic" reads no PNG
         for r in range(repeat + 1):
             for d in ("_compressed", "_uncompressed"):
                 shutil.rmtree(ds + d, ignore_errors=True)
             t0 = time.perf_counter()
-            enc.compress(ds, os.path.join(ck, "encoder"), container=cont)
+            enc.compress(ds, os.path.join(ck, "encoder"), container=cont, **ckw)
             t1 = time.perf_counter()
             dec.uncompress(ds + "_compressed", os.path.join(ck, "decoder"), container=cont, **ukw)
             t2 = time.perf_counter()
@@ -105,8 +109,11 @@ def run_containers(enc, dec, tmp, ds, ck, n, px, containers, repeat, writers=Non
                 best["compress_s"] = min(best.get("compress_s", 1e9), t1 - t0)
                 best["uncompress_s"] = min(best.get("uncompress_s", 1e9), t2 - t1)
                 runs.append(round(t2 - t1, 4))
+                cruns.append(round(t1 - t0, 4))
         sizes = [os.path.getsize(os.path.join(ds + "_compressed", f)) for f in os.listdir(ds + "_compressed")]
         key = f"{cont}+{writer}" if writer else cont
+        if reader:
+            key += f"+read:{reader}"
         if writer:
             rs = [os.path.getsize(os.path.join(ds + "_uncompressed", f)) for f in os.listdir(ds + "_uncompressed")]
             res[key] = {"uncompress_s_runs": runs, "mean_recon_file_bytes": round(float(np.mean(rs)), 1)}
@@ -121,6 +128,8 @@ def run_containers(enc, dec, tmp, ds, ck, n, px, containers, repeat, writers=Non
                      "compress_MP_s": round(n * px / 1e6 / best["compress_s"], 2),
                      "uncompress_MP_s": round(n * px / 1e6 / best["uncompress_s"], 2),
                      "files": len(sizes), "mean_file_bytes": round(float(np.mean(sizes)), 1)})
+        if reader:
+            res[key]["compress_s_runs"] = cruns
     same = all(recon[c] == next(iter(recon.values())) for c in recon)
     return res, same
 
@@ -131,6 +140,8 @@ def main():
                     help="compare these on-disk containers only (default: the driver modes, then both)")
     ap.add_argument("--png-writer", nargs="+", choices=("pillow", "device"), default=None,
                     help="also loop these reconstruction writers of uncompress (default: Pillow's only)")
+    ap.add_argument("--png-reader", nargs="+", choices=("pillow", "device"), default=None,
+                    help="also loop these PNG readers of compress and of uncompress from the PNG container")
     ap.add_argument("--weights", choices=("trained", "spread"), default="trained",
                     help="codec of the container comparison")
     ap.add_argument("--images", type=int, default=192)
@@ -158,7 +169,7 @@ def main():
         modes = [("serial_b4", {"batch_size": 4, "workers": 0}), ("r4_b4_w8", {"batch_size": 4, "workers": 8}),
                  ("pipeline_b64", {})]
         out = {"tool": "compress_bench", "host_cpus": len(os.sched_getaffinity(0))}
-        if args.container is None and args.png_writer is None:
+        if args.container is None and args.png_writer is None and args.png_reader is None:
             res, same = run_modes(enc, dec, tmp, ds, ck, args.images, 65536, modes, args.repeat)
             out["kodim21_tiles"] = {"images": args.images, "tile": "256x256x3 kodim21 tiles", "modes": res,
                                     "files_identical_across_modes": same}
@@ -169,12 +180,12 @@ def main():
             W.save(W.load(pre + "encoder", "encoder"), os.path.join(ckc, "encoder"), "encoder")
             W.save(W.load(pre + "decoder", "decoder"), os.path.join(ckc, "decoder"), "decoder")
         res, same = run_containers(enc, dec, tmp, ds, ckc, args.images, 65536, args.container or ["png", "nic"],
-                                   args.repeat, writers=args.png_writer)
+                                   args.repeat, writers=args.png_writer, readers=args.png_reader)
         out["containers"] = {"images": args.images, "tile": "256x256x3 kodim21 tiles", "weights": args.weights,
                              "driver": "pipeline_b64", "by_container": res, "reconstructions_identical": same}
         if args.png_writer:  # files differ between writers by design: the comparison is of decoded pixels
             out["containers"]["compared"] = "decoded pixels"
-        if args.container is None and args.png_writer is None and os.path.isdir(args.imagenet):
+        if args.container is None and args.png_writer is None and args.png_reader is None and os.path.isdir(args.imagenet):
             inet = os.path.join(tmp, "inet")
             shutil.copytree(args.imagenet, inet)
             n = len([f for f in os.listdir(inet) if f.endswith(".jpg")])
