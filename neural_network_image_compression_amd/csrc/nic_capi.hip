@@ -693,56 +693,34 @@ bool use_chain() {
   return on;
 }
 
-// One encode pass: split-f16 kernels (x3, producers report to rg.flag) or exact-fp32 ones
-// (rg.gate set: a re-run that exits unless the split pass of the same epoch tripped).
-// `timed` brackets the launches with the per-layer events (the gated re-run is not timed).
-int encode_pass(nic_ctx* c, const uint8_t* rgb, int n, int h, int w, uint8_t* latent, float* prequant,
-                hipStream_t st, bool x3, const RangeGuard& rg, bool timed) {
-  const EncGeom g = enc_geom(n, h, w);
-  float* R[4];
-  int rc = ensure_regions(c, g.r0, g.r123, R);
-  if (rc) return rc;
-  const int P = 3 * n;
-  const bool timing_on = c->timing;
-  c->timing = timing_on && timed;
-  struct Restore {
-    nic_ctx* c;
-    bool v;
-    ~Restore() { c->timing = v; }
-  } restore{c, timing_on};
-
-  Conv1Args a1{};
-  a1.rg = rg;
-  a1.rgb = rgb;
-  a1.out = R[0];
-  a1.out_s = x3 ? (uint16_t*)R[0] : nullptr;
-  a1.w = c->wk[L_CONV1];
-  a1.bias = c->wb[L_CONV1];
-  a1.P = P;
-  a1.nimg = n;
-  a1.H = h;
-  a1.W = w;
-  a1.OH = g.c1y.out;
-  a1.OW = g.c1x.out;
-  a1.pad_y = g.c1y.lo;
-  a1.pad_x = g.c1x.lo;
-  // the gated exact-fp32 re-run: all layers recorded into one launch (fp32_chain_kernel)
+// What an encode and a decode pass share: the timing switch for the pass (restored on exit),
+// the guard of the layers behind the head, the chained exact-fp32 re-run, the per-layer
+// dispatch and the common ConvArgs fill.
+struct PassCtx {
+  nic_ctx* c;
+  hipStream_t st;
+  const bool x3;
+  const int n;
+  const bool timing_on;
+  RangeGuard rgl;      // rg without trips: the re-run's head counts the trip, later layers only gate
+  const bool chained;  // the gated exact-fp32 re-run recorded into one launch (fp32_chain_kernel)
   Fp32Chain chain{};
-  const bool chained = !x3 && rg.gate && use_chain();
-  chain.gate = rg;
-  chain.q = c->range + 2;
-  // f16x3: conv1 runs inside the conv2 kernel (launch_conv12_x3, timed as conv2)
-  const bool fuse12 = x3;
-  if (!fuse12) TIMED(L_CONV1, chained ? chain_add_conv1(chain, a1) : launch_conv1(a1, st));
-  // the re-run's head is conv1 (it counts the trip); later layers only gate
-  RangeGuard rgl = rg;
-  rgl.trips = nullptr;
-  auto run = [&](LayerId id, const ConvArgs& a) {
+  PassCtx(nic_ctx* c_, hipStream_t st_, bool x3_, int n_, const RangeGuard& rg, bool timed)
+      : c(c_), st(st_), x3(x3_), n(n_), timing_on(c_->timing), rgl(rg), chained(!x3_ && rg.gate && use_chain()) {
+    c->timing = timing_on && timed;
+    rgl.trips = nullptr;
+    chain.gate = rg;
+    chain.q = c->range + 2;
+  }
+  ~PassCtx() { c->timing = timing_on; }
+  PassCtx(const PassCtx&) = delete;
+  PassCtx& operator=(const PassCtx&) = delete;
+  hipError_t run(LayerId id, const ConvArgs& a) {
     return chained ? chain_add_layer(chain, id, a) : x3 ? launch_layer_x3(id, a, st) : launch_layer(id, a, st);
-  };
-
-  auto conv = [&](LayerId id, const float* in, float* out, const float* res, int H, int W, int OH, int OW, int py,
-                  int px) {
+  }
+  hipError_t finish() { return chained ? launch_fp32_chain(chain, st) : hipSuccess; }
+  ConvArgs conv(LayerId id, const float* in, float* out, const float* res, int H, int W, int OH, int OW, int py,
+                int px) const {
     ConvArgs a{};
     a.rg = rgl;
     a.in = in;
@@ -757,7 +735,7 @@ int encode_pass(nic_ctx* c, const uint8_t* rgb, int n, int h, int w, uint8_t* la
     a.wscale[0] = c->wscale[id][0];
     a.wscale[1] = c->wscale[id][1];
     a.bias = c->wb[id];
-    a.P = P;
+    a.P = 3 * n;
     a.nimg = n;
     a.H = H;
     a.W = W;
@@ -766,9 +744,41 @@ int encode_pass(nic_ctx* c, const uint8_t* rgb, int n, int h, int w, uint8_t* la
     a.pad_y = py;
     a.pad_x = px;
     return a;
-  };
+  }
+};
+
+// One encode pass: split-f16 kernels (x3, producers report to rg.flag) or exact-fp32 ones
+// (rg.gate set: a re-run that exits unless the split pass of the same epoch tripped).
+// `timed` brackets the launches with the per-layer events (the gated re-run is not timed).
+int encode_pass(nic_ctx* c, const uint8_t* rgb, int n, int h, int w, uint8_t* latent, float* prequant,
+                hipStream_t st, bool x3, const RangeGuard& rg, bool timed) {
+  const EncGeom g = enc_geom(n, h, w);
+  float* R[4];
+  int rc = ensure_regions(c, g.r0, g.r123, R);
+  if (rc) return rc;
+  PassCtx ps(c, st, x3, n, rg, timed);
+
+  Conv1Args a1{};
+  a1.rg = rg;  // the re-run's head: it counts the trip
+  a1.rgb = rgb;
+  a1.out = R[0];
+  a1.out_s = x3 ? (uint16_t*)R[0] : nullptr;
+  a1.w = c->wk[L_CONV1];
+  a1.bias = c->wb[L_CONV1];
+  a1.P = 3 * n;
+  a1.nimg = n;
+  a1.H = h;
+  a1.W = w;
+  a1.OH = g.c1y.out;
+  a1.OW = g.c1x.out;
+  a1.pad_y = g.c1y.lo;
+  a1.pad_x = g.c1x.lo;
+  // f16x3: conv1 runs inside the conv2 kernel (launch_conv12_x3, timed as conv2)
+  const bool fuse12 = x3;
+  if (!fuse12) TIMED(L_CONV1, ps.chained ? chain_add_conv1(ps.chain, a1) : launch_conv1(a1, st));
+
   const int h1 = g.c1y.out, w1 = g.c1x.out, h2 = g.c2y.out, w2 = g.c2x.out;
-  ConvArgs a2 = conv(L_CONV2, R[0], R[1], nullptr, h1, w1, h2, w2, g.c2y.lo, g.c2x.lo);
+  ConvArgs a2 = ps.conv(L_CONV2, R[0], R[1], nullptr, h1, w1, h2, w2, g.c2y.lo, g.c2x.lo);
   if (fuse12) {
     a2.rgb = rgb;
     a2.wx1 = c->wx[L_CONV1];
@@ -782,24 +792,24 @@ int encode_pass(nic_ctx* c, const uint8_t* rgb, int n, int h, int w, uint8_t* la
     a2.cplane = (uint16_t*)R[0];  // colour planes (R0 is free: conv1 writes no output)
     TIMED(L_CONV2, launch_conv12_x3(a2, st));
   } else {
-    TIMED(L_CONV2, run(L_CONV2, a2));
+    TIMED(L_CONV2, ps.run(L_CONV2, a2));
   }
   if (x3 && use_k3pair() && k3pair_supported(h2, w2)) {
     // conv3 -> conv4 -> + res as one launch (R1 -> R3, the residual read from the input
     // rows in LDS); timed as conv4
-    TIMED(L_CONV4, launch_pair(c, conv(L_CONV3, R[1], R[3], nullptr, h2, w2, h2, w2, 1, 1), L_CONV4, st));
+    TIMED(L_CONV4, launch_pair(c, ps.conv(L_CONV3, R[1], R[3], nullptr, h2, w2, h2, w2, 1, 1), L_CONV4, st));
   } else {
-    TIMED(L_CONV3, run(L_CONV3, conv(L_CONV3, R[1], R[2], nullptr, h2, w2, h2, w2, 1, 1)));
-    TIMED(L_CONV4, run(L_CONV4, conv(L_CONV4, R[2], R[3], R[1], h2, w2, h2, w2, 1, 1)));
+    TIMED(L_CONV3, ps.run(L_CONV3, ps.conv(L_CONV3, R[1], R[2], nullptr, h2, w2, h2, w2, 1, 1)));
+    TIMED(L_CONV4, ps.run(L_CONV4, ps.conv(L_CONV4, R[2], R[3], R[1], h2, w2, h2, w2, 1, 1)));
   }
-  ConvArgs a8 = conv(L_CONV8, R[3], nullptr, nullptr, h2, w2, g.c8y.out, g.c8x.out, g.c8y.lo, g.c8x.lo);
+  ConvArgs a8 = ps.conv(L_CONV8, R[3], nullptr, nullptr, h2, w2, g.c8y.out, g.c8x.out, g.c8y.lo, g.c8x.lo);
   a8.out_u8 = latent;
   a8.out_f32_latent = prequant;
   if (x3 && c->fold_part) {  // nic_encode_entropy: the split pass's conv8 counts the codes
     a8.hist_part = c->fold_part;
   }
-  TIMED(L_CONV8, run(L_CONV8, a8));
-  if (chained) HIP_TRY(launch_fp32_chain(chain, st));
+  TIMED(L_CONV8, ps.run(L_CONV8, a8));
+  HIP_TRY(ps.finish());
   return NIC_OK;
 }
 
@@ -810,61 +820,20 @@ int decode_pass(nic_ctx* c, const uint8_t* latent, int n, int h8, int w8, uint8_
   float* R[4];
   int rc = ensure_regions(c, g.r0, g.r123, R);
   if (rc) return rc;
-  const int P = 3 * n;
-  const bool timing_on = c->timing;
-  c->timing = timing_on && timed;
-  struct Restore {
-    nic_ctx* c;
-    bool v;
-    ~Restore() { c->timing = v; }
-  } restore{c, timing_on};
-  // the re-run's head is dconv1 (it counts the trip); later layers only gate
-  RangeGuard rgl = rg;
-  rgl.trips = nullptr;
-  Fp32Chain chain{};  // the gated exact-fp32 re-run as one launch (see encode_pass)
-  const bool chained = !x3 && rg.gate && use_chain();
-  chain.gate = rg;
-  chain.q = c->range + 2;
-  auto run = [&](LayerId id, const ConvArgs& a) {
-    return chained ? chain_add_layer(chain, id, a) : x3 ? launch_layer_x3(id, a, st) : launch_layer(id, a, st);
-  };
-  auto conv = [&](LayerId id, const float* in, float* out, const float* res, int H, int W, int OH, int OW) {
-    ConvArgs a{};
-    a.rg = rgl;
-    a.in = in;
-    a.out = out;
-    a.res = res;
-    a.in_s = (const uint16_t*)in;  // the same region read as split f16 (f16x3 kernels)
-    a.out_s = (uint16_t*)out;
-    a.res_s = (const uint16_t*)res;
-    a.zero16 = c->zero16;
-    a.w = c->wk[id];
-    a.wx = c->wx[id];
-    a.wscale[0] = c->wscale[id][0];
-    a.wscale[1] = c->wscale[id][1];
-    a.bias = c->wb[id];
-    a.P = P;
-    a.nimg = n;
-    a.H = H;
-    a.W = W;
-    a.OH = OH;
-    a.OW = OW;
-    a.pad_y = 1;
-    a.pad_x = 1;
-    return a;
-  };
-  ConvArgs d1 = conv(L_DCONV1, nullptr, R[1], nullptr, h8, w8, 2 * h8, 2 * w8);
+  PassCtx ps(c, st, x3, n, rg, timed);
+
+  ConvArgs d1 = ps.conv(L_DCONV1, nullptr, R[1], nullptr, h8, w8, 2 * h8, 2 * w8, 1, 1);
   d1.in_u8 = latent;
-  d1.rg = rg;
-  TIMED(L_DCONV1, run(L_DCONV1, d1));
+  d1.rg = rg;  // the re-run's head: it counts the trip
+  TIMED(L_DCONV1, ps.run(L_DCONV1, d1));
   const int h2 = 2 * h8, w2 = 2 * w8;
   if (x3 && use_k3pair() && k3pair_supported(h2, w2)) {  // dconv5 -> dconv6 -> + res, timed as dconv6
-    TIMED(L_DCONV6, launch_pair(c, conv(L_DCONV5, R[1], R[3], nullptr, h2, w2, h2, w2), L_DCONV6, st));
+    TIMED(L_DCONV6, launch_pair(c, ps.conv(L_DCONV5, R[1], R[3], nullptr, h2, w2, h2, w2, 1, 1), L_DCONV6, st));
   } else {
-    TIMED(L_DCONV5, run(L_DCONV5, conv(L_DCONV5, R[1], R[2], nullptr, h2, w2, h2, w2)));
-    TIMED(L_DCONV6, run(L_DCONV6, conv(L_DCONV6, R[2], R[3], R[1], h2, w2, h2, w2)));
+    TIMED(L_DCONV5, ps.run(L_DCONV5, ps.conv(L_DCONV5, R[1], R[2], nullptr, h2, w2, h2, w2, 1, 1)));
+    TIMED(L_DCONV6, ps.run(L_DCONV6, ps.conv(L_DCONV6, R[2], R[3], R[1], h2, w2, h2, w2, 1, 1)));
   }
-  ConvArgs d7 = conv(L_DCONV7, R[3], R[0], nullptr, h2, w2, 2 * h2, 2 * w2);
+  ConvArgs d7 = ps.conv(L_DCONV7, R[3], R[0], nullptr, h2, w2, 2 * h2, 2 * w2, 1, 1);
   // f16x3: dconv7 writes dconv8's per-pixel tap projections (100 B / pixel instead of 256)
   const bool fuse78 = x3;
   if (fuse78) {
@@ -874,10 +843,10 @@ int decode_pass(nic_ctx* c, const uint8_t* latent, int n, int h8, int w8, uint8_
     d7.proj_scale[1] = c->wscale[L_DCONV8][1];
     TIMED(L_DCONV7, launch_dconv7_proj_x3(d7, st));
   } else {
-    TIMED(L_DCONV7, run(L_DCONV7, d7));
+    TIMED(L_DCONV7, ps.run(L_DCONV7, d7));
   }
   Dconv8Args a8{};
-  a8.rg = rgl;
+  a8.rg = ps.rgl;
   a8.in = R[0];
   a8.in_s = (const uint16_t*)R[0];
   a8.zero16 = c->zero16;
@@ -897,9 +866,9 @@ int decode_pass(nic_ctx* c, const uint8_t* latent, int n, int h8, int w8, uint8_
     a8.tiles_x7 = (w2 + 7) / 8;
     TIMED(L_DCONV8, launch_dconv8_gather(a8, st));
   } else {
-    TIMED(L_DCONV8, chained ? chain_add_dconv8(chain, a8) : launch_dconv8(a8, st));
+    TIMED(L_DCONV8, ps.chained ? chain_add_dconv8(ps.chain, a8) : launch_dconv8(a8, st));
   }
-  if (chained) HIP_TRY(launch_fp32_chain(chain, st));
+  HIP_TRY(ps.finish());
   return NIC_OK;
 }
 

@@ -29,6 +29,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <type_traits>
 #include <utility>
 
@@ -37,8 +38,10 @@
 
 namespace nic {
 
-static int device_cus();  // CUs of the current device (cached)
-
+// ====================================================================================
+// [common]  Vector types, static_for, diagnostic stamp macros, elementwise helpers, the f16 range guard,
+// the colour constants and the device CU count.
+// ====================================================================================
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 // Compile-time loop: f(std::integral_constant<int, I>{}) for I = 0 .. N-1 (register arrays
@@ -146,7 +149,62 @@ __device__ __forceinline__ int chain_take(int* q) {
 __device__ __forceinline__ float project(const float* k, float t0, float t1, float t2) {
   return __fadd_rn(__fadd_rn(__fmul_rn(t0, k[0]), __fmul_rn(t1, k[1])), __fmul_rn(t2, k[2]));
 }
+#ifdef NIC_DIAG_KTIME  // diagnostic build only: first-wave start / last-wave exit of each kernel (100 MHz clock)
+__device__ unsigned long long g_ktime[16][2];
+#define KT_BEGIN(sl)                                                                         \
+  do {                                                                                       \
+    if ((threadIdx.x & 63) == 0) atomicMin(&g_ktime[sl][0], __builtin_amdgcn_s_memrealtime()); \
+  } while (0)
+#define KT_END(sl)                                                                           \
+  do {                                                                                       \
+    if ((threadIdx.x & 63) == 0) atomicMax(&g_ktime[sl][1], __builtin_amdgcn_s_memrealtime()); \
+  } while (0)
+struct KtGuard {
+  int sl;
+  __device__ explicit KtGuard(int s) : sl(s) { KT_BEGIN(s); }
+  __device__ ~KtGuard() { KT_END(sl); }
+};
+#define KT_SCOPE(sl) KtGuard kt_guard_(sl)
+extern "C" int nic_diag_ktime(unsigned long long* out, int reset) {
+  if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ktime), sizeof(g_ktime)) != hipSuccess) return -1;
+  if (reset) {
+    unsigned long long init[16][2];
+    for (int k = 0; k < 16; ++k) init[k][0] = ~0ull, init[k][1] = 0;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_ktime), init, sizeof(init)) != hipSuccess) return -1;
+  }
+  return hipDeviceSynchronize() == hipSuccess ? 0 : -1;
+}
+#else
+#define KT_BEGIN(sl) do { } while (0)
+#define KT_END(sl) do { } while (0)
+#define KT_SCOPE(sl) do { } while (0)
+#endif
 
+// CUs of the current device (cached per device)
+static int device_cus() {
+  static std::atomic<int> cache[64];  // relaxed: any thread's value for a device is the same
+  int d = 0;
+  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return 256;
+  int n = cache[d].load(std::memory_order_relaxed);
+  if (!n) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || n <= 0) n = 256;
+    cache[d].store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
+
+hipError_t upload_constants(const float* u8_to_unit, const float* ycbcr, const float* ycbcr_inv, const float* off) {
+  hipError_t e;
+  if ((e = hipMemcpyToSymbol(HIP_SYMBOL(c_u8_to_unit), u8_to_unit, 256 * sizeof(float))) != hipSuccess) return e;
+  if ((e = hipMemcpyToSymbol(HIP_SYMBOL(c_ycbcr), ycbcr, 9 * sizeof(float))) != hipSuccess) return e;
+  if ((e = hipMemcpyToSymbol(HIP_SYMBOL(c_ycbcr_inv), ycbcr_inv, 9 * sizeof(float))) != hipSuccess) return e;
+  return hipMemcpyToSymbol(HIP_SYMBOL(c_ycbcr_off), off, 3 * sizeof(float));
+}
+
+// ====================================================================================
+// [conv_fp32]  The exact-fp32 implicit-GEMM convolution (ConvGeom, stage_halo, store_tile, conv_mfma_*) and
+// its launchers.
+// ====================================================================================
 // ------------------------------------------------------------------------------------
 // Generic implicit-GEMM convolution on fp32 MFMA.
 //
@@ -445,7 +503,56 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvArgs a) {
   conv_mfma_body<CIN, COUT, KS, S, TR, TH, TW, WM, WN, WK, IN_MODE, OUT_MODE, RESID>(a, lds, blockIdx.x, gridDim.x);
 }
 
+// grid of the fp32 one-tile-per-block launches: 8 blocks per CU, 1 for a gated re-run (NIC_CHAIN=0),
+// which exits at its gate unless the split pass tripped (a smaller grid drains faster)
+static int fp32_grid(const RangeGuard& rg, long long jobs) {
+  return (int)std::min<long long>(jobs, (long long)(rg.gate ? 1 : 8) * device_cus());
+}
 
+template <int CIN, int COUT, int KS, int S, bool TR, int TH, int TW, int WM, int WN, int WK, int IN_MODE,
+          int OUT_MODE, bool RESID>
+static hipError_t launch_conv(ConvArgs a, hipStream_t st) {
+  const int gy = TR ? a.H : a.OH, gx = TR ? a.W : a.OW;  // tile grid over coarse / output coords
+  a.tiles_y = (gy + TH - 1) / TH;
+  a.tiles_x = (gx + TW - 1) / TW;
+  const long long jobs = (long long)a.tiles_y * a.tiles_x * a.P;
+  if (jobs == 0) return hipSuccess;
+  if (jobs > INT32_MAX) return hipErrorInvalidValue;
+  const int grid = fp32_grid(a.rg, jobs);
+  hipLaunchKernelGGL((conv_mfma_kernel<CIN, COUT, KS, S, TR, TH, TW, WM, WN, WK, IN_MODE, OUT_MODE, RESID>),
+                     dim3(grid), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_layer(LayerId id, const ConvArgs& a, hipStream_t st) {
+  switch (id) {
+    // encoder (conv1 has its own kernel)
+    case L_CONV2:  // 32->64 k5 s2: 8x8 tile, 4 waves = 2(M) x 2(N)
+      return launch_conv<32, 64, 5, 2, false, 8, 8, 2, 2, 1, IN_F32, OUT_F32, false>(a, st);
+    case L_CONV3:  // 64->64 k3 s1: 8x16 tile, 4 waves along M, each 32 px x 64 co
+      return launch_conv<64, 64, 3, 1, false, 8, 16, 4, 1, 1, IN_F32, OUT_F32, false>(a, st);
+    case L_CONV4:  // + residual
+      return launch_conv<64, 64, 3, 1, false, 8, 16, 4, 1, 1, IN_F32, OUT_F32, true>(a, st);
+    case L_CONV8:  // 64->32 k5 s2 -> u8 latent: 4x8 tile, taps split over the 4 waves
+      return launch_conv<64, 32, 5, 2, false, 4, 8, 1, 1, 4, IN_F32, OUT_U8_LATENT, false>(a, st);
+    // decoder (dconv8 has its own kernel)
+    case L_DCONV1:  // latent u8 -> 64, transposed k5 s2: 8x8 coarse tile, 2(M) x 2(N)
+      return launch_conv<32, 64, 5, 2, true, 8, 8, 2, 2, 1, IN_U8_LATENT, OUT_F32, false>(a, st);
+    case L_DCONV5:  // transposed k3 s1 == conv k3 s1 with flipped kernel
+      return launch_conv<64, 64, 3, 1, false, 8, 16, 4, 1, 1, IN_F32, OUT_F32, false>(a, st);
+    case L_DCONV6:
+      return launch_conv<64, 64, 3, 1, false, 8, 16, 4, 1, 1, IN_F32, OUT_F32, true>(a, st);
+    case L_DCONV7:  // 64->64 transposed k5 s2: 8x16 coarse tile, 4 waves along M
+      return launch_conv<64, 64, 5, 2, true, 8, 16, 4, 1, 1, IN_F32, OUT_F32, false>(a, st);
+    default:
+      return hipErrorInvalidValue;
+  }
+}
+
+// ====================================================================================
+// [split_f16]  Split-f16 building blocks shared by the f16x3 kernels: split4, LDS-DMA helpers, HaloPieces,
+// HaloDma, add_f16_pair, swap16_pair, TileWalk.
+// ====================================================================================
 // ------------------------------------------------------------------------------------
 // Split-f16 ("f16x3") implicit-GEMM convolution on v_mfma_f32_32x32x16_f16.
 //
@@ -614,36 +721,14 @@ struct HaloPieces {
 // left or right image edge, retargets the slots of out-of-image columns out of range.
 constexpr unsigned kDmaOOR = 0x80000000u;  // an offset past any plane: the DMA writes zeros
 constexpr int kBufWord3 = 0x00020000;      // gfx9 raw-buffer resource word 3
-#ifdef NIC_DIAG_KTIME  // diagnostic build only: first-wave start / last-wave exit of each kernel (100 MHz clock)
-__device__ unsigned long long g_ktime[16][2];
-#define KT_BEGIN(sl)                                                                         \
-  do {                                                                                       \
-    if ((threadIdx.x & 63) == 0) atomicMin(&g_ktime[sl][0], __builtin_amdgcn_s_memrealtime()); \
-  } while (0)
-#define KT_END(sl)                                                                           \
-  do {                                                                                       \
-    if ((threadIdx.x & 63) == 0) atomicMax(&g_ktime[sl][1], __builtin_amdgcn_s_memrealtime()); \
-  } while (0)
-struct KtGuard {
-  int sl;
-  __device__ explicit KtGuard(int s) : sl(s) { KT_BEGIN(s); }
-  __device__ ~KtGuard() { KT_END(sl); }
-};
-#define KT_SCOPE(sl) KtGuard kt_guard_(sl)
-extern "C" int nic_diag_ktime(unsigned long long* out, int reset) {
-  if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ktime), sizeof(g_ktime)) != hipSuccess) return -1;
-  if (reset) {
-    unsigned long long init[16][2];
-    for (int k = 0; k < 16; ++k) init[k][0] = ~0ull, init[k][1] = 0;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_ktime), init, sizeof(init)) != hipSuccess) return -1;
-  }
-  return hipDeviceSynchronize() == hipSuccess ? 0 : -1;
+// resource over one plane of plane_bytes bytes (offsets past it read zeros and drop stores):
+// the plane at `plane`, or plane p of a batch of such planes at `base`
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t plane_rsrc(const void* plane, unsigned plane_bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc((void*)plane, (short)0, (int)plane_bytes, kBufWord3);
 }
-#else
-#define KT_BEGIN(sl) do { } while (0)
-#define KT_END(sl) do { } while (0)
-#define KT_SCOPE(sl) do { } while (0)
-#endif
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t plane_rsrc(const void* base, size_t p, unsigned plane_bytes) {
+  return plane_rsrc((const char*)base + p * plane_bytes, plane_bytes);
+}
 
 __device__ __forceinline__ void dma16_buf(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, char* lds_wave_base) {
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)lds_wave_base, 16, (int)voff, 0, 0, 0);
@@ -675,8 +760,7 @@ struct HaloDma {
   // DMA the halo with origin (gy0, gx0) of the plane at `plane` (plane_bytes long) into buf
   __device__ __forceinline__ void issue(char* buf, const char* plane, unsigned plane_bytes, int W, int gy0, int gx0,
                                         int pw) const {
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)plane, (short)0, (int)plane_bytes,
-                                                                          kBufWord3);
+    const __amdgpu_buffer_rsrc_t rsrc = plane_rsrc(plane, plane_bytes);
     const unsigned org = (unsigned)((gy0 * W + gx0) * CIN * 4);  // may wrap: then out of range
     const bool edge = gx0 < 0 || gx0 + G::HW > W;                // wave-uniform
 #pragma unroll
@@ -704,23 +788,6 @@ __device__ __forceinline__ float add_f16_pair(unsigned H, unsigned L) {
   return t;
 }
 
-// ------------------------------------------------------------------------------------
-// Weight-stationary persistent conv (split-f16 on v_mfma_f32_16x16x32_f16) over a
-// stride-1 window of KH x KW taps: the k3 s1 layers (KH = KW = 3), and each of the four
-// sub-pixel phases of the k5 s2 Conv2DTranspose dconv7 (2x2, 2x3, 3x2, 3x3 taps, TRP).
-// Wave w owns output channels 16w .. 16w+15 and keeps their weights for every tap of its
-// window and every input channel in VGPRs (the MFMA A operand: w_hi and w_lo, at most
-// 9 x 2 k32-steps x 2 = 36 fragments = 144 VGPRs), loaded once per block.  A launch is cut
-// into block groups, one per (tap set, model); a group's blocks loop over that model's
-// tiles, so no weight byte is re-read per tile (the one-tile-per-block kernels move ~8 KB
-// of weight fragments per wave and tap through L2).  The halo of tile i+1 is DMA'd into
-// the other LDS buffer by all waves while tile i's MFMAs run; the epilogue of tile i runs
-// after the next barrier so its stores overlap tile i+1.
-// D[co][pixel] per 16-pixel tile (two 8-pixel rows): lane (g, l16) holds channels
-// 16w + 4g .. +3 of pixel l16.  Phase (py, px) of a transposed layer writes fine pixel
-// (2y + py, 2x + px) for coarse position (y, x), from halo taps (iy, ix) < (KH, KW) at
-// origin (y - 1, x - 1) with weight tap tb + iy * KW + ix (host phase-major repack).
-// ------------------------------------------------------------------------------------
 // 16x16 D layout -> 16-B split stores.  Lane (g, l16) holds hi and lo of 4 channels
 // (4g..4g+3 of its wave's 16); v_permlane16_swap (odd 16-lane rows of the first operand <->
 // even rows of the second) leaves even-g lanes with the hi of 8 channels [own | g+1's] and
@@ -751,13 +818,27 @@ __device__ __forceinline__ void unswap16(const u32x4& q, f16x4& hi, f16x4& lo) {
   lo = __builtin_bit_cast(f16x4, y);
 }
 
-// LDS halo image of the weight-stationary kernels (3x3 window, stride 1): unpadded 256-B
-// pixel records (16 slots: [hi 64 ch | lo 64 ch] in 16-B chunks), rows of HW records, and
-// chunk c of halo column hx stored in slot c ^ (2 hx mod 16).  The B fragment of
-// v_mfma_f32_16x16x32_f16 has lane (g, l16) read chunk c = 4 ks + 8 hl + g of pixel l16 (two
-// 8-pixel rows); every ds_read_b128 16-lane group ({0-3, 12-15, 20-27}, ...) then hits 16
-// distinct slots for every tap shift (exhaustive search over x-linear / XOR swizzles), and
-// the image is whole 1-KB DMA pieces with no pad slots (25 instead of 32 for 10 x 10).
+// The split-f16 epilogue.  Rule: a kernel that writes split activations takes its store record
+// from split_record, which never skips the range guard (conv1_colour_body, whose store layout
+// pairs two vectors, is the one site that tracks and packs by hand).  split_act is the
+// activation in front of it; the sites that zero out-of-plane lanes and d1all_wave spell it out
+// instead, with the reason in a comment at each.
+// Conv sum -> * 2^-k -> BiasAdd -> leaky_relu of one accumulator vector
+__device__ __forceinline__ f32x4 split_act(const f32x4& acc, float scale, const f32x4& bias) {
+  f32x4 v;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) v[r] = leaky02(scale_bias(acc[r], scale, bias[r]));
+  return v;
+}
+// finished values -> this lane's 16-B store record (swap16_pair: EXEC full); lanes that are
+// `valid` (inside the plane) feed the range guard's running max m
+__device__ __forceinline__ u32x4 split_record(const f32x4& v, bool valid, float& m) {
+  if (valid) range_track(m, v);
+  f16x4 hi, lo;
+  split4(v, hi, lo);
+  return swap16_pair(hi, lo);
+}
+
 // Tile coordinates of a persistent block's tiles bi, bi + nb, bi + 2 nb, ... of a plane
 // group (per_plane = tiles_y x tiles_x tiles per plane), walked in order without an integer
 // division per tile (each call sequence -- DMA issue, conv1, epilogue -- keeps its own walk).
@@ -795,6 +876,33 @@ struct TileWalk {
   }
 };
 
+// ====================================================================================
+// [conv_ws]  Weight-stationary k3 s1 conv and the dconv7 phases (ws_body, conv_ws_kernel, launch_ws).
+// ====================================================================================
+// ------------------------------------------------------------------------------------
+// Weight-stationary persistent conv (split-f16 on v_mfma_f32_16x16x32_f16) over a
+// stride-1 window of KH x KW taps: the k3 s1 layers (KH = KW = 3), and each of the four
+// sub-pixel phases of the k5 s2 Conv2DTranspose dconv7 (2x2, 2x3, 3x2, 3x3 taps, TRP).
+// Wave w owns output channels 16w .. 16w+15 and keeps their weights for every tap of its
+// window and every input channel in VGPRs (the MFMA A operand: w_hi and w_lo, at most
+// 9 x 2 k32-steps x 2 = 36 fragments = 144 VGPRs), loaded once per block.  A launch is cut
+// into block groups, one per (tap set, model); a group's blocks loop over that model's
+// tiles, so no weight byte is re-read per tile (the one-tile-per-block kernels move ~8 KB
+// of weight fragments per wave and tap through L2).  The halo of tile i+1 is DMA'd into
+// the other LDS buffer by all waves while tile i's MFMAs run; the epilogue of tile i runs
+// after the next barrier so its stores overlap tile i+1.
+// D[co][pixel] per 16-pixel tile (two 8-pixel rows): lane (g, l16) holds channels
+// 16w + 4g .. +3 of pixel l16.  Phase (py, px) of a transposed layer writes fine pixel
+// (2y + py, 2x + px) for coarse position (y, x), from halo taps (iy, ix) < (KH, KW) at
+// origin (y - 1, x - 1) with weight tap tb + iy * KW + ix (host phase-major repack).
+// ------------------------------------------------------------------------------------
+// LDS halo image of the weight-stationary kernels (3x3 window, stride 1): unpadded 256-B
+// pixel records (16 slots: [hi 64 ch | lo 64 ch] in 16-B chunks), rows of HW records, and
+// chunk c of halo column hx stored in slot c ^ (2 hx mod 16).  The B fragment of
+// v_mfma_f32_16x16x32_f16 has lane (g, l16) read chunk c = 4 ks + 8 hl + g of pixel l16 (two
+// 8-pixel rows); every ds_read_b128 16-lane group ({0-3, 12-15, 20-27}, ...) then hits 16
+// distinct slots for every tap shift (exhaustive search over x-linear / XOR swizzles), and
+// the image is whole 1-KB DMA pieces with no pad slots (25 instead of 32 for 10 x 10).
 template <int CIN, int TH, int TW>
 struct GeomWS {
   static_assert(CIN == 64, "record geometry searched for Cin 64");
@@ -1003,17 +1111,14 @@ __device__ __forceinline__ void ws_body(const ConvArgs& a, char* lds, int model,
       __amdgpu_buffer_rsrc_t out_rs;
       unsigned out_org = 0;
       if constexpr (!PROJ) {
-        out_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(a.out_s + (size_t)ep_p * out_plane / 2), (short)0,
-                                                   (int)out_plane, kBufWord3);
+        out_rs = plane_rsrc(a.out_s, ep_p, out_plane);
         out_org = TRP ? (unsigned)(((2 * ep_y + py) * a.OW + 2 * ep_x + px) * PXB)
                       : (unsigned)((ep_y * a.OW + ep_x) * PXB);
       }
 #pragma unroll
       for (int m = 0; m < MT; ++m) {
         const int y = ep_y + 2 * m + (l16 >> 3), x = ep_x + (l16 & 7);
-        f32x4 v;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = leaky02(scale_bias(acc[m][r], scale, bias[r]));
+        f32x4 v = split_act(acc[m], scale, bias);
         if constexpr (RESID) {
           f16x4 rh, rl;
           if constexpr (kResDma) rq[m] = *(const u32x4*)(res_lds + m * 1024 + lane * 16);
@@ -1025,10 +1130,8 @@ __device__ __forceinline__ void ws_body(const ConvArgs& a, char* lds, int model,
             v[r] = __fadd_rn(v[r], add_f16_pair<r & 1>(H[r >> 1], L[r >> 1]));
           });
         }
-        if (y < a.H && x < a.W) range_track(rmax, v);
-        f16x4 hi, lo;
-        split4(v, hi, lo);
-        u32x4 q = swap16_pair(hi, lo);  // even g: hi of 8 channels, odd g: lo of the same 8
+        // even g: hi of 8 channels, odd g: lo of the same 8
+        const u32x4 q = split_record(v, y < a.H && x < a.W, rmax);
         if constexpr (PROJ) {  // chunk (g & 1) * 8 + 2w + g / 2 of pixel 16m + l16
           const int pp = 16 * m + l16, ch = (g & 1) * 8 + 2 * wave + (g >> 1);
           *(u32x4*)(hproj + pp * 256 + ((ch ^ (pp & 15)) << 4)) = q;
@@ -1062,8 +1165,7 @@ __device__ __forceinline__ void ws_body(const ConvArgs& a, char* lds, int model,
     tile_take(it_ep, ep_p, ep_y, ep_x);
     if constexpr (RESID) {  // consumed by this tile's epilogue, after the next vmcnt(0)
       if constexpr (kResDma) {  // this wave's own LDS region: its reads came first
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(a.res_s + (size_t)ep_p * out_plane / 2), (short)0, (int)out_plane, kBufWord3);
+        const __amdgpu_buffer_rsrc_t rs = plane_rsrc(a.res_s, ep_p, out_plane);
         const unsigned org = (unsigned)((ep_y * a.OW + ep_x) * PXB);
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
@@ -1140,6 +1242,85 @@ __device__ __forceinline__ void ws_body(const ConvArgs& a, char* lds, int model,
 #endif
 }
 
+// Block groups: group gi = blocks [ws_blk[gi], ws_blk[gi + 1]), model gi & 1, tap set gi >> 1
+// (the phase of a transposed layer).
+template <int CIN, int COUT, int TH, int TW, bool RESID, bool TRP, bool PROJ = false>
+__global__ __launch_bounds__(64 * (COUT / 16), 2) void conv_ws_kernel(ConvArgs a) {
+  KT_SCOPE(6);
+  using G = GeomWS<CIN, TH, TW>;
+  __shared__ __attribute__((aligned(16)))
+  char lds[2 * G::HALO_BYTES + (PROJ ? 2 * (CIN / 32) * 2 * 64 * 16 + TH * TW * COUT * 4 : 0) +
+           (RESID && kResDma ? (COUT / 16) * (TH * TW / 16) * 1024 : 0)];
+  // ws_xcd: block b runs on XCD b % 8; the logical block x * (G / 8) + min(x, G % 8) + b / 8
+  // (x = b % 8, a bijection onto [0, G)) gives each XCD a contiguous range of the groups'
+  // blocks, so the tiles its blocks take at one time are neighbours whose shared halo rows /
+  // columns hit that XCD's L2
+  const int xcd = blockIdx.x & 7, ng = gridDim.x;
+  const int lb = a.ws_xcd ? xcd * (ng >> 3) + min(xcd, ng & 7) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+  int gi = 0;
+  while (gi + 1 < a.ws_ngrp && lb >= a.ws_blk[gi + 1]) ++gi;
+  const int bi = lb - a.ws_blk[gi], nb = a.ws_blk[gi + 1] - a.ws_blk[gi];
+  const int model = gi & 1;
+  if constexpr (!TRP) {
+    ws_body<CIN, COUT, TH, TW, RESID, 3, 3, false>(a, lds, model, bi, nb, 0, 0, 0);
+  } else if (a.ws_ngrp == 2) {
+    // every block runs all four sub-pixel phases over its share of the model's tiles, one
+    // after the other (weights reloaded per phase; dconv8's w8 copied to LDS once): equal
+    // work per block whatever the per-tile overheads of the phases
+    ws_body<CIN, COUT, TH, TW, false, 3, 3, true, PROJ>(a, lds, model, bi, nb, 16, 1, 1);
+    ws_body<CIN, COUT, TH, TW, false, 2, 3, true, PROJ>(a, lds, model, bi, nb, 4, 0, 1, false);
+    ws_body<CIN, COUT, TH, TW, false, 3, 2, true, PROJ>(a, lds, model, bi, nb, 10, 1, 0, false);
+    ws_body<CIN, COUT, TH, TW, false, 2, 2, true, PROJ>(a, lds, model, bi, nb, 0, 0, 0, false);
+  } else {
+    switch (gi >> 1) {  // phase-major tap bases 0, 4, 10, 16 (for_each_phase_tap)
+      case 0: ws_body<CIN, COUT, TH, TW, false, 2, 2, true, PROJ>(a, lds, model, bi, nb, 0, 0, 0); break;
+      case 1: ws_body<CIN, COUT, TH, TW, false, 2, 3, true, PROJ>(a, lds, model, bi, nb, 4, 0, 1); break;
+      case 2: ws_body<CIN, COUT, TH, TW, false, 3, 2, true, PROJ>(a, lds, model, bi, nb, 10, 1, 0); break;
+      default: ws_body<CIN, COUT, TH, TW, false, 3, 3, true, PROJ>(a, lds, model, bi, nb, 16, 1, 1); break;
+    }
+  }
+}
+
+// Weight-stationary launch: 2 resident blocks per CU, split into groups (tap set, model)
+// in proportion to each group's MFMA work (planes x taps).
+template <int CIN, int COUT, int TH, int TW, bool RESID, bool TRP, bool PROJ = false>
+static hipError_t launch_ws(ConvArgs a, hipStream_t st) {
+  a.tiles_y = (a.H + TH - 1) / TH;
+  a.tiles_x = (a.W + TW - 1) / TW;
+  const long long per_plane = (long long)a.tiles_y * a.tiles_x;
+  const long long nt = per_plane * a.P;
+  if (nt == 0) return hipSuccess;
+  if (nt > INT32_MAX || a.P != 3 * a.nimg) return hipErrorInvalidValue;
+  // HaloDma: 32-bit plane offsets, out-of-range slots past the plane (kDmaOOR)
+  if ((long long)a.H * a.W * CIN * 4 >= (1LL << 30)) return hipErrorInvalidValue;
+  a.ntiles = (int)nt;
+  // one block group per model (transposed layers: every block runs the four phases over its
+  // tiles; per-phase groups measured 6 % slower, DESIGN section 5)
+  a.ws_taps = TRP ? 25 : 9;
+  a.ws_ngrp = 2;
+  long long work[2], total = 0;
+  for (int gi = 0; gi < 2; ++gi) {
+    work[gi] = ((gi & 1) ? a.P - a.nimg : a.nimg) * per_plane;
+    total += work[gi];
+  }
+  const int target = 2 * device_cus();  // 2 resident blocks per CU
+  a.ws_blk[0] = 0;
+  for (int gi = 0; gi < a.ws_ngrp; ++gi) {
+    const long long tiles = ((gi & 1) ? a.P - a.nimg : a.nimg) * per_plane;
+    long long b = (work[gi] * target + total / 2) / total;
+    b = b < 1 ? 1 : b > tiles ? tiles : b;
+    a.ws_blk[gi + 1] = a.ws_blk[gi] + (int)b;
+  }
+  a.ws_xcd = 1;
+  hipLaunchKernelGGL((conv_ws_kernel<CIN, COUT, TH, TW, RESID, TRP, PROJ>), dim3(a.ws_blk[a.ws_ngrp]),
+                     dim3(64 * (COUT / 16)), 0, st, a);
+  return hipGetLastError();
+}
+
+// ====================================================================================
+// [conv_ws2]  Tap-split weight-stationary k5 s2 forward convs: conv2 / conv8 (ws2_wave, conv_ws2_kernel,
+// launch_ws2).
+// ====================================================================================
 // ------------------------------------------------------------------------------------
 // Weight-stationary persistent conv for the k5 s2 forward layers (conv2 32->64, conv8
 // 64->32 -> u8 latent), split-f16 on v_mfma_f32_16x16x32_f16.  25 taps of resident
@@ -1162,9 +1343,6 @@ struct GeomS2 {
   static constexpr int HALO_BYTES = NPIECE * 1024;
   static __device__ __forceinline__ int col(int hx) { return (hx & 1) * HE + (hx >> 1); }
 };
-
-
-constexpr int C12_PH = 41;  // conv12's colour patch rows / cols: (19 - 1) * 2 + 5
 
 // HIST (conv8 in nic_encode_entropy): the latent histogram counted inside conv8.  The ts = 0
 // epilogue stores each tile's packed codes in LDS; the ts = 1 waves (idle ~1,700 cycles per
@@ -1317,8 +1495,7 @@ __device__ __forceinline__ void ws2_wave(const ConvArgs& a, char* lds, int model
     if (OUT_MODE == OUT_U8_LATENT && i > 1) return;
 #endif
     const int gy0 = 2 * t0y - a.pad_y, gx0 = 2 * t0x - a.pad_x;
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((const char*)a.in_s + (size_t)p * plane_bytes), (short)0, (int)plane_bytes, kBufWord3);
+    const __amdgpu_buffer_rsrc_t rsrc = plane_rsrc(a.in_s, p, plane_bytes);
     const unsigned org = (unsigned)((gy0 * a.W + gx0) * CIN * 4);
     char* buf = lds + (i & 1) * G::HALO_BYTES;
 #pragma unroll
@@ -1369,14 +1546,9 @@ __device__ __forceinline__ void ws2_wave(const ConvArgs& a, char* lds, int model
             for (int r = 0; r < 4; ++r) acc[m][r] = __fadd_rn(acc[m][r], q[r]);
           }
           const int oy = ep_y + 2 * m + (l16 >> 3), ox = ep_x + (l16 & 7);
-          f32x4 v;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = leaky02(scale_bias(acc[m][r], scale, bias[r]));
+          f32x4 v = split_act(acc[m], scale, bias);
           if constexpr (OUT_MODE == OUT_SPLIT) {
-            if (oy < a.OH && ox < a.OW) range_track(rmax, v);
-            f16x4 hi, lo;
-            split4(v, hi, lo);
-            const u32x4 q = swap16_pair(hi, lo);
+            const u32x4 q = split_record(v, oy < a.OH && ox < a.OW, rmax);
             if (oy < a.OH && ox < a.OW)
               *(u32x4*)(a.out_s + (((size_t)ep_p * a.OH + oy) * a.OW + ox) * COUT * 2 + st_off) = q;
           } else {  // clip, round(x*255) into the latent layout (N, h, w, 96)
@@ -1495,6 +1667,100 @@ __device__ __forceinline__ void ws2_wave(const ConvArgs& a, char* lds, int model
 #undef WS2_MARK
 }
 
+// XCD-contiguous tile positions: block b of a group of nb runs on XCD
+// (base + b) % 8, so give the blocks of one XCD consecutive positions in each round of nb
+// tiles -- neighbouring tiles, whose halos overlap, are then fetched into one L2.
+__device__ __forceinline__ int xcd_pos(int b, int nb) {
+  const int x = b & 7, q = nb >> 3, r = nb & 7;
+  return x * q + (x < r ? x : r) + (b >> 3);  // prefix of the XCD classes before x, then rank
+}
+
+template <int CIN, int COUT, int NTS, int TH, int OUT_MODE, bool HIST = false>
+__global__ __launch_bounds__(64 * (COUT / 16) * NTS) void conv_ws2_kernel(ConvArgs a) {
+  KT_SCOPE(3);
+  using G = GeomS2<CIN, TH, 8>;
+  constexpr int NCG = COUT / 16;
+  static_assert(NCG * NTS == 8, "8 waves per block");
+  constexpr int PARTS = 2 * (NTS - 1) * NCG * (TH / 2) * 1024;
+  __shared__ __attribute__((aligned(16)))
+  char lds[2 * G::HALO_BYTES + PARTS + (HIST ? HIST_LDS : 0)];
+  int gi = 0;
+  while (gi + 1 < a.ws_ngrp && (int)blockIdx.x >= a.ws_blk[gi + 1]) ++gi;
+  const int nb = a.ws_blk[gi + 1] - a.ws_blk[gi];
+  const int bi = xcd_pos(blockIdx.x - a.ws_blk[gi], nb);
+  const int ts = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) / NCG;
+  static_for<NTS>([&](auto tsc) {
+    constexpr int TS = decltype(tsc)::value;
+    if (ts == TS) ws2_wave<CIN, COUT, NTS, TH, OUT_MODE, TS, HIST>(a, lds, gi, bi, nb);
+  });
+}
+
+// k5 s2 forward convs: one 8-wave block per CU, split into a Y and a CbCr group in
+// proportion to their planes.
+static void ws2_groups(int nimg, long long per_plane, int* by, int* bc) {
+  const int target = device_cus();
+  const long long ty = per_plane * nimg, tc = per_plane * 2 * nimg;
+  long long y = std::max(1LL, std::min((long long)(target + 1) / 3, ty));
+  *by = (int)y;
+  *bc = (int)std::max(1LL, std::min((long long)target - y, tc));
+}
+
+// conv8's tile grid (4 x 8 output tiles) and the fold's condition: every block meets each plane
+// of its group in >= 2 consecutive tiles (group blocks <= tiles per plane / 2) -- large frames
+// (config 5); batches of small images run the two-call form
+bool hist_fold_supported(int nimg, int h8, int w8) {
+  if (nimg <= 0 || h8 <= 0 || w8 <= 0) return false;
+  const long long pp = (long long)((h8 + 3) / 4) * ((w8 + 7) / 8);
+  int by, bc;
+  ws2_groups(nimg, pp, &by, &bc);
+  return 2LL * by <= pp && 2LL * bc <= pp;
+}
+
+size_t hist_fold_scratch_bytes(int nimg, int h8, int w8) {  // the counts [3 nimg][256]
+  (void)h8;
+  (void)w8;
+  return (size_t)3 * nimg * 256 * sizeof(uint32_t);
+}
+
+// k5 s2 forward convs on the tap-split weight-stationary kernel (conv2 of conv12 with PIPE12,
+// conv8 with the latent histogram fold when a.hist_part is set)
+__global__ void conv12_kernel(ConvArgs a);  // section [conv12]: PIPE12 launches it on this grid
+template <int CIN, int COUT, int NTS, int TH, int OUT_MODE, bool PIPE12 = false>
+static hipError_t launch_ws2(ConvArgs a, hipStream_t st) {
+  a.tiles_y = (a.OH + TH - 1) / TH;
+  a.tiles_x = (a.OW + 7) / 8;
+  const long long per_plane = (long long)a.tiles_y * a.tiles_x;
+  const long long nt = per_plane * a.P;
+  if (nt == 0) return hipSuccess;
+  if (nt > INT32_MAX || a.P != 3 * a.nimg) return hipErrorInvalidValue;
+  a.ntiles = (int)nt;
+  a.ws_taps = 25;
+  a.ws_ngrp = 2;
+  int by, bc;
+  ws2_groups(a.nimg, per_plane, &by, &bc);
+  a.ws_blk[0] = 0;
+  a.ws_blk[1] = by;
+  a.ws_blk[2] = by + bc;
+  if constexpr (PIPE12) {
+    hipLaunchKernelGGL(conv12_kernel, dim3(a.ws_blk[2]), dim3(512), 0, st, a);
+  } else if constexpr (OUT_MODE == OUT_U8_LATENT) {
+    if (a.hist_part) {
+      if (!hist_fold_supported(a.nimg, a.OH, a.OW)) return hipErrorInvalidValue;
+      hipLaunchKernelGGL((conv_ws2_kernel<CIN, COUT, NTS, TH, OUT_MODE, true>), dim3(a.ws_blk[2]), dim3(512), 0, st, a);
+    } else {
+      hipLaunchKernelGGL((conv_ws2_kernel<CIN, COUT, NTS, TH, OUT_MODE>), dim3(a.ws_blk[2]), dim3(512), 0, st, a);
+    }
+  } else {
+    hipLaunchKernelGGL((conv_ws2_kernel<CIN, COUT, NTS, TH, OUT_MODE>), dim3(a.ws_blk[2]), dim3(512), 0, st, a);
+  }
+  return hipGetLastError();
+}
+
+// ====================================================================================
+// [conv12]  conv1 + conv2 fused: the colour pre-pass, c12r_wave, conv12_kernel and its launcher.
+// ====================================================================================
+constexpr int C12_PH = 41;  // conv12's colour patch rows / cols: (19 - 1) * 2 + 5
+
 // conv1 + conv2 fused and software-pipelined (split-f16; encoder.py:10-11, 20-21 with the
 // colour front end utils.py:74-77): conv2 weight-stationary on 8 x 8 output tiles, conv1
 // computed per tile into conv2's LDS halo (its 19 x 19 outputs), two halo buffers so that conv1
@@ -1539,8 +1805,8 @@ struct C12PatchDma {
       const int k = cg + 4 * j;  // wave-uniform
       if (k >= 2 * C12_PPIECE) break;
       const int hl = k / C12_PPIECE;
-      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-          (void*)(a.cplane + ((size_t)hl * a.P + p) * cp_plane), (short)0, (int)(cp_plane * 2), kBufWord3);
+      const __amdgpu_buffer_rsrc_t rs =
+          plane_rsrc(a.cplane + ((size_t)hl * a.P + p) * cp_plane, (unsigned)(cp_plane * 2));
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(dst + hl * C12_PLANE + (k % C12_PPIECE) * 256 * C12_PDW),
                                                4 * C12_PDW, (int)(doff[j] == kDmaOOR ? kDmaOOR : doff[j] + org), 0, 0, 0);
     }
@@ -1864,13 +2130,10 @@ __device__ __forceinline__ void c12r_wave(const ConvArgs& a, char* lds, int mode
         const bool in1 = qv && (unsigned)(c1y0 + hy) < (unsigned)a.H && (unsigned)(c1x0 + hx) < (unsigned)a.W;
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct) {
-          f32x4 v;
+          f32x4 v;  // activation by hand: selecting after split_act changed the s_nop count
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = in1 ? leaky02(scale_bias(c1[u][ct][r], scale1, b1[ct][r])) : 0.f;
-          range_track(rmax, v);
-          f16x4 hi, lo;
-          split4(v, hi, lo);
-          const u32x4 q16 = swap16_pair(hi, lo);
+          const u32x4 q16 = split_record(v, true, rmax);  // the zeros leave the max as it is
           if (qv)
             *(u32x4*)(halo + hy * G::RPB + G::col(hx) * G::PSB + (g & 1) * CIN * 2 + (16 * ct + 4 * (g & ~1)) * 2) = q16;
         }
@@ -1909,14 +2172,8 @@ __device__ __forceinline__ void c12r_wave(const ConvArgs& a, char* lds, int mode
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
           const int oy = t0y + 2 * m + (l16 >> 3), ox = t0x + (l16 & 7);
-          f32x4 v;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = leaky02(scale_bias(acc[m][r], scale, bias[r]));
           const bool inside = oy < a.OH && ox < a.OW;
-          if (inside) range_track(rmax, v);
-          f16x4 hi, lo;
-          split4(v, hi, lo);
-          const u32x4 qv = swap16_pair(hi, lo);
+          const u32x4 qv = split_record(split_act(acc[m], scale, bias), inside, rmax);
           if (inside) *(u32x4*)(a.out_s + (((size_t)p * a.OH + oy) * a.OW + ox) * COUT * 2 + st_off) = qv;
         }
       }
@@ -1951,14 +2208,6 @@ __device__ __forceinline__ void c12r_wave(const ConvArgs& a, char* lds, int mode
   range_report(a.rg, rmax);
 }
 
-// XCD-contiguous tile positions: block b of a group of nb runs on XCD
-// (base + b) % 8, so give the blocks of one XCD consecutive positions in each round of nb
-// tiles -- neighbouring tiles, whose halos overlap, are then fetched into one L2.
-__device__ __forceinline__ int xcd_pos(int b, int nb) {
-  const int x = b & 7, q = nb >> 3, r = nb & 7;
-  return x * q + (x < r ? x : r) + (b >> 3);  // prefix of the XCD classes before x, then rank
-}
-
 __global__ __launch_bounds__(512) void conv12_kernel(ConvArgs a) {
   KT_SCOPE(1);
   using G = GeomS2<32, 8, 8>;
@@ -1974,65 +2223,27 @@ __global__ __launch_bounds__(512) void conv12_kernel(ConvArgs a) {
     c12r_wave<1>(a, lds, gi, bi, nb);
 }
 
-template <int CIN, int COUT, int NTS, int TH, int OUT_MODE, bool HIST = false>
-__global__ __launch_bounds__(64 * (COUT / 16) * NTS) void conv_ws2_kernel(ConvArgs a) {
-  KT_SCOPE(3);
-  using G = GeomS2<CIN, TH, 8>;
-  constexpr int NCG = COUT / 16;
-  static_assert(NCG * NTS == 8, "8 waves per block");
-  constexpr int PARTS = 2 * (NTS - 1) * NCG * (TH / 2) * 1024;
-  __shared__ __attribute__((aligned(16)))
-  char lds[2 * G::HALO_BYTES + PARTS + (HIST ? HIST_LDS : 0)];
-  int gi = 0;
-  while (gi + 1 < a.ws_ngrp && (int)blockIdx.x >= a.ws_blk[gi + 1]) ++gi;
-  const int nb = a.ws_blk[gi + 1] - a.ws_blk[gi];
-  const int bi = xcd_pos(blockIdx.x - a.ws_blk[gi], nb);
-  const int ts = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) / NCG;
-  static_for<NTS>([&](auto tsc) {
-    constexpr int TS = decltype(tsc)::value;
-    if (ts == TS) ws2_wave<CIN, COUT, NTS, TH, OUT_MODE, TS, HIST>(a, lds, gi, bi, nb);
-  });
+hipError_t launch_conv12_x3(const ConvArgs& a0, hipStream_t st) {
+  ConvArgs a = a0;
+  if (!a.rgb || !a.wx1 || !a.bias1 || a.H0 <= 0 || a.W0 <= 0) return hipErrorInvalidValue;
+  if (!a.cplane || a.OH <= 0 || a.OW <= 0) return hipErrorInvalidValue;
+  int oy, ox;
+  c12_plane_geom(a.OH, a.OW, a.pad_y, a.pad_x, a.p1y, a.p1x, &oy, &ox, &a.cp_h, &a.cp_w);
+  // 32-bit byte offsets inside one plane (buffer resources of the patch DMA)
+  if ((long long)a.cp_h * a.cp_w * 2 >= (1LL << 31)) return hipErrorInvalidValue;
+  const long long per_img = (long long)a.cp_h * (a.cp_w / 4);  // < 2^31 (checked above)
+  if (per_img == 0 || a.nimg == 0) return hipSuccess;
+  if (a.nimg > 65535 || (long long)a.W0 * 3 >= (1LL << 31)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(colour_split_kernel, dim3((unsigned)((per_img + 255) / 256), a.nimg),
+                     dim3(256), 0, st, a.rgb, a.cplane, a.nimg, a.H0, a.W0, oy, ox, a.cp_h, a.cp_w);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return launch_ws2<32, 64, 2, 8, OUT_SPLIT, true>(a, st);
 }
 
-// Block groups: group gi = blocks [ws_blk[gi], ws_blk[gi + 1]), model gi & 1, tap set gi >> 1
-// (the phase of a transposed layer).
-template <int CIN, int COUT, int TH, int TW, bool RESID, bool TRP, bool PROJ = false>
-__global__ __launch_bounds__(64 * (COUT / 16), 2) void conv_ws_kernel(ConvArgs a) {
-  KT_SCOPE(6);
-  using G = GeomWS<CIN, TH, TW>;
-  __shared__ __attribute__((aligned(16)))
-  char lds[2 * G::HALO_BYTES + (PROJ ? 2 * (CIN / 32) * 2 * 64 * 16 + TH * TW * COUT * 4 : 0) +
-           (RESID && kResDma ? (COUT / 16) * (TH * TW / 16) * 1024 : 0)];
-  // ws_xcd: block b runs on XCD b % 8; the logical block x * (G / 8) + min(x, G % 8) + b / 8
-  // (x = b % 8, a bijection onto [0, G)) gives each XCD a contiguous range of the groups'
-  // blocks, so the tiles its blocks take at one time are neighbours whose shared halo rows /
-  // columns hit that XCD's L2
-  const int xcd = blockIdx.x & 7, ng = gridDim.x;
-  const int lb = a.ws_xcd ? xcd * (ng >> 3) + min(xcd, ng & 7) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-  int gi = 0;
-  while (gi + 1 < a.ws_ngrp && lb >= a.ws_blk[gi + 1]) ++gi;
-  const int bi = lb - a.ws_blk[gi], nb = a.ws_blk[gi + 1] - a.ws_blk[gi];
-  const int model = gi & 1;
-  if constexpr (!TRP) {
-    ws_body<CIN, COUT, TH, TW, RESID, 3, 3, false>(a, lds, model, bi, nb, 0, 0, 0);
-  } else if (a.ws_ngrp == 2) {
-    // every block runs all four sub-pixel phases over its share of the model's tiles, one
-    // after the other (weights reloaded per phase; dconv8's w8 copied to LDS once): equal
-    // work per block whatever the per-tile overheads of the phases
-    ws_body<CIN, COUT, TH, TW, false, 3, 3, true, PROJ>(a, lds, model, bi, nb, 16, 1, 1);
-    ws_body<CIN, COUT, TH, TW, false, 2, 3, true, PROJ>(a, lds, model, bi, nb, 4, 0, 1, false);
-    ws_body<CIN, COUT, TH, TW, false, 3, 2, true, PROJ>(a, lds, model, bi, nb, 10, 1, 0, false);
-    ws_body<CIN, COUT, TH, TW, false, 2, 2, true, PROJ>(a, lds, model, bi, nb, 0, 0, 0, false);
-  } else {
-    switch (gi >> 1) {  // phase-major tap bases 0, 4, 10, 16 (for_each_phase_tap)
-      case 0: ws_body<CIN, COUT, TH, TW, false, 2, 2, true, PROJ>(a, lds, model, bi, nb, 0, 0, 0); break;
-      case 1: ws_body<CIN, COUT, TH, TW, false, 2, 3, true, PROJ>(a, lds, model, bi, nb, 4, 0, 1); break;
-      case 2: ws_body<CIN, COUT, TH, TW, false, 3, 2, true, PROJ>(a, lds, model, bi, nb, 10, 1, 0); break;
-      default: ws_body<CIN, COUT, TH, TW, false, 3, 3, true, PROJ>(a, lds, model, bi, nb, 16, 1, 1); break;
-    }
-  }
-}
-
+// ====================================================================================
+// [dconv1_all]  dconv1 on the u8 codes, all four sub-pixel phases per staged tile.
+// ====================================================================================
 // ------------------------------------------------------------------------------------
 // dconv1 (Conv2DTranspose 32 -> 64, k5 s2 on the dequantised latent, decoder.py:10,20,40-41)
 // as a persistent weight-stationary kernel on the u8 codes (codes 0..255 are exact in f16:
@@ -2180,28 +2391,25 @@ __device__ __forceinline__ void d1all_wave(const ConvArgs& a, char* lds, int mod
       }
     }
     __builtin_amdgcn_s_setprio(0);
-    const __amdgpu_buffer_rsrc_t out_rs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(a.out_s + (size_t)p * out_plane / 2), (short)0, (int)out_plane, kBufWord3);
+    const __amdgpu_buffer_rsrc_t out_rs = plane_rsrc(a.out_s, p, out_plane);
     const unsigned out_org = (unsigned)(((2 * ty0 + py) * a.OW + 2 * tx0 + px) * PXB);
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
       const int y = ty0 + 2 * m + (l16 >> 3), x = tx0 + (l16 & 7);
-      f32x4 v;
+      f32x4 v;  // activation by hand: with split_act the kernel gains two s_nop
 #pragma unroll
       for (int r = 0; r < 4; ++r) v[r] = leaky02(scale_bias(acc[m][r], scale, bias[r]));
       const bool in = y < a.H && x < a.W;
-      if (in) range_track(rmax, v);
-      f16x4 hi, lo;
-      split4(v, hi, lo);
+      const u32x4 q = split_record(v, in, rmax);
 #ifdef NIC_DIAG_D1NOST  // diagnostic build only: every store dropped (out of range; wrong results)
-      __builtin_amdgcn_raw_buffer_store_b128(swap16_pair(hi, lo), out_rs, kDmaOOR, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(q, out_rs, kDmaOOR, 0, 0);
 #elif defined(NIC_DIAG_D1LIN)  // diagnostic build only: the same bytes as 1-KB contiguous stores (wrong layout)
       {
         const unsigned tq = (unsigned)(((ty0 >> 3) * a.tiles_x + (tx0 >> 3)) * 4 + py * 2 + px) * 4 + cg;
-        __builtin_amdgcn_raw_buffer_store_b128(swap16_pair(hi, lo), out_rs, tq * 4096u + (unsigned)(m * 64 + lane) * 16u, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(q, out_rs, tq * 4096u + (unsigned)(m * 64 + lane) * 16u, 0, 0);
       }
 #else
-      __builtin_amdgcn_raw_buffer_store_b128(swap16_pair(hi, lo), out_rs, in ? out_org + g_off[m] : kDmaOOR, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(q, out_rs, in ? out_org + g_off[m] : kDmaOOR, 0, 0);
 #endif
     }
   };
@@ -2262,6 +2470,29 @@ __global__ __launch_bounds__(512, 1) void dconv1_all_kernel(ConvArgs a) {
     d1all_wave<2, 3, 4, 0, 1, 3, 2, 10, 1, 0>(a, lds, gi, bi, nb);
 }
 
+// all phases per staged tile: one 8-wave block per CU, blocks split between the models in
+// proportion to their tiles (Y : CbCr = 1 : 2)
+static hipError_t launch_dconv1_all(ConvArgs a, hipStream_t st) {
+  a.tiles_y = (a.H + 7) / 8;
+  a.tiles_x = (a.W + 7) / 8;
+  const long long per_plane = (long long)a.tiles_y * a.tiles_x, nt = per_plane * a.P;
+  if (nt == 0) return hipSuccess;
+  if (nt > INT32_MAX || a.P != 3 * a.nimg || a.OH != 2 * a.H || a.OW != 2 * a.W || !a.in_u8) return hipErrorInvalidValue;
+  if ((long long)a.OH * a.OW * 256 >= (1LL << 31)) return hipErrorInvalidValue;  // 32-bit granule offsets
+  const long long target = device_cus();
+  const long long ty = (long long)a.nimg * per_plane, tc = 2LL * a.nimg * per_plane;
+  const int by = (int)std::max(1LL, std::min(ty, (target + 1) / 3)), bc = (int)std::max(1LL, std::min(tc, target - by));
+  a.ws_ngrp = 2;
+  a.ws_blk[0] = 0;
+  a.ws_blk[1] = by;
+  a.ws_blk[2] = by + bc;
+  hipLaunchKernelGGL(dconv1_all_kernel, dim3(a.ws_blk[2]), dim3(512), 0, st, a);
+  return hipGetLastError();
+}
+
+// ====================================================================================
+// [k3pair]  The fused residual pair of the k3 s1 layers (conv_k3pair_kernel) and its row planning.
+// ====================================================================================
 // ------------------------------------------------------------------------------------
 // Fused residual pair of the k3 s1 layers: out = leaky(conv_b(leaky(conv_a(x) + b_a)) + b_b) + x
 // (encoder.py:22-25 conv3 -> conv4 -> + res; decoder.py:26-29 dconv5 -> dconv6 -> + res, the
@@ -2477,17 +2708,12 @@ __global__ __launch_bounds__(512, 1) void conv_k3pair_kernel(ConvArgs a, K3Range
   auto epi_b = [&](int m, int y4, const __amdgpu_buffer_rsrc_t& rs_out) {
     const int jx = 16 * m + l16, x = sx0 + jx;
     const bool valid = jx < jmax && x < W;
-    f32x4 v;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] = leaky02(scale_bias(acc[m][r], scale, bias[r]));
+    f32x4 v = split_act(acc[m], scale, bias);
     static_for<4>([&](auto rc) {  // x = x + res (encoder.py:25, decoder.py:29)
       constexpr int r = decltype(rc)::value;
       v[r] = __fadd_rn(v[r], add_f16_pair<r & 1>(rr[m][0][r >> 1], rr[m][1][r >> 1]));
     });
-    if (valid) range_track(rmax, v);
-    f16x4 hi, lo;
-    split4(v, hi, lo);
-    const u32x4 q = swap16_pair(hi, lo);
+    const u32x4 q = split_record(v, valid, rmax);
     const unsigned orow = (unsigned)(y4 * W) * K3P_REC + (unsigned)chunk_st * 16;
     __builtin_amdgcn_raw_buffer_store_b128(q, rs_out, valid ? orow + (unsigned)(x * K3P_REC) : kDmaOOR, 0, 0);
   };
@@ -2506,10 +2732,8 @@ __global__ __launch_bounds__(512, 1) void conv_k3pair_kernel(ConvArgs a, K3Range
         model = m_item;
         load_weights(model);
       }
-      const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(
-          (void*)((const char*)a.in_s + (size_t)p * plane_bytes), (short)0, (int)plane_bytes, kBufWord3);
-      const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(
-          (void*)((char*)a.out_s + (size_t)p * plane_bytes), (short)0, (int)plane_bytes, kBufWord3);
+      const __amdgpu_buffer_rsrc_t rs_in = plane_rsrc(a.in_s, p, plane_bytes);
+      const __amdgpu_buffer_rsrc_t rs_out = plane_rsrc(a.out_s, p, plane_bytes);
       // input rows r0 - 2 .. r0 (ring slot of row y: (y - r0 + 2) % 5)
 #pragma unroll
       for (int k = 0; k < 3; ++k) dma_row(rs_in, r0 - 2 + k, k);
@@ -2538,13 +2762,11 @@ __global__ __launch_bounds__(512, 1) void conv_k3pair_kernel(ConvArgs a, K3Range
             auto epi = [&](int m) {
               const int i = 16 * m + l16, x = xa0 + i;
               const bool in = (unsigned)x < (unsigned)W;  // outside the plane: zero (conv_b's padding)
+              // activation by hand: selecting after split_act turned the 16 v_cndmask into v_mov
               f32x4 v;
 #pragma unroll
               for (int r = 0; r < 4; ++r) v[r] = in ? leaky02(scale_bias(acc[m][r], scale, bias[r])) : 0.f;
-              if (in) range_track(rmax, v);
-              f16x4 hi, lo;
-              split4(v, hi, lo);
-              const u32x4 q = swap16_pair(hi, lo);
+              const u32x4 q = split_record(v, in, rmax);
               *(u32x4*)(dst + k3p_off(i + ca_off, chunk_st)) = q;
             };
             if ((unsigned)y3 < (unsigned)H) {
@@ -2649,6 +2871,89 @@ bool k3pair_supported(int H, int W) {
 // with one wave per SIMD nothing hides the transform VALU; removed in round 5,
 // see DESIGN section 9 for why a two-wave form does not fit the 160 KB of LDS either.)
 
+// Block row ranges of the fused pair by pipeline steps.  A block pays ~3 fill steps per segment
+// (the part of its range inside one (plane, strip) column of H rows) on top of one step per row:
+// equal-row ranges give the blocks that straddle a plane boundary 2 segments (config 2: 48 rows
+// = 54 steps against 51 for a one-segment block).  Greedy ranges under a step budget T, the
+// smallest T that fits the grid (binary search), even that out.  F = the per-segment cost the
+// budget charges, in steps (2: pair 0.2379-0.2385 ms vs 0.2388-0.2402 at 3, 0.2392-0.2404 at 4
+// and 0.2415-0.2423 for the equal-rows split; same box, profiles/r4_ab_logs.txt).
+static void k3pair_balance(long long total, int H, int G, K3Ranges& r) {
+  constexpr int F = 2;
+  if (G <= 0 || G > K3P_MAX_GRID || total >= (1LL << 31) || H <= 0) return;
+  // blocks the greedy needs under budget T (stops counting past G); fills r when `write`
+  auto fill = [&](long long T, bool write) {
+    long long s = 0;
+    int b = 0;
+    while (s < total) {
+      if (b == G) return G + 1;
+      if (write) r.start[b] = (int)s;
+      ++b;
+      long long budget = T;
+      while (s < total && budget > F) {
+        const long long left = H - s % H, take = std::min(left, budget - F);
+        s += take;
+        budget -= take + F;
+        if (take < left) break;
+      }
+    }
+    if (write)
+      for (int k = b; k <= G; ++k) r.start[k] = (int)total;
+    return b;
+  };
+  const long long per = (total + G - 1) / G;
+  long long lo = F + 1, hi = per + F * (per / H + 2);  // the equal split fits hi
+  if (fill(hi, false) > G) return;
+  while (lo < hi) {
+    const long long mid = (lo + hi) / 2;
+    if (fill(mid, false) <= G)
+      hi = mid;
+    else
+      lo = mid + 1;
+  }
+  fill(hi, true);
+}
+
+hipError_t launch_k3pair_x3(const ConvArgs& a0, hipStream_t st) {
+  ConvArgs a = a0;
+  if (!k3pair_supported(a.H, a.W) || a.OH != a.H || a.OW != a.W || !a.wx2 || !a.bias2 || a.P != 3 * a.nimg)
+    return hipErrorInvalidValue;
+  a.tiles_x = k3pair_strips(a.W);
+  const long long rows = (long long)a.P * a.tiles_x * a.H;
+  if (rows == 0) return hipSuccess;
+  // at most one block per CU, at least 4 rows per block: a block's fixed cost is 3 pipeline fill
+  // steps and 2 recomputed conv_a rows, so small batches (the host surface's chunks: 11-21
+  // images) are faster spread over every CU with few rows each than on fewer CUs with more (16
+  // rows per block left 124 of 256 CUs idle at 11 images)
+  constexpr int sr = 4;
+  const int grid = (int)std::max(1LL, std::min<long long>((rows + sr - 1) / sr, device_cus()));
+  const int mt = (a.W + 15) / 16;
+  // SKEW: conv_b runs each row's epilogue at the start of the next step, beside conv_a's MFMA
+  // stream, instead of after its own stream (the lockstep order measured 1.3 % slower)
+  K3Ranges rng;
+  rng.start[0] = -1;
+  k3pair_balance(rows, a.H, grid, rng);
+  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(512), 0, st, a, rng); };
+  auto pick = [&](auto skc) {
+    constexpr bool SK = decltype(skc)::value;
+    if (a.tiles_x > 1) {
+      go(conv_k3pair_kernel<4, SK, true>);
+    } else {
+      switch (mt) {
+        case 1: go(conv_k3pair_kernel<1, SK, false>); break;
+        case 2: go(conv_k3pair_kernel<2, SK, false>); break;
+        case 3: go(conv_k3pair_kernel<3, SK, false>); break;
+        default: go(conv_k3pair_kernel<4, SK, false>); break;
+      }
+    }
+  };
+  pick(std::true_type{});
+  return hipGetLastError();
+}
+
+// ====================================================================================
+// [colour]  The fp32 colour-fused end layers: conv1_colour_*, dconv8_colour_*, dconv8_gather_kernel.
+// ====================================================================================
 // ------------------------------------------------------------------------------------
 // conv1 (1 -> 32, k5 s2) with the RGB -> YCbCr front end fused (encoder.py:39-41,
 // utils.py:74-77).  Block: 16x16 output pixels of one plane, 4 waves x 2 M tiles x 32 co.
@@ -2967,8 +3272,7 @@ __global__ __launch_bounds__(256) void dconv8_gather_kernel(Dconv8Args a) {
 #pragma unroll
   for (int type = 0; type < 3; ++type) {
     const int p = type * a.nimg + n;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(a.proj + (size_t)p * plane_floats), (short)0, (int)(plane_floats * 4u), kBufWord3);
+    const __amdgpu_buffer_rsrc_t rs = plane_rsrc(a.proj + (size_t)p * plane_floats, plane_floats * 4u);
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int iy = 0; iy < 3; ++iy)
@@ -2992,6 +3296,69 @@ __global__ __launch_bounds__(256) void dconv8_gather_kernel(Dconv8Args a) {
 }
 
 
+hipError_t launch_conv1(Conv1Args a, hipStream_t st) {
+  a.tiles_y = (a.OH + C1_T - 1) / C1_T;
+  a.tiles_x = (a.OW + C1_T - 1) / C1_T;
+  const long long jobs = (long long)a.tiles_y * a.tiles_x * a.P;
+  if (jobs == 0) return hipSuccess;
+  if (jobs > INT32_MAX) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(conv1_colour_kernel, dim3(fp32_grid(a.rg, jobs)), dim3(256), 0,
+                     st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_dconv8(Dconv8Args a, hipStream_t st) {
+  a.tiles_y = (a.H + D8_TH - 1) / D8_TH;
+  a.tiles_x = (a.W + D8_TW - 1) / D8_TW;
+  const long long jobs = (long long)a.tiles_y * a.tiles_x * a.nimg;
+  if (jobs == 0) return hipSuccess;
+  if (jobs > INT32_MAX) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(dconv8_colour_kernel, dim3(fp32_grid(a.rg, jobs)), dim3(256), 0,
+                     st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_dconv8_gather(Dconv8Args a, hipStream_t st) {
+  if (!a.proj || (a.H & 1) || (a.W & 1)) return hipErrorInvalidValue;
+  if (a.tiles_y7 != (a.H / 2 + 7) / 8 || a.tiles_x7 != (a.W / 2 + 7) / 8) return hipErrorInvalidValue;
+  const int tiles_y = (a.H + 15) / 16;
+  a.tiles_x = (a.W + 15) / 16;
+  hipLaunchKernelGGL(dconv8_gather_kernel, dim3(tiles_y * a.tiles_x, a.nimg), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// ====================================================================================
+// [layers_x3]  Per-layer dispatch of the split-f16 kernels.  Template kernels are emitted in the order the
+// non-template host functions name them, so this section sits after [k3pair] and before [latent].
+// ====================================================================================
+hipError_t launch_layer_x3(LayerId id, const ConvArgs& a, hipStream_t st) {
+  switch (id) {
+    case L_CONV2:  // 32->64 k5 s2 (conv12_kernel runs it fused with conv1; this form is unused there)
+      return launch_ws2<32, 64, 2, 8, OUT_SPLIT>(a, st);
+    case L_CONV3:  // 64->64 k3 s1 weight-stationary (the fused pair takes planes it supports)
+    case L_DCONV5:
+      return launch_ws<64, 64, 8, 8, false, false>(a, st);
+    case L_CONV4:
+    case L_DCONV6:
+      return launch_ws<64, 64, 8, 8, true, false>(a, st);
+    case L_CONV8:  // 64->32 k5 s2 -> latent: tap-split weight-stationary (2 channel groups x 4 tap
+                   // quarters, 4x8 tiles)
+      return launch_ws2<64, 32, 4, 4, OUT_U8_LATENT>(a, st);
+    case L_DCONV1:  // latent -> 64, transposed k5 s2: all four phases per staged 8x8 code tile
+      return launch_dconv1_all(a, st);
+    default:  // dconv7 runs with dconv8's projections (launch_dconv7_proj_x3)
+      return hipErrorInvalidValue;
+  }
+}
+
+hipError_t launch_dconv7_proj_x3(const ConvArgs& a, hipStream_t st) {
+  if (!a.proj || !a.proj_w || a.OH != 2 * a.H || a.OW != 2 * a.W) return hipErrorInvalidValue;
+  return launch_ws<64, 64, 8, 8, false, true, true>(a, st);
+}
+
+// ====================================================================================
+// [latent]  Latent histogram / entropy, the histogram fold and bitstream pack / unpack.
+// ====================================================================================
 // ------------------------------------------------------------------------------------
 // Histogram entropy (tf1_13/src/training.py:66-71) and bitstream pack/unpack
 // (utils.py:35-40).
@@ -3175,12 +3542,70 @@ __global__ __launch_bounds__(256) void unpack_latent_kernel(const uint8_t* __res
   }
 }
 
-// ------------------------------------------------------------------------------------
-// launchers
-// ------------------------------------------------------------------------------------
-// Grid of a grid-stride fp32 kernel: 8 blocks per CU, but one per CU for the gated re-run of
-// the range-guard fallback, which exits at once unless its pass tripped (the usual case: a
-// smaller grid drains faster; a tripped pass re-runs on fewer, longer-lived blocks)
+int hist_chunks(int nimg, int plane_px, int* chunk_vec, int blocks) {
+  // `blocks` over the whole batch (one full wave of blocks, no tail round: 6 resident
+  // 256-thread blocks or 2 1024-thread blocks per CU x 256 CUs), 4 KB .. 256 KB of latent each
+  const long long nvec = (long long)plane_px * 6;
+  long long cv = ((nvec * nimg + blocks - 1) / blocks + 255) / 256 * 256;
+  cv = cv < 256 ? 256 : (cv > 16384 ? 16384 : cv);
+  *chunk_vec = (int)cv;
+  return (int)((nvec + cv - 1) / cv);
+}
+
+size_t hist_scratch_bytes(int nimg, int plane_px) {
+  int cv;  // sized for the most partials any variant writes
+  return (size_t)3 * nimg * hist_chunks(nimg, plane_px, &cv, 1536) * 256 * sizeof(uint32_t);
+}
+
+hipError_t launch_hist(const uint8_t* z, int nimg, int plane_px, uint32_t* part, uint32_t* counts, float* bits,
+                       hipStream_t st) {
+  // 1024-thread blocks, 512 of them (2 per CU) with 16 LDS replicas per bin from 24 MB of latent
+  // up, else 256-thread blocks with 8 (>= 48 KB per block: the per-block LDS clear and 768
+  // partial stores amortised).  Measured on 4K x 8 latents (tools/hist_ab.py, round 2):
+  // 16 replicas 21.6 us, 8 25.4, 32 (98 KB, one block per CU) 27.2; a packed-u16 32-replica
+  // layout 15 % slower.  NIC_HIST=big / small forces either form (read per call: the GPU test
+  // runs both on one latent).
+  const char* hv = getenv("NIC_HIST");
+  const int force = !hv ? 0 : hv[0] == 'b' ? 1 : hv[0] == 's' ? 2 : 0;
+  const long long total = (long long)plane_px * 96 * nimg;
+  const bool big = force ? force == 1 : total >= (24ll << 20);
+  int chunk_vec;
+  const int chunks = hist_chunks(nimg, plane_px, &chunk_vec, big ? 512 : 1536);
+  if (big)
+    hipLaunchKernelGGL((latent_hist_kernel<16, false, 1024>), dim3(chunks, nimg), dim3(1024), 0, st, z, nimg, plane_px, part,
+                       chunk_vec);
+  else
+    hipLaunchKernelGGL((latent_hist_kernel<8, false, 256>), dim3(chunks, nimg), dim3(256), 0, st, z, nimg, plane_px, part,
+                       chunk_vec);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(hist_entropy_kernel, dim3(3 * nimg), dim3(1024), 0, st, part, chunks, (float)plane_px * 32.0f,
+                     counts, bits);
+  return hipGetLastError();
+}
+
+hipError_t launch_hist_fold(uint32_t* part, const uint8_t* z, int nimg, int h8, int w8, RangeGuard trip,
+                            uint32_t* counts, float* bits, hipStream_t st) {
+  if (!hist_fold_supported(nimg, h8, w8)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(hist_fold_kernel, dim3(3 * nimg), dim3(256), 0, st, part, nimg, z, h8 * w8, trip,
+                     (float)h8 * w8 * 32.0f, counts, bits);
+  return hipGetLastError();
+}
+
+hipError_t launch_pack(const uint8_t* z, uint8_t* out, int nimg, int h8, int w8, bool unpack, hipStream_t st) {
+  const size_t plane_elems = (size_t)h8 * w8 * 32;
+  const size_t total = plane_elems * nimg;
+  const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+  if (unpack)
+    hipLaunchKernelGGL(unpack_latent_kernel, dim3(blocks), dim3(256), 0, st, z, out, plane_elems, nimg);
+  else
+    hipLaunchKernelGGL(pack_latent_kernel, dim3(blocks), dim3(256), 0, st, z, out, plane_elems, nimg);
+  return hipGetLastError();
+}
+
+// ====================================================================================
+// [fp32_chain]  The gated exact-fp32 re-run of a split-f16 pass as one queued launch.
+// ====================================================================================
 // ------------------------------------------------------------------------------------
 // The gated exact-fp32 re-run of a split-f16 pass as ONE launch: every stage of the pass
 // (conv1 / conv_mfma layers / dconv8) in sequence.  When the split pass stayed in range every
@@ -3310,15 +3735,16 @@ hipError_t chain_add_dconv8(Fp32Chain& ch, Dconv8Args a) {
 // Blocks of fp32_chain_kernel resident per CU (its LDS / VGPRs), per device (informational:
 // the queued chain runs on any number of resident blocks).
 static int chain_occupancy() {
-  static int cache[64] = {};
+  static std::atomic<int> cache[64];  // relaxed: any thread's value for a device is the same
   int d = 0;
   if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return 0;
-  if (!cache[d]) {
-    int n = 0;
+  int n = cache[d].load(std::memory_order_relaxed);
+  if (!n) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fp32_chain_kernel, 256, 0) != hipSuccess) n = 0;
-    cache[d] = n > 0 ? n : -1;
+    n = n > 0 ? n : -1;
+    cache[d].store(n, std::memory_order_relaxed);
   }
-  return cache[d];
+  return n;
 }
 
 // NIC_DIAG_CHAIN=N (GPU test only): the chain's grid is N blocks per CU -- far more than fit at
@@ -3346,404 +3772,6 @@ hipError_t launch_fp32_chain(const Fp32Chain& chain, hipStream_t st) {
   ch.diag_late = diag ? 1 : 0;
   // one 256-thread block per CU; nothing requires them resident together
   hipLaunchKernelGGL(fp32_chain_kernel, dim3(device_cus() * std::max(1, diag)), dim3(256), 0, st, ch);
-  return hipGetLastError();
-}
-
-// grid of the fp32 one-tile-per-block launches: 8 blocks per CU, 1 for a gated re-run (NIC_CHAIN=0),
-// which exits at its gate unless the split pass tripped (a smaller grid drains faster)
-static int fp32_grid(const RangeGuard& rg, long long jobs) {
-  return (int)std::min<long long>(jobs, (long long)(rg.gate ? 1 : 8) * device_cus());
-}
-
-template <int CIN, int COUT, int KS, int S, bool TR, int TH, int TW, int WM, int WN, int WK, int IN_MODE,
-          int OUT_MODE, bool RESID>
-static hipError_t launch_conv(ConvArgs a, hipStream_t st) {
-  const int gy = TR ? a.H : a.OH, gx = TR ? a.W : a.OW;  // tile grid over coarse / output coords
-  a.tiles_y = (gy + TH - 1) / TH;
-  a.tiles_x = (gx + TW - 1) / TW;
-  const long long jobs = (long long)a.tiles_y * a.tiles_x * a.P;
-  if (jobs == 0) return hipSuccess;
-  if (jobs > INT32_MAX) return hipErrorInvalidValue;
-  const int grid = fp32_grid(a.rg, jobs);
-  hipLaunchKernelGGL((conv_mfma_kernel<CIN, COUT, KS, S, TR, TH, TW, WM, WN, WK, IN_MODE, OUT_MODE, RESID>),
-                     dim3(grid), dim3(256), 0, st, a);
-  return hipGetLastError();
-}
-
-hipError_t upload_constants(const float* u8_to_unit, const float* ycbcr, const float* ycbcr_inv, const float* off) {
-  hipError_t e;
-  if ((e = hipMemcpyToSymbol(HIP_SYMBOL(c_u8_to_unit), u8_to_unit, 256 * sizeof(float))) != hipSuccess) return e;
-  if ((e = hipMemcpyToSymbol(HIP_SYMBOL(c_ycbcr), ycbcr, 9 * sizeof(float))) != hipSuccess) return e;
-  if ((e = hipMemcpyToSymbol(HIP_SYMBOL(c_ycbcr_inv), ycbcr_inv, 9 * sizeof(float))) != hipSuccess) return e;
-  return hipMemcpyToSymbol(HIP_SYMBOL(c_ycbcr_off), off, 3 * sizeof(float));
-}
-
-hipError_t launch_layer(LayerId id, const ConvArgs& a, hipStream_t st) {
-  switch (id) {
-    // encoder (conv1 has its own kernel)
-    case L_CONV2:  // 32->64 k5 s2: 8x8 tile, 4 waves = 2(M) x 2(N)
-      return launch_conv<32, 64, 5, 2, false, 8, 8, 2, 2, 1, IN_F32, OUT_F32, false>(a, st);
-    case L_CONV3:  // 64->64 k3 s1: 8x16 tile, 4 waves along M, each 32 px x 64 co
-      return launch_conv<64, 64, 3, 1, false, 8, 16, 4, 1, 1, IN_F32, OUT_F32, false>(a, st);
-    case L_CONV4:  // + residual
-      return launch_conv<64, 64, 3, 1, false, 8, 16, 4, 1, 1, IN_F32, OUT_F32, true>(a, st);
-    case L_CONV8:  // 64->32 k5 s2 -> u8 latent: 4x8 tile, taps split over the 4 waves
-      return launch_conv<64, 32, 5, 2, false, 4, 8, 1, 1, 4, IN_F32, OUT_U8_LATENT, false>(a, st);
-    // decoder (dconv8 has its own kernel)
-    case L_DCONV1:  // latent u8 -> 64, transposed k5 s2: 8x8 coarse tile, 2(M) x 2(N)
-      return launch_conv<32, 64, 5, 2, true, 8, 8, 2, 2, 1, IN_U8_LATENT, OUT_F32, false>(a, st);
-    case L_DCONV5:  // transposed k3 s1 == conv k3 s1 with flipped kernel
-      return launch_conv<64, 64, 3, 1, false, 8, 16, 4, 1, 1, IN_F32, OUT_F32, false>(a, st);
-    case L_DCONV6:
-      return launch_conv<64, 64, 3, 1, false, 8, 16, 4, 1, 1, IN_F32, OUT_F32, true>(a, st);
-    case L_DCONV7:  // 64->64 transposed k5 s2: 8x16 coarse tile, 4 waves along M
-      return launch_conv<64, 64, 5, 2, true, 8, 16, 4, 1, 1, IN_F32, OUT_F32, false>(a, st);
-    default:
-      return hipErrorInvalidValue;
-  }
-}
-
-
-static int device_cus() {
-  static int cache[64] = {};
-  int d = 0;
-  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return 256;
-  if (!cache[d]) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || n <= 0) n = 256;
-    cache[d] = n;
-  }
-  return cache[d];
-}
-
-// Weight-stationary launch: 2 resident blocks per CU, split into groups (tap set, model)
-// in proportion to each group's MFMA work (planes x taps).
-template <int CIN, int COUT, int TH, int TW, bool RESID, bool TRP, bool PROJ = false>
-static hipError_t launch_ws(ConvArgs a, hipStream_t st) {
-  a.tiles_y = (a.H + TH - 1) / TH;
-  a.tiles_x = (a.W + TW - 1) / TW;
-  const long long per_plane = (long long)a.tiles_y * a.tiles_x;
-  const long long nt = per_plane * a.P;
-  if (nt == 0) return hipSuccess;
-  if (nt > INT32_MAX || a.P != 3 * a.nimg) return hipErrorInvalidValue;
-  // HaloDma: 32-bit plane offsets, out-of-range slots past the plane (kDmaOOR)
-  if ((long long)a.H * a.W * CIN * 4 >= (1LL << 30)) return hipErrorInvalidValue;
-  a.ntiles = (int)nt;
-  // one block group per model (transposed layers: every block runs the four phases over its
-  // tiles; per-phase groups measured 6 % slower, DESIGN section 5)
-  a.ws_taps = TRP ? 25 : 9;
-  a.ws_ngrp = 2;
-  long long work[2], total = 0;
-  for (int gi = 0; gi < 2; ++gi) {
-    work[gi] = ((gi & 1) ? a.P - a.nimg : a.nimg) * per_plane;
-    total += work[gi];
-  }
-  const int target = 2 * device_cus();  // 2 resident blocks per CU
-  a.ws_blk[0] = 0;
-  for (int gi = 0; gi < a.ws_ngrp; ++gi) {
-    const long long tiles = ((gi & 1) ? a.P - a.nimg : a.nimg) * per_plane;
-    long long b = (work[gi] * target + total / 2) / total;
-    b = b < 1 ? 1 : b > tiles ? tiles : b;
-    a.ws_blk[gi + 1] = a.ws_blk[gi] + (int)b;
-  }
-  a.ws_xcd = 1;
-  hipLaunchKernelGGL((conv_ws_kernel<CIN, COUT, TH, TW, RESID, TRP, PROJ>), dim3(a.ws_blk[a.ws_ngrp]),
-                     dim3(64 * (COUT / 16)), 0, st, a);
-  return hipGetLastError();
-}
-
-// Block row ranges of the fused pair by pipeline steps.  A block pays ~3 fill steps per segment
-// (the part of its range inside one (plane, strip) column of H rows) on top of one step per row:
-// equal-row ranges give the blocks that straddle a plane boundary 2 segments (config 2: 48 rows
-// = 54 steps against 51 for a one-segment block).  Greedy ranges under a step budget T, the
-// smallest T that fits the grid (binary search), even that out.  F = the per-segment cost the
-// budget charges, in steps (2: pair 0.2379-0.2385 ms vs 0.2388-0.2402 at 3, 0.2392-0.2404 at 4
-// and 0.2415-0.2423 for the equal-rows split; same box, profiles/r4_ab_logs.txt).
-static void k3pair_balance(long long total, int H, int G, K3Ranges& r) {
-  constexpr int F = 2;
-  if (G <= 0 || G > K3P_MAX_GRID || total >= (1LL << 31) || H <= 0) return;
-  // blocks the greedy needs under budget T (stops counting past G); fills r when `write`
-  auto fill = [&](long long T, bool write) {
-    long long s = 0;
-    int b = 0;
-    while (s < total) {
-      if (b == G) return G + 1;
-      if (write) r.start[b] = (int)s;
-      ++b;
-      long long budget = T;
-      while (s < total && budget > F) {
-        const long long left = H - s % H, take = std::min(left, budget - F);
-        s += take;
-        budget -= take + F;
-        if (take < left) break;
-      }
-    }
-    if (write)
-      for (int k = b; k <= G; ++k) r.start[k] = (int)total;
-    return b;
-  };
-  const long long per = (total + G - 1) / G;
-  long long lo = F + 1, hi = per + F * (per / H + 2);  // the equal split fits hi
-  if (fill(hi, false) > G) return;
-  while (lo < hi) {
-    const long long mid = (lo + hi) / 2;
-    if (fill(mid, false) <= G)
-      hi = mid;
-    else
-      lo = mid + 1;
-  }
-  fill(hi, true);
-}
-
-hipError_t launch_k3pair_x3(const ConvArgs& a0, hipStream_t st) {
-  ConvArgs a = a0;
-  if (!k3pair_supported(a.H, a.W) || a.OH != a.H || a.OW != a.W || !a.wx2 || !a.bias2 || a.P != 3 * a.nimg)
-    return hipErrorInvalidValue;
-  a.tiles_x = k3pair_strips(a.W);
-  const long long rows = (long long)a.P * a.tiles_x * a.H;
-  if (rows == 0) return hipSuccess;
-  // at most one block per CU, at least 4 rows per block: a block's fixed cost is 3 pipeline fill
-  // steps and 2 recomputed conv_a rows, so small batches (the host surface's chunks: 11-21
-  // images) are faster spread over every CU with few rows each than on fewer CUs with more (16
-  // rows per block left 124 of 256 CUs idle at 11 images)
-  constexpr int sr = 4;
-  const int grid = (int)std::max(1LL, std::min<long long>((rows + sr - 1) / sr, device_cus()));
-  const int mt = (a.W + 15) / 16;
-  // SKEW: conv_b runs each row's epilogue at the start of the next step, beside conv_a's MFMA
-  // stream, instead of after its own stream (the lockstep order measured 1.3 % slower)
-  K3Ranges rng;
-  rng.start[0] = -1;
-  k3pair_balance(rows, a.H, grid, rng);
-  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(512), 0, st, a, rng); };
-  auto pick = [&](auto skc) {
-    constexpr bool SK = decltype(skc)::value;
-    if (a.tiles_x > 1) {
-      go(conv_k3pair_kernel<4, SK, true>);
-    } else {
-      switch (mt) {
-        case 1: go(conv_k3pair_kernel<1, SK, false>); break;
-        case 2: go(conv_k3pair_kernel<2, SK, false>); break;
-        case 3: go(conv_k3pair_kernel<3, SK, false>); break;
-        default: go(conv_k3pair_kernel<4, SK, false>); break;
-      }
-    }
-  };
-  pick(std::true_type{});
-  return hipGetLastError();
-}
-
-// k5 s2 forward convs: one 8-wave block per CU, split into a Y and a CbCr group in
-// proportion to their planes.
-static void ws2_groups(int nimg, long long per_plane, int* by, int* bc) {
-  const int target = device_cus();
-  const long long ty = per_plane * nimg, tc = per_plane * 2 * nimg;
-  long long y = std::max(1LL, std::min((long long)(target + 1) / 3, ty));
-  *by = (int)y;
-  *bc = (int)std::max(1LL, std::min((long long)target - y, tc));
-}
-
-// conv8's tile grid (4 x 8 output tiles) and the fold's condition: every block meets each plane
-// of its group in >= 2 consecutive tiles (group blocks <= tiles per plane / 2) -- large frames
-// (config 5); batches of small images run the two-call form
-bool hist_fold_supported(int nimg, int h8, int w8) {
-  if (nimg <= 0 || h8 <= 0 || w8 <= 0) return false;
-  const long long pp = (long long)((h8 + 3) / 4) * ((w8 + 7) / 8);
-  int by, bc;
-  ws2_groups(nimg, pp, &by, &bc);
-  return 2LL * by <= pp && 2LL * bc <= pp;
-}
-
-size_t hist_fold_scratch_bytes(int nimg, int h8, int w8) {  // the counts [3 nimg][256]
-  (void)h8;
-  (void)w8;
-  return (size_t)3 * nimg * 256 * sizeof(uint32_t);
-}
-
-// k5 s2 forward convs on the tap-split weight-stationary kernel (conv2 of conv12 with PIPE12,
-// conv8 with the latent histogram fold when a.hist_part is set)
-template <int CIN, int COUT, int NTS, int TH, int OUT_MODE, bool PIPE12 = false>
-static hipError_t launch_ws2(ConvArgs a, hipStream_t st) {
-  a.tiles_y = (a.OH + TH - 1) / TH;
-  a.tiles_x = (a.OW + 7) / 8;
-  const long long per_plane = (long long)a.tiles_y * a.tiles_x;
-  const long long nt = per_plane * a.P;
-  if (nt == 0) return hipSuccess;
-  if (nt > INT32_MAX || a.P != 3 * a.nimg) return hipErrorInvalidValue;
-  a.ntiles = (int)nt;
-  a.ws_taps = 25;
-  a.ws_ngrp = 2;
-  int by, bc;
-  ws2_groups(a.nimg, per_plane, &by, &bc);
-  a.ws_blk[0] = 0;
-  a.ws_blk[1] = by;
-  a.ws_blk[2] = by + bc;
-  if constexpr (PIPE12) {
-    hipLaunchKernelGGL(conv12_kernel, dim3(a.ws_blk[2]), dim3(512), 0, st, a);
-  } else if constexpr (OUT_MODE == OUT_U8_LATENT) {
-    if (a.hist_part) {
-      if (!hist_fold_supported(a.nimg, a.OH, a.OW)) return hipErrorInvalidValue;
-      hipLaunchKernelGGL((conv_ws2_kernel<CIN, COUT, NTS, TH, OUT_MODE, true>), dim3(a.ws_blk[2]), dim3(512), 0, st, a);
-    } else {
-      hipLaunchKernelGGL((conv_ws2_kernel<CIN, COUT, NTS, TH, OUT_MODE>), dim3(a.ws_blk[2]), dim3(512), 0, st, a);
-    }
-  } else {
-    hipLaunchKernelGGL((conv_ws2_kernel<CIN, COUT, NTS, TH, OUT_MODE>), dim3(a.ws_blk[2]), dim3(512), 0, st, a);
-  }
-  return hipGetLastError();
-}
-
-hipError_t launch_conv12_x3(const ConvArgs& a0, hipStream_t st) {
-  ConvArgs a = a0;
-  if (!a.rgb || !a.wx1 || !a.bias1 || a.H0 <= 0 || a.W0 <= 0) return hipErrorInvalidValue;
-  if (!a.cplane || a.OH <= 0 || a.OW <= 0) return hipErrorInvalidValue;
-  int oy, ox;
-  c12_plane_geom(a.OH, a.OW, a.pad_y, a.pad_x, a.p1y, a.p1x, &oy, &ox, &a.cp_h, &a.cp_w);
-  // 32-bit byte offsets inside one plane (buffer resources of the patch DMA)
-  if ((long long)a.cp_h * a.cp_w * 2 >= (1LL << 31)) return hipErrorInvalidValue;
-  const long long per_img = (long long)a.cp_h * (a.cp_w / 4);  // < 2^31 (checked above)
-  if (per_img == 0 || a.nimg == 0) return hipSuccess;
-  if (a.nimg > 65535 || (long long)a.W0 * 3 >= (1LL << 31)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(colour_split_kernel, dim3((unsigned)((per_img + 255) / 256), a.nimg),
-                     dim3(256), 0, st, a.rgb, a.cplane, a.nimg, a.H0, a.W0, oy, ox, a.cp_h, a.cp_w);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  return launch_ws2<32, 64, 2, 8, OUT_SPLIT, true>(a, st);
-}
-
-// all phases per staged tile: one 8-wave block per CU, blocks split between the models in
-// proportion to their tiles (Y : CbCr = 1 : 2)
-static hipError_t launch_dconv1_all(ConvArgs a, hipStream_t st) {
-  a.tiles_y = (a.H + 7) / 8;
-  a.tiles_x = (a.W + 7) / 8;
-  const long long per_plane = (long long)a.tiles_y * a.tiles_x, nt = per_plane * a.P;
-  if (nt == 0) return hipSuccess;
-  if (nt > INT32_MAX || a.P != 3 * a.nimg || a.OH != 2 * a.H || a.OW != 2 * a.W || !a.in_u8) return hipErrorInvalidValue;
-  if ((long long)a.OH * a.OW * 256 >= (1LL << 31)) return hipErrorInvalidValue;  // 32-bit granule offsets
-  const long long target = device_cus();
-  const long long ty = (long long)a.nimg * per_plane, tc = 2LL * a.nimg * per_plane;
-  const int by = (int)std::max(1LL, std::min(ty, (target + 1) / 3)), bc = (int)std::max(1LL, std::min(tc, target - by));
-  a.ws_ngrp = 2;
-  a.ws_blk[0] = 0;
-  a.ws_blk[1] = by;
-  a.ws_blk[2] = by + bc;
-  hipLaunchKernelGGL(dconv1_all_kernel, dim3(a.ws_blk[2]), dim3(512), 0, st, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_layer_x3(LayerId id, const ConvArgs& a, hipStream_t st) {
-  switch (id) {
-    case L_CONV2:  // 32->64 k5 s2 (conv12_kernel runs it fused with conv1; this form is unused there)
-      return launch_ws2<32, 64, 2, 8, OUT_SPLIT>(a, st);
-    case L_CONV3:  // 64->64 k3 s1 weight-stationary (the fused pair takes planes it supports)
-    case L_DCONV5:
-      return launch_ws<64, 64, 8, 8, false, false>(a, st);
-    case L_CONV4:
-    case L_DCONV6:
-      return launch_ws<64, 64, 8, 8, true, false>(a, st);
-    case L_CONV8:  // 64->32 k5 s2 -> latent: tap-split weight-stationary (2 channel groups x 4 tap
-                   // quarters, 4x8 tiles)
-      return launch_ws2<64, 32, 4, 4, OUT_U8_LATENT>(a, st);
-    case L_DCONV1:  // latent -> 64, transposed k5 s2: all four phases per staged 8x8 code tile
-      return launch_dconv1_all(a, st);
-    default:  // dconv7 runs with dconv8's projections (launch_dconv7_proj_x3)
-      return hipErrorInvalidValue;
-  }
-}
-
-hipError_t launch_dconv7_proj_x3(const ConvArgs& a, hipStream_t st) {
-  if (!a.proj || !a.proj_w || a.OH != 2 * a.H || a.OW != 2 * a.W) return hipErrorInvalidValue;
-  return launch_ws<64, 64, 8, 8, false, true, true>(a, st);
-}
-
-hipError_t launch_conv1(Conv1Args a, hipStream_t st) {
-  a.tiles_y = (a.OH + C1_T - 1) / C1_T;
-  a.tiles_x = (a.OW + C1_T - 1) / C1_T;
-  const long long jobs = (long long)a.tiles_y * a.tiles_x * a.P;
-  if (jobs == 0) return hipSuccess;
-  if (jobs > INT32_MAX) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(conv1_colour_kernel, dim3(fp32_grid(a.rg, jobs)), dim3(256), 0,
-                     st, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_dconv8(Dconv8Args a, hipStream_t st) {
-  a.tiles_y = (a.H + D8_TH - 1) / D8_TH;
-  a.tiles_x = (a.W + D8_TW - 1) / D8_TW;
-  const long long jobs = (long long)a.tiles_y * a.tiles_x * a.nimg;
-  if (jobs == 0) return hipSuccess;
-  if (jobs > INT32_MAX) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(dconv8_colour_kernel, dim3(fp32_grid(a.rg, jobs)), dim3(256), 0,
-                     st, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_dconv8_gather(Dconv8Args a, hipStream_t st) {
-  if (!a.proj || (a.H & 1) || (a.W & 1)) return hipErrorInvalidValue;
-  if (a.tiles_y7 != (a.H / 2 + 7) / 8 || a.tiles_x7 != (a.W / 2 + 7) / 8) return hipErrorInvalidValue;
-  const int tiles_y = (a.H + 15) / 16;
-  a.tiles_x = (a.W + 15) / 16;
-  hipLaunchKernelGGL(dconv8_gather_kernel, dim3(tiles_y * a.tiles_x, a.nimg), dim3(256), 0, st, a);
-  return hipGetLastError();
-}
-
-int hist_chunks(int nimg, int plane_px, int* chunk_vec, int blocks) {
-  // `blocks` over the whole batch (one full wave of blocks, no tail round: 6 resident
-  // 256-thread blocks or 2 1024-thread blocks per CU x 256 CUs), 4 KB .. 256 KB of latent each
-  const long long nvec = (long long)plane_px * 6;
-  long long cv = ((nvec * nimg + blocks - 1) / blocks + 255) / 256 * 256;
-  cv = cv < 256 ? 256 : (cv > 16384 ? 16384 : cv);
-  *chunk_vec = (int)cv;
-  return (int)((nvec + cv - 1) / cv);
-}
-
-size_t hist_scratch_bytes(int nimg, int plane_px) {
-  int cv;  // sized for the most partials any variant writes
-  return (size_t)3 * nimg * hist_chunks(nimg, plane_px, &cv, 1536) * 256 * sizeof(uint32_t);
-}
-
-hipError_t launch_hist(const uint8_t* z, int nimg, int plane_px, uint32_t* part, uint32_t* counts, float* bits,
-                       hipStream_t st) {
-  // 1024-thread blocks, 512 of them (2 per CU) with 16 LDS replicas per bin from 24 MB of latent
-  // up, else 256-thread blocks with 8 (>= 48 KB per block: the per-block LDS clear and 768
-  // partial stores amortised).  Measured on 4K x 8 latents (tools/hist_ab.py, round 2):
-  // 16 replicas 21.6 us, 8 25.4, 32 (98 KB, one block per CU) 27.2; a packed-u16 32-replica
-  // layout 15 % slower.  NIC_HIST=big / small forces either form (read per call: the GPU test
-  // runs both on one latent).
-  const char* hv = getenv("NIC_HIST");
-  const int force = !hv ? 0 : hv[0] == 'b' ? 1 : hv[0] == 's' ? 2 : 0;
-  const long long total = (long long)plane_px * 96 * nimg;
-  const bool big = force ? force == 1 : total >= (24ll << 20);
-  int chunk_vec;
-  const int chunks = hist_chunks(nimg, plane_px, &chunk_vec, big ? 512 : 1536);
-  if (big)
-    hipLaunchKernelGGL((latent_hist_kernel<16, false, 1024>), dim3(chunks, nimg), dim3(1024), 0, st, z, nimg, plane_px, part,
-                       chunk_vec);
-  else
-    hipLaunchKernelGGL((latent_hist_kernel<8, false, 256>), dim3(chunks, nimg), dim3(256), 0, st, z, nimg, plane_px, part,
-                       chunk_vec);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(hist_entropy_kernel, dim3(3 * nimg), dim3(1024), 0, st, part, chunks, (float)plane_px * 32.0f,
-                     counts, bits);
-  return hipGetLastError();
-}
-
-hipError_t launch_hist_fold(uint32_t* part, const uint8_t* z, int nimg, int h8, int w8, RangeGuard trip,
-                            uint32_t* counts, float* bits, hipStream_t st) {
-  if (!hist_fold_supported(nimg, h8, w8)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(hist_fold_kernel, dim3(3 * nimg), dim3(256), 0, st, part, nimg, z, h8 * w8, trip,
-                     (float)h8 * w8 * 32.0f, counts, bits);
-  return hipGetLastError();
-}
-
-hipError_t launch_pack(const uint8_t* z, uint8_t* out, int nimg, int h8, int w8, bool unpack, hipStream_t st) {
-  const size_t plane_elems = (size_t)h8 * w8 * 32;
-  const size_t total = plane_elems * nimg;
-  const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-  if (unpack)
-    hipLaunchKernelGGL(unpack_latent_kernel, dim3(blocks), dim3(256), 0, st, z, out, plane_elems, nimg);
-  else
-    hipLaunchKernelGGL(pack_latent_kernel, dim3(blocks), dim3(256), 0, st, z, out, plane_elems, nimg);
   return hipGetLastError();
 }
 

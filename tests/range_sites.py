@@ -2,7 +2,7 @@
 
 The f16x3 mode stores every intermediate activation as a pair of f16 halves; a value at or
 past 65504 would split into +-inf, so each kernel that writes split activations tracks
-max |v| (range_track, csrc/nic_kernels.hip) and a tripped pass is re-run in exact fp32.  A case
+max |v| (split_record -> range_track, csrc/nic_kernels.hip) and a tripped pass is re-run in exact fp32.  A case
 here is (direction, target site, model, shape, input, weights) such that, in the float64
 oracle, the target site reaches at least 2 x 65504 while every other split site of the pass
 stays at or below 65504 / 2: only the target site's own range_track can trip the guard, and
