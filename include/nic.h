@@ -99,7 +99,21 @@ enum { NIC_PRECISION_FP32 = 0, NIC_PRECISION_F16X3 = 1 };
  * nic_range_trips (synchronising) counts the passes that tripped since nic_create.
  * A FALLBACK re-run runs as one chained launch whose stages hand their tiles out through
  * device-side queues (no grid barrier): it completes whatever share of the grid is resident,
- * so a tripped FALLBACK call always returns the exact-fp32 outputs. */
+ * so a tripped FALLBACK call always returns the exact-fp32 outputs.
+ * The guard watches the high side only.  The low half of a split activation is an f16
+ * subnormal once it falls under 2^-14, i.e. for |x| under about 2^-3, and then carries an
+ * absolute error of up to 2^-25 whatever |x| is.  With weights of ordinary size downstream
+ * that is below fp32 rounding; a network whose layer runs at 2^-k and whose next kernel is
+ * larger by 2^k (leaky-ReLU layers are positively homogeneous, so this is the same function)
+ * gets it multiplied back: measured max error 1.8e-5 at k = 8, 3.6e-4 at k = 12, 1.2e-2 at
+ * k = 17 against 1.3e-6 for the balanced network, with no trip under either policy.
+ * nic_set_weights uploads tensors as given, one at a time, and cannot rebalance them.  The
+ * Python Codec.set_weights does it before the upload (weights.lift_low_sites: every split
+ * site whose estimated magnitude is under 2^-3 is lifted by an exact power of two, the next
+ * kernel lowered by the same; the same function bit for bit in fp32, and a no-op for weights
+ * of ordinary scale): with it the cases above measure at most 2.1e-6 at every k.  A caller
+ * of this C interface with such weights does the same, or uses NIC_PRECISION_FP32
+ * (unaffected at any k).  DESIGN.md section 3. */
 enum { NIC_RANGE_FALLBACK = 0, NIC_RANGE_ERROR = 1 };
 int nic_set_range_policy(nic_ctx* ctx, int policy);
 int nic_range_trips(nic_ctx* ctx, int64_t* passes);

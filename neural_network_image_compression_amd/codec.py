@@ -83,7 +83,11 @@ class Codec:
         _lib.check(rc, f"nic_set_weights({model}/{layer}/{kind})")
 
     def set_weights(self, weights: W.Weights) -> None:
-        for key, value in weights.items():
+        """Uploads the tensors.  Every model that `weights` holds completely first gets its small
+        split-f16 sites lifted by exact powers of two (weights.lift_low_sites: the same function,
+        bit for bit in fp32; a no-op for weights of ordinary scale), so that the f16x3 path does
+        not lose a down-scaled layer in f16 subnormals.  set_tensor uploads as given."""
+        for key, value in W.lift_low_sites(weights).items():
             model, layer, kind = key.split("/")
             if model not in W.MODEL_ID:
                 raise KeyError(f"unknown model {model!r} in key {key!r}")

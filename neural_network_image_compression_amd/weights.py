@@ -170,6 +170,91 @@ def validate(w: Weights, models: Iterable[str] = MODEL_NAMES) -> None:
             raise TypeError(f"{k}: dtype {a.dtype} != float32")
 
 
+#: a split site whose estimated magnitude is below this is lifted back to it (lift_low_sites)
+LIFT_FLOOR = 2.0 ** -3
+#: the lift never takes the estimate of a site past this (far below the f16 limit 65504)
+LIFT_CEILING = 2.0 ** 10
+
+
+def _residual(model: str) -> Tuple[int, int]:
+    """(layer whose output is the residual, layer it is added to): conv2 -> conv4, dconv1 -> dconv6."""
+    return (1, 3) if model.startswith("encoder") else (0, 2)
+
+
+def site_estimates(w: Weights, model: str) -> List[float]:
+    """A data-free estimate of every layer's output magnitude for inputs in [0, 1]:
+    m_i = m_(i-1) * g_i + max |bias_i|, g_i the largest root-sum-square of the taps feeding one
+    output channel (per output phase for a strided transposed conv), plus the residual's m where
+    it is added.  It is positively homogeneous exactly like the layers: a layer's kernel and bias
+    x 2^-k scale its m by 2^-k.  Spread weights: 1.4 .. 6 against measured maxima of 1.2 .. 4;
+    trained and glorot weights: 0.24 .. 5.6, up to 18 times their measured maxima."""
+    src, dst = _residual(model)
+    m, out = 1.0, []
+    for i, spec in enumerate(layer_table(model)):
+        sq = w[f"{model}/{spec.name}/kernel"].astype(np.float64) ** 2
+        if spec.transposed:  # (kh, kw, Cout, Cin): an output pixel sees the taps of one phase
+            s = spec.stride
+            g = max(float(sq[a::s, b::s].sum(axis=(0, 1, 3)).max()) for a in range(s) for b in range(s))
+        else:
+            g = float(sq.sum(axis=(0, 1, 2)).max())
+        m = m * np.sqrt(g) + float(np.abs(w[f"{model}/{spec.name}/bias"]).max())
+        if i == dst:
+            m += out[src]
+        out.append(m)
+    return out
+
+
+def site_lifts(w: Weights, model: str) -> List[int]:
+    """The exponent e_i >= 0 by which each layer's output is stored larger, 0 for the last layer:
+    the smallest that brings the site's estimate up to LIFT_FLOOR.  The two residual sites share
+    one exponent (the smaller estimate decides, the larger stays under LIFT_CEILING)."""
+    est = site_estimates(w, model)
+
+    def need(m):
+        return max(0, int(np.ceil(np.log2(LIFT_FLOOR / m)))) if 0 < m < LIFT_FLOOR and np.isfinite(m) else 0
+
+    e = [need(m) for m in est[:-1]] + [0]
+    src, dst = _residual(model)
+    hi = max(est[src], est[dst])
+    room = int(np.floor(np.log2(LIFT_CEILING / hi))) if 0 < hi < LIFT_CEILING else 0
+    e[src] = e[dst] = max(0, min(need(min(est[src], est[dst])), room))
+    return e
+
+
+def lift_low_sites(w: Weights) -> Weights:
+    """The same networks with every small split site lifted by an exact power of two.
+
+    The f16x3 kernels store an activation x as hi = f16(x), lo = f16(x - hi).  Under |x| ~ 2^-3
+    lo is an f16 subnormal and x carries an absolute error of up to 2^-25 whatever its size; a
+    network whose layer runs at 2^-k and whose next kernel is larger by 2^k gets that error
+    multiplied back up (1.2e-2 at k = 17 against a 2e-5 contract).  Every layer here is
+    leaky(conv + b), positively homogeneous, so layer i's kernel x 2^(e_i - e_(i-1)) and bias
+    x 2^(e_i) store its output 2^(e_i) larger and leave the function unchanged, bit for bit in
+    fp32 (powers of two commute with rounding).  e_i comes from site_lifts; it is 0, and the
+    tensors are returned as they are, for every site whose estimate is at or above LIFT_FLOOR
+    (all spread, glorot and trained weights of this project).  Models that are not complete in
+    `w`, and models a lift would take out of fp32's normal range, are left alone."""
+    out = dict(w)
+    for model in MODEL_NAMES:
+        table = layer_table(model)
+        names = [f"{model}/{s.name}/{kind}" for s in table for kind in ("kernel", "bias")]
+        if not all(n in w and w[n].dtype == np.float32 for n in names):
+            continue
+        e = site_lifts(w, model)
+        if not any(e):
+            continue
+        new, prev = {}, 0
+        for spec, ei in zip(table, e):
+            for kind, shift in (("kernel", ei - prev), ("bias", ei)):
+                key = f"{model}/{spec.name}/{kind}"
+                new[key] = np.ldexp(w[key], shift).astype(np.float32)
+            prev = ei
+        tiny = np.finfo(np.float32).tiny
+        if all(np.all(np.isfinite(v)) and not np.any((v != 0) & (np.abs(v) < tiny)) for v in new.values()):
+            out.update(new)
+    return out
+
+
 def digest(w: Weights) -> str:
     """SHA-256 over the tensors in key order (raw little-endian fp32 bytes)."""
     h = hashlib.sha256()

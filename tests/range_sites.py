@@ -50,6 +50,8 @@ class Case:
     centre: Optional[Tuple[int, int]] = None   # chosen pixel in the target layer's plane
     radius: int = 0                  # the target layer's receptive-field radius around it
     cover: List[Tuple[int, int]] = field(default_factory=list)  # pixels that must be over-limit
+    low: Optional[int] = None        # low-side cases: the level k, the targets run at 2^-k
+    targets: Tuple[str, ...] = ()    # low-side cases: every split site that runs small
 
     def prefix(self):
         return ("encoder" if self.direction == "enc" else "decoder") + self.model + "/"
@@ -309,6 +311,69 @@ def below_cases():
 
 def all_cases():
     return site_cases() + position_cases() + below_cases()
+
+
+# ---- the low side of the f16 range -----------------------------------------------------------
+# lo = f16(x - f16(x)) is about 2^-11 |x|: below 2^-14 it is an f16 subnormal with the fixed
+# spacing 2^-24, so a site whose activations run at 2^-k carries an absolute split error of up to
+# 2^-25 whatever k is, and the next layer's kernel, larger by 2^k, multiplies it back up.  The
+# cases scale whole layers down by exact powers of two and compensate downstream: the float64
+# oracle's outputs are those of the unscaled spread network bit for bit (tests/test_range_sites.py),
+# the high-side guard is nowhere near, and tests/split_f16_model.py predicts what the split loses.
+LOW_LEVELS = (4, 8, 12, 17, 24)  # 24: hi itself is flushed to zero for typical values
+LOW_SINGLE = {"enc": ("conv1", "conv3"), "dec": ("dconv5", "dconv7")}
+TRUNK = {"enc": ("conv2", "conv3", "conv4", "conv8"), "dec": ("dconv1", "dconv5", "dconv6", "dconv7")}
+# (shape, fused): the smallest of ENCODE_FORMS / DECODE_FORMS that take the fused pair (the
+# decoder's with the Y -> CbCr switch inside a block) and the two-launch form
+LOW_SHAPES = {"enc": ((E_PAIR, True), (E_WS, False)), "dec": (((2, 3, 8), True), (D_WS, False))}
+
+
+def _low_case(direction, what, targets, model, shape, fused, k):
+    base = spread_weights()
+    c = Case(f"low-{what}-{model}-{'x'.join(map(str, shape))}-k{k}", direction, targets[0], model, shape, "exact",
+             seeded_input(direction, shape), dict(base), base=base, fused=fused, low=k, targets=tuple(targets))
+    c.share = direction == "dec"  # DECODE_FORMS' own inputs, the unscaled network's outputs
+    return c
+
+
+def low_site(direction, site, model, shape, fused, k):
+    """scaled_site's mirror: the site's kernel and bias x 2^-k, the next layer's kernel x 2^k."""
+    assert site in LOW_SINGLE[direction]
+    c = _low_case(direction, site, (site,), model, shape, fused, k)
+    _scale_layer(c.weights, c.prefix(), site, -k)
+    return c
+
+
+def low_trunk(direction, model, shape, fused, k):
+    """conv2's kernel and bias, conv3's bias and conv4's bias x 2^-k, conv8's kernel x 2^k: conv2,
+    conv3 and conv4 + res all run at 2^-k and the network is unchanged (conv3's and conv4's kernels
+    see inputs that are already small).  The only exact way to put the residual sites conv2 and
+    conv4 (dconv1 and dconv6: the decoder's dconv1 / dconv5 / dconv6 / dconv7 alike) on the low
+    side: the residual ties their scales together."""
+    L = TRUNK[direction]
+    c = _low_case(direction, "trunk", L[:3], model, shape, fused, k)
+    w, pre = c.weights, c.prefix()
+    _scale(w, pre + L[0] + "/kernel", 2.0 ** -k)
+    for name in L[:3]:
+        _scale(w, pre + name + "/bias", 2.0 ** -k)
+    _scale(w, pre + L[3] + "/kernel", 2.0 ** k)
+    return c
+
+
+@lru_cache(maxsize=None)
+def low_cases(levels=LOW_LEVELS):
+    """Every single site and the whole trunk, under the Y and the CbCr model, in the fused and the
+    two-launch form, at every level.  No level had to be dropped: nothing underflows in fp32 and
+    the bit-identity holds up to k = 24 (tests/test_range_sites.py)."""
+    out = []
+    for direction in ("enc", "dec"):
+        for shape, fused in LOW_SHAPES[direction]:
+            for model in ("Y", "CbCr"):
+                for k in levels:
+                    for site in LOW_SINGLE[direction]:
+                        out.append(low_site(direction, site, model, shape, fused, k))
+                    out.append(low_trunk(direction, model, shape, fused, k))
+    return out
 
 
 def child_cases():

@@ -192,6 +192,17 @@ def test_power_of_two_weight_scaling_is_exact(golden, weights_spread):
     f = O.encode_f32(w, g["x"])
     np.testing.assert_array_equal(f, g["prequant"])
     np.testing.assert_array_equal(O.decode(w, g["latent"]), g["recon"])
+    # the mirror (tests/range_sites.py low_site): the same layers x 2^-17, the next x 2^17, so the
+    # scaled layers' activations fall towards the bottom of the f16 range instead of past its top
+    from tests.range_sites import _scale_layer
+    w = dict(weights_spread)
+    _scale_layer(w, "encoderY/", "conv3", -17)
+    _scale_layer(w, "decoderCbCr/", "dconv5", -17)
+    np.testing.assert_array_equal(O.encode_f32(w, g["x"]), g["prequant"])
+    np.testing.assert_array_equal(O.decode(w, g["latent"]), g["recon"])
+    a, b = O.encoder_activations(w, g["x"])[0], O.encoder_activations(weights_spread, g["x"])[0]
+    np.testing.assert_array_equal(a["conv3"], b["conv3"] * np.float32(2.0 ** -17))
+    np.testing.assert_array_equal(a["conv4"], b["conv4"])
 
 
 def test_float_decoder_check_sees_what_the_u8_check_cannot(weights_spread):
