@@ -564,8 +564,11 @@ int nic_png_device_read(nic_ctx* ctx, const uint8_t* streams, int64_t stride, co
  *     (Conv2D: gat = x, dir = dy, dw HWIO; Conv2DTranspose: gat = dy, dir = x, dw HWOI);
  *     deterministic (per-slice partials in `work`, summed in order); work must hold
  *     nic_conv_wgrad_work() floats.  ca, cb <= 64.
- * nic_absmax_scale: scale[0] = 2^(13 - floor(log2 max|x|)) (1 for 0 / non-finite), so the
- *     split-f16 operands keep every bit of tiny gradients; work >= 512 floats.
+ * nic_absmax_scale: scale[0] = 2^(13 - floor(log2 max|x|)), the exponent held to -126..126, and
+ *     1 when the maximum is 0 or infinite, so the split-f16 operands keep every bit of tiny
+ *     gradients.  The maximum is fmaxf's, which skips a NaN element: finite elements beside a
+ *     NaN keep the scale of their own maximum (the NaN poisons only the sums it enters), and a
+ *     tensor of NaNs alone gets 1.  count = 0 gives 1.  work >= 512 floats.
  * nic_gauss_1d: one-channel planes (n,h,w): VALID correlation with ntaps taps along x
  *     (vertical 0) or y, or its adjoint (the input gradient); the SSIM loss's separable
  *     Gaussian (tf.image.ssim, training.py:119-121).

@@ -666,7 +666,8 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ x
   if (threadIdx.x == 0) part[blockIdx.x] = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
 }
 
-// scale = 2^(13 - floor(log2 max)): max * scale in [2^13, 2^14) (1 for zero / non-finite)
+// scale = 2^(13 - floor(log2 max)): max * scale in [2^13, 2^14) (1 for a zero / infinite max;
+// fmaxf skips NaN elements, so they never reach max)
 __global__ __launch_bounds__(256) void scale_finish_kernel(const float* __restrict__ part, int nb, float* __restrict__ scale) {
   float m = 0.f;
   for (int i = threadIdx.x; i < nb; i += 256) m = fmaxf(m, part[i]);
