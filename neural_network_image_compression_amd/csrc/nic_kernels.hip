@@ -39,7 +39,7 @@
 namespace nic {
 
 // ====================================================================================
-// [common]  Vector types, static_for, diagnostic stamp macros, elementwise helpers, the f16 range guard,
+// [common]  Vector types, static_for, the diagnostic phase clock, elementwise helpers, the f16 range guard,
 // the colour constants and the device CU count.
 // ====================================================================================
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -63,28 +63,57 @@ __constant__ float c_ycbcr[9];         // fp32(ycbcr_kernel), utils.py:7
 __constant__ float c_ycbcr_inv[9];     // fp32(inv(ycbcr_kernel)), utils.py:8
 __constant__ float c_ycbcr_off[3];     // fp32(ycbcr_off), utils.py:9
 
-// Diagnostic build only (tools/stamps.cpp defines NIC_STAMPS): per-block s_memtime stamps
-// at phase boundaries of the split-f16 conv kernel.  The shipped library never records.
+// Phase clock of the persistent kernels.  Diagnostic builds only (the tools/*_stamps.cpp and
+// tools/d7_diag.cpp harnesses define the switch below and point g_stamps at their records): a
+// wave sums the cycles (s_memtime) it spends in each of N phases and writes the sums, and
+// whatever else the harness's record holds, at the end of the kernel.  Every use sits in
+// NIC_CLK(...), which expands to its argument in those builds and to nothing in the shipped
+// library: no clock, no record, not one instruction.
+//   begin()     kernel start: cycles() / span() count from here; also start()
+//   start()     an interval starts now
+//   lap(k)      phase k += the cycles since the last start() / lap(); the next interval starts
+//   count(k)    slot k += 1 (a slot that counts events instead of cycles)
+//   cycles()    s_memtime since begin();  span(): s_memrealtime (100 MHz) since begin()
+//   store(at, v...)  g_stamps[at ..] = the N sums, then v...;  put(at, v...): v... alone
 #ifdef NIC_STAMPS
 __device__ unsigned long long* g_stamps;
-#define NIC_STAMP(k)                                                                         \
-  do {                                                                                       \
-    __builtin_amdgcn_sched_barrier(0);                                                       \
-    if (threadIdx.x == 0)                                                                    \
-      g_stamps[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 + (k)] = __builtin_amdgcn_s_memtime(); \
-    __builtin_amdgcn_sched_barrier(0);                                                       \
-  } while (0)
-// persistent kernels: per-block cycle sums (tools/ws_stamps.cpp, tools/d8_stamps.cpp)
-#define NIC_PNOW(v)                    \
-  do {                                 \
-    __builtin_amdgcn_sched_barrier(0); \
-    v = __builtin_amdgcn_s_memtime();  \
-    __builtin_amdgcn_sched_barrier(0); \
-  } while (0)
+template <int N>
+struct PhaseClock {
+  unsigned long long sum[N] = {}, last = 0, c0 = 0, rt0 = 0;
+  // one s_memtime read that the scheduler moves nothing across
+  static __device__ __forceinline__ unsigned long long now() {
+    __builtin_amdgcn_sched_barrier(0);
+    const unsigned long long t = __builtin_amdgcn_s_memtime();
+    __builtin_amdgcn_sched_barrier(0);
+    return t;
+  }
+  __device__ __forceinline__ void begin() {
+    rt0 = __builtin_amdgcn_s_memrealtime();
+    c0 = last = now();
+  }
+  __device__ __forceinline__ void start() { last = now(); }
+  __device__ __forceinline__ void lap(int k) {
+    const unsigned long long t = now();
+    sum[k] += t - last;
+    last = t;
+  }
+  __device__ __forceinline__ void count(int k) { ++sum[k]; }
+  __device__ __forceinline__ unsigned long long cycles() const { return __builtin_amdgcn_s_memtime() - c0; }
+  __device__ __forceinline__ unsigned long long span() const { return __builtin_amdgcn_s_memrealtime() - rt0; }
+  template <class... V>
+  static __device__ __forceinline__ void put(size_t at, V... v) {
+    unsigned long long* o = g_stamps + at;
+    ((*o++ = (unsigned long long)v), ...);
+  }
+  template <class... V>
+  __device__ __forceinline__ void store(size_t at, V... v) const {
+    static_for<N>([&](auto k) { g_stamps[at + decltype(k)::value] = sum[decltype(k)::value]; });
+    put(at + N, v...);
+  }
+};
+#define NIC_CLK(...) __VA_ARGS__
 #else
-#define NIC_STAMP(k) \
-  do {               \
-  } while (0)
+#define NIC_CLK(...)
 #endif
 
 // b / 255 for a byte b, correctly rounded like the host table c_u8_to_unit (NumPy's
@@ -550,8 +579,8 @@ hipError_t launch_layer(LayerId id, const ConvArgs& a, hipStream_t st) {
 }
 
 // ====================================================================================
-// [split_f16]  Split-f16 building blocks shared by the f16x3 kernels: split4, LDS-DMA helpers, HaloPieces,
-// HaloDma, add_f16_pair, swap16_pair, TileWalk.
+// [split_f16]  Split-f16 building blocks shared by the f16x3 kernels: split4, LDS-DMA helpers, HaloDma,
+// add_f16_pair, swap16_pair, TileWalk.
 // ====================================================================================
 // ------------------------------------------------------------------------------------
 // Split-f16 ("f16x3") implicit-GEMM convolution on v_mfma_f32_32x32x16_f16.
@@ -577,12 +606,7 @@ hipError_t launch_layer(LayerId id, const ConvArgs& a, hipStream_t st) {
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
-
-#ifndef NIC_MIX_SPLIT
-#define NIC_MIX_SPLIT 1
-#endif
 __device__ __forceinline__ void split4(const f32x4& v, f16x4& hi, f16x4& lo) {
-#if NIC_MIX_SPLIT
   // per pair: hi = cvt_pk_f16 (RNE); the exact differences v - f32(hi) by v_fma_mix_f32 with
   // hi read as an f16 half (one op each instead of cvt back + subtract); lo = cvt_pk_f16 of
   // them.  v - f32(hi) is exact in fp32 (Sterbenz; hi within 2x of v or both tiny), so this
@@ -608,14 +632,6 @@ __device__ __forceinline__ void split4(const f32x4& v, f16x4& hi, f16x4& lo) {
       : "v"(d0), "v"(d1), "v"(d2), "v"(d3));
   hi = __builtin_bit_cast(f16x4, H);
   lo = __builtin_bit_cast(f16x4, L);
-#else
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const _Float16 h = (_Float16)v[r];
-    hi[r] = h;
-    lo[r] = (_Float16)(v[r] - (float)h);  // exact difference, then RNE to f16
-  }
-#endif
 }
 
 // Stage the input halo of one block into LDS as f16 hi / lo images.  Loads are issued in
@@ -627,13 +643,7 @@ typedef __attribute__((address_space(3))) const char* lds_cptr_t;
 // LDS byte offset of a generic pointer into __shared__ memory, and back as an LDS pointer
 __device__ __forceinline__ unsigned lds_off(const void* p) { return (unsigned)(size_t)(lds_ptr_t)p; }
 __device__ __forceinline__ lds_cptr_t lds_at(unsigned off) { return (lds_cptr_t)(size_t)off; }
-typedef __attribute__((address_space(1))) void* gbl_ptr_t;
 
-// One 16-B direct-to-LDS load per lane (global_load_lds_dwordx4): lane l of the wave writes
-// LDS bytes [wave_base + 16*l, +16).  No VGPR destination, counted in vmcnt.
-__device__ __forceinline__ void dma16(const char* src, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((gbl_ptr_t)src, (lds_ptr_t)lds_wave_base, 16, 0, 0);
-}
 // vmcnt(0) through the builtin (simm16 0x0F70: vmcnt 0, expcnt 7, lgkmcnt 15) so hipcc's
 // counter model sees the LDS-DMA drained; behind inline asm it would keep treating the DMA
 // as pending and wait vmcnt(0) before every later LDS read, draining the B prefetches.
@@ -663,7 +673,7 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------------------------
 // Persistent-kernel helpers: a tile barrier that is not a memory fence, and LDS-DMA halo
-// pieces (HaloPieces) shared by the weight-stationary kernels.
+// pieces (HaloDma) shared by the weight-stationary kernels.
 // ------------------------------------------------------------------------------------
 __device__ __forceinline__ void stage_barrier() {
   asm volatile("" ::: "memory");  // no LDS access moves across (s_barrier itself is not a fence)
@@ -673,47 +683,9 @@ __device__ __forceinline__ void stage_barrier() {
 // lgkmcnt(0) (vmcnt 63, expcnt 7): this wave's LDS reads of the stage buffer have returned
 __device__ __forceinline__ void lds_reads_done() { __builtin_amdgcn_s_waitcnt(0xC07F); }
 
-template <class G, int CIN, int CCH, int NPW>
-struct HaloPieces {
-  static constexpr int PSS = G::PSB / 16, RPS = G::RPB / 16, HS = CCH / 8;
-  static constexpr int TOTAL = G::HH * RPS;
-  static constexpr int NPIECE = (TOTAL + 63) / 64;
-  static constexpr int NPP = (NPIECE + NPW - 1) / NPW;  // pieces per loader wave (upper bound)
-  int code[NPP];
-  __device__ __forceinline__ void init(int pw, int lane) {
-#pragma unroll
-    for (int i = 0; i < NPP; ++i) {
-      const int q = (pw + i * NPW) * 64 + lane;
-      const int row = q / RPS, r = q - row * RPS;
-      const int sp = r / PSS, k = r - sp * PSS;
-      const int hx = G::S2 ? (sp < G::HE ? 2 * sp : 2 * (sp - G::HE) + 1) : sp;
-      // data slots (the rest is pad); swizzled records (G::SWZ) hold chunk k ^ swz(hx) in slot k
-      const bool read = q < TOTAL && sp < G::HW && (G::SWZ || k < 2 * HS);
-      const int slot = G::SWZ ? G::chunk_at(k, hx) : k < HS ? k : CIN / 8 + (k - HS);  // + c*HS per stage
-      code[i] = read ? (row | hx << 8 | slot << 16 | 1 << 24) : 0;
-    }
-  }
-  // DMA channel slice c of plane base `base` (halo origin gy0, gx0) into buf.  OPAQUE
-  // keeps the compiler from hoisting the decoded pieces out of the tile loop (64-bit
-  // offsets per piece: spills in register-tight kernels).
-  template <bool OPAQUE = false>
-  __device__ __forceinline__ void issue(char* buf, const char* base, const char* zero16, int H, int W, int gy0,
-                                        int gx0, int c, int pw) const {
-#pragma unroll
-    for (int i = 0; i < NPP; ++i) {
-      const int piece = pw + i * NPW;
-      if (NPP * NPW > NPIECE && piece >= NPIECE) break;  // wave-uniform
-      int e = code[i];
-      if constexpr (OPAQUE) asm volatile("" : "+v"(e));
-      const int gy = gy0 + (e & 255), gx = gx0 + ((e >> 8) & 255);
-      const bool ok = (e >> 24) && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
-      const size_t off = ((size_t)(unsigned)(gy * W + gx) * CIN + (size_t)(((e >> 16) & 255) + c * HS) * 4) * 4;
-      dma16(ok ? base + off : zero16, buf + piece * 1024);
-    }
-  }
-};
-
-// LDS-DMA halo pieces through a buffer resource (buffer_load_dwordx4 ... lds): the
+// LDS-DMA halo pieces through a buffer resource (buffer_load_dwordx4 ... lds; one 16-B load
+// per lane: lane l of the wave writes LDS bytes [wave_base + 16 l, +16), no VGPR destination,
+// counted in vmcnt): the
 // resource spans one plane, so every halo slot above, below or outside the plane is out of
 // range and the DMA writes zeros (TF's SAME padding) with no per-piece address select.
 // Per lane and piece the 32-bit byte offset from the halo origin is precomputed once; a
@@ -922,11 +894,8 @@ struct GeomWS {
 // sum_ci h[px][ci] w8[tap][ci] on the same split-f16 MFMA (2 tap blocks x 2 k32-steps x 3,
 // B fragments from an LDS copy of w8), scaled by 2^-k8 and stored tile-major (a.proj).
 // One extra barrier per tile (hproj complete); the next tile's barrier orders its reuse.
-// residual of the k3 layers: LDS-DMA per wave (NIC_RES_DMA=1, default) or VGPR loads
-#ifndef NIC_RES_DMA
-#define NIC_RES_DMA 1
-#endif
-constexpr bool kResDma = NIC_RES_DMA != 0;
+// RESID (the k3 layers): each wave fetches its residual granules by LDS-DMA into a region of
+// its own (the VGPR loads this replaced kept MT x 4 registers live across the MFMA stream).
 template <int CIN, int COUT, int TH, int TW, bool RESID, int KH, int KW, bool TRP, bool PROJ = false>
 __device__ __forceinline__ void ws_body(const ConvArgs& a, char* lds, int model, int bi, int nb, int tb, int py,
                                         int px, bool copy_w8 = true) {
@@ -935,13 +904,9 @@ __device__ __forceinline__ void ws_body(const ConvArgs& a, char* lds, int model,
   static_assert(!(TRP && RESID), "no residual on the transposed phases");
   static_assert(!PROJ || (TRP && COUT == 64 && TH * TW == 64), "projection: dconv7 8x8 tiles");
   using G = GeomWS<CIN, TH, TW>;
-  // halo DMA: buffer-resource pieces (HaloDma) for the plain and projection variants; the
-  // residual variant keeps the global_load_lds pieces (HaloPieces), measured 6 % faster there
-  // (same-box A/B: with HaloDma its stream carries ~8x the s_waitcnt instructions -- exact
-  // lgkmcnt counts instead of lgkmcnt(0) drains -- which the residual epilogue's partner
-  // wave cannot absorb), while HaloDma saves 2-3 % on conv3 / dconv5 / dconv7
-  constexpr bool kBufHalo = !RESID || kResDma;
-  using HP = std::conditional_t<kBufHalo, HaloDma<G, CIN, NW>, HaloPieces<G, CIN, CIN, NW>>;
+  // halo DMA: buffer-resource pieces, 2-3 % faster on conv3 / dconv5 / dconv7 than the
+  // global_load_lds pieces with per-piece address selects they replaced
+  using HP = HaloDma<G, CIN, NW>;
   constexpr int TAP_BYTES = CIN * COUT * 4;
 
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -994,10 +959,7 @@ __device__ __forceinline__ void ws_body(const ConvArgs& a, char* lds, int model,
 
   HP hp;
   const unsigned plane_bytes = (unsigned)((size_t)a.H * a.W * CIN * 4);
-  if constexpr (kBufHalo)
-    hp.init(wave, lane, a.W);
-  else
-    hp.init(wave, lane);
+  hp.init(wave, lane, a.W);
   TileWalk it_issue, it_ep;  // the DMA issue and the epilogue each visit the tiles in order
   it_issue.init(bi, nb, a.tiles_y, a.tiles_x);
   it_ep = it_issue;
@@ -1011,24 +973,13 @@ __device__ __forceinline__ void ws_body(const ConvArgs& a, char* lds, int model,
   auto issue = [&](int i) {  // called for i = 0, 1, 2, ... in order
     int p, t0y, t0x;
     tile_take(it_issue, p, t0y, t0x);
-#ifdef NIC_DIAG_ONETILE  // diagnostic build only: every tile reads the halo of tile (1,1) of its
-                         // model's first plane (input from L2; wrong results)
-    p = p0;
-    t0y = TH;
-    t0x = TW;
-#endif
-    if constexpr (kBufHalo)
-      hp.issue(lds + (i & 1) * G::HALO_BYTES, (const char*)a.in_s + (size_t)p * plane_bytes, plane_bytes, a.W,
-               t0y - a.pad_y, t0x - a.pad_x, wave);
-    else
-      hp.template issue<true>(lds + (i & 1) * G::HALO_BYTES, (const char*)a.in_s + (size_t)p * plane_bytes, a.zero16,
-                              a.H, a.W, t0y - a.pad_y, t0x - a.pad_x, 0, wave);
+    hp.issue(lds + (i & 1) * G::HALO_BYTES, (const char*)a.in_s + (size_t)p * plane_bytes, plane_bytes, a.W,
+             t0y - a.pad_y, t0x - a.pad_x, wave);
   };
 
   f32x4 acc[MT];
-  u32x4 rq[MT];  // split residual of the tile in flight (RESID), in the 16-B store layout
-  // kResDma: the residual tile DMA'd into this wave's LDS region (MT pieces of 1 KB, lane l
-  // at 16 l: the granule it reads back) instead of into VGPRs
+  // RESID: the split residual of the tile in flight, in the 16-B store layout, DMA'd into this
+  // wave's LDS region (MT pieces of 1 KB, lane l at 16 l: the granule it reads back)
   char* res_lds = lds + 2 * G::HALO_BYTES + wave * MT * 1024;
   // 16-B output granule of this lane after swap16_pair: [hi | lo] half (g & 1), channels
   // 16w + 8 (g >> 1) .. +7
@@ -1083,30 +1034,18 @@ __device__ __forceinline__ void ws_body(const ConvArgs& a, char* lds, int model,
     }
   };
   auto proj_dst = [&] {  // a.proj block of the tile whose epilogue just ran (ep_*)
-#ifdef NIC_DIAG_ONEPROJ  // diagnostic build only: every tile writes the same projection block
-    return a.proj + (size_t)(blockIdx.x & 7) * (25 * 64) + 16 * wave + 4 * g;
-#endif
     return a.proj + ((((size_t)ep_p * 4 + 2 * py + px) * a.tiles_y + ep_y / TH) * a.tiles_x + ep_x / TW) * (25 * 64) +
            16 * wave + 4 * g;
   };
-#ifdef NIC_STAMPS
-  unsigned long long s_wait = 0, s_epi = 0, s_mfma = 0, s_t0, s_t1, s_t2;
-  const unsigned long long s_rt0 = __builtin_amdgcn_s_memrealtime(), s_c0 = __builtin_amdgcn_s_memtime();
-  NIC_PNOW(s_t2);
-#endif
+  enum { PH_WAIT, PH_EPI, PH_MFMA };  // tools/ws_stamps.cpp, tools/d7_diag.cpp
+  NIC_CLK(PhaseClock<3> clk; clk.begin());
   if (ntile > 0) issue(0);
   for (int i = 0; i <= ntile; ++i) {
-#ifdef NIC_STAMPS
-    NIC_PNOW(s_t0);
-    if (i > 0) s_mfma += s_t0 - s_t2;
-#endif
+    NIC_CLK(if (i > 0) clk.lap(PH_MFMA); else clk.start());
     dma_wait_all();  // this wave's DMAs of tile i (and the residual loads of tile i-1)
     lds_reads_done();
     stage_barrier();  // tile i's halo complete; everyone is done reading tile i-1's buffer
-#ifdef NIC_STAMPS
-    NIC_PNOW(s_t1);
-    s_wait += s_t1 - s_t0;
-#endif
+    NIC_CLK(clk.lap(PH_WAIT));
     if (i > 0) {  // epilogue of tile i-1: *2^-k, bias, leaky (+ residual), split, 8-B stores
       __amdgpu_buffer_rsrc_t out_rs;
       unsigned out_org = 0;
@@ -1121,8 +1060,7 @@ __device__ __forceinline__ void ws_body(const ConvArgs& a, char* lds, int model,
         f32x4 v = split_act(acc[m], scale, bias);
         if constexpr (RESID) {
           f16x4 rh, rl;
-          if constexpr (kResDma) rq[m] = *(const u32x4*)(res_lds + m * 1024 + lane * 16);
-          unswap16(rq[m], rh, rl);
+          unswap16(*(const u32x4*)(res_lds + m * 1024 + lane * 16), rh, rl);
           typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
           const u32x2 H = __builtin_bit_cast(u32x2, rh), L = __builtin_bit_cast(u32x2, rl);
           static_for<4>([&](auto rc) {
@@ -1163,28 +1101,18 @@ __device__ __forceinline__ void ws_body(const ConvArgs& a, char* lds, int model,
       }
     if (i == ntile) break;
     tile_take(it_ep, ep_p, ep_y, ep_x);
-    if constexpr (RESID) {  // consumed by this tile's epilogue, after the next vmcnt(0)
-      if constexpr (kResDma) {  // this wave's own LDS region: its reads came first
-        const __amdgpu_buffer_rsrc_t rs = plane_rsrc(a.res_s, ep_p, out_plane);
-        const unsigned org = (unsigned)((ep_y * a.OW + ep_x) * PXB);
+    if constexpr (RESID) {  // consumed by this tile's epilogue, after the next vmcnt(0); this
+                            // wave's own LDS region: its reads of it came first
+      const __amdgpu_buffer_rsrc_t rs = plane_rsrc(a.res_s, ep_p, out_plane);
+      const unsigned org = (unsigned)((ep_y * a.OW + ep_x) * PXB);
 #pragma unroll
-        for (int m = 0; m < MT; ++m) {
-          const bool in = ep_y + 2 * m + (l16 >> 3) < a.OH && ep_x + (l16 & 7) < a.OW;
-          dma16_buf(rs, in ? org + g_off[m] : kDmaOOR, res_lds + m * 1024);
-        }
-      } else {
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-          const int oy = min(ep_y + 2 * m + (l16 >> 3), a.OH - 1), ox = min(ep_x + (l16 & 7), a.OW - 1);
-          rq[m] = *(const u32x4*)(a.res_s + (((size_t)ep_p * a.OH + oy) * a.OW + ox) * COUT * 2 + st_off);
-        }
+      for (int m = 0; m < MT; ++m) {
+        const bool in = ep_y + 2 * m + (l16 >> 3) < a.OH && ep_x + (l16 & 7) < a.OW;
+        dma16_buf(rs, in ? org + g_off[m] : kDmaOOR, res_lds + m * 1024);
       }
     }
     const char* buf = lds + (i & 1) * G::HALO_BYTES;
-#ifdef NIC_STAMPS
-    NIC_PNOW(s_t2);
-    s_epi += s_t2 - s_t1;
-#endif
+    NIC_CLK(clk.lap(PH_EPI));
 #pragma unroll
     for (int m = 0; m < MT; ++m) acc[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
     // bx in this buffer (HALO_BYTES is a multiple of 256: the XOR bits are untouched)
@@ -1227,19 +1155,7 @@ __device__ __forceinline__ void ws_body(const ConvArgs& a, char* lds, int model,
     __builtin_amdgcn_s_setprio(0);
   }
   range_report(a.rg, rmax);
-#ifdef NIC_STAMPS
-  if (threadIdx.x == 0) {
-    unsigned long long* o = g_stamps + blockIdx.x * 8;
-    o[0] = s_wait;
-    o[1] = s_epi;
-    o[2] = s_mfma;
-    o[3] = ntile;
-    o[4] = __builtin_amdgcn_s_memtime() - s_c0;
-    o[5] = __builtin_amdgcn_s_memrealtime() - s_rt0;
-    o[6] = NTAPS;
-    o[7] = model;
-  }
-#endif
+  NIC_CLK(if (threadIdx.x == 0) clk.store(blockIdx.x * 8, ntile, clk.cycles(), clk.span(), NTAPS, model));
 }
 
 // Block groups: group gi = blocks [ws_blk[gi], ws_blk[gi + 1]), model gi & 1, tap set gi >> 1
@@ -1250,7 +1166,7 @@ __global__ __launch_bounds__(64 * (COUT / 16), 2) void conv_ws_kernel(ConvArgs a
   using G = GeomWS<CIN, TH, TW>;
   __shared__ __attribute__((aligned(16)))
   char lds[2 * G::HALO_BYTES + (PROJ ? 2 * (CIN / 32) * 2 * 64 * 16 + TH * TW * COUT * 4 : 0) +
-           (RESID && kResDma ? (COUT / 16) * (TH * TW / 16) * 1024 : 0)];
+           (RESID ? (COUT / 16) * (TH * TW / 16) * 1024 : 0)];
   // ws_xcd: block b runs on XCD b % 8; the logical block x * (G / 8) + min(x, G % 8) + b / 8
   // (x = b % 8, a bijection onto [0, G)) gives each XCD a contiguous range of the groups'
   // blocks, so the tiles its blocks take at one time are neighbours whose shared halo rows /
@@ -1357,9 +1273,6 @@ struct GeomS2 {
 // Measured against other forms (4K frames, conv8 alone 0.891-0.900 ms): counting in the ts = 0
 // epilogue lengthened the critical pair of waves, and walks that give a block fewer planes
 // (a contiguous range per block: 1.069 ms; per XCD: 0.952 ms) lose the strip locality.
-#ifndef NIC_WS2_PRIO
-#define NIC_WS2_PRIO 1  // 0 (A/B build): the tap-split streams at the default priority
-#endif
 constexpr int HIST_R = 2;
 constexpr int HIST_LDS = 2 * 256 * HIST_R * 4 + 2 * 2 * 2 * 64 * 4;  // + codes [2][NCG][MT][64] (conv8)
 template <int CIN, int COUT, int NTS, int TH, int OUT_MODE, int TS, bool HIST = false>
@@ -1491,9 +1404,6 @@ __device__ __forceinline__ void ws2_wave(const ConvArgs& a, char* lds, int model
   auto issue = [&](int i) {  // called for i = 0, 1, 2, ... in order
     int p, t0y, t0x;
     tile_take(w_issue, p, t0y, t0x);
-#ifdef NIC_DIAG_C8NODMA  // diagnostic build only: conv8 fetches the first two halos only (wrong results)
-    if (OUT_MODE == OUT_U8_LATENT && i > 1) return;
-#endif
     const int gy0 = 2 * t0y - a.pad_y, gx0 = 2 * t0x - a.pad_x;
     const __amdgpu_buffer_rsrc_t rsrc = plane_rsrc(a.in_s, p, plane_bytes);
     const unsigned org = (unsigned)((gy0 * a.W + gx0) * CIN * 4);
@@ -1513,27 +1423,16 @@ __device__ __forceinline__ void ws2_wave(const ConvArgs& a, char* lds, int model
   int ep_p = 0, ep_y = 0, ep_x = 0;
   float rmax = 0.f;  // range guard of the split outputs
   if (ntile > 0) issue(0);
-#ifdef NIC_STAMPS
-  unsigned long long sx[8] = {}, sa, sb;
-  NIC_PNOW(sa);
-#define WS2_MARK(kk)      \
-  do {                    \
-    NIC_PNOW(sb);         \
-    sx[kk] += sb - sa;    \
-    sa = sb;              \
-  } while (0)
-#else
-#define WS2_MARK(kk) \
-  do {               \
-  } while (0)
-#endif
+  // per wave (tools/c8_stamps.cpp)
+  enum { PH_BARRIER, PH_EPI, PH_ISSUE, PH_MFMA, PH_PART, PH_DRAIN, PH_TAIL };
+  NIC_CLK(PhaseClock<7> clk; clk.start());
   for (int i = 0; i <= ntile; ++i) {
-    WS2_MARK(6);  // (the previous iteration's tail)
+    NIC_CLK(clk.lap(PH_TAIL));  // (the previous iteration's tail)
     dma_wait_all();
     lds_reads_done();
-    WS2_MARK(5);      // DMA / LDS drain
-    stage_barrier();  // halo of tile i complete; partials of tile i-1 written
-    WS2_MARK(0);      // top barrier
+    NIC_CLK(clk.lap(PH_DRAIN));    // DMA / LDS drain
+    stage_barrier();      // halo of tile i complete; partials of tile i-1 written
+    NIC_CLK(clk.lap(PH_BARRIER));  // top barrier
     if constexpr (TS == 0) {
       if (i > 0) {  // epilogue of tile i-1: own sums + the other tap groups' partials
         const char* pp = part + (((i - 1) & 1) * (NTS - 1) * NCG + cg) * PART + lane * 16;
@@ -1569,13 +1468,13 @@ __device__ __forceinline__ void ws2_wave(const ConvArgs& a, char* lds, int model
         }
       }
     }
-    WS2_MARK(1);  // epilogue (ts 0)
+    NIC_CLK(clk.lap(PH_EPI));  // epilogue (ts 0)
     if (i == ntile) break;
     // the next tile's halo into the buffer of tile i-1.  (Its pieces spread through the MFMA
     // stream below instead, one per 2 / 3 groups, took conv8 from 0.0635 to 0.0665 / 0.0701 ms:
     // a piece waiting for the texture path stalls the in-order wave's MFMAs behind it.)
     if (i + 1 < ntile) issue(i + 1);
-    WS2_MARK(2);  // halo DMA issue
+    NIC_CLK(clk.lap(PH_ISSUE));  // halo DMA issue
     if constexpr (HIST) {
       h2_p = h1_p;
       h2_y = h1_y;
@@ -1601,12 +1500,12 @@ __device__ __forceinline__ void ws2_wave(const ConvArgs& a, char* lds, int model
       fb[gq][0] = *(const f16x8*)(buf + grp_off(gq));
       fb[gq][1] = *(const f16x8*)(buf + grp_off(gq) + CIN * 2);
     }
-    // NIC_WS2_PRIO: the MFMA streams at priority 1, the last tap group's (7 taps in conv8, the
+    // The MFMA streams at priority 1, the last tap group's (7 taps in conv8, the
     // most per SIMD pair; its partner ts 1 waits ~1,740 cycles per tile) at 2: conv8 0.0620-0.0624
     // vs 0.0637-0.0640 ms (3 alternating rounds, profiles/r4_ab_logs.txt).  Not with HIST: the
     // ts 1 waves count the codes after their stream, and behind the priority that took conv8 on
     // 4K frames from 0.925 to 1.047 ms.
-    if constexpr (NIC_WS2_PRIO && !HIST) __builtin_amdgcn_s_setprio(TS == NTS - 1 ? 2 : 1);
+    if constexpr (!HIST) __builtin_amdgcn_s_setprio(TS == NTS - 1 ? 2 : 1);
     static_for<NG>([&](auto gqc) {
       constexpr int gq = decltype(gqc)::value;
       constexpr int st = gq / MT, m = gq - st * MT, t = st / KST, ks = st % KST;
@@ -1620,14 +1519,14 @@ __device__ __forceinline__ void ws2_wave(const ConvArgs& a, char* lds, int model
       }
       __builtin_amdgcn_sched_barrier(0);  // keep the stream order
     });
-    if constexpr (NIC_WS2_PRIO && !HIST) __builtin_amdgcn_s_setprio(0);
-    WS2_MARK(3);  // MFMA stream
+    if constexpr (!HIST) __builtin_amdgcn_s_setprio(0);
+    NIC_CLK(clk.lap(PH_MFMA));  // MFMA stream
     if constexpr (TS > 0) {  // partial sums of tile i for the ts = 0 wave of this cg
       char* pp = part + (((i & 1) * (NTS - 1) + TS - 1) * NCG + cg) * PART + lane * 16;
 #pragma unroll
       for (int m = 0; m < MT; ++m) *(f32x4*)(pp + m * 1024) = acc[m];
     }
-    WS2_MARK(4);  // partials
+    NIC_CLK(clk.lap(PH_PART));  // partials
     // HIST: the ts = 1 waves count after their own MFMA stream, where they would wait at the
     // next barrier: tile i-2's codes (stored by ts = 0 at the top of iteration i-1)
     if constexpr (HIST && TS == 1) {
@@ -1656,15 +1555,7 @@ __device__ __forceinline__ void ws2_wave(const ConvArgs& a, char* lds, int model
       if (ntile > 0) hist_flush(hcur);
     }
   }
-#ifdef NIC_STAMPS
-  if (lane == 0) {
-    unsigned long long* o = g_stamps + ((size_t)blockIdx.x * 8 + wave) * 8;
-#pragma unroll
-    for (int q = 0; q < 7; ++q) o[q] = sx[q];
-    o[7] = ntile;
-  }
-#endif
-#undef WS2_MARK
+  NIC_CLK(if (lane == 0) clk.store(((size_t)blockIdx.x * 8 + wave) * 8, ntile));
 }
 
 // XCD-contiguous tile positions: block b of a group of nb runs on XCD
@@ -1912,9 +1803,6 @@ __global__ __launch_bounds__(256) void colour_split_kernel(const uint8_t* __rest
 // so the LDS flag orders its reuse.  Different summation order from the tap-split form (one
 // 75-MFMA chain per output instead of two 36 / 39 chains added in fp32): a different fp32
 // rounding of the same sums, within the oracle contract.
-#ifndef NIC_C12_REUSE
-#define NIC_C12_REUSE 1  // 0 (A/B build): tiles bi, bi + nb, ... and every conv1 halo computed in full
-#endif
 template <int ROLE>
 __device__ __forceinline__ void c12r_wave(const ConvArgs& a, char* lds, int model, int bi, int nb) {
   constexpr int CIN = 32, COUT = 64, MT = 4, NCG = 4;
@@ -1933,28 +1821,16 @@ __device__ __forceinline__ void c12r_wave(const ConvArgs& a, char* lds, int mode
   // the block's tiles: a contiguous raster range (its successive tiles are row neighbours, so
   // conv1's halo columns shared with the previous tile are copied, not recomputed).  Same box
   // (profiles/r6_ab_logs.txt r6r): 4K conv12 3.397 -> 3.333 ms, config 2 equal (its rows are 8
-  // tiles); the contiguous walk alone 3.414
-  constexpr bool CONTIG = NIC_C12_REUSE != 0;
-  const int t_first = CONTIG ? (int)((long long)bi * ntot / nb) : bi;
-  const int ntile = CONTIG ? (int)((long long)(bi + 1) * ntot / nb) - t_first : bi < ntot ? (ntot - bi + nb - 1) / nb : 0;
-  const int t_step = CONTIG ? 1 : nb;
+  // tiles); the contiguous walk alone 3.414, both against the strided walk (tiles bi, bi + nb,
+  // ...) with every conv1 halo computed in full
+  const int t_first = (int)((long long)bi * ntot / nb);
+  const int ntile = (int)((long long)(bi + 1) * ntot / nb) - t_first;
   float rmax = 0.f;
   if (threadIdx.x < NCG) pflag[threadIdx.x] = 0;
-#ifdef NIC_STAMPS  // per wave cycle sums (tools/c12_stamps.cpp)
-  unsigned long long sx[8] = {}, sa, sb;
-  const unsigned long long s_rt0 = __builtin_amdgcn_s_memrealtime(), s_c0 = __builtin_amdgcn_s_memtime();
-  NIC_PNOW(sa);
-#define C12R_MARK(kk)  \
-  do {                 \
-    NIC_PNOW(sb);      \
-    sx[kk] += sb - sa; \
-    sa = sb;           \
-  } while (0)
-#else
-#define C12R_MARK(kk) \
-  do {                \
-  } while (0)
-#endif
+  // per wave (tools/c12_stamps.cpp).  R2: stream, acc stores (+ flag wait), barrier.  R1:
+  // epilogue, conv1, DMA / LDS drain, barrier.
+  enum { PH_BARRIER, PH_EPI, PH_ACC, PH_CONV1, PH_DRAIN, PH_STREAM, PH_PROLOGUE };
+  NIC_CLK(PhaseClock<7> clk; clk.begin());
 
   if constexpr (ROLE == 2) {
     f16x8 wr[25][2];
@@ -1971,7 +1847,7 @@ __device__ __forceinline__ void c12r_wave(const ConvArgs& a, char* lds, int mode
     lds_reads_done();
     stage_barrier();  // prologue barrier 1 (patches 0, 1)
     stage_barrier();  // prologue barrier 2 (halo 0)
-    C12R_MARK(6);
+    NIC_CLK(clk.lap(PH_PROLOGUE));
     for (int i = 0; i < ntile; ++i) {
       const char* buf = lds + (i & 1) * G::HALO_BYTES + boff;
       f32x4 acc[MT];
@@ -1988,27 +1864,20 @@ __device__ __forceinline__ void c12r_wave(const ConvArgs& a, char* lds, int mode
         fb[gq][0] = *(const f16x8*)(buf + grp_off(gq));
         fb[gq][1] = *(const f16x8*)(buf + grp_off(gq) + CIN * 2);
       }
-#if defined(NIC_DIAG_C12R) && NIC_DIAG_C12R == 2  // diagnostic: no R2 stream at all (R1 alone)
-      if (false)
-#endif
       static_for<NG>([&](auto gqc) {
         constexpr int gq = decltype(gqc)::value;
         constexpr int t = gq / MT, m = gq - t * MT;
         f16x8(&cur)[2] = fb[gq % DEPTH];
-#if defined(NIC_DIAG_C12R) && NIC_DIAG_C12R == 1  // diagnostic: the stream's LDS reads, no MFMAs
-        asm volatile("" ::"v"(cur[0]), "v"(cur[1]), "v"(wr[t][0]), "v"(wr[t][1]));
-#else
         acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wr[t][1], cur[0], acc[m], 0, 0, 0);  // w_lo*a_hi
         acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wr[t][0], cur[1], acc[m], 0, 0, 0);  // w_hi*a_lo
         acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wr[t][0], cur[0], acc[m], 0, 0, 0);  // w_hi*a_hi
-#endif
         if constexpr (gq + DEPTH < NG) {
           cur[0] = *(const f16x8*)(buf + grp_off(gq + DEPTH));
           cur[1] = *(const f16x8*)(buf + grp_off(gq + DEPTH) + CIN * 2);
         }
         __builtin_amdgcn_sched_barrier(0);  // keep the stream order
       });
-      C12R_MARK(5);
+      NIC_CLK(clk.lap(PH_STREAM));
       if (i > 0)
         while (__hip_atomic_load(pflag + cg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < i)
           __builtin_amdgcn_s_sleep(1);
@@ -2016,14 +1885,14 @@ __device__ __forceinline__ void c12r_wave(const ConvArgs& a, char* lds, int mode
 #pragma unroll
       for (int m = 0; m < MT; ++m) *(f32x4*)(pp + m * 1024) = acc[m];
       lds_reads_done();  // (lgkmcnt 0: the acc stores too) before the barrier publishes them
-      C12R_MARK(2);
+      NIC_CLK(clk.lap(PH_ACC));
       stage_barrier();   // B_top(i+1)
-      C12R_MARK(0);
+      NIC_CLK(clk.lap(PH_BARRIER));
     }
   } else {
     __builtin_amdgcn_s_setprio(1);  // the vector wave's MFMAs and VALU ahead of the bare stream
     TileWalk w_patch, w_c1, w_ep;
-    w_patch.init(t_first, t_step, a.tiles_y, a.tiles_x);
+    w_patch.init(t_first, 1, a.tiles_y, a.tiles_x);
     w_c1 = w_ep = w_patch;
     auto tile_take = [&](TileWalk& w, int& p, int& t0y, int& t0x) {
       int pl, ty, tx;
@@ -2142,7 +2011,7 @@ __device__ __forceinline__ void c12r_wave(const ConvArgs& a, char* lds, int mode
     auto conv1 = [&](int i) {
       int p, t0y, t0x;
       tile_take(w_c1, p, t0y, t0x);
-      if (CONTIG && i > 0 && t0x > 0)
+      if (i > 0 && t0x > 0)
         conv1_tiles(std::integral_constant<bool, true>{}, i, t0y, t0x);
       else
         conv1_tiles(std::integral_constant<bool, false>{}, i, t0y, t0x);
@@ -2156,7 +2025,7 @@ __device__ __forceinline__ void c12r_wave(const ConvArgs& a, char* lds, int mode
     if (ntile > 0) conv1(0);
     lds_reads_done();
     stage_barrier();
-    C12R_MARK(6);
+    NIC_CLK(clk.lap(PH_PROLOGUE));
     for (int i = 0; i <= ntile; ++i) {
       if (i > 0) {
         // acc(i-1) of this channel group, then the flag that frees the buffer for R2
@@ -2177,34 +2046,20 @@ __device__ __forceinline__ void c12r_wave(const ConvArgs& a, char* lds, int mode
           if (inside) *(u32x4*)(a.out_s + (((size_t)p * a.OH + oy) * a.OW + ox) * COUT * 2 + st_off) = qv;
         }
       }
-      C12R_MARK(1);
+      NIC_CLK(clk.lap(PH_EPI));
       if (i == ntile) break;
       if (i == 0 && ntile > 2) patch_dma(2);
-#if defined(NIC_DIAG_C12R) && NIC_DIAG_C12R == 3  // diagnostic: no conv1 (R2 alone, stale halos)
-      if (false)
-#endif
       if (i + 1 < ntile) conv1(i + 1);
-      C12R_MARK(3);
+      NIC_CLK(clk.lap(PH_CONV1));
       dma_wait_all();   // patch(i+2) landed (the epilogue's stores too)
       lds_reads_done();
-      C12R_MARK(4);
+      NIC_CLK(clk.lap(PH_DRAIN));
       stage_barrier();  // B_top(i+1)
-      C12R_MARK(0);
+      NIC_CLK(clk.lap(PH_BARRIER));
     }
   }
-#ifdef NIC_STAMPS
-  if (lane == 0) {
-    unsigned long long* o = g_stamps + ((size_t)blockIdx.x * 8 + wave) * 8;
-#pragma unroll
-    for (int q = 0; q < 7; ++q) o[q] = sx[q];
-    o[7] = ntile;
-    if (wave == 0) {
-      g_stamps[256 * 64 + 2 * blockIdx.x] = __builtin_amdgcn_s_memtime() - s_c0;
-      g_stamps[256 * 64 + 2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime() - s_rt0;
-    }
-  }
-#endif
-#undef C12R_MARK
+  NIC_CLK(if (lane == 0) clk.store(((size_t)blockIdx.x * 8 + wave) * 8, ntile));
+  NIC_CLK(if (threadIdx.x == 0) clk.put(256 * 64 + 2 * blockIdx.x, clk.cycles(), clk.span()));  // the block's life
   range_report(a.rg, rmax);
 }
 
@@ -2268,9 +2123,6 @@ constexpr int D1_PSB = 64;           // LDS bytes per halo pixel: 32 f16 codes, 
 constexpr int D1_RPB = 800;          // halo row pitch (10 pixels + 160 B): 50 slots = 2 mod 16
 constexpr int D1_HB = 10 * D1_RPB;   // one halo buffer
 constexpr int D1A_LD = 2;  // code dwords per thread per tile (800 over 512 threads)
-#ifndef NIC_D1A_PF
-#define NIC_D1A_PF 2  // code prefetch distance in tiles (1: A/B build)
-#endif
 
 template <int KH1, int KW1, int TB1, int PY1, int PX1, int KH2, int KW2, int TB2, int PY2, int PX2>
 __device__ __forceinline__ void d1all_wave(const ConvArgs& a, char* lds, int model, int bi, int nb) {
@@ -2328,8 +2180,7 @@ __device__ __forceinline__ void d1all_wave(const ConvArgs& a, char* lds, int mod
   // past the walk: an empty resource): with no branch around them the compiler counts them
   // exactly and waits for a tile's codes with vmcnt(N), past the stores issued since, instead of
   // vmcnt(0), which drained the previous tile's stores first (0.0555 vs 0.0568-0.0572 ms,
-  // profiles/r5n_d1_ab; the stores themselves cost ~13 us: 0.043 ms with them dropped,
-  // diagnostic build NIC_DIAG_D1NOST)
+  // profiles/r5n_d1_ab; the stores themselves cost ~13 us: 0.043 ms with them dropped)
   const size_t img_bytes = (size_t)a.H * a.W * 96;
   auto load_codes = [&](uint32_t (&cq)[D1A_LD], bool live) __attribute__((always_inline)) {
     int pl, ty, tx;
@@ -2369,24 +2220,17 @@ __device__ __forceinline__ void d1all_wave(const ConvArgs& a, char* lds, int mod
     f32x4 acc[MT];
 #pragma unroll
     for (int m = 0; m < MT; ++m) acc[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#ifndef NIC_D1_LA
-#define NIC_D1_LA 1  // B-fragment read-ahead in taps (A/B build: 2)
-#endif
-    f16x8 fb[NIC_D1_LA][MT];
+    f16x8 fb[MT];  // B fragments read one tap ahead (two taps were tried: DESIGN section 5c, read-ahead)
 #pragma unroll
-    for (int u = 0; u < NIC_D1_LA; ++u)
-#pragma unroll
-      for (int m = 0; m < MT; ++m)
-        if (u < NTAPS) fb[u][m] = frag(m, u);
+    for (int m = 0; m < MT; ++m) fb[m] = frag(m, 0);
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int t = 0; t < NTAPS; ++t) {
 #pragma unroll
       for (int m = 0; m < MT; ++m) {
-        f16x8& cur = fb[t % NIC_D1_LA][m];
-        acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wr[2 * t + 1], cur, acc[m], 0, 0, 0);  // w_lo*c
-        acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wr[2 * t], cur, acc[m], 0, 0, 0);      // w_hi*c
-        if (t + NIC_D1_LA < NTAPS) cur = frag(m, t + NIC_D1_LA);
+        acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wr[2 * t + 1], fb[m], acc[m], 0, 0, 0);  // w_lo*c
+        acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wr[2 * t], fb[m], acc[m], 0, 0, 0);      // w_hi*c
+        if (t + 1 < NTAPS) fb[m] = frag(m, t + 1);
         __builtin_amdgcn_sched_barrier(0);  // keep the rolling order
       }
     }
@@ -2401,16 +2245,7 @@ __device__ __forceinline__ void d1all_wave(const ConvArgs& a, char* lds, int mod
       for (int r = 0; r < 4; ++r) v[r] = leaky02(scale_bias(acc[m][r], scale, bias[r]));
       const bool in = y < a.H && x < a.W;
       const u32x4 q = split_record(v, in, rmax);
-#ifdef NIC_DIAG_D1NOST  // diagnostic build only: every store dropped (out of range; wrong results)
-      __builtin_amdgcn_raw_buffer_store_b128(q, out_rs, kDmaOOR, 0, 0);
-#elif defined(NIC_DIAG_D1LIN)  // diagnostic build only: the same bytes as 1-KB contiguous stores (wrong layout)
-      {
-        const unsigned tq = (unsigned)(((ty0 >> 3) * a.tiles_x + (tx0 >> 3)) * 4 + py * 2 + px) * 4 + cg;
-        __builtin_amdgcn_raw_buffer_store_b128(q, out_rs, tq * 4096u + (unsigned)(m * 64 + lane) * 16u, 0, 0);
-      }
-#else
       __builtin_amdgcn_raw_buffer_store_b128(q, out_rs, in ? out_org + g_off[m] : kDmaOOR, 0, 0);
-#endif
     }
   };
   auto step = [&](int i, uint32_t (&cq)[D1A_LD]) __attribute__((always_inline)) {
@@ -2427,35 +2262,27 @@ __device__ __forceinline__ void d1all_wave(const ConvArgs& a, char* lds, int mod
     stage_barrier();  // tile i's halo complete; tile i-2's reads of this buffer done everywhere
     int pl, ty, tx;
     it_run.take(pl, ty, tx);
-    if constexpr (NIC_D1A_PF == 2) {
-      load_codes(cq, i + 2 < ntile);  // tile i+2: lands during this tile's and the next's MFMAs
-    } else {  // A/B build: one tile ahead
-      load_codes(cq, i + 1 < ntile);
-    }
+    load_codes(cq, i + 2 < ntile);  // tile i+2: lands during this tile's and the next's MFMAs
     phase(buf, &w1[0][0], std::integral_constant<int, KH1 * 4 + KW1>{}, PY1, PX1, p0 + pl, ty * 8, tx * 8);
     phase(buf, &w2[0][0], std::integral_constant<int, KH2 * 4 + KW2>{}, PY2, PX2, p0 + pl, ty * 8, tx * 8);
   };
   load_codes(cqa, true);
-  if constexpr (NIC_D1A_PF == 2) {
-    load_codes(cqb, ntile > 1);
-    // 16 dropped stores (empty resource): the loop header then sees as many memory operations
-    // younger than cqa / cqb on entry as on the back edge (a tile's 8 stores, the next codes, the
-    // next tile's 8 stores), so the compiler's merged counter waits stay at vmcnt(18) instead of
-    // the prologue's vmcnt(2), which drained the last tile's stores before every other tile
-    {
-      const __amdgpu_buffer_rsrc_t none = __builtin_amdgcn_make_buffer_rsrc((void*)a.out_s, (short)0, 0, kBufWord3);
+  load_codes(cqb, ntile > 1);
+  // 16 dropped stores (empty resource): the loop header then sees as many memory operations
+  // younger than cqa / cqb on entry as on the back edge (a tile's 8 stores, the next codes, the
+  // next tile's 8 stores), so the compiler's merged counter waits stay at vmcnt(18) instead of
+  // the prologue's vmcnt(2), which drained the last tile's stores before every other tile
+  {
+    const __amdgpu_buffer_rsrc_t none = __builtin_amdgcn_make_buffer_rsrc((void*)a.out_s, (short)0, 0, kBufWord3);
 #pragma unroll
-      for (int k = 0; k < 16; ++k) __builtin_amdgcn_raw_buffer_store_b32(0u, none, kDmaOOR + 256u * k, 0, 0);
-    }
-    int i = 0;
-    for (; i + 1 < ntile; i += 2) {  // no branch inside: the back edge's counter state is exact
-      step(i, cqa);
-      step(i + 1, cqb);
-    }
-    if (i < ntile) step(i, cqa);
-  } else {
-    for (int i = 0; i < ntile; ++i) step(i, cqa);
+    for (int k = 0; k < 16; ++k) __builtin_amdgcn_raw_buffer_store_b32(0u, none, kDmaOOR + 256u * k, 0, 0);
   }
+  int i = 0;
+  for (; i + 1 < ntile; i += 2) {  // no branch inside: the back edge's counter state is exact
+    step(i, cqa);
+    step(i + 1, cqb);
+  }
+  if (i < ntile) step(i, cqa);
   range_report(a.rg, rmax);
 }
 
@@ -2523,12 +2350,10 @@ constexpr int K3P_REC = 256;                        // split record: 64 ch x [hi
 constexpr int K3P_RW = K3P_MAX_W + 4;               // records per LDS row (66 used, whole DMA pieces)
 constexpr int K3P_ROWB = K3P_RW * K3P_REC;          // 17,408 B
 constexpr int K3P_NI = 5, K3P_NC = 4;               // input / conv_a ring rows
-// skewed pair: the next input row's DMA issued by conv_b after its deferred epilogue
-// (NIC_K3P_DMAB=1) instead of by conv_a at the step start, whose stream then starts at once
-#ifndef NIC_K3P_DMAB
-#define NIC_K3P_DMAB 1
-#endif
-constexpr bool kK3pDmaB = NIC_K3P_DMAB != 0;
+// skewed pair: the next input row's DMA is issued by conv_b after its deferred epilogue; conv_a's
+// stream then starts at the step barrier.  (conv_a issuing it at the step start was the losing
+// side of the A/B: 460k against 433k cycles per launch by stamps, DESIGN section 5, "Fused k3
+// residual pair".)
 constexpr int K3P_LDS = (K3P_NI + K3P_NC) * K3P_ROWB;  // 156,672 B
 
 __device__ __forceinline__ int k3p_off(int rec, int chunk) { return rec * K3P_REC + ((chunk ^ ((2 * rec) & 15)) << 4); }
@@ -2614,12 +2439,13 @@ __global__ __launch_bounds__(512, 1) void conv_k3pair_kernel(ConvArgs a, K3Range
   int sx0 = 0;
   // input row y (zeros outside the plane) into ring slot `slot`: 1-KB DMA pieces over the 8
   // waves; LDS slot k of record rec holds chunk k ^ (2 rec & 15) of column xi0 + rec
-  // SKEW: the conv_a waves issue every piece (conv_b's step then starts with its epilogue)
+  // SKEW: the conv_b waves issue every piece (the segment's first three rows at its start,
+  // then the next row after their deferred epilogue); a call from conv_a does nothing
   auto dma_row = [&](const __amdgpu_buffer_rsrc_t& rs, int y, int slot) {
     const int npiece = STRIP ? K3P_RW / 4 : (W * 16 + 63) / 64;
     const int xi0 = STRIP ? sx0 - 2 : -1;
     char* dst = in_ring + slot * K3P_ROWB + rec0 * K3P_REC;
-    if (SKEW && role == (kK3pDmaB ? 0 : 1)) return;
+    if (SKEW && role == 0) return;
     for (int k = SKEW ? w : wave; k < npiece; k += SKEW ? 4 : 8) {
       const int q = 64 * k + lane, rec = rec0 + (q >> 4), x = xi0 + rec, ch = (q & 15) ^ ((2 * rec) & 15);
       const bool ok = (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W && rec < K3P_MAX_W + 2;
@@ -2630,15 +2456,12 @@ __global__ __launch_bounds__(512, 1) void conv_k3pair_kernel(ConvArgs a, K3Range
   // one output row of this wave's layer: taps (kh, kw) over LDS rows r_kh (byte offsets), then
   // `epi(m)` for each M tile (a no-op for conv_b in SKEW mode: its epilogue runs next step)
   f32x4 acc[MT];
-#ifdef NIC_STAMPS  // tools/k3p_stamps.cpp: per role, cycles waiting at the step barrier, in the
-                   // MFMA stream, in the epilogue, and in the DMA issue
-  unsigned long long s_wait = 0, s_mfma = 0, s_epi = 0, s_dma = 0, s_t0, s_t1, s_steps = 0;
-  const unsigned long long s_rt0 = __builtin_amdgcn_s_memrealtime(), s_c0 = __builtin_amdgcn_s_memtime();
-#endif
+  // tools/k3p_stamps.cpp: per role, cycles waiting at the step barrier, in the MFMA stream, in
+  // the epilogue and in the DMA issue, and the steps taken
+  enum { PH_WAIT, PH_MFMA, PH_EPI, PH_DMA, N_STEPS };
+  NIC_CLK(PhaseClock<5> clk; clk.begin());
   auto conv_row = [&](unsigned r0b, unsigned r1b, unsigned r2b, auto&& epi) {
-#ifdef NIC_STAMPS
-    NIC_PNOW(s_t0);
-#endif
+    NIC_CLK(clk.start());
 #pragma unroll
     for (int m = 0; m < MT; ++m) acc[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
     constexpr int NSTEP = 9 * KST;
@@ -2681,15 +2504,9 @@ __global__ __launch_bounds__(512, 1) void conv_k3pair_kernel(ConvArgs a, K3Range
       });
     });
     __builtin_amdgcn_s_setprio(0);
-#ifdef NIC_STAMPS
-    NIC_PNOW(s_t1);
-    s_mfma += s_t1 - s_t0;
-#endif
+    NIC_CLK(clk.lap(PH_MFMA));
     static_for<MT>([&](auto mc) { epi(decltype(mc)::value); });
-#ifdef NIC_STAMPS
-    NIC_PNOW(s_t0);
-    s_epi += s_t0 - s_t1;
-#endif
+    NIC_CLK(clk.lap(PH_EPI));
   };
 
   const unsigned in_base = lds_off(in_ring), c3_base = lds_off(c3_ring);
@@ -2741,19 +2558,12 @@ __global__ __launch_bounds__(512, 1) void conv_k3pair_kernel(ConvArgs a, K3Range
       lds_reads_done();  // (first item) the zero records are written
       stage_barrier();
       for (int j = 0; j <= nrow + 2; ++j) {
-#ifdef NIC_STAMPS
-        unsigned long long s_a, s_b;
-        NIC_PNOW(s_a);
-#endif
-        // the next input row lands during this step.  (SKEW: issuing conv_a's pieces inside its
-        // MFMA stream instead measured no faster -- 4 LDS-DMA issues cost ~700 cycles either way)
-        // kK3pDmaB: conv_b issues it, after its deferred epilogue once it has rows (j >= 3)
-        if (j <= nrow && !(SKEW && kK3pDmaB && ROLE == 1 && j >= 3)) dma_row(rs_in, r0 + j + 1, (j + 3) % K3P_NI);
-#ifdef NIC_STAMPS
-        NIC_PNOW(s_b);
-        s_dma += s_b - s_a;
-        ++s_steps;
-#endif
+        NIC_CLK(clk.start());
+        // the next input row lands during this step.  SKEW: conv_b issues it here only until it
+        // has rows to convolve (j < 3), afterwards below, behind its deferred epilogue
+        if (j <= nrow && !(SKEW && ROLE == 1 && j >= 3)) dma_row(rs_in, r0 + j + 1, (j + 3) % K3P_NI);
+        NIC_CLK(clk.lap(PH_DMA));
+        NIC_CLK(clk.count(N_STEPS));
         if constexpr (ROLE == 0) {
           if (j <= nrow + 1) {  // conv_a row y3 = r0 - 1 + j into conv_a ring slot j % 4
             const int y3 = r0 - 1 + j;
@@ -2785,19 +2595,12 @@ __global__ __launch_bounds__(512, 1) void conv_k3pair_kernel(ConvArgs a, K3Range
                          cb2 = c3_base + (unsigned)(((j + 3) % K3P_NC) * K3P_ROWB);
           if constexpr (SKEW) {
             if (j >= 4) {  // row y4 - 1: its accumulators and residual are still in registers
-#ifdef NIC_STAMPS
-              unsigned long long s_e0, s_e1;
-              NIC_PNOW(s_e0);
-#endif
+              NIC_CLK(clk.start());
               static_for<MT>([&](auto mc) { epi_b(decltype(mc)::value, y4 - 1, rs_out); });
-#ifdef NIC_STAMPS
-              NIC_PNOW(s_e1);
-              s_epi += s_e1 - s_e0;
-#endif
+              NIC_CLK(clk.lap(PH_EPI));
             }
             // slot (j + 3) % 5 held row y4 - 1's residual, in registers since the last step
-            if constexpr (kK3pDmaB)
-              if (j <= nrow) dma_row(rs_in, r0 + j + 1, (j + 3) % K3P_NI);
+            if (j <= nrow) dma_row(rs_in, r0 + j + 1, (j + 3) % K3P_NI);
             conv_row(cb0, cb1, cb2, [](int) {});
             load_res(res);  // row y4's residual, read before the next step's DMA reuses its slot
           } else {
@@ -2809,24 +2612,19 @@ __global__ __launch_bounds__(512, 1) void conv_k3pair_kernel(ConvArgs a, K3Range
         }
         // this wave's DMA of the next input row landed; conv_b's MT output stores, issued after
         // it, may stay in flight (vector memory operations complete in issue order on gfx9).
-        // SKEW: conv_b issues no DMA -- only its LDS reads must be done
-#ifdef NIC_STAMPS
-        NIC_PNOW(s_a);
-#endif
-        if (ROLE == 1 && (SKEW || j >= 3)) {
-          if constexpr (!SKEW)
-            __builtin_amdgcn_s_waitcnt(0x0F70 | MT);  // vmcnt(MT), expcnt 7, lgkmcnt 15
-          else if constexpr (kK3pDmaB)
-            dma_wait_all();  // conv_b's pieces of the next row (and its older output stores)
-        } else if (!(SKEW && kK3pDmaB)) {
+        // SKEW: conv_b waits for its pieces of the next row (and its older output stores);
+        // conv_a issues no DMA -- only its LDS reads and writes must be done
+        NIC_CLK(clk.start());
+        if constexpr (SKEW) {
+          if (ROLE == 1) dma_wait_all();
+        } else if (ROLE == 1 && j >= 3) {
+          __builtin_amdgcn_s_waitcnt(0x0F70 | MT);  // vmcnt(MT), expcnt 7, lgkmcnt 15
+        } else {
           dma_wait_all();
         }
         lds_reads_done();  // and its LDS reads / conv_a writes are done
         stage_barrier();
-#ifdef NIC_STAMPS
-        NIC_PNOW(s_b);
-        s_wait += s_b - s_a;
-#endif
+        NIC_CLK(clk.lap(PH_WAIT));
       }
       if constexpr (SKEW)  // the segment's last conv_b row
         if (ROLE == 1 && nrow > 0) static_for<MT>([&](auto mc) { epi_b(decltype(mc)::value, r0 + nrow - 1, rs_out); });
@@ -2837,19 +2635,7 @@ __global__ __launch_bounds__(512, 1) void conv_k3pair_kernel(ConvArgs a, K3Range
   else
     run(std::integral_constant<int, 1>{});
   range_report(a.rg, rmax);
-#ifdef NIC_STAMPS
-  if (lane == 0 && (wave == 0 || wave == 4)) {
-    unsigned long long* o = g_stamps + (size_t)blockIdx.x * 16 + role * 8;
-    o[0] = s_wait;
-    o[1] = s_mfma;
-    o[2] = s_epi;
-    o[3] = s_dma;
-    o[4] = s_steps;
-    o[5] = __builtin_amdgcn_s_memtime() - s_c0;
-    o[6] = __builtin_amdgcn_s_memrealtime() - s_rt0;
-    o[7] = 1;
-  }
-#endif
+  NIC_CLK(if (lane == 0 && (wave == 0 || wave == 4)) clk.store((size_t)blockIdx.x * 16 + role * 8, clk.cycles(), clk.span(), 1));
 }
 
 // strips for a plane of W columns (0: the fused pair does not take it): one for W <= 64, else

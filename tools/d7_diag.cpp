@@ -1,10 +1,12 @@
 // Diagnostic harness (NOT part of the product): dconv7 with dconv8's projection fused
 // (conv_ws_kernel<64,64,8,8,false,true,true>) and conv3 at the config-2 shapes on synthetic
-// data, timed with hipEvents after 30 warm-up launches.  Built in variants with the
-// NIC_DIAG_* switches of nic_kernels.hip (each removes one part of the work and gives wrong
-// results) to bound what each part costs; with -DNIC_STAMPS it prints the per-tile cycle split.
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off [-DNIC_DIAG_ONETILE ...] \
-//     tools/d7_diag.cpp -o ab/d7_base
+// data, timed with hipEvents after 30 warm-up launches.  With -DNIC_STAMPS it also prints the
+// per-tile cycle split (wait / epilogue + issue / MFMA stream) of the kernels' phase clock.
+// (The builds that dropped one part of the work each, with wrong results, to bound its cost
+// are in history; their measurements are in DESIGN section 9.)
+// Usage: d7_diag [iters] [r|z|w|a]   (zero operands: z all, w weights, a activations)
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DNIC_STAMPS \
+//     -I neural_network_image_compression_amd/csrc tools/d7_diag.cpp -o /tmp/d7_diag && /tmp/d7_diag
 #include "../neural_network_image_compression_amd/csrc/nic_kernels.hip"
 
 #include <cstdio>

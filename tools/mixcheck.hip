@@ -1,5 +1,6 @@
-// Diagnostic (NOT part of the product): the v_fma_mix split (csrc/nic_kernels.hip split4,
-// NIC_MIX_SPLIT) against the plain C++ split over 16M fp32 values; exit 0 iff bit-identical.
+// Diagnostic (NOT part of the product): the v_fma_mix split (csrc/nic_kernels.hip split4)
+// against the plain C++ split, kept here as the reference, over 16M fp32 values; exit 0 iff
+// bit-identical.
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off tools/mixcheck.hip -o /tmp/mixcheck
 #include <hip/hip_runtime.h>
 #include <cstdio>

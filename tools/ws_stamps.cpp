@@ -2,7 +2,8 @@
 // with NIC_STAMPS, run at the config-2 shapes on synthetic data.  Wave 0 of every block
 // sums its cycles (s_memtime) in: waiting at the tile barrier (vmcnt drain + s_barrier),
 // the epilogue, the next halo's DMA issue (+ residual loads), and the MFMA stream; s_memrealtime (100 MHz) gives the
-// shader clock.  Build + run (GPU box):
+// shader clock.  The k3 layer with and without the residual; dconv7, which runs with dconv8's
+// projection only, is in tools/d7_diag.cpp.  Build + run (GPU box):
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DNIC_STAMPS \
 //     -I neural_network_image_compression_amd/csrc tools/ws_stamps.cpp -o /tmp/ws_stamps && /tmp/ws_stamps
 #include "../neural_network_image_compression_amd/csrc/nic_kernels.hip"
@@ -35,7 +36,6 @@ int main() {
   const Case cases[] = {
       {"k3", L_CONV3, 64, 64, 64, 64, 9, false},
       {"k3_resid", L_CONV4, 64, 64, 64, 64, 9, true},
-      {"dconv7", L_DCONV7, 64, 64, 128, 128, 25, false},
   };
   float lut[256], k9[9] = {0}, off[3] = {0, .5f, .5f};
   for (int i = 0; i < 256; ++i) lut[i] = i / 255.f;
