@@ -67,6 +67,10 @@ struct WaveEnv {
       out[at] = (uint8_t)byte;
     }
   }
+  // For dist > kWin - len a match's source slots are ring slots its own destination overwrites (lane i
+  // reads what index i + kWin - dist stores; at dist = kWin both are one slot): right only because the
+  // wave loads every lane's byte of a trip before any lane stores, and a later trip's stores come after
+  // (tests/test_gpu_png_read.py::test_edge_streams_are_read_as_pillow_reads_them[far] holds it).
   __device__ void copy_match(uint32_t at, uint32_t dist, uint32_t len) {
     __syncthreads();
     if (dist == 0 || dist > at || len > 258u || at > T || len > T - at) return;

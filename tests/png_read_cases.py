@@ -1,6 +1,9 @@
 """The files and streams shared by the tests of the device PNG reader (tests/test_png_read_format.py,
-tests/test_gpu_png_read.py) and by the CPU corpus of tools/png_read_host_check.cpp, so that what runs
-on the GPU has run through the CPU program first.  Built once per process."""
+tests/test_png_inflate_host.py, tests/test_gpu_png_read.py) and by the CPU corpus of
+tools/png_read_host_check.cpp, so that what runs on the GPU has run through the CPU program first:
+well-formed, unsupported and corrupt files, the status streams, and the edge streams -- deflate that
+is legal but that zlib never writes, and one defect each for the refused ones.  Built once per
+process."""
 import functools
 import io
 import os
@@ -144,3 +147,214 @@ def status_streams() -> dict:
         "one_byte_long": (M.deflate(filt + b"\0", 9), T, 4),
         "filter_5_row_1": (M.deflate(five, 9), T, 16),
     }
+
+
+# ---- deflate's edges: streams zlib does not write (tests/png_make.py's Deflate) ----------------------
+FAR_SHAPE = (140, 257, 1)    # T = 140 * 258 = 36,120: room for a 258-byte match at distance 32,768
+SMALL_SHAPE = (16, 255, 1)   # T = 4,096
+BIG_SHAPE = (255, 256, 1)    # T = 65,535: one stored block of the largest length
+FAR_DISTANCES = (32768, 32767, 32705, 32704, 32511, 32510, 32506)
+RESTAGE_BYTES = tuple(range(2040, 2049))  # around the first re-base of the kernel's 2 KB input ring
+
+# every literal at 9 bits, end-of-block at 2, lengths 3..10 at 5: Kraft-complete, HLIT 265
+GENERIC_LIT = [9] * 256 + [2] + [5] * 8
+GENERIC_DIST = [4, 4] + [5] * 28
+# one code of each length 1..14 and two of 15: Kraft-complete
+LONG_LENS = list(range(1, 15)) + [15, 15]
+
+
+def _grey_stream(shape, seed: int, alphabet: int = 256) -> bytearray:
+    """The filtered stream (filter 0) of a pseudo-random grey image of pixel values < alphabet."""
+    h, w, _ = shape
+    s = np.random.default_rng(seed).integers(0, alphabet, (h, w + 1), dtype=np.uint8)
+    s[:, 0] = 0
+    return bytearray(s.tobytes())
+
+
+def _plant(s: bytearray, shape, at: int, length: int, dist: int) -> tuple:
+    """Make s hold a match of `length` at `at` from `dist` back, keeping every filter byte 0 (one that
+    the match copies is 0 at its source too).  -> the (at, length, dist) for png_make.tokens_of."""
+    row = shape[1] + 1
+    assert 1 <= dist <= at and at + length <= len(s)
+    for p in range(at, at + length):
+        if p % row == 0:
+            assert dist >= length
+            s[p - dist] = 0
+    for p in range(at, at + length):
+        s[p] = s[p - dist]
+    assert all(s[p] == 0 for p in range(0, len(s), row))
+    return (at, length, dist)
+
+
+def _far_stream(at: int, length: int, dist: int, seed: int, lensym=None):
+    """Stored block(s) up to `at`, one fixed block holding the one match (it ends mid-byte), a final
+    stored block for the rest."""
+    s = _grey_stream(FAR_SHAPE, seed)
+    m = _plant(s, FAR_SHAPE, at, length, dist)
+    d = M.Deflate().stored(s[:at])
+    d.fixed([(length, dist) if lensym is None else (length, dist, lensym)])
+    d.stored(s[at + length:], final=True)
+    assert m[0] == at
+    return M.zlib_wrap(d.bytes(), bytes(s)), bytes(s)
+
+
+def _small(seed: int, alphabet: int = 256) -> bytearray:
+    return _grey_stream(SMALL_SHAPE, seed, alphabet)
+
+
+def _long_lit_lens(with_length: bool):
+    """LONG_LENS over the literals 0..14 (0..13 when a length symbol takes part) and end-of-block:
+    literal v at v + 1 bits, 256 at 15 bits, and 257 at 15 bits in place of literal 14."""
+    lens = [0] * (258 if with_length else 257)
+    for v in range(14 if with_length else 15):
+        lens[v] = v + 1
+    lens[256] = 15
+    if with_length:
+        lens[257] = 15
+    assert sorted(l for l in lens if l) == LONG_LENS
+    return lens
+
+
+@functools.lru_cache(maxsize=None)
+def edge_streams() -> dict:
+    """name -> (zlib stream, (h, w, channels), the status nic_png_device_read must give).  The accepted
+    ones (status 0) each reach one edge of legal deflate, which tests/test_png_inflate_host.py proves
+    on png_parse.deflate_blocks' report; the refused ones carry one defect each."""
+    out = {}
+    T = SMALL_SHAPE[0] * (SMALL_SHAPE[1] + 1)
+
+    def small(name, d, s, status=0, **wrap):
+        out[name] = (M.zlib_wrap(d.bytes() if isinstance(d, M.Deflate) else d, bytes(s), **wrap), SMALL_SHAPE, status)
+
+    # -- the far edge of the window: matches whose source and destination share slots of a 32 KB ring
+    for k, dist in enumerate(FAR_DISTANCES):
+        out[f"far_{dist}_at_dist"] = (_far_stream(dist, 258, dist, 100 + k)[0], FAR_SHAPE, 0)
+        out[f"far_{dist}_at_33000"] = (_far_stream(33000, 258, dist, 200 + k)[0], FAR_SHAPE, 0)
+    out["far_wrap_32668_at_dist"] = (_far_stream(32768 - 100, 258, 32768 - 100, 300)[0], FAR_SHAPE, 0)
+    out["far_wrap_32511"] = (_far_stream(32768 - 100, 258, 32511, 301)[0], FAR_SHAPE, 0)
+    out["far_32768_len3"] = (_far_stream(33000, 3, 32768, 302)[0], FAR_SHAPE, 0)
+    out["far_32768_len130"] = (_far_stream(32900, 130, 32768, 303)[0], FAR_SHAPE, 0)
+    out["far_32768_sym284"] = (_far_stream(33000, 258, 32768, 304, lensym=284)[0], FAR_SHAPE, 0)
+
+    # -- codes longer than the 10-bit fast table
+    s = _small(1, 15)
+    s[300:305] = bytes([10, 11, 12, 13, 14])
+    small("long_lit_codes", M.Deflate().dynamic(M.tokens_of(s, 0, T), _long_lit_lens(False), [0], final=True), s)
+    s = _small(2, 14)
+    ms = [_plant(s, SMALL_SHAPE, 700, 3, 1), _plant(s, SMALL_SHAPE, 710, 3, 2), _plant(s, SMALL_SHAPE, 720, 3, 200),
+          _plant(s, SMALL_SHAPE, 730, 3, 100), _plant(s, SMALL_SHAPE, 740, 3, 70), _plant(s, SMALL_SHAPE, 750, 3, 150)]
+    # distance symbols 0 and 1 at 15 bits, symbol k >= 2 at k - 1 bits: 12..15 (distances 65..256) at 11..14 bits
+    dist_lens = [15, 15] + list(range(1, 15))
+    small("long_dist_codes", M.Deflate().dynamic(M.tokens_of(s, 0, T, ms), _long_lit_lens(True), dist_lens, final=True), s)
+
+    # -- dynamic headers zlib does not write
+    six = [3] * 6 + [0] * 250 + [3, 3]  # literals 0..5, end-of-block and length 3 at 3 bits each
+    s = _small(3, 6)
+    ms = [_plant(s, SMALL_SHAPE, 600, 3, 1), _plant(s, SMALL_SHAPE, 610, 3, 4)]
+    cl = [(3, 0)] * 6 + [(18, 127), (18, 101), (3, 0), (16, 3), (3, 0), (3, 0), (3, 0)]  # the 16: lit 257, dist 0..4
+    small("code16_across_hlit", M.Deflate().dynamic(M.tokens_of(s, 0, T, ms), six, [3] * 8, final=True, cl_symbols=cl), s)
+    s = _small(4, 7)
+    seven = [3] * 7 + [0] * 249 + [3] + [0] * 13  # HLIT 270
+    cl = [(3, 0)] * 7 + [(18, 127), (18, 100), (3, 0), (18, 7), (1, 0), (1, 0)]  # the last 18: lit 257..269, dist 0..4
+    small("code18_across_hlit", M.Deflate().dynamic(M.tokens_of(s, 0, T), seven, [0] * 5 + [1, 1], final=True, cl_symbols=cl), s)
+    eight = [8] * 255 + [0, 8]  # every length 8 or 0: only the first five code-length lengths are needed
+    s = _small(5, 255)
+    small("hclen_5", M.Deflate().dynamic(M.tokens_of(s, 0, T), eight, [0], final=True), s)
+    s = _small(6, 15)
+    small("hclen_19", M.Deflate().dynamic(M.tokens_of(s, 0, T), _long_lit_lens(False), [0], final=True), s)
+    s = _small(7, 255)
+    small("hlit_257_hdist_1", M.Deflate().dynamic(M.tokens_of(s, 0, T), eight, [1], final=True), s)
+    s = _small(8, 6)
+    ms = [_plant(s, SMALL_SHAPE, 520 + 10 * k, 3, 1) for k in range(4)]
+    small("one_code_distance_set", M.Deflate().dynamic(M.tokens_of(s, 0, T, ms), six, [1], final=True), s)
+    s = _small(9, 6)
+    small("empty_distance_set", M.Deflate().dynamic(M.tokens_of(s, 0, T), six, [0], final=True), s)
+
+    # -- block sequencing
+    s = _small(10, 4)
+    s[2048:3072] = s[0:1024]  # rows 8..11 repeat rows 0..3: zlib finds the matches across the flush
+    c = zlib.compressobj(9)
+    z = c.compress(bytes(s[:2048])) + c.flush(zlib.Z_SYNC_FLUSH) + c.compress(bytes(s[2048:3072])) + c.flush(zlib.Z_FULL_FLUSH)
+    out["sync_and_full_flush"] = (z + c.compress(bytes(s[3072:])) + c.flush(), SMALL_SHAPE, 0)
+    s = _small(11)
+    ms = {k: _plant(s, SMALL_SHAPE, 340 * k + 20, 10, 335) for k in range(1, 12)}  # each reaches into the block before
+    d = M.Deflate()
+    for k in range(12):
+        lo, hi, m = 340 * k, (340 * (k + 1) if k < 11 else T), ([ms[k]] if k in ms else [])
+        if k % 3 == 0:
+            d.stored(s[lo:hi], final=k == 11)
+        elif k % 3 == 1:
+            d.fixed(M.tokens_of(s, lo, hi, m), final=k == 11)
+        else:
+            d.dynamic(M.tokens_of(s, lo, hi, m), GENERIC_LIT, GENERIC_DIST, final=k == 11)
+    small("twelve_blocks", d, s)
+    s = _grey_stream(BIG_SHAPE, 12)
+    out["stored_65535_then_0"] = (M.zlib_wrap(M.Deflate().stored(s).stored(b"", final=True).bytes(), bytes(s)), BIG_SHAPE, 0)
+    for p in RESTAGE_BYTES:
+        s = _small(1000 + p)
+        # 2 bytes of zlib header, the first block's header byte and LEN / NLEN: its data starts at byte 7
+        d = M.Deflate().stored(s[:p - 7]).fixed(M.tokens_of(s, p - 7, T), final=True)
+        small(f"block_header_at_{p}", d, s)
+        d = M.Deflate().stored(s[:p - 8]).stored(s[p - 8:], final=True)  # header byte at p - 1, LEN at p
+        small(f"stored_len_at_{p}", d, s)
+    s = _small(13)
+    out["bytes_after_adler"] = (M.zlib_wrap(M.Deflate().stored(s, final=True).bytes(), bytes(s)) + b"after", SMALL_SHAPE, 0)
+
+    # -- refused, status 1: the zlib header
+    s = _small(14)
+    body = M.Deflate().stored(s, final=True).bytes()
+    small("cm_7", body, s, 1, cmf=0x77)
+    small("cinfo_8", body, s, 1, cmf=0x88)
+    small("fcheck_off_by_one", body, s, 1, flg=2)
+    small("fdict", body, s, 1, flg=0x20 + (31 - (0x7820 % 31)) % 31)
+    assert ((0x78 << 8) | out["fdict"][0][1]) % 31 == 0 and (0x7700 | out["cm_7"][0][1]) % 31 == 0
+    out["one_byte_stream"] = (b"\x78", SMALL_SHAPE, 1)
+    out["empty_stream"] = (b"", SMALL_SHAPE, 1)
+
+    # -- refused, status 2: the deflate data
+    small("distance_one_past_start", M.Deflate().fixed(list(s[:40]) + [(3, 41)] + list(s[43:T]), final=True), s, 2)
+    out["stored_len_past_input"] = (b"\x78\x01" + M.Deflate().stored(s[:100], final=True, length=4000).bytes(), SMALL_SHAPE, 2)
+    toks = M.tokens_of(s, 0, T)
+    for hlit in (287, 288):
+        small(f"hlit_{hlit}", M.Deflate().dynamic(toks, GENERIC_LIT + [0] * (hlit - 265), GENERIC_DIST, final=True), s, 2)
+    for hdist in (31, 32):
+        small(f"hdist_{hdist}", M.Deflate().dynamic(toks, GENERIC_LIT, GENERIC_DIST + [0] * (hdist - 30), final=True), s, 2)
+    plain = [(ln, 0) for ln in GENERIC_LIT + GENERIC_DIST]
+    used = {sym for sym, _ in plain} | {16}
+    small("code16_first", M.Deflate().dynamic(toks, GENERIC_LIT, GENERIC_DIST, final=True, cl_symbols=[(16, 0)] + plain[3:],
+                                              cl_lens=M.default_cl_lens(used)), s, 2)
+    small("repeat_overruns", M.Deflate().dynamic(toks, GENERIC_LIT, GENERIC_DIST, final=True, cl_symbols=plain[:-2] + [(16, 3)],
+                                                 cl_lens=M.default_cl_lens(used)), s, 2)
+    small("no_end_of_block_code", M.Deflate().dynamic(toks, [8] * 256 + [0], [0], final=True, eob=False), s, 2)
+    small("incomplete_length_set", M.Deflate().dynamic(toks, GENERIC_LIT[:-1] + [0], GENERIC_DIST, final=True), s, 2)
+    small("incomplete_code_length_code", M.Deflate().dynamic(toks, GENERIC_LIT, GENERIC_DIST, final=True,
+                                                             cl_lens=[5 if v in (2, 4, 5, 9) else 0 for v in range(19)]), s, 2)
+    small("hclen_4", M.Deflate().dynamic([], [0] * 257, [0], final=True, cl_symbols=[(18, 127), (18, 109)], cl_lens=[1] + [0] * 17 + [1],
+                                         hclen=4, eob=False), s, 2)
+    s6 = _small(15, 6)
+    codes = M.canonical_codes(six)
+    small("one_code_distance_set_other_code", M.Deflate().dynamic(
+        list(s6[:50]) + [M.Raw(codes[257], 3), M.Raw(1, 1)] + list(s6[53:T]), six, [1], final=True), s6, 2)
+    small("length_under_empty_distance_set", M.Deflate().dynamic(
+        list(s6[:50]) + [M.Raw(codes[257], 3)] + list(s6[53:T]), six, [0], final=True), s6, 2)
+    for sym in (286, 287):
+        small(f"fixed_length_symbol_{sym}", M.Deflate().fixed(list(s[:50]) + [M.Raw(0xC0 + sym - 280, 8)] + list(s[50:T]), final=True), s, 2)
+    for sym in (30, 31):
+        small(f"fixed_distance_symbol_{sym}", M.Deflate().fixed(list(s[:50]) + [M.Raw(1, 7), M.Raw(sym, 5)] + list(s[53:T]), final=True), s, 2)
+
+    # -- refused, status 4: the length
+    s = _small(16)
+    _plant(s, SMALL_SHAPE, T - 2, 2, 1)
+    small("match_passes_T", M.Deflate().fixed(list(s[:T - 2]) + [(3, 1)], final=True), bytes(s) + bytes(s[-1:]), 4)
+    small("stored_passes_T", M.Deflate().stored(bytes(s) + b"\0", final=True), bytes(s) + b"\0", 4)
+    small("three_adler_bytes", M.Deflate().fixed(list(s), final=True), s, 4, adler_bytes=3)
+    return out
+
+
+def edge_image(name: str) -> np.ndarray:
+    """The (h, w) grey image of an accepted edge stream: zlib's bytes of it without the filter bytes."""
+    stream, (h, w, _), status = edge_streams()[name]
+    assert status == 0
+    filt = np.frombuffer(zlib.decompress(stream), np.uint8).reshape(h, w + 1)
+    assert not filt[:, 0].any()
+    return np.ascontiguousarray(filt[:, 1:])

@@ -1,7 +1,11 @@
 """The device PNG reader on the GPU: Codec.png_read against Pillow's pixels, byte for byte, over the
-block types, filters, window distances and writers; the status bits; the drivers with
-png_reader="device" against the "pillow" run's files.  Every malformed stream here has been through
-tools/png_read_host_check.cpp (the same nic_inflate.h on the CPU, under sanitizers) first."""
+block types, filters, window distances and writers; deflate's edges that zlib never writes (the edge
+streams of tests/png_read_cases.py: matches whose source and destination share slots of the 32 KB LDS
+ring, codes longer than the fast table, header forms, block sequences, headers on the input ring's
+first restage); unfilter at the widest rows; the status bits, with nothing stored outside the images;
+the drivers with png_reader="device" against the "pillow" run's files.  Every hand-made stream here
+goes through tools/png_read_host_check.cpp (the same nic_inflate.h on the CPU, under sanitizers) in
+tests/test_png_inflate_host.py first, which also proves that each reaches its edge."""
 import io
 import os
 import zlib
@@ -103,17 +107,121 @@ def test_overlapping_matches_of_length_258(codec):
 
 
 def test_far_window_and_small_window(codec):
-    """png_parse.deflate_blocks cannot walk these two streams (it stops short of the Adler-32 on the
-    first and does not end on the second), so that they differ is asserted on what the streams state
-    themselves: CINFO 7 against 1, and the 512-byte window's stream more than twice as long, since it
-    cannot reach the repeat at distance 18,496."""
+    """The 32 KB window's stream reaches the repeat at distance 18,496; the 512-byte window's cannot go
+    beyond 250 (the window less zlib's 262-byte lookahead) and is more than twice as long.  (The walker
+    could not walk these streams while it dropped the bits of every distance code: `pos += f(pos)`
+    reads pos before f moves it.)"""
     top = C.rgb_image(64, 96)
     a = np.ascontiguousarray(np.concatenate([top, top]))  # rows 64..127 repeat rows 0..63: distance 64 * 289 = 18,496
     far, near = M.make_png(a, 0, level=9), M.make_png(a, 0, level=9, wbits=9)
     zf, zn = png_parse.parse(far).idat, png_parse.parse(near).idat
     assert zf[0] >> 4 == 7 and zn[0] >> 4 == 1
     assert zf[2:] != zn[2:] and 2 * len(zf) < len(zn)
+    bf, bn = png_parse.deflate_blocks(zf), png_parse.deflate_blocks(zn)
+    assert max(b["max_dist"] for b in bf) == 18496 and sum(len(b["far"]) for b in bf) > 0
+    assert max(b["max_dist"] for b in bn) == 250 and len(bn) > len(bf)
     check_files(codec, [far, near])
+
+
+# ---- deflate's edges (tests/png_read_cases.py edge_streams) -----------------------------------------
+def edge_files(names):
+    return [M.frame(*C.edge_streams()[n][1], C.edge_streams()[n][0]) for n in names]
+
+
+def edge_groups():
+    """shape -> the accepted edge streams' names of that shape"""
+    groups = {}
+    for name, (_, shape, status) in sorted(C.edge_streams().items()):
+        if status == 0:
+            groups.setdefault(shape, []).append(name)
+    return groups
+
+
+@pytest.mark.parametrize("shape", [C.FAR_SHAPE, C.SMALL_SHAPE, C.BIG_SHAPE], ids=["far", "small", "big"])
+def test_edge_streams_are_read_as_pillow_reads_them(codec, shape):
+    """One batch per shape: the far-distance matches (FAR_SHAPE), the long codes, header forms, block
+    sequences and restage positions (SMALL_SHAPE), the 65,535-byte stored block (BIG_SHAPE)."""
+    import torch
+
+    names = edge_groups()[shape]
+    assert len(names) == {C.FAR_SHAPE: 19, C.SMALL_SHAPE: 30, C.BIG_SHAPE: 1}[shape]
+    images = check_files(codec, edge_files(names))
+    want = np.stack([C.edge_image(n) for n in names])[..., None]  # zlib's bytes, as the CPU check compared them
+    assert torch.equal(images.cpu(), torch.from_numpy(want))
+
+
+def test_far_matches_do_not_depend_on_the_batch(codec):
+    """The far-distance group again with a short stream (a flat image, under 200 bytes) on either side of
+    every member: the same pixels as in the batch of their own."""
+    import torch
+
+    names = edge_groups()[C.FAR_SHAPE]
+    h, w, _ = C.FAR_SHAPE
+    flat = M.make_png(np.full((h, w), 9, np.uint8), 0, level=9)
+    assert len(png_parse.parse(flat).idat) < 200
+    alone = check_files(codec, edge_files(names))
+    files = [flat]
+    for f in edge_files(names):
+        files += [f, flat]
+    mixed = check_files(codec, files)
+    assert torch.equal(mixed[1::2], alone) and bool((mixed[0::2] == 9).all())
+
+
+def test_refused_edge_streams_give_their_status_and_touch_nothing_else(codec):
+    """[good, bad, good, bad, ..., good] in one batch: every bad stream gives exactly its status, every
+    good image is intact, and nothing is stored outside the images tensor."""
+    import torch
+
+    h, w, ch = C.SMALL_SHAPE
+    names = sorted(n for n, v in C.edge_streams().items() if v[2] != 0)
+    assert len(names) == 27 and all(C.edge_streams()[n][1] == C.SMALL_SHAPE for n in names)
+    a = C.edge_image("twelve_blocks")
+    good = C.edge_streams()["twelve_blocks"][0]
+    streams, want = [good], [0]
+    for n in names:
+        streams += [C.edge_streams()[n][0], good]
+        want += [C.edge_streams()[n][2], 0]
+    count, pad = len(streams) * h * w * ch, 1 << 16
+    big = torch.full((pad + count + pad,), 0xA5, dtype=torch.uint8, device="cuda")
+    out = big[pad:pad + count].view(len(streams), h, w, ch)
+    from neural_network_image_compression_amd import bitstream as B
+
+    buf, lens = B._upload_files(codec, [s if s else b"\0" for s in streams])
+    lens = lens.new_tensor([len(s) for s in streams])
+    images, status = codec.png_read_status(buf, lens, h, w, ch, out=out)
+    assert images.data_ptr() == out.data_ptr()
+    got = dict(zip(names, status.cpu().tolist()[1::2]))
+    assert got == {n: C.edge_streams()[n][2] for n in names}
+    assert status.cpu().tolist() == want
+    good_px = torch.from_numpy(a[..., None]).cuda()
+    assert all(torch.equal(out[k], good_px) for k in range(0, len(streams), 2))
+    assert bool((big[:pad] == 0xA5).all()) and bool((big[pad + count:] == 0xA5).all())
+
+
+# ---- unfilter at the widest rows ----------------------------------------------------------------
+def band_filters(h):
+    """Rows 63, 64, 65, 127 and 128 take Paeth, Average, Up, Paeth and Average: row 64 k is lane 0 of a
+    band and reads the row above through LDS."""
+    return [(4, 3, 2, 1)[(r - 63) % 4] for r in range(h)]
+
+
+@pytest.mark.parametrize("w,ch", [(16384, 1), (5461, 3)], ids=["grey16384", "rgb5461"])
+@pytest.mark.parametrize("h", [65, 129])
+def test_unfilter_at_the_widest_rows(codec, h, w, ch):
+    """Rows of 16,384 and 16,383 bytes: the whole of uprow, which is indexed by mask.  Noise, so that
+    every predictor's choice matters; with h = 129 and one channel also an all-255 image under filter
+    0 (T = 2,113,665 bytes of which 2,113,536 are 255: both Adler sums wrap many times)."""
+    rng = np.random.default_rng(h * 7 + ch)
+    a = rng.integers(0, 256, (h, w) if ch == 1 else (h, w, ch), dtype=np.uint8)
+    fs = band_filters(h)
+    assert all(fs[r] == f for r, f in {63: 4, 64: 3, 65: 2, 127: 4, 128: 3}.items() if r < h) and len(fs) == h
+    files = [M.make_png(a, fs, level=1)]
+    got = png_parse.parse(files[0])
+    assert list(got.filter_bytes()) == fs and got.width * got.channels == w * ch >= 16383
+    if h == 129 and ch == 1:
+        files.append(M.make_png(np.full((h, w), 255, np.uint8), 0, level=1))
+        assert len(png_parse.parse(files[1]).filtered) == 2113665
+    check_files(codec, files)
 
 
 def test_huffman_only_and_rle(codec):

@@ -1,7 +1,9 @@
 """CPU checks of the device PNG reader's host half: nic_png_inspect on Pillow's, the native writer's
-and hand-built files, its unsupported and corrupt verdicts, and the drivers' option checks (which
-raise before any GPU call)."""
+and hand-built files (the framed edge streams of tests/png_read_cases.py among them, which Pillow
+must read as the images they were built from), its unsupported and corrupt verdicts, the drivers'
+option checks (which raise before any GPU call), and png_make's filters against Pillow."""
 import ctypes
+import io
 
 import numpy as np
 import pytest
@@ -9,6 +11,9 @@ import pytest
 from neural_network_image_compression_amd import _lib
 from neural_network_image_compression_amd import bitstream as B
 from neural_network_image_compression_amd.codec import Decoder, Encoder
+from PIL import Image
+
+from tests import png_make as M
 from tests import png_parse, png_read_cases as C
 
 
@@ -30,6 +35,35 @@ def test_inspect_returns_shape_and_stream(name):
     assert shape == (p.height, p.width, p.channels)
     assert stream == p.idat
     assert B.png_stream(data) == (p.height, p.width, p.channels, p.idat)
+
+
+def pillow_pixels(data: bytes) -> np.ndarray:
+    with Image.open(io.BytesIO(data)) as im:
+        return np.array(im)
+
+
+@pytest.mark.parametrize("name", sorted(n for n, v in C.edge_streams().items() if v[2] == 0))
+def test_framed_edge_streams_are_files_pillow_and_inspect_take(name):
+    """The GPU test's reference for an edge stream is Pillow's reading of the framed file: here it is
+    the image the stream was built from, and nic_png_inspect hands the stream back unchanged."""
+    stream, (h, w, ch), _ = C.edge_streams()[name]
+    data = M.frame(h, w, ch, stream)
+    rc, shape, got = inspect(data)
+    assert rc == _lib.NIC_OK, _lib.last_error()
+    assert shape == (h, w, ch) and got == stream
+    assert np.array_equal(pillow_pixels(data), C.edge_image(name))
+
+
+@pytest.mark.parametrize("f", range(5))
+def test_png_make_filters_are_png_s(f):
+    """filter_rows (Paeth vectorised) against Pillow's unfilter, RGB and grey, more than one row."""
+    a = C.rgb_image(37, 53)
+    g = np.ascontiguousarray(a[:, :, 1])
+    assert np.array_equal(pillow_pixels(M.make_png(a, f)), a) and np.array_equal(pillow_pixels(M.make_png(g, f)), g)
+    mixed = [(f + r) % 5 for r in range(37)]
+    assert np.array_equal(pillow_pixels(M.make_png(a, mixed)), a)
+    one = np.ascontiguousarray(a[:, :1])  # one pixel per row: no left neighbour anywhere
+    assert np.array_equal(pillow_pixels(M.make_png(one, f)), one)
 
 
 def test_idat_sizes_and_ancillary_chunks_really_occur():

@@ -2,13 +2,16 @@
 // compiles -- run serially over a corpus of zlib streams, meant to be built with
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
 //       tools/png_read_host_check.cpp -o png_read_host_check
-// and fed the directory tools/png_read_corpus.py writes.  Every corpus file is
+// and fed the directory tools/png_read_corpus.py writes (tests/test_png_inflate_host.py does both).
+// Every corpus file is
 //   u32 T (little-endian) | u8 expect (0: zlib.decompress gives exactly T bytes; 1: it raises, or the
-//   length is not T) | the stream
+//   length is not T) | u8 status (the exact status bits 1..8 the stream must give; 255: not pinned) |
+//   u8 bytes (1: zlib's T output bytes follow) | [T bytes] | the stream
 // and its buffers are heap blocks of exactly the stream's and T bytes, so an index a check let through
-// is a sanitizer report.  The program fails (exit 1) when a status disagrees with `expect`, when the
-// block + symbol loop ran more than 8 * size + 1 times, or when a status-0 output differs in its
-// Adler-32 from the stream's field (then the status carries bit 8, which `expect` 0 forbids).
+// is a sanitizer report.  The program fails (exit 1) when a status disagrees with `expect` or with a
+// pinned `status`, when the block + symbol loop ran more than 8 * size + 1 times, when a status-0
+// output differs in its Adler-32 from the stream's field (then the status carries bit 8, which
+// `expect` 0 forbids), or when the output differs from zlib's bytes.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -51,22 +54,28 @@ int main(int argc, char** argv) {
   for (const auto& e : std::filesystem::directory_iterator(argv[1]))
     if (e.path().extension() == ".bin") paths.push_back(e.path().string());
   std::sort(paths.begin(), paths.end());
-  long files = 0, bad = 0, ok0 = 0, by_bit[5] = {0, 0, 0, 0, 0};
+  long files = 0, bad = 0, ok0 = 0, compared = 0, pinned_n = 0, by_bit[5] = {0, 0, 0, 0, 0};
   uint64_t worst_iters = 0, worst_bound = 0;
   auto lit = std::make_unique<inf::Huff>(), dst = std::make_unique<inf::Huff>();
   for (const std::string& p : paths) {
     std::ifstream f(p, std::ios::binary);
     std::vector<char> raw((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-    if (raw.size() < 5) {
+    if (raw.size() < 7) {
       std::fprintf(stderr, "%s: short corpus file\n", p.c_str());
       return 2;
     }
     uint32_t T;
     std::memcpy(&T, raw.data(), 4);
-    const int expect = (uint8_t)raw[4];
-    const uint32_t size = (uint32_t)(raw.size() - 5);
+    const int expect = (uint8_t)raw[4], pinned = (uint8_t)raw[5];
+    const size_t head = 7 + (raw[6] ? (size_t)T : 0);
+    if (raw.size() < head) {
+      std::fprintf(stderr, "%s: short corpus file\n", p.c_str());
+      return 2;
+    }
+    const uint8_t* want = raw[6] ? (const uint8_t*)raw.data() + 7 : nullptr;
+    const uint32_t size = (uint32_t)(raw.size() - head);
     std::unique_ptr<uint8_t[]> in(new uint8_t[size]), out(new uint8_t[T]), lens(new uint8_t[inf::kLensSize]);
-    std::memcpy(in.get(), raw.data() + 5, size);
+    std::memcpy(in.get(), raw.data() + head, size);
     std::memset(out.get(), 0, T);
     HostEnv env{in.get(), size, out.get(), T};
     uint32_t adler = 0;
@@ -93,8 +102,20 @@ int main(int argc, char** argv) {
       std::printf("FAIL %s: status %d, zlib %s\n", p.c_str(), st, expect ? "refuses it" : "takes it");
       ++bad;
     }
+    if (pinned != 255 && st != pinned) {
+      std::printf("FAIL %s: status %d, expected exactly %d\n", p.c_str(), st, pinned);
+      ++bad;
+    }
+    if (want && (st != 0 || std::memcmp(out.get(), want, T) != 0)) {
+      std::printf("FAIL %s: the output differs from zlib's bytes\n", p.c_str());
+      ++bad;
+    }
+    compared += want != nullptr;
+    pinned_n += pinned != 255;
   }
-  std::printf("%ld streams: %ld status 0; bits 1/2/4/8: %ld %ld %ld %ld; most loop iterations %llu (bound %llu); %ld failures\n", files,
-              ok0, by_bit[0], by_bit[1], by_bit[2], by_bit[3], (unsigned long long)worst_iters, (unsigned long long)worst_bound, bad);
+  std::printf("%ld streams: %ld status 0; bits 1/2/4/8: %ld %ld %ld %ld; most loop iterations %llu (bound %llu); %ld outputs compared with "
+              "zlib's bytes; %ld exact statuses; %ld failures\n",
+              files, ok0, by_bit[0], by_bit[1], by_bit[2], by_bit[3], (unsigned long long)worst_iters, (unsigned long long)worst_bound,
+              compared, pinned_n, bad);
   return bad ? 1 : 0;
 }
