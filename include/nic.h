@@ -464,6 +464,45 @@ int nic_rans3_decode_windows(nic_ctx* ctx, const uint8_t* files, int64_t stride,
 int nic_cut_boxes(nic_ctx* ctx, const uint8_t* images, int n, int Hs, int Ws, const int32_t* offsets, int bh, int bw, uint8_t* boxes,
                   void* stream);
 
+/* ---- Crops of mixed sizes, resized on the device for training ------------------------------------
+ * A training loader draws a box of another size out of every image and resizes it to one output size
+ * ("Crops of mixed sizes, resized on the device").  Boxes of different sizes get latent
+ * windows of one shape from nic_region_plan_window, so they decode as one batch; nic_resample_boxes
+ * turns the windows' reconstructions into the model's input.
+ *
+ * nic_region_plan_window: HOST only, beside nic_region_plan_fixed (the same boxes are valid, the same
+ *     error codes), with the window's shape given: per axis R = (bh + 6) / 8 + 1 + 2 NIC_DECODE_HALO
+ *     as in the fixed plan, rows_want >= R and cols_want >= C (NIC_ESHAPE otherwise), rows = min(h8,
+ *     rows_want), r0 = clamp(y / 8 - NIC_DECODE_HALO, 0, h8 - rows); columns likewise.  win4 and off2
+ *     as in the fixed plan, and at (R, C) the fixed plan's values.  The window holds
+ *     nic_region_plan's, and each of its edges lies on the latent's edge or at least NIC_DECODE_HALO
+ *     beyond the box's latent pixels, so the cut at off2 is as exact.
+ * nic_resample_boxes: images (n, Hs, Ws, 3) u8; table int32[n][6] = {oy, ox, bh, bw, flip, dst} on the
+ *     DEVICE (4-byte aligned): the bh x bw box at (oy, ox) of image i, resized to oh x ow, mirrored
+ *     left to right where flip is 1, becomes image dst of out (16-byte aligned):
+ *       NIC_RESAMPLE_F32  (n_out, 3, oh, ow) fp32,  v scale3[c] + bias3[c] (one fma; v in 0..255)
+ *       NIC_RESAMPLE_F16  the same, rounded to f16
+ *       NIC_RESAMPLE_U8   (n_out, oh, ow, 3) u8, v rounded half to even and clamped to 0..255; scale3
+ *                         and bias3 are not read and may be NULL
+ *     scale3 and bias3 are HOST arrays of 3 floats.  One launch on `stream`, no host synchronisation,
+ *     no workspace.  The resize is torch.nn.functional.interpolate(mode="bilinear", align_corners=
+ *     False, antialias=True) on float input: per axis s = in / out (in = bh or bw), support = max(s,
+ *     1), c = s (i + 0.5), taps [max(0, int(c - support + 0.5)), min(int(c + support + 0.5), in)),
+ *     tap p weighs max(0, 1 - |p + 0.5 - c| / support) over the taps' sum; separable; taps never
+ *     leave the box.  At bh = oh and bw = ow the output is the source pixel.  fp32 arithmetic.
+ *     The kernel does not trust the table: a row with bh < 1, bw < 1, oy < 0, ox < 0, oy + bh > Hs,
+ *     ox + bw > Ws, flip not 0 or 1, or dst outside [0, n_out) is skipped and stores nothing; no row
+ *     reads outside images[i] or writes outside out[dst].  Rows that name one dst race.
+ *     Validated before any HIP call: n in 0..65535, Hs, Ws >= 1, Hs Ws <= 2^29, 1 <= oh, ow <= 16384,
+ *     n_out >= 1, n_out 3 oh ow < 2^40 (NIC_ESHAPE); out_kind (NIC_EINVAL); empty batch (OK); NULL;
+ *     alignment (NIC_EINVAL). */
+#define NIC_RESAMPLE_F32 0
+#define NIC_RESAMPLE_F16 1
+#define NIC_RESAMPLE_U8 2
+int nic_region_plan_window(int H, int W, int y, int x, int bh, int bw, int rows_want, int cols_want, int* win4, int* off2);
+int nic_resample_boxes(nic_ctx* ctx, const uint8_t* images, int n, int Hs, int Ws, const int32_t* table, int oh, int ow, int n_out,
+                       int out_kind, const float* scale3, const float* bias3, void* out, void* stream);
+
 /* ---- The device PNG writer: complete PNG files written on the device --------------------------
  * An optional writer for reconstructions (Pillow's optimize=True file, nic_png_encode, stays the
  * default and the bitstream's format).  Format: DESIGN.md, "The device PNG writer":

@@ -37,6 +37,7 @@ NIC_EUNSUPPORTED = -9
 
 RANGE_POLICIES = {"fallback": 0, "error": 1}  # nic.h NIC_RANGE_FALLBACK / NIC_RANGE_ERROR
 PNG_FILTER_ADAPTIVE = -1  # nic.h NIC_PNG_FILTER_ADAPTIVE
+DECODE_HALO = 3  # nic.h NIC_DECODE_HALO
 
 _lib: Optional[ctypes.CDLL] = None
 _lock = threading.Lock()
@@ -126,6 +127,9 @@ _SIGNATURES = {
     "nic_rans3_decode_windows": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp, ctypes.c_int, c_vp] + [ctypes.c_int] * 3
                                  + [c_vp] * 3),
     "nic_cut_boxes": (ctypes.c_int, [c_vp, c_vp] + [ctypes.c_int] * 3 + [c_vp] + [ctypes.c_int] * 2 + [c_vp, c_vp]),
+    # crops of mixed sizes (nic_capi.hip nic_region_plan_window, nic_resample.hip)
+    "nic_region_plan_window": (ctypes.c_int, [ctypes.c_int] * 8 + [ctypes.POINTER(ctypes.c_int)] * 2),
+    "nic_resample_boxes": (ctypes.c_int, [c_vp, c_vp] + [ctypes.c_int] * 3 + [c_vp] + [ctypes.c_int] * 4 + [c_vp] * 4),
     # device PNG writer (nic_png_dev.hip)
     "nic_png_device_block_bytes": (ctypes.c_int, []),
     "nic_png_device_bound": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int64)]),

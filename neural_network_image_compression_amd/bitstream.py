@@ -443,6 +443,102 @@ def decode_regions(decoder, files: Sequence, boxes):
     return out
 
 
+def _window_groups_any(codec, files: Sequence[bytes], boxes, bucket, who: str, names: Sequence[str]):
+    """_window_groups for boxes of any sizes: its checks without the equal-size one, then
+    Codec.region_plan_window towards the call's one target shape (bucket None) or each box's own need
+    rounded up to multiples of bucket.  Returns the boxes, the version and the groups, as there."""
+    boxes = [tuple(int(v) for v in b) for b in boxes]
+    if len(boxes) != len(files):
+        raise ValueError(f"{who}: {len(boxes)} boxes for {len(files)} files: one box (y, x, h, w) per file")
+    if bucket is not None and (isinstance(bucket, bool) or not isinstance(bucket, int) or bucket < 1):
+        raise ValueError(f"{who}: bucket must be None or an int >= 1, got {bucket!r}")
+    sizes, keys, ver0 = [], [], None
+    for i, (data, b) in enumerate(zip(files, boxes)):
+        if len(b) != 4:
+            raise ValueError(f"{who}: {names[i]}: box must be (y, x, h, w), got {b!r}")
+        try:
+            key, size = _inspect_any(codec, i, data, who)
+        except ValueError as e:
+            raise ValueError(f"{names[i]}: {e}") from None
+        if ver0 is None:
+            ver0 = key[0]
+        if key[0] != ver0:
+            raise ValueError(f"{who}: {names[i]}: version {key[0]}, but {names[0]} is version {ver0}: the files of one "
+                             "call must share the container version")
+        if not _fits(b, size):
+            raise ValueError(f"{who}: {names[i]}: box (y {b[0]}, x {b[1]}, {b[2]} x {b[3]}) does not lie inside its "
+                             f"{size[0]} x {size[1]} image")
+        sizes.append(size)
+        keys.append(key)
+    needs = [codec.window_need(b[2], b[3]) for b in boxes]
+    if bucket is None:
+        one = (max((r for r, _ in needs), default=0), max((c for _, c in needs), default=0))
+        targets = [one] * len(needs)
+    else:
+        targets = [(-(-r // bucket) * bucket, -(-c // bucket) * bucket) for r, c in needs]
+    groups = {}
+    for i, (b, size, key, target) in enumerate(zip(boxes, sizes, keys, targets)):
+        win, off = codec.region_plan_window(size[0], size[1], b, target)
+        groups.setdefault(win[2:], []).append((i, (key[1], key[2], win[0], win[1]), off))
+    return boxes, ver0, groups
+
+
+def read_nic_windows_any(codec, files: Sequence[bytes], boxes, bucket=None):
+    """read_nic_windows for boxes of different sizes: one box (y, x, h, w) per .nic file, the same
+    checks without the equal-size one, the same result -- one (file indices, (n,rows,cols,96) window
+    latents, [(off_y, off_x)]) per group of one window shape.  bucket None (the default): the call has
+    one target shape, the largest rows and the largest columns any box needs (Codec.window_need), and
+    Codec.region_plan_window plans every box towards it, so the files form one group unless a latent
+    is smaller than the target in a dimension; a window larger than its box needs changes no pixel of
+    the box.  bucket = q (an int >= 1): every box's own need is rounded up to multiples of q and the
+    files are grouped by the result: smaller windows, more groups, each of which pays the entropy
+    stage's fixed cost."""
+    names = [f"file {i}" for i in range(len(files))]
+    _, ver, groups = _window_groups_any(codec, files, boxes, bucket, "read_nic_windows_any", names)
+    return _read_window_groups(codec, files, ver, groups, "read_nic_windows_any", names)
+
+
+def decode_crops(decoder, files: Sequence, boxes, size, flip=None, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), dtype=None,
+                 bucket=None):
+    """One pixel box (y, x, h, w) per .nic file (bytes, or paths to read), the boxes of any sizes: every
+    box is cut out of its file's reconstruction, resized to size = (oh, ow) as F.interpolate(mode=
+    "bilinear", antialias=True) resizes float input, mirrored left to right where flip[i] is true,
+    and returned as (N, 3, oh, ow) torch.float32 (the default) or torch.float16 holding (v / 255 -
+    mean[c]) / std[c], or as (N, oh, ow, 3) torch.uint8, on the decoder's device, in the files' order.
+    read_nic_windows_any's checks and groups (ValueError naming the file, by its path where it was
+    given as one; bucket as there); per group one upload, one window entropy decode, the decoder on
+    the (n,rows,cols,96) windows and one Codec.resample_boxes, which writes the group's images into
+    their places of the one result."""
+    import torch
+
+    who = "decode_crops"
+    dtype = torch.float32 if dtype is None else dtype
+    if dtype not in (torch.float32, torch.float16, torch.uint8):
+        raise ValueError(f"{who}: dtype {dtype} is not torch.float32, torch.float16 or torch.uint8")
+    try:
+        oh, ow = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: size must be (oh, ow), got {size!r}") from None
+    if not (1 <= oh <= 16384 and 1 <= ow <= 16384):
+        raise ValueError(f"{who}: size {oh} x {ow} not in 1..16384")
+    mean64, std64 = np.asarray(mean, dtype=np.float64), np.asarray(std, dtype=np.float64)
+    if mean64.shape != (3,) or std64.shape != (3,) or not np.all(np.isfinite(mean64)) or not np.all(np.isfinite(std64)) \
+            or np.any(std64 == 0):
+        raise ValueError(f"{who}: mean and std must be 3 finite numbers each, std not 0; got {mean!r}, {std!r}")
+    datas, names = _files_and_names(files)
+    flips = [0] * len(datas) if flip is None else [int(bool(f)) for f in flip]
+    if len(flips) != len(datas):
+        raise ValueError(f"{who}: {len(flips)} flips for {len(datas)} files: one per file, or None")
+    codec = decoder.codec
+    boxes, ver, groups = _window_groups_any(codec, datas, boxes, bucket, who, names)
+    shape = (len(datas), oh, ow, 3) if dtype == torch.uint8 else (len(datas), 3, oh, ow)
+    out = torch.empty(shape, dtype=dtype, device=f"cuda:{codec.device}")
+    for idx, z, offs in _read_window_groups(codec, datas, ver, groups, who, names):
+        table = [(off[0], off[1], boxes[i][2], boxes[i][3], flips[i], i) for i, off in zip(idx, offs)]
+        codec.resample_boxes(codec.decode(z), table, (oh, ow), dtype, mean, std, out=out)
+    return out
+
+
 PNG_WRITERS = ("pillow", "device")
 
 

@@ -695,6 +695,82 @@ class Codec:
                                          _stream_ptr(torch, self.device)), "nic_cut_boxes")
         return out
 
+    # -- crops of mixed sizes, resized for training (nic_region_plan_window, nic_resample_boxes) --
+    @staticmethod
+    def region_plan_window(H: int, W: int, box, shape):
+        """region_plan_fixed with the window's shape given (nic_region_plan_window; host only):
+        ((r0, c0, rows, cols), (off_y, off_x)) with rows = min(h8, shape[0]), cols = min(w8, shape[1]).
+        shape must be at least the fixed plan's (h + 6) // 8 + 1 + 2 NIC_DECODE_HALO per axis
+        (ValueError), so boxes of different sizes can share the largest one's window shape; the cut
+        is as exact as region_plan's."""
+        y, x, bh, bw = (int(v) for v in box)
+        rows, cols = (int(v) for v in shape)
+        win, off = (ctypes.c_int * 4)(), (ctypes.c_int * 2)()
+        _lib.check(_lib.lib().nic_region_plan_window(int(H), int(W), y, x, bh, bw, rows, cols, win, off),
+                   "nic_region_plan_window")
+        return tuple(win), tuple(off)
+
+    @staticmethod
+    def window_need(h: int, w: int):
+        """The smallest window shape region_plan_window takes for an h x w box: the fixed plan's (R, C)."""
+        return tuple((int(v) + 6) // 8 + 1 + 2 * _lib.DECODE_HALO for v in (h, w))
+
+    _RESAMPLE_KINDS = {"float32": 0, "float16": 1, "uint8": 2}  # nic.h NIC_RESAMPLE_*
+
+    def resample_boxes(self, x, table, size, dtype=None, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), n_out=None, out=None):
+        """Row i of table = (oy, ox, bh, bw, flip, dst): the bh x bw box at (oy, ox) of image i of x
+        (N,Hs,Ws,3) u8, resized to size = (oh, ow) as F.interpolate(mode="bilinear", antialias=True)
+        does, mirrored left to right where flip is 1, becomes image dst of the result; one launch on
+        the current stream (nic_resample_boxes).  dtype torch.float32 (the default) or torch.float16:
+        (n_out, 3, oh, ow), (v / 255 - mean[c]) / std[c] as one fma with scale 1 / (255 std) and bias
+        -mean / std, computed in float64 and rounded to fp32.  torch.uint8: (n_out, oh, ow, 3), rounded
+        half to even; mean and std are not used.  n_out: the result's image count (default N; the
+        images no row names keep what they held).  out: the tensor to fill (default: a new one, not
+        initialised).  table: N rows of host integers, checked here against the images and n_out
+        (ValueError naming the row) and uploaded, or an (N,6) int32 tensor on the device, which is not
+        read back: there a row that does not fit is skipped by the kernel."""
+        torch = _torch()
+        x = self._check_dev(x, 4, 3, "resample_boxes")
+        n, Hs, Ws, _ = x.shape
+        dtype = torch.float32 if dtype is None else dtype
+        kind = self._RESAMPLE_KINDS.get(str(dtype).replace("torch.", ""))
+        if kind is None:
+            raise ValueError(f"resample_boxes: dtype {dtype} is not torch.float32, torch.float16 or torch.uint8")
+        try:
+            oh, ow = (int(v) for v in size)
+        except (TypeError, ValueError):
+            raise ValueError(f"resample_boxes: size must be (oh, ow), got {size!r}") from None
+        mean64, std64 = np.asarray(mean, dtype=np.float64), np.asarray(std, dtype=np.float64)
+        if mean64.shape != (3,) or std64.shape != (3,) or not np.all(np.isfinite(mean64)) or not np.all(np.isfinite(std64)) \
+                or np.any(std64 == 0):
+            raise ValueError(f"resample_boxes: mean and std must be 3 finite numbers each, std not 0; got {mean!r}, {std!r}")
+        scale = (1.0 / (255.0 * std64)).astype(np.float32)
+        bias = (-mean64 / std64).astype(np.float32)
+        tab, host = self._device_table(table, 6, "resample_boxes", "table")
+        if tab.shape[0] != n:
+            raise ValueError(f"resample_boxes: {tab.shape[0]} table rows for {n} images")
+        if n_out is None:
+            n_out = out.shape[0] if isinstance(out, torch.Tensor) and out.ndim == 4 else n
+        n_out = int(n_out)
+        if host is not None:
+            for i, (oy, ox, bh, bw, flip, dst) in enumerate(host.tolist()):
+                if bh < 1 or bw < 1 or oy < 0 or ox < 0 or oy + bh > Hs or ox + bw > Ws:
+                    raise ValueError(f"resample_boxes: row {i}: a {bh} x {bw} box at ({oy}, {ox}) does not lie inside the "
+                                     f"{Hs} x {Ws} images")
+                if flip not in (0, 1):
+                    raise ValueError(f"resample_boxes: row {i}: flip {flip} is not 0 or 1")
+                if dst < 0 or dst >= n_out:
+                    raise ValueError(f"resample_boxes: row {i}: dst {dst} is not one of the {n_out} output images")
+        shape = (n_out, max(oh, 0), max(ow, 0), 3) if kind == 2 else (n_out, 3, max(oh, 0), max(ow, 0))
+        if out is None:
+            out = torch.empty(tuple(max(v, 0) for v in shape), dtype=dtype, device=x.device)
+        elif out.dtype != dtype or tuple(out.shape) != shape or out.device != x.device or not out.is_contiguous():
+            raise TypeError(f"resample_boxes: out must be a contiguous {shape} {dtype} tensor on the codec's device")
+        _lib.check(self._L.nic_resample_boxes(self._h, x.data_ptr(), n, Hs, Ws, tab.data_ptr(), oh, ow, n_out, kind,
+                                              scale.ctypes.data, bias.ctypes.data, out.data_ptr(),
+                                              _stream_ptr(torch, self.device)), "nic_resample_boxes")
+        return out
+
     # -- device PNG writer (nic_png_device_*) -------------------------------------------------
     def png_reserve(self, n: int, h: int, w: int, channels: int = 3) -> None:
         """Grow the workspace so png_encode of n (h, w, channels) images allocates nothing."""
@@ -891,6 +967,17 @@ class Decoder(ProClass):
         from .bitstream import decode_regions
 
         return decode_regions(self, files, boxes)
+
+    def decode_crops(self, files, boxes, size, flip=None, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), dtype=None, bucket=None):
+        """One pixel box (y, x, h, w) per .nic file, the boxes of any sizes, each resized to size =
+        (oh, ow) (bilinear, antialiased), mirrored where flip[i] is true, normalised with mean and std
+        and laid out for a model: (N, 3, oh, ow) torch.float32 (the default) or torch.float16, or
+        (N, oh, ow, 3) torch.uint8, on this device, in the files' order -- what RandomResizedCrop,
+        a flip, ToTensor and Normalize give, from the files' bytes, in one call
+        (bitstream.decode_crops)."""
+        from .bitstream import decode_crops
+
+        return decode_crops(self, files, boxes, size, flip=flip, mean=mean, std=std, dtype=dtype, bucket=bucket)
 
     def uncompress(self, dataset_path: str, checkpoint_path: str, batch_size: int = 64, workers=None,
                    container: str = "png", png_writer: str = "pillow", prior=None, region=None,

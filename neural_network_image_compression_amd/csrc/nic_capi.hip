@@ -464,7 +464,7 @@ bool models_ready(const nic_ctx* c, int m0) {
 
 extern "C" {
 
-int nic_version(void) { return 800; }
+int nic_version(void) { return 900; }
 
 int nic_constants(float* ycbcr9, float* ycbcr_inv9, float* off3) {
   // host copy of what nic_create uploads; lets tests compare with np.linalg.inv (utils.py:8)
@@ -1604,6 +1604,50 @@ int nic_cut_boxes(nic_ctx* c, const uint8_t* images, int n, int Hs, int Ws, cons
     return fail(NIC_EINVAL, "nic_cut_boxes: boxes and offsets must be 4-byte aligned");
   DeviceGuard guard(c->device);
   HIP_TRY(launch_cut_boxes(images, n, Hs, Ws, offsets, bh, bw, boxes, (hipStream_t)stream));
+  return NIC_OK;
+}
+
+// ---- crops of mixed sizes (nic_resample.hip; nic_region_plan_window is host-only) ----
+int nic_region_plan_window(int H, int W, int y, int x, int bh, int bw, int rows_want, int cols_want, int* win4, int* off2) {
+  if (!win4 || !off2) return fail(NIC_EINVAL, "nic_region_plan_window: win4 or off2 is NULL");
+  if (H < 1 || W < 1 || y < 0 || x < 0 || bh < 1 || bw < 1 || (long long)y + bh > H || (long long)x + bw > W)
+    return fail(NIC_ESHAPE, "nic_region_plan_window: box (y %d, x %d, %d x %d) does not lie inside a %d x %d image", y, x, bh, bw,
+                H, W);
+  const int need_rows = (bh + 6) / 8 + 1 + 2 * NIC_DECODE_HALO, need_cols = (bw + 6) / 8 + 1 + 2 * NIC_DECODE_HALO;
+  if (rows_want < need_rows || cols_want < need_cols)
+    return fail(NIC_ESHAPE, "nic_region_plan_window: a %d x %d box needs a window of at least %d x %d latent pixels, not %d x %d",
+                bh, bw, need_rows, need_cols, rows_want, cols_want);
+  const int h8 = (H >> 3) + ((H & 7) != 0), w8 = (W >> 3) + ((W & 7) != 0);
+  auto axis = [](int at, int want, int n8, int* lo, int* count) {
+    *count = want < n8 ? want : n8;
+    const int from = at / 8 - NIC_DECODE_HALO, last = n8 - *count;
+    *lo = from < 0 ? 0 : (from > last ? last : from);
+  };
+  axis(y, rows_want, h8, &win4[0], &win4[2]);
+  axis(x, cols_want, w8, &win4[1], &win4[3]);
+  off2[0] = y - 8 * win4[0];
+  off2[1] = x - 8 * win4[1];
+  return NIC_OK;
+}
+
+int nic_resample_boxes(nic_ctx* c, const uint8_t* images, int n, int Hs, int Ws, const int32_t* table, int oh, int ow, int n_out,
+                       int out_kind, const float* scale3, const float* bias3, void* out, void* stream) {
+  if (n < 0 || n > 65535 || Hs < 1 || Ws < 1 || (long long)Hs * Ws > (1ll << 29))
+    return fail(NIC_ESHAPE, "nic_resample_boxes: bad image shape (%d,%d,%d,3)", n, Hs, Ws);
+  if (oh < 1 || ow < 1 || oh > 16384 || ow > 16384)
+    return fail(NIC_ESHAPE, "nic_resample_boxes: output size %d x %d not in 1..16384", oh, ow);
+  if (n_out < 1 || (long long)n_out * 3 * oh * ow >= (1ll << 40))
+    return fail(NIC_ESHAPE, "nic_resample_boxes: %d outputs of 3 x %d x %d: none, or 2^40 elements and more", n_out, oh, ow);
+  if (out_kind != NIC_RESAMPLE_F32 && out_kind != NIC_RESAMPLE_F16 && out_kind != NIC_RESAMPLE_U8)
+    return fail(NIC_EINVAL, "nic_resample_boxes: out_kind %d is not one of NIC_RESAMPLE_F32, _F16, _U8", out_kind);
+  if (n == 0) return NIC_OK;
+  if (!c) return fail(NIC_EINVAL, "nic_resample_boxes: NULL ctx");
+  if (!images || !table || !out) return fail(NIC_EINVAL, "nic_resample_boxes: NULL buffer");
+  if (out_kind != NIC_RESAMPLE_U8 && (!scale3 || !bias3)) return fail(NIC_EINVAL, "nic_resample_boxes: NULL scale3 or bias3");
+  if ((uintptr_t)table % 4 || (uintptr_t)out % 16)
+    return fail(NIC_EINVAL, "nic_resample_boxes: table must be 4-byte aligned and out 16-byte aligned");
+  DeviceGuard guard(c->device);
+  HIP_TRY(launch_resample_boxes(images, n, Hs, Ws, table, oh, ow, n_out, out_kind, scale3, bias3, out, (hipStream_t)stream));
   return NIC_OK;
 }
 

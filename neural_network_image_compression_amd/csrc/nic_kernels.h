@@ -221,6 +221,16 @@ hipError_t launch_rans_decode(int ver, const uint8_t* files, long long stride, c
 hipError_t launch_cut_boxes(const uint8_t* src, int n, int Hs, int Ws, const int* off, int bh, int bw, uint8_t* dst,
                             hipStream_t st);
 
+// --- crops for training (nic_resample.hip) ------------------------------------------------------
+// Row i of table (int32[n][6] = (oy, ox, bh, bw, flip, dst) on the device) names a box of image i of
+// images (n, Hs, Ws, 3) u8; the box is resized to oh x ow (bilinear, antialiased), mirrored where flip
+// is 1, and stored as image dst of out: (n_out, 3, oh, ow) fp32 or f16 as v scale3[c] + bias3[c], or
+// (n_out, oh, ow, 3) u8 (out_kind: NIC_RESAMPLE_*; scale3 and bias3 are host arrays, not read for u8).
+// One launch, n >= 1; the arguments are nic_resample_boxes' and checked there.  A row that does not
+// lie inside its image or out stores nothing.
+hipError_t launch_resample_boxes(const uint8_t* images, int n, int Hs, int Ws, const int* table, int oh, int ow, int n_out,
+                                 int out_kind, const float* scale3, const float* bias3, void* out, hipStream_t st);
+
 // --- device PNG writer (nic_png_dev.hip) ------------------------------------------------------
 // Byte offsets of one call's scratch inside the ctx workspace (256-B aligned), from png_dev_plan:
 // the filtered streams (fstride bytes per image), and per deflate block its code table, header
