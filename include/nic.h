@@ -503,6 +503,31 @@ int nic_region_plan_window(int H, int W, int y, int x, int bh, int bw, int rows_
 int nic_resample_boxes(nic_ctx* ctx, const uint8_t* images, int n, int Hs, int Ws, const int32_t* table, int oh, int ow, int n_out,
                        int out_kind, const float* scale3, const float* bias3, void* out, void* stream);
 
+/* ---- Images of mixed sizes, resized in one launch ------------------------------------------------
+ * The write side's preparation step: photographs of any sizes go up as one pool and come out at one
+ * size, ready for nic_encode ("Images of mixed sizes, resized and encoded in one batch").
+ *
+ * nic_resample_ragged: nic_resample_boxes with ragged sources.  pool: pool_bytes bytes of u8 on the
+ *     DEVICE, 4-byte aligned.  table: int64[n][8] on the DEVICE, 8-byte aligned, row i =
+ *       {offset, Hs, Ws, oy, ox, bh, bw, dst | flip << 32}
+ *     source i is the tightly packed (Hs, Ws, 3) u8 image whose first byte is pool[offset] (no padding
+ *     between its rows; offset a multiple of 4); the bh x bw box at (oy, ox) of it, resized to oh x ow,
+ *     mirrored where flip is 1, becomes image dst of out.  dst is the low 32 bits of the last field as
+ *     a signed integer, flip the high 32.  Images may overlap or repeat: the pool is only read.
+ *     oh, ow, n_out, out_kind, scale3, bias3, out, stream and the arithmetic, bit for bit, are
+ *     nic_resample_boxes': the same box of the same pixels gives the same output whichever entry reads it.
+ *     The kernel does not trust the table.  A row with offset < 0, offset not a multiple of 4, Hs < 1,
+ *     Ws < 1, Hs Ws > 2^29 (nic_resample_boxes' limit on a shape), offset + 3 Hs Ws > pool_bytes
+ *     (compared in 64 bits, without overflow for any field values), a box outside its image (bh < 1,
+ *     bw < 1, oy < 0, ox < 0, oy + bh > Hs, ox + bw > Ws), flip not 0 or 1, or dst outside [0, n_out)
+ *     is skipped by its whole block before anything else is read, and stores nothing; no row reads
+ *     outside its own image or writes outside out[dst].  Rows that name one dst race.
+ *     Validated before any HIP call: n in 0..65535, pool_bytes >= 0, 1 <= oh, ow <= 16384, n_out >= 1,
+ *     n_out 3 oh ow < 2^40 (NIC_ESHAPE); out_kind (NIC_EINVAL); empty batch (OK); NULL; alignment of
+ *     pool (4), table (8) and out (16) (NIC_EINVAL). */
+int nic_resample_ragged(nic_ctx* ctx, const uint8_t* pool, int64_t pool_bytes, int n, const int64_t* table, int oh, int ow,
+                        int n_out, int out_kind, const float* scale3, const float* bias3, void* out, void* stream);
+
 /* ---- The device PNG writer: complete PNG files written on the device --------------------------
  * An optional writer for reconstructions (Pillow's optimize=True file, nic_png_encode, stays the
  * default and the bitstream's format).  Format: DESIGN.md, "The device PNG writer":

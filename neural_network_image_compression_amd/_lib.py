@@ -130,6 +130,8 @@ _SIGNATURES = {
     # crops of mixed sizes (nic_capi.hip nic_region_plan_window, nic_resample.hip)
     "nic_region_plan_window": (ctypes.c_int, [ctypes.c_int] * 8 + [ctypes.POINTER(ctypes.c_int)] * 2),
     "nic_resample_boxes": (ctypes.c_int, [c_vp, c_vp] + [ctypes.c_int] * 3 + [c_vp] + [ctypes.c_int] * 4 + [c_vp] * 4),
+    # images of mixed sizes, resized in one launch (nic_resample.hip)
+    "nic_resample_ragged": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int, c_vp] + [ctypes.c_int] * 4 + [c_vp] * 4),
     # device PNG writer (nic_png_dev.hip)
     "nic_png_device_block_bytes": (ctypes.c_int, []),
     "nic_png_device_bound": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int64)]),

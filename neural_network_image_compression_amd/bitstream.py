@@ -760,6 +760,38 @@ WRITES_IN_FLIGHT = 2  # batches handed to the PNG writer and not yet written (us
 BATCH_PIXELS = 64 * 512 * 768  # pixels staged per device batch (use_model): 64 Kodak-sized images, 3 4K frames
 
 
+RESIZE_POOL_BYTES = 1 << 29  # source bytes staged per device batch of resize= (use_model): 64 photographs of 2.8 megapixels
+
+
+def _check_resize(resize, resize_mode: str):
+    from .codec import FIT_MODES
+
+    try:
+        oh, ow = (int(v) for v in resize)
+    except (TypeError, ValueError):
+        raise ValueError(f"resize must be (oh, ow), got {resize!r}") from None
+    if not (1 <= oh <= 16384 and 1 <= ow <= 16384):
+        raise ValueError(f"resize {oh} x {ow} not in 1..16384")
+    if resize_mode not in FIT_MODES:
+        raise ValueError(f"resize_mode must be one of {FIT_MODES}, got {resize_mode!r}")
+    return oh, ow
+
+
+def resize_batch(codec, images: Sequence[np.ndarray], names: Sequence[str], size, mode: str = "center"):
+    """Host images of any sizes -> one (N, oh, ow, 3) u8 tensor on the codec's device: one pool, one
+    upload, one Codec.resample_ragged from the boxes codec.fit_boxes(shapes, size, mode).  ValueError
+    naming the file that is not an (H, W, 3) image."""
+    import torch
+
+    from .codec import fit_boxes
+
+    for a, name in zip(images, names):
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError(f"{name}: resize takes (H, W, 3) images, got shape {tuple(a.shape)}")
+    boxes = fit_boxes([a.shape[:2] for a in images], size, mode)
+    return codec.resample_ragged(list(images), boxes, size, dtype=torch.uint8)
+
+
 def _set_any_prior(codec, prior) -> None:
     """prior= of the drivers: a prior.Prior or a .nicp path sets the codec's prior (version 2), a
     prior.ContextPrior or a .nicc path its context prior (version 3); a path by its magic."""
@@ -774,7 +806,7 @@ def _set_any_prior(codec, prior) -> None:
 
 def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, in_cshape: int,
               batch_size: int = 64, workers=None, container: str = "png", png_writer: str = "pillow",
-              prior=None, region=None, png_reader: str = "pillow") -> None:
+              prior=None, region=None, png_reader: str = "pillow", resize=None, resize_mode: str = "center") -> None:
     """utils.py:46-62: every colour image of ``dataset_path`` (sorted; read_dataset's filter)
     through the codec into ``output_dir``, one PNG per image named after its source.
 
@@ -811,7 +843,14 @@ def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, i
     PNG): the reader pool reads the files' bytes and runs nic_png_inspect on them (framing and every
     CRC-32); the PNG files it takes go to the device as zlib streams and are inflated and unfiltered
     there (Codec.png_read), JPEGs and the PNG kinds it does not take go through Pillow as before.
-    File order, batching and the files written are those of ``"pillow"``."""
+    File order, batching and the files written are those of ``"pillow"``.
+
+    ``resize=(oh, ow)`` (the encoder side only, with ``png_reader="pillow"``; ValueError otherwise):
+    the reader pool's images, of any sizes, are batched by count alone (``batch_size``, and at most
+    ``RESIZE_POOL_BYTES`` of source pixels), go up as one pool and are resized to oh x ow on the device
+    from the boxes ``codec.fit_boxes(shapes, resize, resize_mode)`` (resize_batch); what is encoded and
+    written is the resized image, and version-2 and version-3 ``.nic`` files record oh x ow as its size.
+    A colour image that is not (H, W, 3), such as RGBA, is a ValueError naming the file."""
     if container not in CONTAINERS:
         raise ValueError(f"container must be one of {CONTAINERS}, got {container!r}")
     _check_png_writer(png_writer, decoder_side=in_cshape == 96)
@@ -819,6 +858,11 @@ def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, i
     if region is not None and not (container == "nic" and in_cshape == 96):
         raise ValueError('region applies to the decoder side of container="nic" only: a packed PNG has no index, '
                          "so a part of it cannot be decoded on its own")
+    if resize is not None:
+        if in_cshape != 3 or png_reader != "pillow":
+            raise ValueError('resize applies to the encoder side with png_reader="pillow" only: it resizes the images '
+                             "the reader pool decoded")
+        resize = _check_resize(resize, resize_mode)
     if prior is not None:
         if container != "nic":
             raise ValueError('prior applies to container="nic" only: the PNG container has no entropy model')
@@ -839,8 +883,11 @@ def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, i
             imgs, names = [a for a, _ in pairs if a.ndim == 3], [s for a, s in pairs if a.ndim == 3]
         else:
             imgs, names = read_dataset(dataset_path)
-        for i, j in _batches([a.shape for a in imgs], batch_size):
-            x = _stage_batch(model.codec, imgs[i:j], names[i:j]) if device_reader else np.stack(imgs[i:j])
+        for i, j in _batches([a.shape if resize is None else () for a in imgs], batch_size):
+            if resize is not None:
+                x = resize_batch(model.codec, imgs[i:j], names[i:j], resize, resize_mode)
+            else:
+                x = _stage_batch(model.codec, imgs[i:j], names[i:j]) if device_reader else np.stack(imgs[i:j])
             feed_batch(model, x, names[i:j], output_dir, in_cshape, **extra)
         return
     from concurrent.futures import ThreadPoolExecutor
@@ -859,7 +906,10 @@ def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, i
                 # (slower) PNG writer; the device pass of the next batch still overlaps them
                 while len(futures) >= WRITES_IN_FLIGHT:
                     futures.pop(0).result()  # re-raises a write error
-                x = _stage_batch(model.codec, batch, names) if device_reader else np.stack(batch)
+                if resize is not None:
+                    x = resize_batch(model.codec, batch, names, resize, resize_mode)
+                else:
+                    x = _stage_batch(model.codec, batch, names) if device_reader else np.stack(batch)
                 futures.extend(feed_batch(model, x, list(names), output_dir, in_cshape, pool=writer,
                                           png_threads=png_threads, **extra))
                 batch.clear()
@@ -874,8 +924,11 @@ def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, i
             pending[k] = None
             if a.ndim != 3:  # read_dataset keeps colour (3-D) images only
                 continue
-            if batch and (a.shape != batch[0].shape or len(batch) >= batch_size
-                          or (len(batch) + 1) * a.shape[0] * a.shape[1] > BATCH_PIXELS):
+            if resize is not None:
+                if batch and (len(batch) >= batch_size or sum(b.size for b in batch) + a.size > RESIZE_POOL_BYTES):
+                    flush()
+            elif batch and (a.shape != batch[0].shape or len(batch) >= batch_size
+                            or (len(batch) + 1) * a.shape[0] * a.shape[1] > BATCH_PIXELS):
                 flush()
             batch.append(a if isinstance(a, _PngStream) else a.astype(np.uint8, copy=False))
             names.append(".".join(fn.split(".")[:-1]))

@@ -48,6 +48,83 @@ def _as_u8_array(x, what: str) -> np.ndarray:
     raise TypeError(f"{what}: unsupported dtype {a.dtype}")
 
 
+FIT_MODES = ("stretch", "center", "shorter")
+POOL_ALIGN = 16  # bytes: every image of a pool starts at a multiple of it (nic_resample_ragged needs 4)
+
+
+def fit_boxes(shapes, size, mode: str = "center") -> np.ndarray:
+    """The box (oy, ox, bh, bw) of every (H, W) of shapes that a resize to size = (oh, ow) reads: an
+    (N, 4) int64 array, rows for Codec.resample_ragged.  Integer arithmetic throughout.
+
+    "stretch": the whole image, (0, 0, H, W); the resize changes the aspect ratio.
+    "center":  the largest centred box with the output's aspect ratio.  One side is the image's own:
+               where W oh >= H ow (the image is at least as wide as the output) bh = H and
+                   bw = max(1, (2 H ow + oh) // (2 oh)),
+               which is H ow / oh rounded to the nearest integer, halves up, and never above W; else
+               bw = W and bh = max(1, (2 W oh + ow) // (2 ow)).  Among the boxes with that full side
+               no other width has bw / bh nearer to ow / oh (no other height bh / bw nearer to
+               oh / ow), and where W oh == H ow the box is the whole image.  oy = (H - bh) // 2 and ox = (W - bw) // 2, so the box's centre is the
+               image's or half a pixel before it.
+    "shorter": "center" under the name of torchvision's Resize(shorter side) + CenterCrop, which is
+               what it stands for.  The two differ in one thing: torchvision first resizes the whole
+               image to an integer size (the longer side rounded) and then cuts oh x ow output pixels
+               out of it, so its crop edges fall on output pixels; here the box's edges fall on source
+               pixels and the box is resized once.  The source region differs by less than one output
+               pixel's footprint per side, and the single resize does not filter twice.
+
+    ValueError for a shape or size that is not two integers >= 1, or another mode."""
+    if mode not in FIT_MODES:
+        raise ValueError(f"fit_boxes: mode must be one of {FIT_MODES}, got {mode!r}")
+    try:
+        oh, ow = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"fit_boxes: size must be (oh, ow), got {size!r}") from None
+    hw = np.asarray(shapes, dtype=np.int64).reshape(-1, 2) if len(shapes) else np.zeros((0, 2), np.int64)
+    if oh < 1 or ow < 1 or (hw.size and hw.min() < 1):
+        raise ValueError("fit_boxes: shapes and size must be integers >= 1")
+    H, W = hw[:, 0], hw[:, 1]
+    if mode == "stretch":
+        bh, bw = H.copy(), W.copy()
+    else:
+        wide = W * oh >= H * ow
+        bw = np.where(wide, np.maximum(1, (2 * H * ow + oh) // (2 * oh)), W)
+        bh = np.where(wide, H, np.maximum(1, (2 * W * oh + ow) // (2 * ow)))
+    return np.stack([(H - bh) // 2, (W - bw) // 2, bh, bw], axis=1)
+
+
+def pool_layout(shapes):
+    """Where tightly packed (H, W, 3) u8 images of the (H, W) of shapes go in one pool: (their byte
+    offsets, each a multiple of POOL_ALIGN, in order and as close as that allows; the pool's size,
+    which ends on the last image's last byte)."""
+    offsets, at, end = [], 0, 0
+    for h, w in shapes:
+        offsets.append(at)
+        end = at + 3 * int(h) * int(w)
+        at = -(-end // POOL_ALIGN) * POOL_ALIGN
+    return offsets, end
+
+
+def pack_images(images, pool: Optional[np.ndarray] = None):
+    """Host (H, W, 3) u8 arrays of any sizes -> (pool, offsets): image i's bytes, rows tight, are
+    pool[offsets[i] : offsets[i] + 3 H W] (pool_layout).  pool: the u8 array to fill (at least the
+    layout's size; page-locked for an asynchronous upload), default a new one; the padding between
+    images is left as it was.  ValueError naming the image that is not (H, W, 3) u8 with H, W >= 1."""
+    arrays = []
+    for i, a in enumerate(images):
+        a = np.asarray(a)
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+            raise ValueError(f"pack_images: image {i}: expected an (H, W, 3) uint8 array with H, W >= 1, got {a.dtype} {a.shape}")
+        arrays.append(a)
+    offsets, total = pool_layout([a.shape[:2] for a in arrays])
+    if pool is None:
+        pool = np.zeros(total, np.uint8)
+    elif pool.dtype != np.uint8 or pool.ndim != 1 or pool.size < total or not pool.flags.c_contiguous:
+        raise ValueError(f"pack_images: pool must be a contiguous 1-D uint8 array of at least {total} bytes")
+    for a, off in zip(arrays, offsets):
+        pool[off:off + a.size].reshape(a.shape)[...] = a
+    return pool, offsets
+
+
 class Codec:
     """One ``nic_ctx`` on one HIP device: weights + workspace for encode/decode/entropy."""
 
@@ -771,6 +848,141 @@ class Codec:
                                               _stream_ptr(torch, self.device)), "nic_resample_boxes")
         return out
 
+    # -- images of mixed sizes, resized in one launch (nic_resample_ragged) ---------------------
+    def _resample_args(self, who: str, size, dtype, mean, std):
+        torch = _torch()
+        dtype = torch.float32 if dtype is None else dtype
+        kind = self._RESAMPLE_KINDS.get(str(dtype).replace("torch.", ""))
+        if kind is None:
+            raise ValueError(f"{who}: dtype {dtype} is not torch.float32, torch.float16 or torch.uint8")
+        try:
+            oh, ow = (int(v) for v in size)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: size must be (oh, ow), got {size!r}") from None
+        mean64, std64 = np.asarray(mean, dtype=np.float64), np.asarray(std, dtype=np.float64)
+        if mean64.shape != (3,) or std64.shape != (3,) or not np.all(np.isfinite(mean64)) or not np.all(np.isfinite(std64)) \
+                or np.any(std64 == 0):
+            raise ValueError(f"{who}: mean and std must be 3 finite numbers each, std not 0; got {mean!r}, {std!r}")
+        return dtype, kind, oh, ow, (1.0 / (255.0 * std64)).astype(np.float32), (-mean64 / std64).astype(np.float32)
+
+    def resample_pool(self, pool, table, size, dtype=None, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), n_out=None, out=None):
+        """nic_resample_ragged as it is: pool a 1-D u8 tensor on this device, table an (N, 8) int64
+        tensor there, row i = (offset, Hs, Ws, oy, ox, bh, bw, dst | flip << 32) (nic.h).  The table is
+        not read back: a row that does not fit its image, the pool or the result is skipped by the
+        kernel.  size, dtype, mean, std, n_out, out and the result as resample_boxes'."""
+        torch = _torch()
+        who = "resample_pool"
+        if not isinstance(pool, torch.Tensor) or pool.dtype != torch.uint8 or pool.device.type != "cuda" or pool.ndim != 1 \
+                or pool.device.index != self.device or not pool.is_contiguous():
+            raise TypeError(f"{who}: pool must be a contiguous 1-D torch.uint8 tensor on cuda:{self.device}")
+        if not isinstance(table, torch.Tensor) or table.dtype != torch.int64 or table.ndim != 2 or table.shape[1] != 8 \
+                or table.device != pool.device or not table.is_contiguous():
+            raise TypeError(f"{who}: table must be a contiguous (N,8) torch.int64 tensor on cuda:{self.device}")
+        dtype, kind, oh, ow, scale, bias = self._resample_args(who, size, dtype, mean, std)
+        n = table.shape[0]
+        if n_out is None:
+            n_out = out.shape[0] if isinstance(out, torch.Tensor) and out.ndim == 4 else n
+        n_out = int(n_out)
+        shape = (n_out, max(oh, 0), max(ow, 0), 3) if kind == 2 else (n_out, 3, max(oh, 0), max(ow, 0))
+        if out is None:
+            out = torch.empty(tuple(max(v, 0) for v in shape), dtype=dtype, device=pool.device)
+        elif out.dtype != dtype or tuple(out.shape) != shape or out.device != pool.device or not out.is_contiguous():
+            raise TypeError(f"{who}: out must be a contiguous {shape} {dtype} tensor on the codec's device")
+        _lib.check(self._L.nic_resample_ragged(self._h, pool.data_ptr(), pool.numel(), n, table.data_ptr(), oh, ow, n_out, kind,
+                                               scale.ctypes.data, bias.ctypes.data, out.data_ptr(),
+                                               _stream_ptr(torch, self.device)), "nic_resample_ragged")
+        return out
+
+    def upload_pool(self, images):
+        """(H, W, 3) u8 images of any sizes (NumPy arrays or torch tensors, on the host or on this
+        device) -> (pool, offsets, shapes): one 1-D u8 tensor on this device that holds them all at
+        pool_layout's offsets.  The host's images are packed into one page-locked buffer and go up in
+        one transfer on the current stream; the device's are copied into their places there.
+        ValueError naming the image that is not (H, W, 3) u8 with H, W >= 1 and H W <= 2^29."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        items = []
+        for i, a in enumerate(images):
+            on_dev = isinstance(a, torch.Tensor) and a.device.type == "cuda"
+            if on_dev and a.device.index != self.device:
+                raise ValueError(f"resample_ragged: image {i}: tensor on cuda:{a.device.index}, codec on cuda:{self.device}")
+            if not on_dev:
+                a = a.numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+            ok = a.ndim == 3 and a.shape[2] == 3 and a.shape[0] >= 1 and a.shape[1] >= 1 and a.shape[0] * a.shape[1] <= 1 << 29
+            if not ok or a.dtype != (torch.uint8 if on_dev else np.uint8):
+                raise ValueError(f"resample_ragged: image {i}: expected an (H, W, 3) uint8 image with H, W >= 1 and H W <= 2^29, "
+                                 f"got {a.dtype} {tuple(a.shape)}")
+            items.append((on_dev, a))
+        # the host's images first, so that they are one run of the pool and one transfer
+        order = [i for i, (d, _) in enumerate(items) if not d] + [i for i, (d, _) in enumerate(items) if d]
+        shapes = [tuple(int(v) for v in a.shape[:2]) for _, a in items]
+        offs, total = pool_layout([shapes[i] for i in order])
+        offsets = [0] * len(items)
+        for i, off in zip(order, offs):
+            offsets[i] = off
+        pool = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)[:total]
+        host_idx = [i for i in order if not items[i][0]]
+        if host_idx:
+            last = host_idx[-1]
+            host_bytes = offsets[last] + 3 * shapes[last][0] * shapes[last][1]
+            staging = torch.empty(host_bytes, dtype=torch.uint8, pin_memory=True)
+            pack_images([items[i][1] for i in host_idx], staging.numpy())
+            pool[:host_bytes].copy_(staging, non_blocking=True)
+        for i in order:
+            if items[i][0]:
+                a = items[i][1]
+                pool[offsets[i]:offsets[i] + a.numel()].view(a.shape).copy_(a)
+        return pool, offsets, shapes
+
+    def resample_ragged(self, images, boxes=None, size=None, flip=None, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), dtype=None):
+        """images: a list of (H, W, 3) u8 images of any sizes, NumPy arrays or torch tensors, on the
+        host or on this device.  Box i = (oy, ox, bh, bw) of image i (boxes=None: each image whole;
+        fit_boxes gives the usual ones), resized to size = (oh, ow) as resample_boxes resizes, bit
+        for bit, mirrored where flip[i] is true, becomes image i of the result: (N, 3, oh, ow)
+        torch.float32 (the default) or torch.float16 holding (v / 255 - mean[c]) / std[c], or
+        (N, oh, ow, 3) torch.uint8.  One upload (upload_pool) and one launch on the current stream
+        (nic_resample_ragged) for at most 65535 images.  Every row is checked here before the upload:
+        ValueError naming the image or the row."""
+        torch = _torch()
+        who = "resample_ragged"
+        if size is None:
+            raise ValueError(f"{who}: size = (oh, ow) is required")
+        dtype, kind, oh, ow, _, _ = self._resample_args(who, size, dtype, mean, std)
+        if not (1 <= oh <= 16384 and 1 <= ow <= 16384):
+            raise ValueError(f"{who}: size {oh} x {ow} not in 1..16384")
+        images = list(images)
+        n = len(images)
+        if n > 65535:
+            raise ValueError(f"{who}: {n} images in one call, at most 65535")
+        flips = [0] * n if flip is None else [int(bool(f)) for f in flip]
+        if len(flips) != n:
+            raise ValueError(f"{who}: {len(flips)} flips for {n} images: one per image, or None")
+        if boxes is not None:
+            boxes = np.asarray(boxes.cpu() if isinstance(boxes, torch.Tensor) else boxes, dtype=np.int64).reshape(-1, 4) \
+                if len(boxes) else np.zeros((0, 4), np.int64)
+            if boxes.shape[0] != n:
+                raise ValueError(f"{who}: {boxes.shape[0]} boxes for {n} images: one per image, or None")
+        dev = torch.device("cuda", self.device)
+        if n == 0:
+            return torch.empty((0, oh, ow, 3) if kind == 2 else (0, 3, oh, ow), dtype=dtype, device=dev)
+        # the shapes and the boxes first: nothing goes up for a call that is refused
+        for i, a in enumerate(images):
+            shape = tuple(a.shape) if hasattr(a, "shape") else np.asarray(a).shape
+            if len(shape) != 3 or shape[2] != 3 or shape[0] < 1 or shape[1] < 1:
+                raise ValueError(f"{who}: image {i}: expected an (H, W, 3) uint8 image with H, W >= 1, got shape {shape}")
+            if boxes is not None:
+                oy, ox, bh, bw = boxes[i].tolist()
+                if bh < 1 or bw < 1 or oy < 0 or ox < 0 or oy + bh > shape[0] or ox + bw > shape[1]:
+                    raise ValueError(f"{who}: row {i}: a {bh} x {bw} box at ({oy}, {ox}) does not lie inside its "
+                                     f"{shape[0]} x {shape[1]} image")
+        pool, offsets, shapes = self.upload_pool(images)
+        table = np.empty((n, 8), np.int64)
+        table[:, 0] = offsets
+        table[:, 1:3] = shapes
+        table[:, 3:7] = boxes if boxes is not None else [(0, 0, h, w) for h, w in shapes]
+        table[:, 7] = np.arange(n, dtype=np.int64) | (np.asarray(flips, np.int64) << 32)
+        return self.resample_pool(pool, torch.from_numpy(table).to(dev), (oh, ow), dtype, mean, std, n_out=n)
+
     # -- device PNG writer (nic_png_device_*) -------------------------------------------------
     def png_reserve(self, n: int, h: int, w: int, channels: int = 3) -> None:
         """Grow the workspace so png_encode of n (h, w, channels) images allocates nothing."""
@@ -918,8 +1130,48 @@ class Encoder(ProClass):
             raise ValueError(f"Encoder: expected shape (N,H,W,3), got {a.shape}")
         return self.codec.encode_host(a, self.host_chunks)
 
+    #: images per device batch of encode_resized: cut by count, since every batch has one shape
+    resized_batch = 64
+
+    def encode_resized(self, images, size, boxes=None, mode: str = "center"):
+        """(H, W, 3) u8 images of any sizes (a list; NumPy or torch, host or device) -> their latents at
+        one working size: box i of image i (default: fit_boxes(shapes, size, mode)) is resized to
+        size = (oh, ow) on the device (Codec.resample_ragged to u8, rounded half to even) and encoded.
+        (N, ceil(oh/8), ceil(ow/8), 96) u8 on the codec's device, in the images' order, equal to
+        encode(resample_ragged(images, boxes, size, dtype=torch.uint8)).  The images go through the
+        device ``resized_batch`` (64) at a time whatever their sizes: one upload, one resize launch and
+        one encode per batch."""
+        torch = _torch()
+        images = list(images)
+        try:
+            oh, ow = (int(v) for v in size)
+        except (TypeError, ValueError):
+            raise ValueError(f"encode_resized: size must be (oh, ow), got {size!r}") from None
+        if boxes is None:
+            shapes = []
+            for i, a in enumerate(images):
+                shape = tuple(a.shape) if hasattr(a, "shape") else np.asarray(a).shape
+                if len(shape) != 3 or shape[0] < 1 or shape[1] < 1:
+                    raise ValueError(f"encode_resized: image {i}: expected an (H, W, 3) uint8 image with H, W >= 1, got shape {shape}")
+                shapes.append(shape[:2])
+            boxes = fit_boxes(shapes, (oh, ow), mode)
+        elif len(boxes) != len(images):
+            raise ValueError(f"encode_resized: {len(boxes)} boxes for {len(images)} images: one per image, or None")
+        codec = self.codec
+        h8, w8 = _lib.latent_shape(oh, ow)
+        z = torch.empty((len(images), h8, w8, 96), dtype=torch.uint8, device=f"cuda:{codec.device}")
+        for i in range(0, len(images), self.resized_batch):
+            j = min(i + self.resized_batch, len(images))
+            try:
+                x = codec.resample_ragged(images[i:j], boxes[i:j], (oh, ow), dtype=torch.uint8)
+            except ValueError as e:
+                raise ValueError(f"encode_resized: images {i}..{j - 1}: {e}") from None
+            codec.encode(x, out=z[i:j])
+        return z
+
     def compress(self, dataset_path: str, checkpoint_path: str, batch_size: int = 64, workers=None,
-                 container: str = "png", prior=None, png_reader: str = "pillow") -> None:
+                 container: str = "png", prior=None, png_reader: str = "pillow", resize=None,
+                 resize_mode: str = "center") -> None:
         """encoder.py:49-51: every image in ``dataset_path`` -> ``dataset_path + '_compressed'``.
         Pipelined over the host cores in batches of ``batch_size`` (bitstream.use_model);
         ``workers=0, batch_size=4`` is the reference's serial loop (same files).
@@ -929,10 +1181,16 @@ class Encoder(ProClass):
         image's true H x W.  A prior.ContextPrior or a ``.nicc`` path: version-3 files, coded
         against the context prior.
         ``png_reader="device"``: the directory's PNG files are inflated and unfiltered on the device
-        (Codec.png_read) instead of by Pillow on the reader pool; the files written are the same."""
+        (Codec.png_read) instead of by Pillow on the reader pool; the files written are the same.
+        ``resize=(oh, ow)``: every image, whatever its size, is first resized on the device to oh x ow
+        from the box fit_boxes(..., resize_mode) gives it, and the directory goes through the device
+        ``batch_size`` images at a time whatever their sizes (bitstream.use_model); version-2 and
+        version-3 ``.nic`` files record oh x ow as the image's size.  Without it nothing changes."""
         from .bitstream import use_model
 
         more = {"png_reader": png_reader} if png_reader != "pillow" else {}
+        if resize is not None:
+            more.update(resize=resize, resize_mode=resize_mode)
         use_model(self, dataset_path, checkpoint_path, dataset_path + "_compressed", in_cshape=3,
                   batch_size=batch_size, workers=workers, container=container, prior=prior, **more)
 

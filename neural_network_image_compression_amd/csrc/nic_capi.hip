@@ -464,7 +464,7 @@ bool models_ready(const nic_ctx* c, int m0) {
 
 extern "C" {
 
-int nic_version(void) { return 900; }
+int nic_version(void) { return 1000; }
 
 int nic_constants(float* ycbcr9, float* ycbcr_inv9, float* off3) {
   // host copy of what nic_create uploads; lets tests compare with np.linalg.inv (utils.py:8)
@@ -1648,6 +1648,27 @@ int nic_resample_boxes(nic_ctx* c, const uint8_t* images, int n, int Hs, int Ws,
     return fail(NIC_EINVAL, "nic_resample_boxes: table must be 4-byte aligned and out 16-byte aligned");
   DeviceGuard guard(c->device);
   HIP_TRY(launch_resample_boxes(images, n, Hs, Ws, table, oh, ow, n_out, out_kind, scale3, bias3, out, (hipStream_t)stream));
+  return NIC_OK;
+}
+
+int nic_resample_ragged(nic_ctx* c, const uint8_t* pool, int64_t pool_bytes, int n, const int64_t* table, int oh, int ow, int n_out,
+                        int out_kind, const float* scale3, const float* bias3, void* out, void* stream) {
+  if (n < 0 || n > 65535 || pool_bytes < 0) return fail(NIC_ESHAPE, "nic_resample_ragged: bad pool (%d rows, %lld bytes)", n, (long long)pool_bytes);
+  if (oh < 1 || ow < 1 || oh > 16384 || ow > 16384)
+    return fail(NIC_ESHAPE, "nic_resample_ragged: output size %d x %d not in 1..16384", oh, ow);
+  if (n_out < 1 || (long long)n_out * 3 * oh * ow >= (1ll << 40))
+    return fail(NIC_ESHAPE, "nic_resample_ragged: %d outputs of 3 x %d x %d: none, or 2^40 elements and more", n_out, oh, ow);
+  if (out_kind != NIC_RESAMPLE_F32 && out_kind != NIC_RESAMPLE_F16 && out_kind != NIC_RESAMPLE_U8)
+    return fail(NIC_EINVAL, "nic_resample_ragged: out_kind %d is not one of NIC_RESAMPLE_F32, _F16, _U8", out_kind);
+  if (n == 0) return NIC_OK;
+  if (!c) return fail(NIC_EINVAL, "nic_resample_ragged: NULL ctx");
+  if (!pool || !table || !out) return fail(NIC_EINVAL, "nic_resample_ragged: NULL buffer");
+  if (out_kind != NIC_RESAMPLE_U8 && (!scale3 || !bias3)) return fail(NIC_EINVAL, "nic_resample_ragged: NULL scale3 or bias3");
+  if ((uintptr_t)pool % 4 || (uintptr_t)table % 8 || (uintptr_t)out % 16)
+    return fail(NIC_EINVAL, "nic_resample_ragged: pool must be 4-byte aligned, table 8-byte aligned and out 16-byte aligned");
+  DeviceGuard guard(c->device);
+  HIP_TRY(launch_resample_ragged(pool, pool_bytes, n, (const long long*)table, oh, ow, n_out, out_kind, scale3, bias3, out,
+                                 (hipStream_t)stream));
   return NIC_OK;
 }
 

@@ -230,6 +230,12 @@ hipError_t launch_cut_boxes(const uint8_t* src, int n, int Hs, int Ws, const int
 // lie inside its image or out stores nothing.
 hipError_t launch_resample_boxes(const uint8_t* images, int n, int Hs, int Ws, const int* table, int oh, int ow, int n_out,
                                  int out_kind, const float* scale3, const float* bias3, void* out, hipStream_t st);
+// The same with sources of any shapes: row i of table (int64[n][8] = (offset, Hs, Ws, oy, ox, bh, bw,
+// dst | flip << 32) on the device) names the tightly packed (Hs, Ws, 3) image at pool + offset and a
+// box of it.  A row whose image does not lie inside the pool's pool_bytes, at a multiple of 4, stores
+// nothing either.  The arguments are nic_resample_ragged's and checked there.
+hipError_t launch_resample_ragged(const uint8_t* pool, long long pool_bytes, int n, const long long* table, int oh, int ow,
+                                  int n_out, int out_kind, const float* scale3, const float* bias3, void* out, hipStream_t st);
 
 // --- device PNG writer (nic_png_dev.hip) ------------------------------------------------------
 // Byte offsets of one call's scratch inside the ctx workspace (256-B aligned), from png_dev_plan:

@@ -27,6 +27,13 @@
 //   5. the tile is stored: fp32 planes straight from the registers (4 bytes per lane, contiguous
 //      along ow), f16 planes and the u8 NHWC rows through an LDS tile, as whole aligned dwords with
 //      single elements only where a run starts or ends inside a dword.
+//
+// Steps 2 to 5 are resample_tile, which knows one source image by its first byte, its shape and its
+// end.  resample_boxes finds image i of a dense (n, Hs, Ws, 3) stack; resample_ragged finds it in a pool
+// of images of any shapes through the row's own offset, Hs and Ws ("Images of mixed sizes,
+// resized and encoded in one batch").  There the pitch 3 Ws and the base differ per row, and a source
+// row starts at any of a dword's four bytes; step 3 already aligns by the address and guards by the
+// image's own end, so it is the same code.
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
@@ -40,6 +47,7 @@ namespace {
 
 constexpr int kTH = 8, kTW = 32;     // the tile: output rows x columns, one thread each
 constexpr int kStageDwords = 8192;   // 32 KB of source per block: scales up to about 5.5 are staged
+constexpr long long kMaxPixels = 1ll << 29;  // Hs Ws of one source: nic_resample_boxes' limit, a ragged row's too
 
 struct Taps {
   int lo, cnt, n0;  // the first tap, the tap count, N(lo)
@@ -98,21 +106,17 @@ struct Float3 {
   float v[3];
 };
 
+// One tile of one table row, for both kernels: `image` is the row's (Hs, Ws, 3) source, whose first byte
+// and whose end are all the staging knows of the memory around it; the caller has checked the row.
 template <int kKind>
-__global__ __launch_bounds__(256) void resample_boxes(const uint8_t* __restrict__ src, int Hs, int Ws,
-                                                       const int* __restrict__ table, int oh, int ow, int n_out, Float3 scale,
-                                                       Float3 bias, void* __restrict__ out, int tiles_x) {
+__device__ __forceinline__ void resample_tile(const uint8_t* __restrict__ image, int Hs, int Ws, int oy, int ox, int bh, int bw,
+                                              int flip, int dst, int oh, int ow, const Float3& scale, const Float3& bias,
+                                              void* __restrict__ out, int tiles_x) {
   __shared__ Taps ytab[kTH], xtab[kTW];
   __shared__ uint32_t stage[kStageDwords];
   __shared__ float otile[kKind == NIC_RESAMPLE_F32 ? 1 : 3 * kTH * kTW];
 
-  const int img = blockIdx.y, t = threadIdx.x;
-  const int* row6 = table + 6 * (size_t)img;
-  const int oy = row6[0], ox = row6[1], bh = row6[2], bw = row6[3], flip = row6[4], dst = row6[5];
-  // the table is the device's: a row the kernel may not act on stores nothing
-  if (bh < 1 || bw < 1 || oy < 0 || ox < 0 || (long long)oy + bh > Hs || (long long)ox + bw > Ws || (flip != 0 && flip != 1) ||
-      dst < 0 || dst >= n_out)
-    return;
+  const int t = threadIdx.x;
   const int Y0 = (int)(blockIdx.x / (unsigned)tiles_x) * kTH, X0 = (int)(blockIdx.x % (unsigned)tiles_x) * kTW;
   const int th = oh - Y0 < kTH ? oh - Y0 : kTH, tw = ow - X0 < kTW ? ow - X0 : kTW;  // the tile's valid part, both >= 1
 
@@ -133,7 +137,6 @@ __global__ __launch_bounds__(256) void resample_boxes(const uint8_t* __restrict_
   const long long pitch = (3ll * ncols + 3) / 4 + 1;  // dwords: a row's bytes and the up to 3 before its first
   const bool staged = (long long)nrows * pitch <= kStageDwords;
   const size_t row_bytes = 3 * (size_t)Ws;
-  const uint8_t* image = src + (size_t)img * Hs * row_bytes;
   const uint8_t* first = image + (size_t)(oy + y_lo) * row_bytes + 3 * (size_t)(ox + x_lo);  // (y_lo, x_lo) of the box
 
   if (staged) {
@@ -245,6 +248,42 @@ __global__ __launch_bounds__(256) void resample_boxes(const uint8_t* __restrict_
   }
 }
 
+// Sources of one shape, stacked: row i of the table is a box of image i.
+template <int kKind>
+__global__ __launch_bounds__(256) void resample_boxes(const uint8_t* __restrict__ src, int Hs, int Ws,
+                                                       const int* __restrict__ table, int oh, int ow, int n_out, Float3 scale,
+                                                       Float3 bias, void* __restrict__ out, int tiles_x) {
+  const int img = blockIdx.y;
+  const int* row6 = table + 6 * (size_t)img;
+  const int oy = row6[0], ox = row6[1], bh = row6[2], bw = row6[3], flip = row6[4], dst = row6[5];
+  // the table is the device's: a row the kernel may not act on stores nothing
+  if (bh < 1 || bw < 1 || oy < 0 || ox < 0 || (long long)oy + bh > Hs || (long long)ox + bw > Ws || (flip != 0 && flip != 1) ||
+      dst < 0 || dst >= n_out)
+    return;
+  resample_tile<kKind>(src + (size_t)img * Hs * (3 * (size_t)Ws), Hs, Ws, oy, ox, bh, bw, flip, dst, oh, ow, scale, bias, out,
+                       tiles_x);
+}
+
+// Sources of any shapes, packed into one pool: row i of the table names its image by offset and shape
+// (nic.h, nic_resample_ragged).  Every field is a 64-bit integer of the device's, so every comparison
+// below is made where it cannot overflow, and only a row that passes all of them is narrowed to int.
+template <int kKind>
+__global__ __launch_bounds__(256) void resample_ragged(const uint8_t* __restrict__ pool, long long pool_bytes,
+                                                        const long long* __restrict__ table, int oh, int ow, int n_out,
+                                                        Float3 scale, Float3 bias, void* __restrict__ out, int tiles_x) {
+  const long long* row8 = table + 8 * (size_t)blockIdx.y;
+  const long long offset = row8[0], Hs = row8[1], Ws = row8[2], oy = row8[3], ox = row8[4], bh = row8[5], bw = row8[6];
+  const long long flip = row8[7] >> 32;
+  const int dst = (int)(uint32_t)row8[7];
+  if (offset < 0 || (offset & 3) || offset > pool_bytes) return;
+  if (Hs < 1 || Ws < 1 || Hs > kMaxPixels || Ws > kMaxPixels || Hs * Ws > kMaxPixels) return;
+  if (3 * Hs * Ws > pool_bytes - offset) return;
+  if (bh < 1 || bw < 1 || oy < 0 || ox < 0 || oy > Hs - bh || ox > Ws - bw) return;
+  if ((flip != 0 && flip != 1) || dst < 0 || dst >= n_out) return;
+  resample_tile<kKind>(pool + offset, (int)Hs, (int)Ws, (int)oy, (int)ox, (int)bh, (int)bw, (int)flip, dst, oh, ow, scale, bias, out,
+                       tiles_x);
+}
+
 }  // namespace
 
 hipError_t launch_resample_boxes(const uint8_t* images, int n, int Hs, int Ws, const int* table, int oh, int ow, int n_out,
@@ -258,6 +297,22 @@ hipError_t launch_resample_boxes(const uint8_t* images, int n, int Hs, int Ws, c
     case NIC_RESAMPLE_F32: resample_boxes<NIC_RESAMPLE_F32><<<grid, 256, 0, st>>>(images, Hs, Ws, table, oh, ow, n_out, s, b, out, tiles_x); break;
     case NIC_RESAMPLE_F16: resample_boxes<NIC_RESAMPLE_F16><<<grid, 256, 0, st>>>(images, Hs, Ws, table, oh, ow, n_out, s, b, out, tiles_x); break;
     case NIC_RESAMPLE_U8: resample_boxes<NIC_RESAMPLE_U8><<<grid, 256, 0, st>>>(images, Hs, Ws, table, oh, ow, n_out, s, b, out, tiles_x); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_resample_ragged(const uint8_t* pool, long long pool_bytes, int n, const long long* table, int oh, int ow,
+                                  int n_out, int out_kind, const float* scale3, const float* bias3, void* out, hipStream_t st) {
+  const int tiles_x = (ow + kTW - 1) / kTW, tiles_y = (oh + kTH - 1) / kTH;
+  const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)n);
+  Float3 s{{1.f, 1.f, 1.f}}, b{{0.f, 0.f, 0.f}};
+  if (out_kind != NIC_RESAMPLE_U8)
+    for (int c = 0; c < 3; ++c) s.v[c] = scale3[c], b.v[c] = bias3[c];
+  switch (out_kind) {
+    case NIC_RESAMPLE_F32: resample_ragged<NIC_RESAMPLE_F32><<<grid, 256, 0, st>>>(pool, pool_bytes, table, oh, ow, n_out, s, b, out, tiles_x); break;
+    case NIC_RESAMPLE_F16: resample_ragged<NIC_RESAMPLE_F16><<<grid, 256, 0, st>>>(pool, pool_bytes, table, oh, ow, n_out, s, b, out, tiles_x); break;
+    case NIC_RESAMPLE_U8: resample_ragged<NIC_RESAMPLE_U8><<<grid, 256, 0, st>>>(pool, pool_bytes, table, oh, ow, n_out, s, b, out, tiles_x); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
