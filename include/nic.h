@@ -642,6 +642,24 @@ int nic_png_device_read(nic_ctx* ctx, const uint8_t* streams, int64_t stride, co
  *     lum = (num0 + c1)/(den0 + c1), cs = ((2 sxy - num0) + c2)/((sxx - den0) + c2); ssim_mean[i] =
  *     mean of lum cs over plane i (deterministic; work >= nic_ssim_map_work() floats).
  * nic_ssim_map_grad: the gradients of sum_i g[i] ssim_mean[i] with respect to mx, my, sxy, sxx.
+ * The MS-SSIM loss (tf.image.ssim_multiscale on one-channel fp32 planes; scale k is the 2x2 mean
+ * pool of scale k-1, an odd height or width SYMMETRIC-padded by one on the far side first):
+ * nic_msssim_terms: as nic_ssim_map, both means of one scale in one pass: ssim_mean[i] = mean of
+ *     lum cs, cs_mean[i] = mean of cs over plane i (deterministic: per-block partial sums, added
+ *     in block order; work >= nic_msssim_terms_work() floats).
+ * nic_msssim_terms_grad: the gradients of sum_i g_ssim[i] ssim_mean[i] + g_cs[i] cs_mean[i] with
+ *     respect to mx, my, sxy, sxx.
+ * nic_pool2_prep: the step to the next scale of planes x, y (n,h,w), oh = ceil(h/2), ow = ceil(w/2):
+ *     xp = 0.25 ((x[2i][2j] + x[2i][2j+1]) + (x[2i+1][2j] + x[2i+1][2j+1])), each op rounded, row h
+ *     / column w of an odd size reading row h-1 / column w-1; yp likewise; and the planes the
+ *     Gaussian reads next, pxy = xp yp, pss = xp xp + yp yp; all (n,oh,ow).
+ *     mode NIC_POOL2_PREP: all four; NIC_POOL2_POOL: xp, yp only (pxy, pss ignored);
+ *     NIC_POOL2_PRODUCTS: no pooling (scale 0): pxy = x y, pss = x x + y y, (n,h,w), and copies
+ *     of x, y in xp, yp when those are not NULL.
+ * nic_pool2_prep_grad: its adjoint: dx, dy (n,h,w) from the gradients dxp, dyp, dp, dq of the four
+ *     outputs (each nullable: zero) and the saved xp, yp (needed with dp or dq); the repeated row
+ *     and column of an odd size fold back onto the last real one; every element of dx, dy is
+ *     written once, no atomics.  Same modes (NIC_POOL2_POOL ignores dp, dq).
  * nic_adam_keras: the step's optimiser update (training.py:147-149, tf.keras Adam = TF's
  *     ResourceApplyAdam) over `count` tensors in one launch; table = device int64 records
  *     {var, m, v, grad, n} (pointers to fp32 device buffers, n elements), max_n their largest n:
@@ -671,6 +689,19 @@ int nic_ssim_map(const float* mx, const float* my, const float* sxy, const float
                  float c2, float* ssim_mean, float* work, int64_t work_floats, void* stream);
 int nic_ssim_map_grad(const float* mx, const float* my, const float* sxy, const float* sxx, const float* g, int n,
                       int64_t hw, float c1, float c2, float* gmx, float* gmy, float* gsxy, float* gsxx, void* stream);
+#define NIC_POOL2_PREP 0
+#define NIC_POOL2_PRODUCTS 1
+#define NIC_POOL2_POOL 2
+int nic_msssim_terms_work(int n, int64_t hw, int64_t* floats);
+int nic_msssim_terms(const float* mx, const float* my, const float* sxy, const float* sxx, int n, int64_t hw, float c1,
+                     float c2, float* ssim_mean, float* cs_mean, float* work, int64_t work_floats, void* stream);
+int nic_msssim_terms_grad(const float* mx, const float* my, const float* sxy, const float* sxx, const float* g_ssim,
+                          const float* g_cs, int n, int64_t hw, float c1, float c2, float* gmx, float* gmy, float* gsxy,
+                          float* gsxx, void* stream);
+int nic_pool2_prep(const float* x, const float* y, int n, int h, int w, int mode, float* xp, float* yp, float* pxy,
+                   float* pss, void* stream);
+int nic_pool2_prep_grad(const float* dxp, const float* dyp, const float* dp, const float* dq, const float* xp,
+                        const float* yp, int n, int h, int w, int mode, float* dx, float* dy, void* stream);
 int nic_adam_keras(const int64_t* table, int count, int64_t max_n, float alpha, float beta1, float beta2,
                    float epsilon, void* stream);
 

@@ -162,6 +162,13 @@ _SIGNATURES = {
                      + [c_vp, c_vp, ctypes.c_int64, c_vp]),
     "nic_ssim_map_grad": (ctypes.c_int, [c_vp] * 5 + [ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_float]
                           + [c_vp] * 5),
+    "nic_msssim_terms_work": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
+    "nic_msssim_terms": (ctypes.c_int, [c_vp] * 4 + [ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_float]
+                         + [c_vp, c_vp, c_vp, ctypes.c_int64, c_vp]),
+    "nic_msssim_terms_grad": (ctypes.c_int, [c_vp] * 6 + [ctypes.c_int, ctypes.c_int64, ctypes.c_float,
+                                                         ctypes.c_float] + [c_vp] * 5),
+    "nic_pool2_prep": (ctypes.c_int, [c_vp] * 2 + [ctypes.c_int] * 4 + [c_vp] * 5),
+    "nic_pool2_prep_grad": (ctypes.c_int, [c_vp] * 6 + [ctypes.c_int] * 4 + [c_vp] * 3),
     "nic_adam_keras": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int64] + [ctypes.c_float] * 4 + [c_vp]),
 }
 

@@ -464,7 +464,7 @@ bool models_ready(const nic_ctx* c, int m0) {
 
 extern "C" {
 
-int nic_version(void) { return 1000; }
+int nic_version(void) { return 1100; }
 
 int nic_constants(float* ycbcr9, float* ycbcr_inv9, float* off3) {
   // host copy of what nic_create uploads; lets tests compare with np.linalg.inv (utils.py:8)
@@ -1903,6 +1903,73 @@ int nic_ssim_map_grad(const float* mx, const float* my, const float* sxy, const 
   if (!mx || !my || !sxy || !sxx || !g || !gmx || !gmy || !gsxy || !gsxx)
     return fail(NIC_EINVAL, "nic_ssim_map_grad: NULL argument");
   HIP_TRY(launch_ssim_map_grad(mx, my, sxy, sxx, g, n, hw, c1, c2, gmx, gmy, gsxy, gsxx, (hipStream_t)stream));
+  return NIC_OK;
+}
+
+int nic_msssim_terms_work(int n, int64_t hw, int64_t* floats) {
+  if (!floats) return fail(NIC_EINVAL, "nic_msssim_terms_work: NULL argument");
+  if (n < 0 || hw <= 0) return fail(NIC_ESHAPE, "nic_msssim_terms_work: bad shape");
+  *floats = (int64_t)train_msssim_work_floats(n, hw);
+  return NIC_OK;
+}
+
+int nic_msssim_terms(const float* mx, const float* my, const float* sxy, const float* sxx, int n, int64_t hw, float c1,
+                     float c2, float* ssim_mean, float* cs_mean, float* work, int64_t work_floats, void* stream) {
+  if (n < 0 || hw <= 0 || (int64_t)n * hw > ((int64_t)1 << 40)) return fail(NIC_ESHAPE, "nic_msssim_terms: bad shape");
+  if (n == 0) return NIC_OK;
+  if (!mx || !my || !sxy || !sxx || !ssim_mean || !cs_mean || !work)
+    return fail(NIC_EINVAL, "nic_msssim_terms: NULL argument");
+  if (work_floats < (int64_t)train_msssim_work_floats(n, hw))
+    return fail(NIC_EINVAL, "nic_msssim_terms: work holds %lld floats, needs %lld", (long long)work_floats,
+                (long long)train_msssim_work_floats(n, hw));
+  HIP_TRY(launch_msssim_terms(mx, my, sxy, sxx, n, hw, c1, c2, ssim_mean, cs_mean, work, (hipStream_t)stream));
+  return NIC_OK;
+}
+
+int nic_msssim_terms_grad(const float* mx, const float* my, const float* sxy, const float* sxx, const float* g_ssim,
+                          const float* g_cs, int n, int64_t hw, float c1, float c2, float* gmx, float* gmy, float* gsxy,
+                          float* gsxx, void* stream) {
+  if (n < 0 || hw <= 0 || (int64_t)n * hw > ((int64_t)1 << 40))
+    return fail(NIC_ESHAPE, "nic_msssim_terms_grad: bad shape");
+  if (n == 0) return NIC_OK;
+  if (!mx || !my || !sxy || !sxx || !g_ssim || !g_cs || !gmx || !gmy || !gsxy || !gsxx)
+    return fail(NIC_EINVAL, "nic_msssim_terms_grad: NULL argument");
+  HIP_TRY(launch_msssim_terms_grad(mx, my, sxy, sxx, g_ssim, g_cs, n, hw, c1, c2, gmx, gmy, gsxy, gsxx,
+                                   (hipStream_t)stream));
+  return NIC_OK;
+}
+
+// planes of the scale step: n * h * w elements must fit an int (the callers' tensors do by far)
+static int pool2_shape(const char* who, int n, int h, int w, int mode) {
+  if (n < 0 || h <= 0 || w <= 0 || (int64_t)n * h * w > INT32_MAX)
+    return fail(NIC_ESHAPE, "%s: bad shape n %d, %d x %d", who, n, h, w);
+  if (mode != NIC_POOL2_PREP && mode != NIC_POOL2_PRODUCTS && mode != NIC_POOL2_POOL)
+    return fail(NIC_EINVAL, "%s: bad mode %d", who, mode);
+  return NIC_OK;
+}
+
+int nic_pool2_prep(const float* x, const float* y, int n, int h, int w, int mode, float* xp, float* yp, float* pxy,
+                   float* pss, void* stream) {
+  const int rc = pool2_shape("nic_pool2_prep", n, h, w, mode);
+  if (rc != NIC_OK) return rc;
+  if (n == 0) return NIC_OK;
+  const bool prod = mode != NIC_POOL2_POOL, pool = mode != NIC_POOL2_PRODUCTS;
+  if (!x || !y || (pool && (!xp || !yp)) || (prod && (!pxy || !pss)))
+    return fail(NIC_EINVAL, "nic_pool2_prep: NULL argument");
+  HIP_TRY(launch_pool2_prep(x, y, n, h, w, pool ? 1 : 0, xp, yp, prod ? pxy : nullptr, prod ? pss : nullptr,
+                            (hipStream_t)stream));
+  return NIC_OK;
+}
+
+int nic_pool2_prep_grad(const float* dxp, const float* dyp, const float* dp, const float* dq, const float* xp,
+                        const float* yp, int n, int h, int w, int mode, float* dx, float* dy, void* stream) {
+  const int rc = pool2_shape("nic_pool2_prep_grad", n, h, w, mode);
+  if (rc != NIC_OK) return rc;
+  if (n == 0) return NIC_OK;
+  if (mode == NIC_POOL2_POOL) dp = dq = nullptr;
+  if (!dx || !dy || ((dp || dq) && (!xp || !yp))) return fail(NIC_EINVAL, "nic_pool2_prep_grad: NULL argument");
+  HIP_TRY(launch_pool2_prep_grad(dxp, dyp, dp, dq, xp, yp, n, h, w, mode != NIC_POOL2_PRODUCTS ? 1 : 0, dx, dy,
+                                 (hipStream_t)stream));
   return NIC_OK;
 }
 

@@ -321,6 +321,19 @@ hipError_t launch_ssim_map(const float* mx, const float* my, const float* sxy, c
 hipError_t launch_ssim_map_grad(const float* mx, const float* my, const float* sxy, const float* sxx, const float* g,
                                 int n, long long hw, float c1, float c2, float* gmx, float* gmy, float* gsxy,
                                 float* gsxx, hipStream_t st);
+// MS-SSIM loss: one scale's plane means of lum cs and of cs (and their backward), and the
+// step between scales (2x2 mean pool of SYMMETRIC-padded planes + the Gaussian's product planes)
+size_t train_msssim_work_floats(int n, long long hw);
+hipError_t launch_msssim_terms(const float* mx, const float* my, const float* sxy, const float* sxx, int n,
+                               long long hw, float c1, float c2, float* lcs_mean, float* cs_mean, float* work,
+                               hipStream_t st);
+hipError_t launch_msssim_terms_grad(const float* mx, const float* my, const float* sxy, const float* sxx,
+                                    const float* g_ssim, const float* g_cs, int n, long long hw, float c1, float c2,
+                                    float* gmx, float* gmy, float* gsxy, float* gsxx, hipStream_t st);
+hipError_t launch_pool2_prep(const float* x, const float* y, int n, int h, int w, int pool, float* xp, float* yp,
+                             float* pxy, float* pss, hipStream_t st);
+hipError_t launch_pool2_prep_grad(const float* dxp, const float* dyp, const float* dp, const float* dq, const float* xp,
+                                  const float* yp, int n, int h, int w, int pool, float* dx, float* dy, hipStream_t st);
 hipError_t launch_gauss1d(const float* in, int n, int hi, int wi, const float* taps, int nt, int vertical, int adjoint,
                           float* out, int ho, int wo, hipStream_t st);
 

@@ -30,6 +30,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
+
 #include "nic_kernels.h"
 
 namespace nic {
@@ -459,6 +461,293 @@ __global__ __launch_bounds__(256) void ssim_map_grad_kernel(const float* __restr
   }
 }
 
+// ---- MS-SSIM loss: one scale's two means, and the step between scales ------------------------
+// tf.image.ssim_multiscale keeps, per scale, the plane means of cs (scales 0 .. K-2) and of
+// lum cs (scale K-1).  msssim_terms_kernel gives both from the same ssim_terms as the
+// single-scale map, in one pass: block bk of plane n sums its kSsimPix pixels, thread t its
+// pixels 4t .. 4t+3 in that order (one 16-byte load per map when VEC: hw % 4 == 0 and the maps
+// 16-byte aligned; the scalar form adds in the same order), then the tree over the 256 threads;
+// part[2 blk] / part[2 blk + 1] hold the lum cs / cs partials, msssim_mean_kernel adds them in
+// block order.
+__device__ __forceinline__ void ld4(float* dst, const float* src) {  // src 16-byte aligned
+  const float4 v = *reinterpret_cast<const float4*>(src);
+  dst[0] = v.x, dst[1] = v.y, dst[2] = v.z, dst[3] = v.w;
+}
+__device__ __forceinline__ void st4(float* dst, const float* src) {  // dst 16-byte aligned
+  *reinterpret_cast<float4*>(dst) = make_float4(src[0], src[1], src[2], src[3]);
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void msssim_terms_kernel(const float* __restrict__ mx, const float* __restrict__ my,
+                                                           const float* __restrict__ sxy, const float* __restrict__ sxx,
+                                                           long long hw, int bpi, float c1, float c2,
+                                                           float* __restrict__ part) {
+  __shared__ float red[2][256];
+  const int n = blockIdx.x / bpi, bk = blockIdx.x - n * bpi, t = threadIdx.x;
+  const long long p = (long long)bk * kSsimPix + 4 * t, e = (long long)n * hw + p;
+  float a[4] = {0.f, 0.f, 0.f, 0.f}, b[4], c[4], d[4];
+  int cnt = 0;
+  if constexpr (VEC) {
+    if (p < hw) {  // hw % 4 == 0: the four pixels are all inside the plane
+      ld4(a, mx + e);
+      ld4(b, my + e);
+      ld4(c, sxy + e);
+      ld4(d, sxx + e);
+      cnt = 4;
+    }
+  } else {
+    for (int k = 0; k < 4 && p + k < hw; ++k, ++cnt) {
+      a[k] = mx[e + k];
+      b[k] = my[e + k];
+      c[k] = sxy[e + k];
+      d[k] = sxx[e + k];
+    }
+  }
+  float s = 0.f, sc = 0.f;
+  for (int k = 0; k < cnt; ++k) {
+    const SsimTerms q = ssim_terms(a[k], b[k], c[k], d[k], c1, c2);
+    s = __fadd_rn(s, __fmul_rn(q.lum, q.cs));
+    sc = __fadd_rn(sc, q.cs);
+  }
+  red[0][t] = s;
+  red[1][t] = sc;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (t < o) {
+      red[0][t] = __fadd_rn(red[0][t], red[0][t + o]);
+      red[1][t] = __fadd_rn(red[1][t], red[1][t + o]);
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    part[2 * (long long)blockIdx.x] = red[0][0];
+    part[2 * (long long)blockIdx.x + 1] = red[1][0];
+  }
+}
+__global__ __launch_bounds__(64) void msssim_mean_kernel(const float* __restrict__ part, int n, int bpi, long long hw,
+                                                         float* __restrict__ lcs_mean, float* __restrict__ cs_mean) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  float s = 0.f, sc = 0.f;
+  for (int k = 0; k < bpi; ++k) {
+    s = __fadd_rn(s, part[2 * ((long long)i * bpi + k)]);
+    sc = __fadd_rn(sc, part[2 * ((long long)i * bpi + k) + 1]);
+  }
+  lcs_mean[i] = __fdiv_rn(s, (float)hw);
+  cs_mean[i] = __fdiv_rn(sc, (float)hw);
+}
+// The four terms' gradients of sum_n g_ssim[n] mean(lum cs) + g_cs[n] mean(cs): ssim_map_grad_kernel's
+// arithmetic on the first path (G1 = g_ssim / hw), with cs = c / d on the second (G2 = g_cs / hw):
+// dcs/dnum0 = -1/d, dcs/dden0 = cs/d, dcs/d(2 sxy) = 1/d, dcs/dsxx = -cs/d.
+struct SsimTermGrads {
+  float gmx, gmy, gsxy, gsxx;
+};
+__device__ __forceinline__ SsimTermGrads msssim_term_grads(float x, float y, float sxy, float sxx, float c1, float c2,
+                                                           float G1, float G2) {
+  const SsimTerms q = ssim_terms(x, y, sxy, sxx, c1, c2);
+  const float ib = __frcp_rn(q.b), id = __frcp_rn(q.d), v = __fmul_rn(q.lum, q.cs);
+  const float csd = __fmul_rn(q.cs, id);
+  const float dnum0 = __fsub_rn(__fmul_rn(G1, __fsub_rn(__fmul_rn(q.cs, ib), __fmul_rn(q.lum, id))), __fmul_rn(G2, id));
+  const float dden0 = __fadd_rn(__fmul_rn(G1, __fsub_rn(__fmul_rn(v, id), __fmul_rn(v, ib))), __fmul_rn(G2, csd));
+  SsimTermGrads r;
+  r.gmx = __fmul_rn(2.0f, __fadd_rn(__fmul_rn(dnum0, y), __fmul_rn(dden0, x)));
+  r.gmy = __fmul_rn(2.0f, __fadd_rn(__fmul_rn(dnum0, x), __fmul_rn(dden0, y)));
+  r.gsxy = __fmul_rn(2.0f, __fadd_rn(__fmul_rn(G1, __fmul_rn(q.lum, id)), __fmul_rn(G2, id)));
+  r.gsxx = -__fadd_rn(__fmul_rn(G1, __fmul_rn(v, id)), __fmul_rn(G2, csd));
+  return r;
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void msssim_terms_grad_kernel(
+    const float* __restrict__ mx, const float* __restrict__ my, const float* __restrict__ sxy,
+    const float* __restrict__ sxx, const float* __restrict__ g_ssim, const float* __restrict__ g_cs, int n, long long hw,
+    float c1, float c2, float* __restrict__ gmx, float* __restrict__ gmy, float* __restrict__ gsxy,
+    float* __restrict__ gsxx) {
+  constexpr int V = VEC ? 4 : 1;  // VEC: hw % 4 == 0, so the four elements share their plane
+  const long long total = (long long)n * hw / V;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const long long e = i * V, pl = e / hw;
+    const float G1 = __fdiv_rn(g_ssim[pl], (float)hw), G2 = __fdiv_rn(g_cs[pl], (float)hw);
+    float a[V], b[V], c[V], d[V], o0[V], o1[V], o2[V], o3[V];
+    if constexpr (VEC) {
+      ld4(a, mx + e);
+      ld4(b, my + e);
+      ld4(c, sxy + e);
+      ld4(d, sxx + e);
+    } else {
+      a[0] = mx[e], b[0] = my[e], c[0] = sxy[e], d[0] = sxx[e];
+    }
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      const SsimTermGrads r = msssim_term_grads(a[k], b[k], c[k], d[k], c1, c2, G1, G2);
+      o0[k] = r.gmx, o1[k] = r.gmy, o2[k] = r.gsxy, o3[k] = r.gsxx;
+    }
+    if constexpr (VEC) {
+      st4(gmx + e, o0);
+      st4(gmy + e, o1);
+      st4(gsxy + e, o2);
+      st4(gsxx + e, o3);
+    } else {
+      gmx[e] = o0[0], gmy[e] = o1[0], gsxy[e] = o2[0], gsxx[e] = o3[0];
+    }
+  }
+}
+
+// The step between scales (tf.image.ssim_multiscale: an odd height or width SYMMETRIC-padded by
+// one on the far side, i.e. its last row / column repeated, then a 2x2 average pool, stride 2) and
+// the two product planes the Gaussian reads next.  One thread per four output columns of one output
+// row (VEC: w % 8 == 0 and everything 16-byte aligned, so two float4 loads per input row and one
+// float4 store per output; otherwise the same work with scalar accesses):
+//   x' = 0.25 ((x[2i][2j] + x[2i][2j+1]) + (x[2i+1][2j] + x[2i+1][2j+1])),  P = x' y',  Q = x' x' + y' y'
+struct PoolPrepArgs {
+  const float *x, *y;          // (n, h, w)
+  float *xp, *yp, *pxy, *pss;  // (n, oh, ow); null: not written
+  int n, h, w, oh, ow;
+  int pool;                    // 0: x' = x (oh = h, ow = w)
+};
+__device__ __forceinline__ float pool4(float a, float b, float c, float d) {
+  return __fmul_rn(0.25f, __fadd_rn(__fadd_rn(a, b), __fadd_rn(c, d)));
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void pool2_prep_kernel(PoolPrepArgs a) {
+  const int gw = (a.ow + 3) / 4;  // groups of four output columns per row
+  const long long total = (long long)a.n * a.oh * gw;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int g = (int)(i % gw);
+    const long long r = i / gw;  // output row over all planes
+    const int oy = (int)(r % a.oh);
+    const long long b = r / a.oh;
+    const int ox = 4 * g, cnt = min(4, a.ow - ox);
+    float xv[4], yv[4];
+    if (a.pool) {
+      const int y0 = 2 * oy, y1 = min(2 * oy + 1, a.h - 1);
+      const long long r0 = (b * a.h + y0) * a.w, r1 = (b * a.h + y1) * a.w;
+      float t0[8], t1[8], u0[8], u1[8];
+      if constexpr (VEC) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          ld4(t0 + 4 * k, a.x + r0 + 2 * ox + 4 * k);
+          ld4(t1 + 4 * k, a.x + r1 + 2 * ox + 4 * k);
+          ld4(u0 + 4 * k, a.y + r0 + 2 * ox + 4 * k);
+          ld4(u1 + 4 * k, a.y + r1 + 2 * ox + 4 * k);
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const int xx = min(2 * ox + k, a.w - 1);  // the repeated last column; past cnt: unused
+          t0[k] = a.x[r0 + xx], t1[k] = a.x[r1 + xx], u0[k] = a.y[r0 + xx], u1[k] = a.y[r1 + xx];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        xv[k] = pool4(t0[2 * k], t0[2 * k + 1], t1[2 * k], t1[2 * k + 1]);
+        yv[k] = pool4(u0[2 * k], u0[2 * k + 1], u1[2 * k], u1[2 * k + 1]);
+      }
+    } else {
+      const long long r0 = r * a.w + ox;
+      if constexpr (VEC) {
+        ld4(xv, a.x + r0);
+        ld4(yv, a.y + r0);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int kk = min(k, cnt - 1);
+          xv[k] = a.x[r0 + kk], yv[k] = a.y[r0 + kk];
+        }
+      }
+    }
+    float pv[4], qv[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      pv[k] = __fmul_rn(xv[k], yv[k]);
+      qv[k] = __fadd_rn(__fmul_rn(xv[k], xv[k]), __fmul_rn(yv[k], yv[k]));
+    }
+    const long long o = r * a.ow + ox;
+    if constexpr (VEC) {
+      if (a.xp) st4(a.xp + o, xv);
+      if (a.yp) st4(a.yp + o, yv);
+      if (a.pxy) st4(a.pxy + o, pv);
+      if (a.pss) st4(a.pss + o, qv);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (k < cnt) {
+          if (a.xp) a.xp[o + k] = xv[k];
+          if (a.yp) a.yp[o + k] = yv[k];
+          if (a.pxy) a.pxy[o + k] = pv[k];
+          if (a.pss) a.pss[o + k] = qv[k];
+        }
+      }
+    }
+  }
+}
+// Its adjoint.  At the coarse size the gradient that reaches x' is gx = dx' + dP y' + 2 dQ x' (and
+// gy = dy' + dP x' + 2 dQ y'); every fine pixel (r, c) belongs to exactly one 2x2 window, the
+// repeated last row / column of an odd size a second time to the same one, so
+//   dx[r][c] = 0.25 gx[r / 2][c / 2] (2 if r is the repeated row) (2 if c is the repeated column)
+// and each output element is written once.  One thread per four fine columns of one fine row.
+struct PoolPrepGradArgs {
+  const float *dxp, *dyp, *dp, *dq;  // (n, oh, ow); null: zero
+  const float *xp, *yp;              // the saved x', y' (read only with dp or dq)
+  float *dx, *dy;                    // (n, h, w)
+  int n, h, w, oh, ow, pool;
+};
+template <bool VEC>
+__global__ __launch_bounds__(256) void pool2_prep_grad_kernel(PoolPrepGradArgs a) {
+  const int gw = (a.w + 3) / 4;
+  const long long total = (long long)a.n * a.h * gw;
+  const bool prod = a.dp || a.dq;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int g = (int)(i % gw);
+    const long long r = i / gw;  // fine row over all planes
+    const int fy = (int)(r % a.h);
+    const long long b = r / a.h;
+    const int fx = 4 * g, cnt = min(4, a.w - fx);
+    // the coarse elements under the four fine columns: two (pool) or four (no pool)
+    const int nc = a.pool ? 2 : 4;
+    const int cy = a.pool ? fy >> 1 : fy, cx = a.pool ? fx >> 1 : fx;
+    const long long co = (b * a.oh + cy) * a.ow + cx;
+    float gx[4], gy[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      gx[k] = 0.f, gy[k] = 0.f;
+      if (k < nc && cx + k < a.ow) {
+        const long long e = co + k;
+        const float dxp = a.dxp ? a.dxp[e] : 0.f, dyp = a.dyp ? a.dyp[e] : 0.f;
+        float sx = dxp, sy = dyp;
+        if (prod) {
+          const float xv = a.xp[e], yv = a.yp[e];
+          const float dp = a.dp ? a.dp[e] : 0.f, dq2 = a.dq ? __fmul_rn(2.0f, a.dq[e]) : 0.f;
+          sx = fmaf(dq2, xv, fmaf(dp, yv, dxp));
+          sy = fmaf(dq2, yv, fmaf(dp, xv, dyp));
+        }
+        gx[k] = sx, gy[k] = sy;
+      }
+    }
+    float ox[4], oy[4];
+    if (a.pool) {
+      const float ry = ((a.h & 1) && fy == a.h - 1) ? 0.5f : 0.25f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float f = ((a.w & 1) && fx + k == a.w - 1) ? __fmul_rn(2.0f, ry) : ry;
+        ox[k] = __fmul_rn(f, gx[k >> 1]);
+        oy[k] = __fmul_rn(f, gy[k >> 1]);
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) ox[k] = gx[k], oy[k] = gy[k];
+    }
+    const long long o = r * a.w + fx;
+    if constexpr (VEC) {
+      st4(a.dx + o, ox);
+      st4(a.dy + o, oy);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (k < cnt) a.dx[o + k] = ox[k], a.dy[o + k] = oy[k];
+      }
+    }
+  }
+}
+
 // ---- separable Gaussian of the SSIM loss (tf.image.ssim's 11-tap window) --------------------
 // One-channel planes (n, h, w): VALID correlation along x (vertical = 0) or y, or its adjoint
 // (the input gradient: a full convolution with the same taps).
@@ -812,6 +1101,85 @@ hipError_t launch_ssim_map_grad(const float* mx, const float* my, const float* s
   const long long blocks = (total + 255) / 256;
   hipLaunchKernelGGL(ssim_map_grad_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, mx, my,
                      sxy, sxx, g, n, hw, c1, c2, gmx, gmy, gsxy, gsxx);
+  return hipGetLastError();
+}
+
+static bool aligned16(std::initializer_list<const void*> ps) {
+  for (const void* p : ps)
+    if ((uintptr_t)p & 15) return false;  // (null counts as aligned: it is not accessed)
+  return true;
+}
+
+size_t train_msssim_work_floats(int n, long long hw) { return 2 * train_ssim_work_floats(n, hw); }
+
+hipError_t launch_msssim_terms(const float* mx, const float* my, const float* sxy, const float* sxx, int n,
+                               long long hw, float c1, float c2, float* lcs_mean, float* cs_mean, float* work,
+                               hipStream_t st) {
+  const long long bpi = (hw + kSsimPix - 1) / kSsimPix;
+  if (n == 0) return hipSuccess;
+  if (bpi * n > INT32_MAX || bpi > INT32_MAX) return hipErrorInvalidValue;
+  const bool vec = hw % 4 == 0 && aligned16({mx, my, sxy, sxx});
+  const dim3 grid((unsigned)(bpi * n));
+  if (vec)
+    hipLaunchKernelGGL(msssim_terms_kernel<true>, grid, dim3(256), 0, st, mx, my, sxy, sxx, hw, (int)bpi, c1, c2, work);
+  else
+    hipLaunchKernelGGL(msssim_terms_kernel<false>, grid, dim3(256), 0, st, mx, my, sxy, sxx, hw, (int)bpi, c1, c2, work);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(msssim_mean_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, work, n, (int)bpi, hw,
+                     lcs_mean, cs_mean);
+  return hipGetLastError();
+}
+
+hipError_t launch_msssim_terms_grad(const float* mx, const float* my, const float* sxy, const float* sxx,
+                                    const float* g_ssim, const float* g_cs, int n, long long hw, float c1, float c2,
+                                    float* gmx, float* gmy, float* gsxy, float* gsxx, hipStream_t st) {
+  if ((long long)n * hw == 0) return hipSuccess;
+  const bool vec = hw % 4 == 0 && aligned16({mx, my, sxy, sxx, gmx, gmy, gsxy, gsxx});
+  const long long blocks = ((long long)n * hw / (vec ? 4 : 1) + 255) / 256;
+  const dim3 grid((unsigned)(blocks < 65536 ? blocks : 65536));
+  if (vec)
+    hipLaunchKernelGGL(msssim_terms_grad_kernel<true>, grid, dim3(256), 0, st, mx, my, sxy, sxx, g_ssim, g_cs, n, hw, c1,
+                       c2, gmx, gmy, gsxy, gsxx);
+  else
+    hipLaunchKernelGGL(msssim_terms_grad_kernel<false>, grid, dim3(256), 0, st, mx, my, sxy, sxx, g_ssim, g_cs, n, hw,
+                       c1, c2, gmx, gmy, gsxy, gsxx);
+  return hipGetLastError();
+}
+
+hipError_t launch_pool2_prep(const float* x, const float* y, int n, int h, int w, int pool, float* xp, float* yp,
+                             float* pxy, float* pss, hipStream_t st) {
+  PoolPrepArgs a;
+  a.x = x, a.y = y, a.xp = xp, a.yp = yp, a.pxy = pxy, a.pss = pss;
+  a.n = n, a.h = h, a.w = w, a.pool = pool;
+  a.oh = pool ? (h + 1) / 2 : h, a.ow = pool ? (w + 1) / 2 : w;
+  const long long total = (long long)n * a.oh * ((a.ow + 3) / 4);
+  if (total == 0) return hipSuccess;
+  const bool vec = w % (pool ? 8 : 4) == 0 && aligned16({x, y, xp, yp, pxy, pss});
+  const long long blocks = (total + 255) / 256;
+  const dim3 grid((unsigned)(blocks < 65536 ? blocks : 65536));
+  if (vec)
+    hipLaunchKernelGGL(pool2_prep_kernel<true>, grid, dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL(pool2_prep_kernel<false>, grid, dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_pool2_prep_grad(const float* dxp, const float* dyp, const float* dp, const float* dq, const float* xp,
+                                  const float* yp, int n, int h, int w, int pool, float* dx, float* dy, hipStream_t st) {
+  PoolPrepGradArgs a;
+  a.dxp = dxp, a.dyp = dyp, a.dp = dp, a.dq = dq, a.xp = xp, a.yp = yp, a.dx = dx, a.dy = dy;
+  a.n = n, a.h = h, a.w = w, a.pool = pool;
+  a.oh = pool ? (h + 1) / 2 : h, a.ow = pool ? (w + 1) / 2 : w;
+  const long long total = (long long)n * h * ((w + 3) / 4);
+  if (total == 0) return hipSuccess;
+  const bool vec = w % 4 == 0 && aligned16({dx, dy});
+  const long long blocks = (total + 255) / 256;
+  const dim3 grid((unsigned)(blocks < 65536 ? blocks : 65536));
+  if (vec)
+    hipLaunchKernelGGL(pool2_prep_grad_kernel<true>, grid, dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL(pool2_prep_grad_kernel<false>, grid, dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

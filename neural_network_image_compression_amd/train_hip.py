@@ -14,7 +14,9 @@ Conv2DTranspose dW     wgrad(gat = dy, dir = x) -> HWOI
 =====================  ==========================================================
 
 The SSIM loss's separable Gaussian (one-channel VALID correlation) runs on a 1-D HIP
-kernel and its adjoint (``gauss_valid``, ``nic_gauss_1d``).
+kernel and its adjoint (``gauss_valid``, ``nic_gauss_1d``).  The MS-SSIM loss (``ms_ssim_mean``)
+adds the step between scales with the Gaussian's product planes (``nic_pool2_prep`` and its
+adjoint) and both per-plane means of a scale in one pass (``nic_msssim_terms`` and its backward).
 
 Each operand gets a power-of-two scale (max |t| * scale in [2^13, 2^14)) computed on the
 device once per tensor (x and the kernel in the forward, dy in the backward), so the f16 hi/lo split keeps tiny gradients exact to ~2^-22.  The layers' leaky-ReLU runs in
@@ -175,6 +177,89 @@ def gauss_1d(t, taps, vertical: int, adjoint: int):
     return out
 
 
+POOL2_PREP, POOL2_PRODUCTS, POOL2_POOL = 0, 1, 2  # nic.h NIC_POOL2_*
+
+
+def pool2_prep(x, y, mode: int = POOL2_PREP):
+    """nic_pool2_prep on one-channel planes (n, h, w): the MS-SSIM loss's step to the next scale.
+    POOL2_PREP -> (x', y', x'y', x'x' + y'y') at (n, ceil(h/2), ceil(w/2)); POOL2_POOL -> (x', y');
+    POOL2_PRODUCTS (no pooling, scale 0) -> (x y, x x + y y) at (n, h, w)."""
+    torch = _torch()
+    x, y = _check(x, "pool2_prep x"), _check(y, "pool2_prep y")
+    dev = _same_device(x, y)
+    if x.dim() != 3 or x.shape != y.shape:
+        raise ValueError(f"pool2_prep: planes (n, h, w) of one shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    n, h, w = x.shape
+    shape = (n, h, w) if mode == POOL2_PRODUCTS else (n, -(-h // 2), -(-w // 2))
+    outs = [torch.empty(shape, dtype=torch.float32, device=x.device)
+            for _ in range(4 if mode == POOL2_PREP else 2)]
+    ptrs = [t.data_ptr() for t in outs]
+    ptrs = {POOL2_PREP: ptrs, POOL2_PRODUCTS: [None, None] + ptrs, POOL2_POOL: ptrs + [None, None]}.get(mode, ptrs)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().nic_pool2_prep(x.data_ptr(), y.data_ptr(), n, h, w, mode, *ptrs[:4], _stream(dev)),
+                   "nic_pool2_prep")
+    return tuple(outs)
+
+
+def pool2_prep_grad(dxp, dyp, dp, dq, xp, yp, hw: Tuple[int, int], mode: int = POOL2_PREP):
+    """nic_pool2_prep_grad: (dx, dy) at (n, h, w) = ``hw`` from the gradients of pool2_prep's
+    outputs (each may be None: zero) and its saved x', y' (None without dp and dq)."""
+    torch = _torch()
+    ts = [None if t is None else _check(t, "pool2_prep_grad operand") for t in (dxp, dyp, dp, dq, xp, yp)]
+    given = [t for t in ts if t is not None]
+    if not given:
+        raise ValueError("pool2_prep_grad: no operand")
+    dev = _same_device(*given)
+    h, w = hw
+    coarse = (h, w) if mode == POOL2_PRODUCTS else (-(-h // 2), -(-w // 2))
+    n = given[0].shape[0]
+    for t in given:
+        if tuple(t.shape) != (n, *coarse):
+            raise ValueError(f"pool2_prep_grad: operand {tuple(t.shape)}, expected {(n, *coarse)}")
+    dx = torch.empty((n, h, w), dtype=torch.float32, device=given[0].device)
+    dy = torch.empty_like(dx)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().nic_pool2_prep_grad(*(None if t is None else t.data_ptr() for t in ts), n, h, w, mode,
+                                                  dx.data_ptr(), dy.data_ptr(), _stream(dev)), "nic_pool2_prep_grad")
+    return dx, dy
+
+
+def msssim_terms(mx, my, sxy, sxx, c1: float, c2: float):
+    """nic_msssim_terms: the (n,) plane means of lum cs and of cs from one scale's filtered terms."""
+    torch = _torch()
+    ts = [_check(t, "msssim_terms term") for t in (mx, my, sxy, sxx)]
+    dev = _same_device(*ts)
+    n = ts[0].shape[0]
+    hw = ts[0].numel() // max(n, 1)
+    lcs = torch.empty((n,), dtype=torch.float32, device=ts[0].device)
+    cs = torch.empty_like(lcs)
+    need = 2 * n * (-(-hw // SSIM_PIX))  # nic_msssim_terms_work (checked by the call)
+    work = torch.empty(max(need, 1), dtype=torch.float32, device=ts[0].device)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().nic_msssim_terms(*(t.data_ptr() for t in ts), n, hw, c1, c2, lcs.data_ptr(),
+                                               cs.data_ptr(), work.data_ptr(), need, _stream(dev)), "nic_msssim_terms")
+    return lcs, cs
+
+
+def msssim_terms_grad(mx, my, sxy, sxx, g_ssim, g_cs, c1: float, c2: float, out=None):
+    """nic_msssim_terms_grad: the four terms' gradients of sum g_ssim mean(lum cs) + g_cs mean(cs);
+    ``out``: a (4, ...) buffer to write them into (its four slices are returned)."""
+    torch = _torch()
+    ts = [_check(t, "msssim_terms_grad term") for t in (mx, my, sxy, sxx)]
+    g_ssim, g_cs = _check(g_ssim, "msssim_terms_grad g_ssim"), _check(g_cs, "msssim_terms_grad g_cs")
+    dev = _same_device(*ts, g_ssim, g_cs)
+    n = ts[0].shape[0]
+    hw = ts[0].numel() // max(n, 1)
+    if g_ssim.numel() != n or g_cs.numel() != n:
+        raise ValueError("msssim_terms_grad: one g_ssim and one g_cs per plane")
+    grads = [torch.empty_like(t) for t in ts] if out is None else list(out.unbind(0))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().nic_msssim_terms_grad(*(t.data_ptr() for t in ts), g_ssim.data_ptr(), g_cs.data_ptr(), n,
+                                                    hw, c1, c2, *(t.data_ptr() for t in grads), _stream(dev)),
+                   "nic_msssim_terms_grad")
+    return tuple(grads)
+
+
 def _conv_fn():
     torch = _torch()
 
@@ -288,7 +373,61 @@ def _conv_fn():
                            "nic_ssim_map_grad")
             return (*grads, None, None)
 
-    return Conv2DSame, Conv2DTransposeSame, Gauss1D, SsimMap
+    class Pool2Prep(torch.autograd.Function):
+        """The MS-SSIM loss's step between scales (nic_pool2_prep / nic_pool2_prep_grad) on planes
+        (n, h, w); outputs as :func:`pool2_prep` for the mode."""
+
+        @staticmethod
+        def forward(ctx, x, y, mode):
+            outs = pool2_prep(x, y, mode)
+            ctx.mode, ctx.hw = mode, tuple(x.shape[1:])
+            ctx.set_materialize_grads(False)  # an unused output's gradient stays None: not read
+            if mode == POOL2_PREP:
+                ctx.save_for_backward(outs[0], outs[1])
+            elif mode == POOL2_PRODUCTS:
+                ctx.save_for_backward(x, y)
+            return outs
+
+        @staticmethod
+        def backward(ctx, *gs):
+            gs = [None if g is None else g.contiguous() for g in gs]
+            if ctx.mode == POOL2_PREP:
+                args = (*gs, *ctx.saved_tensors)
+            elif ctx.mode == POOL2_PRODUCTS:
+                args = (None, None, *gs, *ctx.saved_tensors)
+            else:
+                args = (*gs, None, None, None, None)
+            dx, dy = pool2_prep_grad(*args, ctx.hw, ctx.mode)
+            return dx, dy, None
+
+    class MsssimTerms(torch.autograd.Function):
+        """Per-plane means of lum cs and of cs from one scale's filtered terms, stacked as
+        f = (mx, my, sxy, sxx): (4, N, ...) (nic_msssim_terms / nic_msssim_terms_grad); the
+        gradient comes back as one such stack."""
+
+        @staticmethod
+        def forward(ctx, f, c1, c2):
+            f = _check(f, "MsssimTerms terms")
+            if f.shape[0] != 4:
+                raise ValueError("MsssimTerms: the four terms stacked along dim 0")
+            ctx.save_for_backward(f)
+            ctx.consts = (c1, c2)
+            ctx.set_materialize_grads(False)
+            return msssim_terms(*f.unbind(0), c1, c2)
+
+        @staticmethod
+        def backward(ctx, g_ssim, g_cs):
+            (f,) = ctx.saved_tensors
+            n = f.shape[1]
+            zero = None
+            if g_ssim is None or g_cs is None:
+                zero = torch.zeros((n,), dtype=torch.float32, device=f.device)
+            out = torch.empty_like(f)
+            msssim_terms_grad(*f.unbind(0), zero if g_ssim is None else g_ssim, zero if g_cs is None else g_cs,
+                              *ctx.consts, out=out)
+            return out, None, None
+
+    return Conv2DSame, Conv2DTransposeSame, Gauss1D, SsimMap, Pool2Prep, MsssimTerms
 
 
 _FNS = None
@@ -329,6 +468,44 @@ def gauss_valid(t, g1d):
     x = _fns()[2].apply(t.reshape(n, h, w), g1d, 0)
     x = _fns()[2].apply(x, g1d, 1)
     return x.reshape(n, 1, x.shape[1], x.shape[2])
+
+
+def pool2_prep_fn(x, y, mode: int = POOL2_PREP):
+    """:func:`pool2_prep`, differentiable."""
+    return _fns()[4].apply(x, y, mode)
+
+
+def msssim_terms_mean(mx, my, sxy, sxx, c1: float, c2: float):
+    """(N,) plane means of lum cs and of cs from one scale's filtered terms (HIP, differentiable)."""
+    return _fns()[5].apply(_torch().stack([mx, my, sxy, sxx]), float(c1), float(c2))
+
+
+def ms_ssim_mean(x, y, scales: int, max_val: float = 1.0):
+    """tf.image.ssim_multiscale(x, y, max_val, power_factors=MSSSIM_WEIGHTS[:scales]) of one-channel
+    NCHW planes (N,1,H,W) -> (N,), differentiable, on HIP: per scale one nic_pool2_prep (pool and
+    the two product planes), one Gaussian over the four stacked planes (nic_gauss_1d, twice) and
+    nic_msssim_terms; the N x scales combination stays on torch."""
+    from .training import _gauss_window, ms_ssim_combine, ms_ssim_sizes
+
+    torch = _torch()
+    n, c, h, w = x.shape
+    if c != 1 or y.shape != x.shape:
+        raise ValueError("ms_ssim_mean: two one-channel planes (N,1,H,W) of one shape")
+    ms_ssim_sizes(h, w, scales)
+    c1, c2 = (0.01 * max_val) ** 2, (0.03 * max_val) ** 2
+    g = _gauss_window(torch, x.device, torch.float32)
+    xs, ys = x.reshape(n, h, w), y.reshape(n, h, w)
+    terms = []
+    for k in range(scales):
+        if k == 0:
+            p, q = pool2_prep_fn(xs, ys, POOL2_PRODUCTS)
+        else:
+            xs, ys, p, q = pool2_prep_fn(xs, ys, POOL2_PREP)
+        f = torch.cat([xs, ys, p, q], dim=0)  # one Gaussian over the four planes
+        f = _fns()[2].apply(_fns()[2].apply(f, g, 0), g, 1)
+        lcs, cs = _fns()[5].apply(f.view(4, n, f.shape[1], f.shape[2]), c1, c2)
+        terms.append(lcs if k == scales - 1 else cs)
+    return ms_ssim_combine(torch.stack(terms, dim=1), scales)
 
 
 def keras_adam_alpha(step: int, lr: float = 1e-4, beta1: float = 0.9, beta2: float = 0.999) -> float:

@@ -154,6 +154,77 @@ def ssim(x, y, max_val: float = 1.0, hip: bool = False):
     return (lum * cs).mean(dim=(1, 2, 3))
 
 
+MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)  # tf.image.ssim_multiscale's power factors
+
+
+def ms_ssim_sizes(h: int, w: int, scales: int):
+    """The plane size at each of ``scales`` scales (each ceil(previous / 2)); ValueError when
+    ``scales`` is not 1..5 or a scale cannot hold the 11x11 window."""
+    if not 1 <= scales <= len(MSSSIM_WEIGHTS):
+        raise ValueError(f"ms_ssim: scales must be 1..{len(MSSSIM_WEIGHTS)}, not {scales}")
+    sizes = []
+    for k in range(scales):
+        if min(h, w) < 11:
+            raise ValueError(f"ms_ssim: scale {k} of {scales} is {h}x{w}, smaller than the 11x11 window")
+        sizes.append((h, w))
+        h, w = -(-h // 2), -(-w // 2)
+    return sizes
+
+
+def ms_ssim_combine(terms, scales: int):
+    """tf.image.ssim_multiscale's combination of the (N, K) per-scale terms: each clamped at 0,
+    raised to its weight, multiplied.  A term <= 0 contributes 0 with a zero (not inf / nan)
+    gradient."""
+    torch = _torch()
+    wts = torch.tensor(MSSSIM_WEIGHTS[:scales], dtype=terms.dtype, device=terms.device)
+    pos = terms > 0
+    powed = torch.where(pos, terms, torch.ones_like(terms)) ** wts
+    return torch.where(pos, powed, torch.zeros_like(powed)).prod(dim=1)
+
+
+def ms_ssim(x, y, scales: int = 4, max_val: float = 1.0, hip: bool = False):
+    """tf.image.ssim_multiscale(x, y, max_val, power_factors=MSSSIM_WEIGHTS[:scales]) of one-channel
+    NCHW planes (N,1,H,W) -> (N,); differentiable.  Scale k is the 2x2 mean pool of scale k-1 (an
+    odd height or width SYMMETRIC-padded by one on the far side first); scales 0 .. K-2 give the
+    plane mean of cs, scale K-1 that of lum cs; each is clamped at 0, raised to its weight (not
+    renormalised) and the K are multiplied.  A term <= 0 gives 0 with a zero gradient.  ValueError
+    when a scale cannot hold the 11x11 window (128 x 128 patches allow 4 scales).  ``hip``: on
+    the HIP kernels (train_hip.ms_ssim_mean); otherwise this PyTorch restatement."""
+    torch = _torch()
+    import torch.nn.functional as F
+
+    n, c, h, w = x.shape
+    if c != 1 or y.shape != x.shape:
+        raise ValueError("ms_ssim: two one-channel planes (N,1,H,W) of one shape")
+    ms_ssim_sizes(h, w, scales)
+    if hip:
+        from . import train_hip
+
+        return train_hip.ms_ssim_mean(x, y, scales, max_val)
+    g = _gauss_window(torch, x.device, x.dtype)
+
+    def filt(t):
+        return F.conv2d(F.conv2d(t, g.view(1, 1, 1, -1)), g.view(1, 1, -1, 1))
+
+    def pool(t):
+        t = F.pad(t, (0, t.shape[3] % 2, 0, t.shape[2] % 2), mode="replicate")  # SYMMETRIC by one
+        return 0.25 * ((t[:, :, 0::2, 0::2] + t[:, :, 0::2, 1::2]) + (t[:, :, 1::2, 0::2] + t[:, :, 1::2, 1::2]))
+
+    c1, c2 = (0.01 * max_val) ** 2, (0.03 * max_val) ** 2
+    terms = []
+    for k in range(scales):
+        if k:
+            x, y = pool(x), pool(y)
+        mx, my = filt(x), filt(y)
+        num0 = mx * my * 2.0
+        den0 = mx * mx + my * my
+        cs = (filt(x * y) * 2.0 - num0 + c2) / (filt(x * x + y * y) - den0 + c2)
+        if k == scales - 1:
+            cs = (num0 + c1) / (den0 + c1) * cs
+        terms.append(cs.mean(dim=(1, 2, 3)))
+    return ms_ssim_combine(torch.stack(terms, dim=1), scales)
+
+
 def png_bpp_planes(encoded_u8: np.ndarray, tot_pixels: float, threads: int = 16, mode: str = "tf") -> np.ndarray:
     """get_bpp (training.py:14-21): latent planes (M,h,w,32) u8 -> (M,) 8*len(PNG((4h,8w)))/pixels.
 
@@ -231,15 +302,22 @@ class Training:
 
     def __init__(self, device: str = "cuda", weights: Optional[W.Weights] = None, seed: int = 0,
                  checkpoint_dir: str = "../checkpoints/", backend: Optional[str] = None,
-                 png_threads: int = 16):
+                 png_threads: int = 16, distortion: str = "ssim", ms_scales: int = 4):
         """backend "hip" (default on a GPU): every convolution of the step, forward and
         backward, on the HIP split-f16x3 MFMA kernels (train_hip, NHWC); "torch" (default on
         the CPU): PyTorch autograd convolutions (MIOpen / oneDNN, NCHW) -- the restatement the
-        HIP path is tested against."""
+        HIP path is tested against.  distortion "ssim" (default, the reference's loss):
+        tf.image.ssim; "ms_ssim": tf.image.ssim_multiscale over ``ms_scales`` scales
+        (:func:`ms_ssim`), the metric the codecs are scored by, in both codec losses."""
         torch = _torch()
         backend = backend or ("hip" if torch.device(device).type == "cuda" else "torch")
         if backend not in ("hip", "torch"):
             raise ValueError(f"backend must be 'hip' or 'torch', not {backend!r}")
+        if distortion not in ("ssim", "ms_ssim"):
+            raise ValueError(f"distortion must be 'ssim' or 'ms_ssim', not {distortion!r}")
+        if not 1 <= ms_scales <= len(MSSSIM_WEIGHTS):
+            raise ValueError(f"ms_scales must be 1..{len(MSSSIM_WEIGHTS)}, not {ms_scales}")
+        self.distortion, self.ms_scales = distortion, ms_scales
         self.hip = backend == "hip"
         self.hip_adam = True  # HIP backend: the Keras Adam update on HIP (False: torch.optim.Adam)
         self.device = torch.device(device)
@@ -387,8 +465,12 @@ class Training:
         dec1 = base_decoder(self._model("decoderCbCr"), noisy1, hip)
         if hip:  # back to (N,1,H,W) views for the SSIM filter
             p0, p1, dec0, dec1 = (t.reshape(t.shape[0], 1, *t.shape[1:3]) for t in (p0, p1, dec0, dec1))
-        ssim0 = ssim(p0, dec0, hip=hip).mean()
-        ssim1_each = ssim(p1, dec1, hip=hip)
+        if self.distortion == "ms_ssim":
+            ssim0 = ms_ssim(p0, dec0, self.ms_scales, hip=hip).mean()
+            ssim1_each = ms_ssim(p1, dec1, self.ms_scales, hip=hip)
+        else:
+            ssim0 = ssim(p0, dec0, hip=hip).mean()
+            ssim1_each = ssim(p1, dec1, hip=hip)
         ssim1 = ssim1_each.mean()
         loss0 = ((1 - ssim0) / 2 + entropy_loss_coef * ent[0]).sum()
         loss1 = ((1 - ssim1) / 2 + 0.01 * torch.cat(ent[1:], dim=0)).sum()  # reference: 0.01 (training.py:124)

@@ -1,0 +1,135 @@
+"""The MS-SSIM training loss on the CPU: the float64 reference (tests/msssim_ref.py) against the
+oracle's tf.image.ssim_multiscale, training.ms_ssim's PyTorch restatement against the reference
+(value and autograd gradients), the argument errors, the zero-gradient rule at a non-positive
+term, and Training(distortion="ms_ssim") on the torch backend."""
+import numpy as np
+import pytest
+import torch
+
+from oracle import nic_oracle as O
+from neural_network_image_compression_amd import training as T
+from tests import msssim_ref as R
+
+
+def _u8_pair(h, w, seed):
+    """(2,h,w,1) u8 image pairs: a smooth ramp with texture, and a noisy copy."""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:h, 0:w]
+    base = 128 + 80 * np.sin(yy / 17.0 + seed) * np.cos(xx / 23.0) + rng.integers(-20, 21, (2, h, w))
+    a = np.clip(base, 0, 255).astype(np.uint8)[..., None]
+    b = np.clip(a.astype(np.int64) + rng.integers(-12, 13, a.shape), 0, 255).astype(np.uint8)
+    return a, b
+
+
+def _planes64(u8):
+    """The oracle's u8 -> float conversion (x * float32(1/255) in float64) as (N,1,H,W)."""
+    return torch.from_numpy(u8[..., 0].astype(np.float64) * np.float32(1.0 / 255))[:, None]
+
+
+@pytest.mark.parametrize("hw", [(161, 163), (176, 176)])
+def test_reference_matches_oracle_per_scale_and_in_value(hw):
+    a, b = _u8_pair(*hw, seed=hw[0])
+    want_terms = O.ms_ssim_terms(a, b)  # (N, C=1, 5, 2): one channel, so no averaging over channels
+    want = O.ms_ssim(a, b)
+    x, y = _planes64(a), _planes64(b)
+    got_terms = R.terms(x, y, 5).numpy()
+    assert got_terms.shape == want_terms[:, 0].shape
+    assert np.abs(got_terms - want_terms[:, 0]).max() <= 1e-12
+    assert np.abs(R.ms_ssim(x, y, 5).numpy() - want).max() <= 1e-12
+    assert want_terms[:, 0, :, 1].min() > 0  # every term positive: the clamp is not what is compared
+
+
+@pytest.mark.parametrize("h,w,scales", [(22, 22, 2), (23, 27, 2), (45, 50, 3)])
+def test_torch_restatement_matches_reference_value_and_gradients(h, w, scales):
+    x, y = R.planes(3, h, w, seed=h * w)
+    wts = torch.tensor([1.0, -0.5, 2.0], dtype=torch.float64)
+    xr, yr = x.clone().requires_grad_(), y.clone().requires_grad_()
+    ref = R.ms_ssim(xr, yr, scales)
+    (ref * wts).sum().backward()
+    xt, yt = x.clone().requires_grad_(), y.clone().requires_grad_()
+    got = T.ms_ssim(xt, yt, scales=scales)
+    (got * wts).sum().backward()
+    assert got.shape == (3,) and got.dtype == torch.float64
+    assert float((got - ref).detach().abs().max()) <= 1e-12
+    assert float((xt.grad - xr.grad).abs().max()) <= 1e-12
+    assert float((yt.grad - yr.grad).abs().max()) <= 1e-12
+    assert float(xr.grad.abs().max()) > 1e-6 and float(yr.grad.abs().max()) > 1e-6
+
+
+def test_size_and_scale_errors():
+    # Every scale must hold the 11x11 window, and a scale is ceil(previous / 2) (the SYMMETRIC pad):
+    # 21x40 gives 11x20 at scale 1, which tf.image.ssim_multiscale and the oracle accept, so K=2 is
+    # the legal edge there (checked against the reference below) and the first refusals around it
+    # are 20x40 with K=2 (scale 1 is 10x20) and 21x40 with K=3 (scale 2 is 6x10).
+    assert T.ms_ssim_sizes(21, 40, 2) == [(21, 40), (11, 20)]
+    x, y = R.planes(2, 21, 40, seed=1)
+    assert float((T.ms_ssim(x, y, scales=2) - R.ms_ssim(x, y, 2)).abs().max()) <= 1e-12
+    with pytest.raises(ValueError, match="10x20"):  # names the offending scale's size
+        T.ms_ssim(*R.planes(1, 20, 40, seed=1), scales=2)
+    with pytest.raises(ValueError, match="6x10"):
+        T.ms_ssim(x, y, scales=3)
+    with pytest.raises(ValueError, match="10x40"):
+        T.ms_ssim(*R.planes(1, 10, 40, seed=1), scales=1)
+    big = R.planes(1, 40, 21, seed=1)
+    for bad in (0, 6):
+        with pytest.raises(ValueError, match="scales"):
+            T.ms_ssim(*big, scales=bad)
+    with pytest.raises(ValueError, match="distortion"):
+        T.Training(device="cpu", backend="torch", distortion="bad")
+    with pytest.raises(ValueError, match="ms_scales"):
+        T.Training(device="cpu", backend="torch", distortion="ms_ssim", ms_scales=6)
+
+
+def test_negative_term_gives_zero_with_a_finite_gradient():
+    # y = 1 - x on a textured plane: the covariance is negative, so scale 0's mean cs is < 0
+    g = torch.Generator().manual_seed(7)
+    x = (0.5 + 0.4 * (torch.rand((2, 1, 24, 26), generator=g, dtype=torch.float64) - 0.5))
+    y = 1.0 - x
+    assert float(R.used_terms(x, y, 2)[:, 0].max()) < 0  # the precondition, on the reference
+    for fn in (lambda a, b: R.ms_ssim(a, b, 2), lambda a, b: T.ms_ssim(a, b, scales=2)):
+        xa, ya = x.clone().requires_grad_(), y.clone().requires_grad_()
+        v = fn(xa, ya)
+        v.sum().backward()
+        assert torch.equal(v, torch.zeros_like(v))
+        assert bool(torch.isfinite(xa.grad).all()) and bool(torch.isfinite(ya.grad).all())
+    # fp32 too (the training dtype)
+    xa, ya = x.float().requires_grad_(), y.float().requires_grad_()
+    v = T.ms_ssim(xa, ya, scales=2)
+    v.sum().backward()
+    assert torch.equal(v, torch.zeros_like(v)) and bool(torch.isfinite(ya.grad).all())
+
+
+def _smooth(n, h, w, seed):  # as tests/test_training.py
+    rng = np.random.default_rng(seed)
+    a = np.cumsum(np.cumsum(rng.integers(-2, 3, (n, h, w, 3)), axis=1), axis=2).astype(np.float64)
+    a -= a.min(axis=(1, 2, 3), keepdims=True)
+    a *= 255.0 / np.maximum(a.max(axis=(1, 2, 3), keepdims=True), 1)
+    return a.astype(np.uint8)
+
+
+def test_training_on_the_cpu_uses_ms_ssim(monkeypatch, tmp_path):
+    # the PNG target runs as in tests/test_training.py (the native host encoder, nothing stubbed)
+    tr = T.Training(device="cpu", backend="torch", seed=0, checkpoint_dir=str(tmp_path) + "/",
+                    distortion="ms_ssim", ms_scales=2)
+    seen = []
+    real = T.ms_ssim
+
+    def spy(x, y, scales=4, max_val=1.0, hip=False):
+        seen.append((x.detach().clone(), y.detach().clone(), scales, hip))
+        return real(x, y, scales, max_val, hip)
+
+    monkeypatch.setattr(T, "ms_ssim", spy)
+    f = tr.losses(torch.from_numpy(_smooth(4, 32, 32, 5)), 0.01, flip=False)
+    for k in ("loss0", "loss1", "ssim0", "entropy_loss"):
+        assert bool(torch.isfinite(f[k]).all()), k
+    assert f["ssim1_each"].shape == (8,) and bool(torch.isfinite(f["ssim1_each"]).all())
+    assert [(s[2], s[3]) for s in seen] == [(2, False), (2, False)]
+    p0, dec0 = seen[0][0], seen[0][1]
+    assert p0.shape == (4, 1, 32, 32)
+    want = R.ms_ssim(p0.double(), dec0.double(), 2).mean()
+    # fp32 against float64: a pixel's cs loses at most ~4 eps32 max(sxx) / c2 = 4 * 6e-8 / 9e-4 < 3e-4
+    # of itself to the sums' rounding; a relative error d of a term moves t^w by w d t^w <= d
+    assert abs(float(f["ssim0"].detach()) - float(want)) <= 3e-4
+    m = tr.train_step(torch.from_numpy(_smooth(4, 32, 32, 6)), 0.01)
+    assert set(m) == {"ssim", "bpp", "entropy_loss", "loss"}
+    assert all(np.isfinite(m["ssim"])) and all(np.isfinite(m["loss"]))

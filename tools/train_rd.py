@@ -51,6 +51,9 @@ def main():
     ap.add_argument("--seeds", default="0", help="weight-init / shuffling seeds per coefficient (label suffix _sN for N > 0)")
     ap.add_argument("--png-mode", default="tf", choices=("tf", "pillow"),
                     help="the PNG encoder of the entropy net's target (get_bpp: tf.image.encode_png settings)")
+    ap.add_argument("--distortion", default="ssim", choices=("ssim", "ms_ssim"),
+                    help="the codec losses' distortion term (ssim: the reference's; ms_ssim: tf.image.ssim_multiscale)")
+    ap.add_argument("--ms-scales", type=int, default=4, help="scales of --distortion ms_ssim (128 px patches: <= 4)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     x = load_patches(args.data)
@@ -64,7 +67,8 @@ def main():
     for coef, seed in runs:
         t0 = time.perf_counter()
         with tempfile.TemporaryDirectory() as d:
-            tr = T.Training(device="cuda", weights=W.seeded_weights(seed, init="glorot"), seed=seed, checkpoint_dir=d + "/")
+            tr = T.Training(device="cuda", weights=W.seeded_weights(seed, init="glorot"), seed=seed, checkpoint_dir=d + "/",
+                            distortion=args.distortion, ms_scales=args.ms_scales)
             tr.png_mode = args.png_mode
             epochs = args.epochs
             if args.steps:
@@ -85,7 +89,8 @@ def main():
             for kind in ("encoder", "decoder"):  # <dir>/<label>_encoderY.safetensors, ...
                 W.save(w, os.path.join(args.save_dir, f"{label}_{kind}"), kind)
         tail = log[-20:]
-        train_log[label] = {"steps": len(log), "epochs": epochs, "seed": seed, "png_mode": args.png_mode, "seconds": round(time.perf_counter() - t0, 1),
+        train_log[label] = {"steps": len(log), "epochs": epochs, "seed": seed, "png_mode": args.png_mode, "distortion": args.distortion,
+                            "ms_scales": args.ms_scales if args.distortion == "ms_ssim" else None, "seconds": round(time.perf_counter() - t0, 1),
                             "train_seconds": round(t_train, 1),
                             "first": {k: log[0][k] for k in ("ssim", "bpp", "entropy_loss")},
                             "last20_mean": {k: [float(np.mean([m[k][j] for m in tail])) for j in range(3)]
