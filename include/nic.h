@@ -636,19 +636,17 @@ int nic_png_device_read(nic_ctx* ctx, const uint8_t* streams, int64_t stride, co
  * nic_gauss_1d: one-channel planes (n,h,w): VALID correlation with ntaps taps along x
  *     (vertical 0) or y, or its adjoint (the input gradient); the SSIM loss's separable
  *     Gaussian (tf.image.ssim, training.py:119-121).
- * nic_ssim_map: the SSIM loss's map from its Gaussian-filtered terms (tf.image.ssim,
- *     training.py:119-121): per pixel of n planes of hw pixels, from mx = G*x, my = G*y,
- *     sxy = G*(x y), sxx = G*(x^2 + y^2): num0 = (mx my) 2, den0 = mx mx + my my,
- *     lum = (num0 + c1)/(den0 + c1), cs = ((2 sxy - num0) + c2)/((sxx - den0) + c2); ssim_mean[i] =
- *     mean of lum cs over plane i (deterministic; work >= nic_ssim_map_work() floats).
- * nic_ssim_map_grad: the gradients of sum_i g[i] ssim_mean[i] with respect to mx, my, sxy, sxx.
- * The MS-SSIM loss (tf.image.ssim_multiscale on one-channel fp32 planes; scale k is the 2x2 mean
- * pool of scale k-1, an odd height or width SYMMETRIC-padded by one on the far side first):
- * nic_msssim_terms: as nic_ssim_map, both means of one scale in one pass: ssim_mean[i] = mean of
- *     lum cs, cs_mean[i] = mean of cs over plane i (deterministic: per-block partial sums, added
- *     in block order; work >= nic_msssim_terms_work() floats).
+ * The SSIM loss (tf.image.ssim, training.py:119-121) and the MS-SSIM loss (tf.image.ssim_multiscale
+ * on one-channel fp32 planes; scale k is the 2x2 mean pool of scale k-1, an odd height or width
+ * SYMMETRIC-padded by one on the far side first; the SSIM loss is scale 0 alone):
+ * nic_msssim_terms: both means of one scale from its Gaussian-filtered terms in one pass: per pixel
+ *     of n planes of hw pixels, from mx = G*x, my = G*y, sxy = G*(x y), sxx = G*(x^2 + y^2):
+ *     num0 = (mx my) 2, den0 = mx mx + my my, lum = (num0 + c1)/(den0 + c1),
+ *     cs = ((2 sxy - num0) + c2)/((sxx - den0) + c2), every op an fp32 rounding; ssim_mean[i] = mean
+ *     of lum cs (tf.image.ssim's value), cs_mean[i] = mean of cs over plane i (deterministic:
+ *     per-block partial sums, added in block order; work >= nic_msssim_terms_work() floats).
  * nic_msssim_terms_grad: the gradients of sum_i g_ssim[i] ssim_mean[i] + g_cs[i] cs_mean[i] with
- *     respect to mx, my, sxy, sxx.
+ *     respect to mx, my, sxy, sxx; g_ssim and g_cs each hold n floats (zeros for a mean not used).
  * nic_pool2_prep: the step to the next scale of planes x, y (n,h,w), oh = ceil(h/2), ow = ceil(w/2):
  *     xp = 0.25 ((x[2i][2j] + x[2i][2j+1]) + (x[2i+1][2j] + x[2i+1][2j+1])), each op rounded, row h
  *     / column w of an odd size reading row h-1 / column w-1; yp likewise; and the planes the
@@ -684,11 +682,6 @@ int nic_conv_wgrad(const float* gat, int n, int gh, int gw, int ca, const float*
 int nic_absmax_scale(const float* x, int64_t count, float* scale, float* work, void* stream);
 int nic_gauss_1d(const float* in, int n, int h_in, int w_in, const float* taps, int ntaps, int vertical, int adjoint,
                  float* out, int h_out, int w_out, void* stream);
-int nic_ssim_map_work(int n, int64_t hw, int64_t* floats);
-int nic_ssim_map(const float* mx, const float* my, const float* sxy, const float* sxx, int n, int64_t hw, float c1,
-                 float c2, float* ssim_mean, float* work, int64_t work_floats, void* stream);
-int nic_ssim_map_grad(const float* mx, const float* my, const float* sxy, const float* sxx, const float* g, int n,
-                      int64_t hw, float c1, float c2, float* gmx, float* gmy, float* gsxy, float* gsxx, void* stream);
 #define NIC_POOL2_PREP 0
 #define NIC_POOL2_PRODUCTS 1
 #define NIC_POOL2_POOL 2

@@ -464,7 +464,7 @@ bool models_ready(const nic_ctx* c, int m0) {
 
 extern "C" {
 
-int nic_version(void) { return 1100; }
+int nic_version(void) { return 1200; }
 
 int nic_constants(float* ycbcr9, float* ycbcr_inv9, float* off3) {
   // host copy of what nic_create uploads; lets tests compare with np.linalg.inv (utils.py:8)
@@ -1874,35 +1874,6 @@ int nic_gauss_1d(const float* in, int n, int h_in, int w_in, const float* taps, 
   if (!in || !taps || !out) return fail(NIC_EINVAL, "nic_gauss_1d: NULL argument");
   HIP_TRY(launch_gauss1d(in, n, h_in, w_in, taps, ntaps, vertical ? 1 : 0, adjoint ? 1 : 0, out, h_out, w_out,
                          (hipStream_t)stream));
-  return NIC_OK;
-}
-
-int nic_ssim_map_work(int n, int64_t hw, int64_t* floats) {
-  if (!floats) return fail(NIC_EINVAL, "nic_ssim_map_work: NULL argument");
-  if (n < 0 || hw <= 0) return fail(NIC_ESHAPE, "nic_ssim_map_work: bad shape");
-  *floats = (int64_t)train_ssim_work_floats(n, hw);
-  return NIC_OK;
-}
-
-int nic_ssim_map(const float* mx, const float* my, const float* sxy, const float* sxx, int n, int64_t hw, float c1,
-                 float c2, float* ssim_mean, float* work, int64_t work_floats, void* stream) {
-  if (n < 0 || hw <= 0 || (int64_t)n * hw > ((int64_t)1 << 40)) return fail(NIC_ESHAPE, "nic_ssim_map: bad shape");
-  if (n == 0) return NIC_OK;
-  if (!mx || !my || !sxy || !sxx || !ssim_mean || !work) return fail(NIC_EINVAL, "nic_ssim_map: NULL argument");
-  if (work_floats < (int64_t)train_ssim_work_floats(n, hw))
-    return fail(NIC_EINVAL, "nic_ssim_map: work holds %lld floats, needs %lld", (long long)work_floats,
-                (long long)train_ssim_work_floats(n, hw));
-  HIP_TRY(launch_ssim_map(mx, my, sxy, sxx, n, hw, c1, c2, ssim_mean, work, (hipStream_t)stream));
-  return NIC_OK;
-}
-
-int nic_ssim_map_grad(const float* mx, const float* my, const float* sxy, const float* sxx, const float* g, int n,
-                      int64_t hw, float c1, float c2, float* gmx, float* gmy, float* gsxy, float* gsxx, void* stream) {
-  if (n < 0 || hw <= 0 || (int64_t)n * hw > ((int64_t)1 << 40)) return fail(NIC_ESHAPE, "nic_ssim_map_grad: bad shape");
-  if (n == 0) return NIC_OK;
-  if (!mx || !my || !sxy || !sxx || !g || !gmx || !gmy || !gsxy || !gsxx)
-    return fail(NIC_EINVAL, "nic_ssim_map_grad: NULL argument");
-  HIP_TRY(launch_ssim_map_grad(mx, my, sxy, sxx, g, n, hw, c1, c2, gmx, gmy, gsxy, gsxx, (hipStream_t)stream));
   return NIC_OK;
 }
 

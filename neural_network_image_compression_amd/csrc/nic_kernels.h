@@ -315,13 +315,7 @@ hipError_t launch_conv_wgrad(const float* gat, int n, int gh, int gw, int ca, co
 // tf.keras Adam over `count` tensors (table: {var, m, v, grad, n} int64 records on the device)
 hipError_t launch_adam_keras(const long long* table, int count, long long max_n, float alpha, float beta1,
                              float beta2, float eps, hipStream_t st);
-size_t train_ssim_work_floats(int n, long long hw);
-hipError_t launch_ssim_map(const float* mx, const float* my, const float* sxy, const float* sxx, int n, long long hw,
-                           float c1, float c2, float* out, float* work, hipStream_t st);
-hipError_t launch_ssim_map_grad(const float* mx, const float* my, const float* sxy, const float* sxx, const float* g,
-                                int n, long long hw, float c1, float c2, float* gmx, float* gmy, float* gsxy,
-                                float* gsxx, hipStream_t st);
-// MS-SSIM loss: one scale's plane means of lum cs and of cs (and their backward), and the
+// SSIM and MS-SSIM losses: one scale's plane means of lum cs and of cs (and their backward), and the
 // step between scales (2x2 mean pool of SYMMETRIC-padded planes + the Gaussian's product planes)
 size_t train_msssim_work_floats(int n, long long hw);
 hipError_t launch_msssim_terms(const float* mx, const float* my, const float* sxy, const float* sxx, int n,

@@ -13,21 +13,23 @@ Conv2DTranspose dx     gather, src = s*o + k - pad, same kernel (layout 0)
 Conv2DTranspose dW     wgrad(gat = dy, dir = x) -> HWOI
 =====================  ==========================================================
 
-The SSIM loss's separable Gaussian (one-channel VALID correlation) runs on a 1-D HIP
-kernel and its adjoint (``gauss_valid``, ``nic_gauss_1d``).  The MS-SSIM loss (``ms_ssim_mean``)
-adds the step between scales with the Gaussian's product planes (``nic_pool2_prep`` and its
-adjoint) and both per-plane means of a scale in one pass (``nic_msssim_terms`` and its backward).
+The SSIM loss (``ssim_mean``) and the MS-SSIM loss (``ms_ssim_mean``) share one per-scale step
+(``ssim_scale``): the Gaussian's product planes, pooled between scales (``nic_pool2_prep`` and its
+adjoint), the separable Gaussian over the four stacked planes (a 1-D one-channel VALID
+correlation and its adjoint, ``nic_gauss_1d``) and both per-plane means of the scale in one pass
+(``nic_msssim_terms`` and its backward).  The SSIM loss is that step once, on scale 0.
 
 Each operand gets a power-of-two scale (max |t| * scale in [2^13, 2^14)) computed on the
 device once per tensor (x and the kernel in the forward, dy in the backward), so the f16 hi/lo split keeps tiny gradients exact to ~2^-22.  The layers' leaky-ReLU runs in
 the gather's epilogue (``nic_conv_gather_act``), and its gradient with the bias gradient in
 one deterministic pass (``nic_act_bias_grad``: dz = dy * leaky'(y), db = column sums of dz).
-The clip, residual-add, noise and SSIM elementwise parts and the Entropynet's two dense layers
+The clip, residual-add and noise elementwise parts and the Entropynet's two dense layers
 (plain library GEMMs) stay on torch.  There is no fallback: without the built library these
 raise.
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import Tuple
 
 from . import _lib
@@ -340,39 +342,6 @@ def _conv_fn():
             (taps,) = ctx.saved_tensors
             return gauss_1d(dy.contiguous(), taps, ctx.vertical, 1), None, None
 
-    class SsimMap(torch.autograd.Function):
-        """Per-plane mean of tf.image.ssim's map from its filtered terms (nic_ssim_map /
-        nic_ssim_map_grad): mx, my, sxy = G*(x y), sxx = G*(x^2 + y^2), each (N, ...) planes."""
-
-        @staticmethod
-        def forward(ctx, mx, my, sxy, sxx, c1, c2):
-            ts = [_check(t, "SsimMap term") for t in (mx, my, sxy, sxx)]
-            dev = _same_device(*ts)
-            n = ts[0].shape[0]
-            hw = ts[0].numel() // max(n, 1)
-            out = torch.empty((n,), dtype=torch.float32, device=ts[0].device)
-            need = n * (-(-hw // SSIM_PIX))  # nic_ssim_map_work (checked by the call)
-            work = torch.empty(max(need, 1), dtype=torch.float32, device=ts[0].device)
-            with torch.cuda.device(dev):
-                _lib.check(_lib.lib().nic_ssim_map(*(t.data_ptr() for t in ts), n, hw, c1, c2, out.data_ptr(),
-                                                   work.data_ptr(), need, _stream(dev)), "nic_ssim_map")
-            ctx.save_for_backward(*ts)
-            ctx.consts = (c1, c2, n, hw)
-            return out
-
-        @staticmethod
-        def backward(ctx, g):
-            ts = ctx.saved_tensors
-            c1, c2, n, hw = ctx.consts
-            g = g.contiguous()
-            grads = [torch.empty_like(t) for t in ts]
-            dev = ts[0].device
-            with torch.cuda.device(dev):
-                _lib.check(_lib.lib().nic_ssim_map_grad(*(t.data_ptr() for t in ts), g.data_ptr(), n, hw, c1, c2,
-                                                        *(t.data_ptr() for t in grads), _stream(dev)),
-                           "nic_ssim_map_grad")
-            return (*grads, None, None)
-
     class Pool2Prep(torch.autograd.Function):
         """The MS-SSIM loss's step between scales (nic_pool2_prep / nic_pool2_prep_grad) on planes
         (n, h, w); outputs as :func:`pool2_prep` for the mode."""
@@ -427,9 +396,11 @@ def _conv_fn():
                               *ctx.consts, out=out)
             return out, None, None
 
-    return Conv2DSame, Conv2DTransposeSame, Gauss1D, SsimMap, Pool2Prep, MsssimTerms
+    return _Fns(Conv2DSame, Conv2DTransposeSame, Gauss1D, Pool2Prep, MsssimTerms)
 
 
+# the autograd classes, looked up by name (callers that still index find the two convolutions first)
+_Fns = namedtuple("_Fns", "Conv2DSame Conv2DTransposeSame Gauss1D Pool2Prep MsssimTerms")
 _FNS = None
 
 
@@ -442,20 +413,15 @@ def _fns():
 
 def conv_same(x, kernel_hwio, bias, stride: int, act: bool = True):
     """Keras Conv2D(padding='SAME') + leaky_relu(0.2) on NHWC (HIP, activation in the epilogue)."""
-    return _fns()[0].apply(x, kernel_hwio, bias, stride, bool(act))
+    return _fns().Conv2DSame.apply(x, kernel_hwio, bias, stride, bool(act))
 
 
 def tconv_same(x, kernel_hwoi, bias, stride: int):
     """Keras Conv2DTranspose(padding='SAME') + leaky_relu(0.2) on NHWC (HIP, activation in the epilogue)."""
-    return _fns()[1].apply(x, kernel_hwoi, bias, stride, True)
+    return _fns().Conv2DTransposeSame.apply(x, kernel_hwoi, bias, stride, True)
 
 
-SSIM_PIX = 1024  # map pixels per block of nic_ssim_map (its work: one partial sum per block)
-
-
-def ssim_map_mean(mx, my, sxy, sxx, c1: float, c2: float):
-    """(N,) per-plane mean of tf.image.ssim's map from its filtered terms (HIP, differentiable)."""
-    return _fns()[3].apply(mx, my, sxy, sxx, float(c1), float(c2))
+SSIM_PIX = 1024  # map pixels per block of nic_msssim_terms (its work: two partial sums per block)
 
 
 def gauss_valid(t, g1d):
@@ -465,47 +431,74 @@ def gauss_valid(t, g1d):
     if c != 1:
         raise ValueError("gauss_valid: one-channel planes")
     g1d = g1d.contiguous()
-    x = _fns()[2].apply(t.reshape(n, h, w), g1d, 0)
-    x = _fns()[2].apply(x, g1d, 1)
+    x = _fns().Gauss1D.apply(t.reshape(n, h, w), g1d, 0)
+    x = _fns().Gauss1D.apply(x, g1d, 1)
     return x.reshape(n, 1, x.shape[1], x.shape[2])
 
 
 def pool2_prep_fn(x, y, mode: int = POOL2_PREP):
     """:func:`pool2_prep`, differentiable."""
-    return _fns()[4].apply(x, y, mode)
+    return _fns().Pool2Prep.apply(x, y, mode)
 
 
 def msssim_terms_mean(mx, my, sxy, sxx, c1: float, c2: float):
     """(N,) plane means of lum cs and of cs from one scale's filtered terms (HIP, differentiable)."""
-    return _fns()[5].apply(_torch().stack([mx, my, sxy, sxx]), float(c1), float(c2))
+    return _fns().MsssimTerms.apply(_torch().stack([mx, my, sxy, sxx]), float(c1), float(c2))
+
+
+def ssim_map_mean(mx, my, sxy, sxx, c1: float, c2: float):
+    """(N,) per-plane mean of tf.image.ssim's map from its filtered terms (HIP, differentiable)."""
+    return msssim_terms_mean(mx, my, sxy, sxx, c1, c2)[0]
+
+
+def ssim_scale(xs, ys, g, c1: float, c2: float, mode: int):
+    """One scale of the SSIM / MS-SSIM loss on planes (n, h, w), differentiable: one nic_pool2_prep
+    (POOL2_PRODUCTS: the product planes of xs, ys themselves, scale 0; POOL2_PREP: pooled first),
+    one Gaussian over the four stacked planes (nic_gauss_1d, twice) and nic_msssim_terms.  Returns
+    (xs', ys', f, lcs, cs): this scale's planes, their filtered terms (mx, my, sxy, sxx) stacked
+    (4, n, h' - 10, w' - 10), and the (n,) plane means of lum cs and of cs."""
+    if mode == POOL2_PRODUCTS:
+        p, q = pool2_prep_fn(xs, ys, mode)
+    else:
+        xs, ys, p, q = pool2_prep_fn(xs, ys, mode)
+    f = _torch().cat([xs, ys, p, q], dim=0)  # one Gaussian over the four planes
+    f = _fns().Gauss1D.apply(_fns().Gauss1D.apply(f, g, 0), g, 1)
+    f = f.view(4, xs.shape[0], f.shape[1], f.shape[2])
+    lcs, cs = _fns().MsssimTerms.apply(f, c1, c2)
+    return xs, ys, f, lcs, cs
+
+
+def _ssim_planes(who, x, y, max_val):
+    torch = _torch()
+    from .training import _gauss_window
+
+    n, c, h, w = x.shape
+    if c != 1 or y.shape != x.shape:
+        raise ValueError(f"{who}: two one-channel planes (N,1,H,W) of one shape")
+    g = _gauss_window(torch, x.device, torch.float32)
+    return x.reshape(n, h, w), y.reshape(n, h, w), g, (0.01 * max_val) ** 2, (0.03 * max_val) ** 2
+
+
+def ssim_mean(x, y, max_val: float = 1.0):
+    """tf.image.ssim(x, y, max_val) of one-channel NCHW planes (N,1,H,W) -> (N,), differentiable, on
+    HIP: :func:`ssim_scale` once, on the planes themselves; the plane mean of lum cs."""
+    xs, ys, g, c1, c2 = _ssim_planes("ssim_mean", x, y, max_val)
+    return ssim_scale(xs, ys, g, c1, c2, POOL2_PRODUCTS)[3]
 
 
 def ms_ssim_mean(x, y, scales: int, max_val: float = 1.0):
     """tf.image.ssim_multiscale(x, y, max_val, power_factors=MSSSIM_WEIGHTS[:scales]) of one-channel
-    NCHW planes (N,1,H,W) -> (N,), differentiable, on HIP: per scale one nic_pool2_prep (pool and
-    the two product planes), one Gaussian over the four stacked planes (nic_gauss_1d, twice) and
-    nic_msssim_terms; the N x scales combination stays on torch."""
-    from .training import _gauss_window, ms_ssim_combine, ms_ssim_sizes
+    NCHW planes (N,1,H,W) -> (N,), differentiable, on HIP: :func:`ssim_scale` per scale; the
+    N x scales combination stays on torch."""
+    from .training import ms_ssim_combine, ms_ssim_sizes
 
-    torch = _torch()
-    n, c, h, w = x.shape
-    if c != 1 or y.shape != x.shape:
-        raise ValueError("ms_ssim_mean: two one-channel planes (N,1,H,W) of one shape")
-    ms_ssim_sizes(h, w, scales)
-    c1, c2 = (0.01 * max_val) ** 2, (0.03 * max_val) ** 2
-    g = _gauss_window(torch, x.device, torch.float32)
-    xs, ys = x.reshape(n, h, w), y.reshape(n, h, w)
+    xs, ys, g, c1, c2 = _ssim_planes("ms_ssim_mean", x, y, max_val)
+    ms_ssim_sizes(xs.shape[1], xs.shape[2], scales)
     terms = []
     for k in range(scales):
-        if k == 0:
-            p, q = pool2_prep_fn(xs, ys, POOL2_PRODUCTS)
-        else:
-            xs, ys, p, q = pool2_prep_fn(xs, ys, POOL2_PREP)
-        f = torch.cat([xs, ys, p, q], dim=0)  # one Gaussian over the four planes
-        f = _fns()[2].apply(_fns()[2].apply(f, g, 0), g, 1)
-        lcs, cs = _fns()[5].apply(f.view(4, n, f.shape[1], f.shape[2]), c1, c2)
+        xs, ys, _, lcs, cs = ssim_scale(xs, ys, g, c1, c2, POOL2_PREP if k else POOL2_PRODUCTS)
         terms.append(lcs if k == scales - 1 else cs)
-    return ms_ssim_combine(torch.stack(terms, dim=1), scales)
+    return ms_ssim_combine(_torch().stack(terms, dim=1), scales)
 
 
 def keras_adam_alpha(step: int, lr: float = 1e-4, beta1: float = 0.9, beta2: float = 0.999) -> float:

@@ -243,6 +243,27 @@ def test_ms_ssim_mean_refuses_small_scales():
         train_hip.ms_ssim_mean(x, x, 6)
 
 
+def test_single_scale_ssim_is_the_shared_scale_step():
+    # training.ssim(hip=True) is train_hip.ssim_scale once in POOL2_PRODUCTS mode, not a second
+    # route: value and input gradients equal, bit for bit, what the raw terms calls give on the
+    # four filtered planes that step produces.  (3, 1, 22, 23): the smallest planes that hold the
+    # window with a block tail (12 x 13 = 156 of 1,024 pixels) and an odd width.
+    x, y, _, _ = _pool_planes(3, (22, 23))
+    wts = torch.tensor([1.0, -0.5, 2.0]).cuda()
+    xd, yd = x.cuda()[:, None].requires_grad_(), y.cuda()[:, None].requires_grad_()
+    s = T.ssim(xd, yd, hip=True)
+    (s * wts).sum().backward()
+    xs, ys = x.cuda().requires_grad_(), y.cuda().requires_grad_()
+    g = T._gauss_window(torch, xs.device, torch.float32)
+    _, _, f, lcs, _ = train_hip.ssim_scale(xs, ys, g, C1, C2, train_hip.POOL2_PRODUCTS)
+    assert tuple(f.shape) == (4, 3, 12, 13)
+    terms = f.detach().unbind(0)
+    assert torch.equal(s.detach(), train_hip.msssim_terms(*terms, C1, C2)[0])
+    assert torch.equal(s.detach(), lcs.detach())
+    f.backward(torch.stack(train_hip.msssim_terms_grad(*terms, wts, torch.zeros_like(wts), C1, C2)))
+    assert torch.equal(xd.grad[:, 0], xs.grad) and torch.equal(yd.grad[:, 0], ys.grad)
+
+
 # ---- Training ------------------------------------------------------------------------------------------
 def _imgs(n, hw, seed):
     g = torch.Generator().manual_seed(seed)

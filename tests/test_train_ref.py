@@ -143,8 +143,8 @@ def test_work_sizes_match_the_formulas_at_every_case():
             assert v.value == R.act_bias_grad_work_floats(rows, cols), (rows, cols)
     for n in R.SSIM_N:
         for h, w in R.SSIM_HW:
-            assert L.nic_ssim_map_work(n, h * w, ctypes.byref(v)) == _lib.NIC_OK
-            assert v.value == R.ssim_map_work_floats(n, h * w), (n, h * w)
+            assert L.nic_msssim_terms_work(n, h * w, ctypes.byref(v)) == _lib.NIC_OK
+            assert v.value == 2 * R.ssim_map_work_floats(n, h * w), (n, h * w)
 
 
 def test_gauss_reference_equals_float64_torch_and_its_adjoint():

@@ -115,7 +115,7 @@ def gauss_window(size=11, sigma=1.5):
     return g / g.sum()
 
 
-# ---- nic_ssim_map / nic_ssim_map_grad ----------------------------------------------------------
+# ---- the lum cs mean of nic_msssim_terms / nic_msssim_terms_grad (train_hip.ssim_map_mean) -----
 def _ssim_terms(mx, my, sxy, sxx, c1, c2):
     mx, my, sxy, sxx = (np.asarray(t, dtype=np.float64) for t in (mx, my, sxy, sxx))
     num0 = mx * my * 2.0
@@ -206,7 +206,7 @@ def act_bias_grad_work_floats(rows, cols):
 
 
 def ssim_map_work_floats(n, hw):
-    """n x ceil(hw / 1024)."""
+    """n x ceil(hw / 1024): the blocks of nic_msssim_terms, whose work holds two partials for each."""
     return n * _cdiv(hw, 1024)
 
 

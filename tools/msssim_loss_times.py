@@ -3,7 +3,9 @@ one process, at the training shape: 64 planes of 128 x 128, K = 4 scales.
 
   loss         forward plus backward (gradient to the decoded plane) of the loss alone:
                train_hip.ms_ssim_mean against the baseline, the fp32 PyTorch restatement
-               training.ms_ssim(hip=False) -- backend="torch"'s loss -- on the same tensors
+               training.ms_ssim(hip=False) -- backend="torch"'s loss -- on the same tensors; and
+               loss_ssim_hip, the single-scale training.ssim(hip=True) alone on those tensors (the
+               default loss, which train_step_ssim's total hides)
   train_step   Training.train_step on a batch of 64 patches (192 planes through the codec, the
                loss on 64 Y and 128 CbCr planes), backend "hip", with distortion "ms_ssim"
                (HIP loss), with distortion "ms_ssim" and the loss on the PyTorch restatement, and
@@ -76,6 +78,11 @@ def main():
             return v, gy
         return run
 
+    def loss_ssim_hip():
+        y = y0.detach().requires_grad_()
+        v = T.ssim(x, y, hip=True)
+        return v, torch.autograd.grad(((1 - v.mean()) / 2), y)[0]
+
     v_h, g_h = loss_fn(True)()
     v_t, g_t = loss_fn(False)()
     dv = float((v_h - v_t).detach().abs().max() / v_t.detach().abs().max())
@@ -102,7 +109,7 @@ def main():
                 T.ms_ssim = real
         return run
 
-    forms = {"loss_hip": loss_fn(True), "loss_torch_fp32": loss_fn(False),
+    forms = {"loss_hip": loss_fn(True), "loss_ssim_hip": loss_ssim_hip, "loss_torch_fp32": loss_fn(False),
              "train_step_ms_ssim_hip_loss": step_fn("ms_ssim", True),
              "train_step_ms_ssim_torch_loss": step_fn("ms_ssim", False),
              "train_step_ssim": step_fn("ssim", True)}
