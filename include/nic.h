@@ -658,6 +658,22 @@ int nic_png_device_read(nic_ctx* ctx, const uint8_t* streams, int64_t stride, co
  *     outputs (each nullable: zero) and the saved xp, yp (needed with dp or dq); the repeated row
  *     and column of an odd size fold back onto the last real one; every element of dx, dy is
  *     written once, no atomics.  Same modes (NIC_POOL2_POOL ignores dp, dq).
+ * The table rate loss (no counterpart in the reference's trainer): the code length of a latent under
+ * a learnable per-channel table, the quantity .nic version 2 prices.  L is (groups * channels, 256)
+ * fp32, L[r][j] = -log2 p_r(j); y is (m, h, w, channels) NHWC fp32, m % groups == 0; plane i belongs
+ * to group i / (m / groups) and its channel c reads row r = group * channels + c.  Per element, every
+ * op one fp32 rounding:
+ *     v = fminf(fmaxf(255 y, 0), 255) (a NaN becomes 0; no index leaves the row),
+ *     k = min((int)floorf(v), 254), t = v - k, bits = L[r][k] + t (L[r][k+1] - L[r][k]).
+ * nic_rate_table: plane_bits[i] = sum of bits over plane i's h w channels elements (deterministic:
+ *     per-block partial sums of 1,024 elements, added in block order).
+ * nic_rate_table_grad: for an upstream g[i] per plane, dy = (255 g[i]) (L[r][k+1] - L[r][k]), every
+ *     element written once, and dL[r][j] = sum over row r's elements of g (1 - t) at j = k plus g t at
+ *     j = k + 1 (deterministic, no atomics: per-block tables built by one owner per word in pixel
+ *     order, added in block order).  dy and dL are each nullable, not both; m = 0 zeroes dL.
+ * Both take `work` of nic_rate_table_work() floats: max(m ceil(h w channels / 1024),
+ *     groups ceil((m / groups) h w / 128) channels 256); nic_rate_table_grad reads it only with dL.
+ *     channels <= 64; m h w channels and groups channels 256 must fit an int.
  * nic_adam_keras: the step's optimiser update (training.py:147-149, tf.keras Adam = TF's
  *     ResourceApplyAdam) over `count` tensors in one launch; table = device int64 records
  *     {var, m, v, grad, n} (pointers to fp32 device buffers, n elements), max_n their largest n:
@@ -695,6 +711,11 @@ int nic_pool2_prep(const float* x, const float* y, int n, int h, int w, int mode
                    float* pss, void* stream);
 int nic_pool2_prep_grad(const float* dxp, const float* dyp, const float* dp, const float* dq, const float* xp,
                         const float* yp, int n, int h, int w, int mode, float* dx, float* dy, void* stream);
+int nic_rate_table_work(int m, int h, int w, int channels, int groups, int64_t* floats);
+int nic_rate_table(const float* y, const float* L, int m, int h, int w, int channels, int groups, float* plane_bits,
+                   float* work, int64_t work_floats, void* stream);
+int nic_rate_table_grad(const float* y, const float* L, const float* g, int m, int h, int w, int channels, int groups,
+                        float* dy, float* dL, float* work, int64_t work_floats, void* stream);
 int nic_adam_keras(const int64_t* table, int count, int64_t max_n, float alpha, float beta1, float beta2,
                    float epsilon, void* stream);
 

@@ -464,7 +464,7 @@ bool models_ready(const nic_ctx* c, int m0) {
 
 extern "C" {
 
-int nic_version(void) { return 1200; }
+int nic_version(void) { return 1300; }
 
 int nic_constants(float* ycbcr9, float* ycbcr_inv9, float* off3) {
   // host copy of what nic_create uploads; lets tests compare with np.linalg.inv (utils.py:8)
@@ -1907,6 +1907,51 @@ int nic_msssim_terms_grad(const float* mx, const float* my, const float* sxy, co
     return fail(NIC_EINVAL, "nic_msssim_terms_grad: NULL argument");
   HIP_TRY(launch_msssim_terms_grad(mx, my, sxy, sxx, g_ssim, g_cs, n, hw, c1, c2, gmx, gmy, gsxy, gsxx,
                                    (hipStream_t)stream));
+  return NIC_OK;
+}
+
+// the table rate loss: m * h * w * channels elements and the groups * channels * 256 table must fit an int
+static int rate_table_shape(const char* who, int m, int h, int w, int channels, int groups) {
+  if (m < 0 || h <= 0 || w <= 0 || !train_dims_ok(channels) || groups < 1 || m % groups != 0 ||
+      (int64_t)m * h * w * channels > INT32_MAX || (int64_t)groups * channels * 256 > INT32_MAX)
+    return fail(NIC_ESHAPE, "%s: bad shape m=%d %dx%dx%d groups=%d", who, m, h, w, channels, groups);
+  return NIC_OK;
+}
+
+int nic_rate_table_work(int m, int h, int w, int channels, int groups, int64_t* floats) {
+  if (!floats) return fail(NIC_EINVAL, "nic_rate_table_work: NULL argument");
+  const int rc = rate_table_shape("nic_rate_table_work", m, h, w, channels, groups);
+  if (rc != NIC_OK) return rc;
+  *floats = (int64_t)train_rate_table_work_floats(m, h, w, channels, groups);
+  return NIC_OK;
+}
+
+int nic_rate_table(const float* y, const float* L, int m, int h, int w, int channels, int groups, float* plane_bits,
+                   float* work, int64_t work_floats, void* stream) {
+  const int rc = rate_table_shape("nic_rate_table", m, h, w, channels, groups);
+  if (rc != NIC_OK) return rc;
+  if (m == 0) return NIC_OK;
+  if (!y || !L || !plane_bits || !work) return fail(NIC_EINVAL, "nic_rate_table: NULL argument");
+  const int64_t need = (int64_t)train_rate_table_work_floats(m, h, w, channels, groups);
+  if (work_floats < need)
+    return fail(NIC_EINVAL, "nic_rate_table: work holds %lld floats, needs %lld", (long long)work_floats, (long long)need);
+  HIP_TRY(launch_rate_table(y, L, m, h, w, channels, groups, plane_bits, work, (hipStream_t)stream));
+  return NIC_OK;
+}
+
+int nic_rate_table_grad(const float* y, const float* L, const float* g, int m, int h, int w, int channels, int groups,
+                        float* dy, float* dL, float* work, int64_t work_floats, void* stream) {
+  const int rc = rate_table_shape("nic_rate_table_grad", m, h, w, channels, groups);
+  if (rc != NIC_OK) return rc;
+  if (!dy && !dL) return fail(NIC_EINVAL, "nic_rate_table_grad: no gradient requested (dy and dL both NULL)");
+  if (m > 0) {
+    if (!y || !L || !g || (dL && !work)) return fail(NIC_EINVAL, "nic_rate_table_grad: NULL argument");
+    const int64_t need = (int64_t)train_rate_table_work_floats(m, h, w, channels, groups);
+    if (dL && work_floats < need)
+      return fail(NIC_EINVAL, "nic_rate_table_grad: work holds %lld floats, needs %lld", (long long)work_floats,
+                  (long long)need);
+  }
+  HIP_TRY(launch_rate_table_grad(y, L, g, m, h, w, channels, groups, dy, dL, work, (hipStream_t)stream));
   return NIC_OK;
 }
 

@@ -88,6 +88,39 @@ class Prior:
         return PriorAccumulator(codec)
 
 
+PSEUDO_COUNT_BITS = 40  # from_probabilities: a row's probabilities as counts out of 2^40
+
+
+def pseudo_counts(p) -> np.ndarray:
+    """(96, 256) probabilities -> the int64 pseudo-counts rint(p 2^40) that from_probabilities
+    normalises (and nic_rans_prior_build normalises to the same freqs)."""
+    a = np.asarray(p, dtype=np.float64)
+    if a.shape != (CHANNELS, 256) or not np.all(np.isfinite(a)) or a.min() < 0 or \
+            np.abs(a.sum(axis=1) - 1.0).max() > 1e-6:
+        raise ValueError("from_probabilities: expected (96, 256) probabilities, every row summing to 1")
+    return np.rint(a * float(1 << PSEUDO_COUNT_BITS)).astype(np.int64)
+
+
+def from_probabilities(p) -> Prior:
+    """A Prior from a (96, 256) float64 table of probabilities (a trained table's softmax,
+    training.Training.prior): pseudo-counts c = rint(p 2^40), normalised on the host by the rule of
+    nic_rans_prior_build (DESIGN section 12): f = max(1, floor(4096 c / N)) with N the row's count;
+    a deficit goes onto the largest entry, a surplus is taken one at a time from the currently
+    largest entry, the lowest symbol on ties; N = 0 gives 16 everywhere."""
+    counts = pseudo_counts(p)
+    freqs = np.empty((CHANNELS, 256), np.int64)
+    for r, c in enumerate(counts):
+        n = int(c.sum())
+        f = np.maximum(1, (c << 12) // n) if n else np.full(256, 16, np.int64)  # c 4096 < 2^53
+        diff = 4096 - int(f.sum())
+        if diff > 0:
+            f[np.argmax(f)] += diff  # argmax: the lowest symbol on ties
+        for _ in range(-diff):
+            f[np.argmax(f)] -= 1
+        freqs[r] = f
+    return Prior(freqs)
+
+
 def as_prior(prior):
     """A Prior from a Prior or a .nicp path (None stays None)."""
     if prior is None or isinstance(prior, Prior):

@@ -19,6 +19,10 @@ adjoint), the separable Gaussian over the four stacked planes (a 1-D one-channel
 correlation and its adjoint, ``nic_gauss_1d``) and both per-plane means of the scale in one pass
 (``nic_msssim_terms`` and its backward).  The SSIM loss is that step once, on scale 0.
 
+The table rate loss (``rate_table``, ``Training(rate="table")``) is ``nic_rate_table`` and
+``nic_rate_table_grad``: per-plane code lengths under a table of -log2 p, the latent's gradient
+and the table's (no atomics; each only when asked for).
+
 Each operand gets a power-of-two scale (max |t| * scale in [2^13, 2^14)) computed on the
 device once per tensor (x and the kernel in the forward, dy in the backward), so the f16 hi/lo split keeps tiny gradients exact to ~2^-22.  The layers' leaky-ReLU runs in
 the gather's epilogue (``nic_conv_gather_act``), and its gradient with the bias gradient in
@@ -262,8 +266,76 @@ def msssim_terms_grad(mx, my, sxy, sxx, g_ssim, g_cs, c1: float, c2: float, out=
     return tuple(grads)
 
 
+RATE_PIX, RATE_SLAB = 1024, 128  # nic_rate_table's elements / nic_rate_table_grad's pixels per block
+
+
+def _rate_shape(y, L, groups: int):
+    m, h, w, c = y.shape
+    if L.dim() != 2 or tuple(L.shape) != (groups * c, 256):
+        raise ValueError(f"rate_table: L must be ({groups * c}, 256) for {groups} groups of {c} channels, "
+                         f"got {tuple(L.shape)}")
+    # nic_rate_table_work (checked by the calls)
+    need = max(m * -(-(h * w * c) // RATE_PIX), groups * -(-(m // max(groups, 1) * h * w) // RATE_SLAB) * c * 256)
+    return m, h, w, c, need
+
+
+def rate_table_bits(y, L, groups: int):
+    """nic_rate_table: the (m,) code lengths in bits of the planes of y (m, h, w, c) NHWC under the
+    table L (groups * c, 256) of -log2 p."""
+    torch = _torch()
+    y, L = _check(y, "rate_table y"), _check(L, "rate_table L")
+    dev = _same_device(y, L)
+    m, h, w, c, need = _rate_shape(y, L, groups)
+    bits = torch.empty((m,), dtype=torch.float32, device=y.device)
+    work = torch.empty(max(need, 1), dtype=torch.float32, device=y.device)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().nic_rate_table(y.data_ptr(), L.data_ptr(), m, h, w, c, groups, bits.data_ptr(),
+                                             work.data_ptr(), need, _stream(dev)), "nic_rate_table")
+    return bits
+
+
+def rate_table_grad(y, L, g, groups: int, want_dy: bool = True, want_dl: bool = True):
+    """nic_rate_table_grad: (dy, dL) of sum_m g[m] plane_bits[m]; one is None when not wanted (its
+    pointer goes down as NULL and its kernel does not run)."""
+    torch = _torch()
+    y, L, g = _check(y, "rate_table_grad y"), _check(L, "rate_table_grad L"), _check(g, "rate_table_grad g")
+    dev = _same_device(y, L, g)
+    m, h, w, c, need = _rate_shape(y, L, groups)
+    if g.numel() != m:
+        raise ValueError("rate_table_grad: one g per plane")
+    dy = torch.empty_like(y) if want_dy else None
+    dl = torch.empty_like(L) if want_dl else None
+    work = torch.empty(max(need, 1), dtype=torch.float32, device=y.device) if want_dl else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().nic_rate_table_grad(
+            y.data_ptr(), L.data_ptr(), g.data_ptr(), m, h, w, c, groups, dy.data_ptr() if want_dy else None,
+            dl.data_ptr() if want_dl else None, work.data_ptr() if want_dl else None, need if want_dl else 0,
+            _stream(dev)), "nic_rate_table_grad")
+    return dy, dl
+
+
 def _conv_fn():
     torch = _torch()
+
+    class RateTable(torch.autograd.Function):
+        """Per-plane code length of y (m, h, w, c) under the table L (groups * c, 256) of -log2 p
+        (nic_rate_table / nic_rate_table_grad); a gradient nobody asked for is not computed."""
+
+        @staticmethod
+        def forward(ctx, y, L, groups):
+            y, L = _check(y, "RateTable y"), _check(L, "RateTable L")
+            ctx.save_for_backward(y, L)
+            ctx.groups = groups
+            return rate_table_bits(y, L, groups)
+
+        @staticmethod
+        def backward(ctx, g):
+            y, L = ctx.saved_tensors
+            want_dy, want_dl = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+            if not (want_dy or want_dl):
+                return None, None, None
+            dy, dl = rate_table_grad(y, L, g.contiguous(), ctx.groups, want_dy, want_dl)
+            return dy, dl, None
 
     class Conv2DSame(torch.autograd.Function):
         """Keras Conv2D(padding='SAME'), leaky_relu(0.2) when act, NHWC; kernel (kh, kw, Cin, Cout)."""
@@ -396,11 +468,11 @@ def _conv_fn():
                               *ctx.consts, out=out)
             return out, None, None
 
-    return _Fns(Conv2DSame, Conv2DTransposeSame, Gauss1D, Pool2Prep, MsssimTerms)
+    return _Fns(Conv2DSame, Conv2DTransposeSame, Gauss1D, Pool2Prep, MsssimTerms, RateTable)
 
 
 # the autograd classes, looked up by name (callers that still index find the two convolutions first)
-_Fns = namedtuple("_Fns", "Conv2DSame Conv2DTransposeSame Gauss1D Pool2Prep MsssimTerms")
+_Fns = namedtuple("_Fns", "Conv2DSame Conv2DTransposeSame Gauss1D Pool2Prep MsssimTerms RateTable")
 _FNS = None
 
 
@@ -419,6 +491,13 @@ def conv_same(x, kernel_hwio, bias, stride: int, act: bool = True):
 def tconv_same(x, kernel_hwoi, bias, stride: int):
     """Keras Conv2DTranspose(padding='SAME') + leaky_relu(0.2) on NHWC (HIP, activation in the epilogue)."""
     return _fns().Conv2DTransposeSame.apply(x, kernel_hwoi, bias, stride, True)
+
+
+def rate_table(y, L, groups: int):
+    """The (m,) code lengths in bits of the planes of y (m, h, w, c) NHWC under the table L
+    (groups * c, 256) of -log2 p, plane i reading the rows of group i // (m / groups) (HIP,
+    differentiable in y and in L; training.table_rate states the formula)."""
+    return _fns().RateTable.apply(y, L, int(groups))
 
 
 SSIM_PIX = 1024  # map pixels per block of nic_msssim_terms (its work: two partial sums per block)

@@ -19,6 +19,10 @@ restated so that trained weights exist for the codec and the config-4 RD sweep:
   ``entropy_loss_coef += 0.01`` per epoch, validation through the HIP codec's
   ``compress``/``uncompress`` every 10 steps.  TF's ``tape.gradient`` of a non-scalar
   loss sums its elements; the losses here are summed the same way.
+* ``Training(rate="table")`` (no counterpart in the reference): the rate term is the code length
+  of the noisy latent under a learnable 96 x 256 table (:func:`table_rate`), the quantity .nic
+  version 2 prices; the third tape fits the table instead of an Entropynet, nothing runs on the
+  host, and ``Training.prior()`` exports the table as the container's ``.nicp``.
 * ``_save`` (training.py:167-172) writes the reference's own TF checkpoint format
   (``weights.save_tf``), which ``ProClass.load`` / the HIP codec read back.
 
@@ -225,6 +229,52 @@ def ms_ssim(x, y, scales: int = 4, max_val: float = 1.0, hip: bool = False):
     return ms_ssim_combine(torch.stack(terms, dim=1), scales)
 
 
+TABLE_GROUPS, TABLE_CHANNELS = 3, 32  # prior.Prior's rows: Y0..31, Cb0..31, Cr0..31
+
+
+def table_code_lengths(logits):
+    """L = -log2(softmax(logits, dim=1)): the (rows, 256) ideal code lengths in bits of a table of
+    logits; differentiable.  Zero logits give 8 exactly."""
+    torch = _torch()
+    return -torch.log2(torch.softmax(logits, dim=1))
+
+
+def table_bits(y, L, groups: int, hip: bool = False):
+    """:func:`table_rate` from the code lengths L (groups * C, 256) themselves."""
+    torch = _torch()
+    if hip:
+        from . import train_hip
+
+        return train_hip.rate_table(y, L, groups)
+    m, c = y.shape[0], y.shape[1]
+    if groups < 1 or m % groups or L.dim() != 2 or tuple(L.shape) != (groups * c, 256):
+        raise ValueError(f"table_rate: {m} planes of {c} channels in {groups} groups need a ({groups * c}, 256) table, "
+                         f"got {tuple(L.shape)}")
+    v = torch.fmin(torch.fmax(255 * y, y.new_zeros(())), y.new_full((), 255.0))  # a NaN becomes 0
+    k = v.detach().floor().clamp(max=254).long()
+    t = v - k.to(v.dtype)
+    group = torch.arange(m, device=y.device) // max(m // groups, 1)
+    rows = (group[:, None] * c + torch.arange(c, device=y.device)[None, :])[:, :, None, None]
+    l0 = L[rows, k]
+    bits = l0 + t * (L[rows, k + 1] - l0)
+    return bits.sum(dim=(1, 2, 3))
+
+
+def table_rate(y, logits, groups: int, hip: bool = False):
+    """The code length in bits of each latent plane under a learnable per-channel table, the
+    quantity .nic version 2 prices: y (M, C, h, w) NCHW in [0, 1] (``hip``: (M, h, w, C) NHWC, on
+    the HIP kernels, train_hip.rate_table), logits (groups * C, 256), M divisible by groups ->
+    (M,); differentiable in both.  With L = -log2(softmax(logits, dim=1)), plane m belongs to
+    group m // (M / groups) and its channel c reads row r = group * C + c; per element, in fp32,
+        v = fmin(fmax(255 y, 0), 255), k = min(floor(v), 254), t = v - k,
+        bits = L[r][k] + t (L[r][k+1] - L[r][k])
+    summed over the plane.  At y = code / 255 that is the symbol's ideal code length; between codes
+    it is linear, so its slope carries the rate's gradient to the encoder.  This PyTorch
+    restatement is the CPU path and what the kernels are tested against (its gradient in y is 0
+    outside [0, 1], where the kernel keeps the end slope; the step's latents are clamped)."""
+    return table_bits(y, table_code_lengths(logits), groups, hip)
+
+
 def png_bpp_planes(encoded_u8: np.ndarray, tot_pixels: float, threads: int = 16, mode: str = "tf") -> np.ndarray:
     """get_bpp (training.py:14-21): latent planes (M,h,w,32) u8 -> (M,) 8*len(PNG((4h,8w)))/pixels.
 
@@ -302,13 +352,20 @@ class Training:
 
     def __init__(self, device: str = "cuda", weights: Optional[W.Weights] = None, seed: int = 0,
                  checkpoint_dir: str = "../checkpoints/", backend: Optional[str] = None,
-                 png_threads: int = 16, distortion: str = "ssim", ms_scales: int = 4):
+                 png_threads: int = 16, distortion: str = "ssim", ms_scales: int = 4, rate: str = "png",
+                 table_lr: float = 1e-2):
         """backend "hip" (default on a GPU): every convolution of the step, forward and
         backward, on the HIP split-f16x3 MFMA kernels (train_hip, NHWC); "torch" (default on
         the CPU): PyTorch autograd convolutions (MIOpen / oneDNN, NCHW) -- the restatement the
         HIP path is tested against.  distortion "ssim" (default, the reference's loss):
         tf.image.ssim; "ms_ssim": tf.image.ssim_multiscale over ``ms_scales`` scales
-        (:func:`ms_ssim`), the metric the codecs are scored by, in both codec losses."""
+        (:func:`ms_ssim`), the metric the codecs are scored by, in both codec losses.  rate "png"
+        (default, the reference's): an Entropynet regressed onto the PNG size of the rounded
+        latent; "table": the code length of the noisy latent under a learnable 96 x 256 table
+        (:func:`table_rate`; ``table_logits``, zeros: 8 bits per symbol), fitted by maximum
+        likelihood in the same step with its own Adam at ``table_lr`` (an untuned choice) and
+        exported by :meth:`prior` as the .nicp that .nic version 2 codes under -- no Entropynet, no
+        PNG encode and no host work in the step, and no parameter shaped by the patch size."""
         torch = _torch()
         backend = backend or ("hip" if torch.device(device).type == "cuda" else "torch")
         if backend not in ("hip", "torch"):
@@ -317,7 +374,10 @@ class Training:
             raise ValueError(f"distortion must be 'ssim' or 'ms_ssim', not {distortion!r}")
         if not 1 <= ms_scales <= len(MSSSIM_WEIGHTS):
             raise ValueError(f"ms_scales must be 1..{len(MSSSIM_WEIGHTS)}, not {ms_scales}")
+        if rate not in ("png", "table"):
+            raise ValueError(f"rate must be 'png' or 'table', not {rate!r}")
         self.distortion, self.ms_scales = distortion, ms_scales
+        self.rate, self.table_lr = rate, table_lr
         self.hip = backend == "hip"
         self.hip_adam = True  # HIP backend: the Keras Adam update on HIP (False: torch.optim.Adam)
         self.device = torch.device(device)
@@ -328,6 +388,10 @@ class Training:
         self.epoch = 0
         self.checkpoint_dir = checkpoint_dir
         self.entropy_model: Optional[Entropynet] = None
+        self.table_logits = None
+        if rate == "table":
+            self.table_logits = torch.zeros((TABLE_GROUPS * TABLE_CHANNELS, 256), dtype=torch.float32,
+                                            device=self.device, requires_grad=True)
         self._opt = None
         self._gen = torch.Generator(device=self.device).manual_seed(seed)
         # the PNG-size target (get_bpp, training.py:14-21: 3B PNG encodes per step) runs on
@@ -345,9 +409,13 @@ class Training:
         return [v for k, v in self.params.items() if k.startswith("encoder" + plane + "/") or
                 k.startswith("decoder" + plane + "/")]
 
+    def _rate_params(self) -> List[object]:
+        """What the third tape trains: the Entropynet, or the table."""
+        return [self.table_logits] if self.rate == "table" else self.entropy_model.parameters()
+
     def _setup(self, hw):
         torch = _torch()
-        if self.entropy_model is None:
+        if self.rate == "png" and self.entropy_model is None:
             self.entropy_model = Entropynet((-(-hw[0] // 8), -(-hw[1] // 8)), self.device, self.seed)
         if self._opt is None:
             # tf.keras.optimizers.Adam(1e-4): beta 0.9 / 0.999, epsilon 1e-7 -- on HIP, TF's
@@ -356,10 +424,11 @@ class Training:
             if self.hip and self.hip_adam:
                 from .train_hip import KerasAdam
 
-                mk = lambda ps: KerasAdam(ps, lr=1e-4, beta1=0.9, beta2=ADAM_BETA2, epsilon=KERAS_ADAM_EPS)  # noqa: E731
+                mk = lambda ps, lr=1e-4: KerasAdam(ps, lr=lr, beta1=0.9, beta2=ADAM_BETA2, epsilon=KERAS_ADAM_EPS)  # noqa: E731
             else:
-                mk = lambda ps: torch.optim.Adam(ps, lr=1e-4, betas=(0.9, ADAM_BETA2), eps=KERAS_ADAM_EPS)  # noqa: E731
-            self._opt = (mk(self._variables("Y")), mk(self._variables("CbCr")), mk(self.entropy_model.parameters()))
+                mk = lambda ps, lr=1e-4: torch.optim.Adam(ps, lr=lr, betas=(0.9, ADAM_BETA2), eps=KERAS_ADAM_EPS)  # noqa: E731
+            third = mk(self._rate_params(), self.table_lr) if self.rate == "table" else mk(self._rate_params())
+            self._opt = (mk(self._variables("Y")), mk(self._variables("CbCr")), third)
 
     def train_step(self, images, entropy_loss_coef: float, flip: bool = True) -> Dict[str, object]:
         """One batch (training.py:67-147): u8 NHWC images (B,H,W,3) -> metrics."""
@@ -367,7 +436,7 @@ class Training:
         f = self.losses(images, entropy_loss_coef, flip, defer_png=True)
         loss0, loss1 = f["loss0"], f["loss1"]
         opt_y, opt_c, opt_e = self._opt
-        ent_params = self.entropy_model.parameters()
+        ent_params = self._rate_params()
         # three tapes: main losses update the codec models only, the entropy loss the net only;
         # the codec gradients are queued while the host threads size the PNG target
         gy = torch.autograd.grad(loss0, self._variables("Y"), retain_graph=True)
@@ -389,6 +458,8 @@ class Training:
         b = images.shape[0]
         cb, cr = torch.split(f["ssim1_each"].detach(), b)
         bpp = f["bpp"]
+        if torch.is_tensor(bpp):  # the table rate's, still on the device
+            bpp = bpp.cpu().numpy()
         return {"ssim": [float(f["ssim0"].detach()), float(cb.mean()), float(cr.mean())],
                 "bpp": [float(v.mean()) for v in np.split(bpp, 3)],
                 "entropy_loss": float(aprox_entropy_loss.detach()), "loss": [float(loss0.detach()), float(loss1.detach())]}
@@ -455,11 +526,24 @@ class Training:
 
         noisy0 = (enc0 + noise(enc0) / 255).clamp(0, 1)
         noisy1 = (enc1 + noise(enc1) / 255).clamp(0, 1)
-        batch_enc = torch.cat([enc0, enc1], dim=0)
-        aprox = self.entropy_model(batch_enc, hip)  # (3B, 1)
-        codes = torch.round(batch_enc.detach() * 255).clamp(0, 255).to(torch.uint8)
-        codes = codes if hip else codes.permute(0, 2, 3, 1)
-        bpp_future = self._png_target(codes.contiguous(), float(x.shape[1] * x.shape[2]))
+        if self.rate == "table":
+            # the table's bpp of the noisy latents: the codec tapes read it through the code lengths
+            # detached (a gradient to the latents alone), the third tape with the latents detached
+            # (a maximum-likelihood fit of the table alone)
+            pixels = float(x.shape[1] * x.shape[2])
+            code_len = table_code_lengths(self.table_logits)
+            fixed = code_len.detach()
+            aprox = torch.cat([table_bits(noisy0, fixed[:TABLE_CHANNELS], 1, hip),
+                               table_bits(noisy1, fixed[TABLE_CHANNELS:], 2, hip)]).view(-1, 1) / pixels  # (3B, 1)
+            latents = torch.cat([noisy0, noisy1], dim=0).detach()
+            rate = {"bpp": aprox.detach().view(-1),
+                    "entropy_loss": (table_bits(latents, code_len, TABLE_GROUPS, hip) / pixels).mean()}
+        else:
+            batch_enc = torch.cat([enc0, enc1], dim=0)
+            aprox = self.entropy_model(batch_enc, hip)  # (3B, 1)
+            codes = torch.round(batch_enc.detach() * 255).clamp(0, 255).to(torch.uint8)
+            codes = codes if hip else codes.permute(0, 2, 3, 1)
+            rate = {"bpp_future": self._png_target(codes.contiguous(), float(x.shape[1] * x.shape[2]))}
         ent = torch.split(aprox, b, dim=0)
         dec0 = base_decoder(self._model("decoderY"), noisy0, hip)
         dec1 = base_decoder(self._model("decoderCbCr"), noisy1, hip)
@@ -474,8 +558,7 @@ class Training:
         ssim1 = ssim1_each.mean()
         loss0 = ((1 - ssim0) / 2 + entropy_loss_coef * ent[0]).sum()
         loss1 = ((1 - ssim1) / 2 + 0.01 * torch.cat(ent[1:], dim=0)).sum()  # reference: 0.01 (training.py:124)
-        f = {"loss0": loss0, "loss1": loss1, "ssim0": ssim0, "ssim1_each": ssim1_each, "aprox": aprox,
-             "bpp_future": bpp_future}
+        f = {"loss0": loss0, "loss1": loss1, "ssim0": ssim0, "ssim1_each": ssim1_each, "aprox": aprox, **rate}
         if not defer_png:
             self.finish_entropy_loss(f)
         return f
@@ -488,6 +571,20 @@ class Training:
         w = self.weights()
         W.save_tf(w, os.path.join(self.checkpoint_dir, "encoder"), "encoder")
         W.save_tf(w, os.path.join(self.checkpoint_dir, "decoder"), "decoder")
+        if self.rate == "table":
+            self.prior().save(os.path.join(self.checkpoint_dir, "prior.nicp"))
+
+    def prior(self):
+        """The table as the :class:`prior.Prior` that ``compress(..., container="nic", prior=p)``
+        codes under: softmax(table_logits) in float64 on the host, through
+        :func:`prior.from_probabilities`."""
+        from . import prior as P
+
+        if self.rate != "table":
+            raise ValueError("prior(): only Training(rate='table') has a table to export")
+        z = self.table_logits.detach().cpu().numpy().astype(np.float64)
+        e = np.exp(z - z.max(axis=1, keepdims=True))
+        return P.from_probabilities(e / e.sum(axis=1, keepdims=True))
 
     def __call__(self, x: np.ndarray, x_val_path: Optional[str], max_epochs: int, batch_size: int,
                  entropy_loss_coef: float, verbose: bool = True,

@@ -1,0 +1,234 @@
+"""The table rate loss on the GPU: nic_rate_table / nic_rate_table_grad against the float64
+reference (tests/rate_table_ref.py), Training(rate="table") on the HIP backend against the torch
+backend, and the exported prior in the .nic version 2 coder.
+
+The yardstick is that of tests/test_gpu_msssim_loss.py: on the same inputs (one fp32 table L on every
+side) the fp32 PyTorch restatement (training.table_bits on the device) has an error e32 against
+the float64 reference; the HIP error may be at most 2 e32 + EPS x the sum of the absolute terms
+(per plane for the bits; for dL per row, the largest entry's).  dy is elementwise: the kernel and
+the formula (255 g) (L[k+1] - L[k]) evaluated in fp32 by PyTorch do the same arithmetic, 1 ulp.
+
+Measured on the MI355X (pytest -s prints them), worst case over the shapes, error / yardstick:
+see DESIGN section 21.
+"""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+from neural_network_image_compression_amd import _lib  # noqa: E402
+from neural_network_image_compression_amd import prior as P  # noqa: E402
+from neural_network_image_compression_amd import train_hip  # noqa: E402
+from neural_network_image_compression_amd import training as T  # noqa: E402
+from tests import rate_table_ref as R  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+EPS = 2.0 ** -23
+# the CPU test's shapes, and 15 planes of 16 x 16 x 32: eight forward blocks per plane, ten slabs
+# per group (the last one ragged) in the backward
+SHAPES = R.SHAPES + [(15, 16, 16, 32, 3)]
+G_KINDS = ("equal", "first_group", "signs")
+
+
+def _report(what, *figs):
+    print(f"\n[rate-table] {what}: " + " ".join(f"{f:.3e}" if isinstance(f, float) else str(f) for f in figs))
+
+
+def _g(kind, m, groups):
+    if kind == "equal":
+        return np.full(m, 1.0 / 4096, np.float32)
+    if kind == "first_group":  # what loss0 sends down: nothing outside the Y planes
+        g = np.zeros(m, np.float32)
+        g[:m // groups] = 0.01 / 1024
+        return g
+    rng = np.random.default_rng(m)
+    return (rng.standard_normal(m) * 1e-3).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def _case(shape):
+    """Inputs and float64 references of one shape, computed once: y (NHWC), L (fp32, shared by every
+    side), the bits, and per g kind the gradients."""
+    m, h, w, c, groups = shape
+    y, logits = R.case(shape)
+    L = T.table_code_lengths(torch.from_numpy(logits)).numpy()
+    bits, bits_abs = R.rate_table(y, L, groups)
+    grads = {kind: R.rate_table_grad(y, L, _g(kind, m, groups), groups) for kind in G_KINDS}
+    return y, L, bits, bits_abs, grads
+
+
+def _nchw(t):
+    return t.permute(0, 3, 1, 2).contiguous()
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=str)
+def test_forward_matches_float64(shape):
+    m, h, w, c, groups = shape
+    y, L, ref, ref_abs, _ = _case(shape)
+    yd, Ld = torch.from_numpy(y).cuda(), torch.from_numpy(L).cuda()
+    got = train_hip.rate_table(yd, Ld, groups)
+    assert got.shape == (m,) and got.dtype == torch.float32
+    e32 = np.abs(T.table_bits(_nchw(yd), Ld, groups).double().cpu().numpy() - ref)
+    err = np.abs(got.double().cpu().numpy() - ref)
+    _report(f"forward {shape}", float((err / ref_abs).max()), float((e32 / ref_abs).max()))
+    assert np.all(err <= 2 * e32 + EPS * ref_abs)
+    assert torch.equal(train_hip.rate_table(yd, Ld, groups), got)  # deterministic
+    assert torch.equal(train_hip.rate_table_bits(yd, Ld, groups), got)
+
+
+def test_edge_inputs_equal_the_clamped_reference():
+    f = np.float32
+    codes = (np.arange(256) / f(255)).astype(f)
+    vals = np.concatenate([codes, np.nextafter(codes, f(-1)), f([-0.5, 1.5, np.nan, 0.0, 1.0, np.inf, -np.inf])])
+    c, groups = 32, 3
+    n = -(-vals.size // 16)
+    flat = np.resize(vals, n * 16)
+    y = np.broadcast_to(flat.reshape(1, n, 16, 1), (3, n, 16, c)).copy()
+    with np.errstate(invalid="ignore"):
+        yc = np.where(np.isnan(y), f(0), np.clip(y, 0, 1)).astype(f)
+    _, logits = R.case((3, 2, 2, c, groups))
+    L = T.table_code_lengths(torch.from_numpy(logits)).numpy()
+    ref, ref_abs = R.rate_table(y, L, groups)
+    assert np.array_equal(ref, R.rate_table(yc, L, groups)[0])  # the reference of the clamped v
+    Ld = torch.from_numpy(L).cuda()
+    got = train_hip.rate_table(torch.from_numpy(y).cuda(), Ld, groups)
+    assert torch.equal(got, train_hip.rate_table(torch.from_numpy(yc).cuda(), Ld, groups))
+    e32 = np.abs(T.table_bits(_nchw(torch.from_numpy(yc).cuda()), Ld, groups).double().cpu().numpy() - ref)
+    err = np.abs(got.double().cpu().numpy() - ref)
+    assert np.all(np.isfinite(err)) and np.all(err <= 2 * e32 + EPS * ref_abs)
+    # the gradient at the edges: finite, and the table's gradient stays inside its rows' sums
+    g = torch.full((3,), 1.0 / 64, device="cuda")
+    dy, dl = train_hip.rate_table_grad(torch.from_numpy(y).cuda(), Ld, g, groups)
+    assert bool(torch.isfinite(dy).all()) and bool(torch.isfinite(dl).all())
+    want = R.rate_table_grad(y, L, np.full(3, 1.0 / 64), groups)[1]
+    assert np.abs(dl.double().cpu().numpy() - want).max() <= 1e-5 * np.abs(want).max()
+
+
+def _ulps(a, ref):
+    a, ref = a.double().cpu(), ref.double().cpu()
+    spacing = torch.ldexp(torch.ones_like(ref), torch.floor(torch.log2(ref.abs().clamp_min(1e-37))).int() - 23)
+    return float(((a - ref).abs() / spacing).max())
+
+
+@pytest.mark.parametrize("kind", G_KINDS)
+@pytest.mark.parametrize("shape", SHAPES, ids=str)
+def test_backward_matches_float64(shape, kind):
+    m, h, w, c, groups = shape
+    y, L, _, _, grads = _case(shape)
+    dy_ref, dl_ref, dl_abs = grads[kind]
+    g = _g(kind, m, groups)
+    yd, Ld, gd = torch.from_numpy(y).cuda(), torch.from_numpy(L).cuda(), torch.from_numpy(g).cuda()
+    dy, dl = train_hip.rate_table_grad(yd, Ld, gd, groups)
+    # dy: the formula in fp32, the same arithmetic
+    k, _ = R.elements(y)
+    rows = np.broadcast_to(R.rows_of(m, c, groups), k.shape)
+    rt, kt = torch.from_numpy(rows.copy()).cuda(), torch.from_numpy(k).cuda()
+    dy32 = (255 * gd)[:, None, None, None] * (Ld[rt, kt + 1] - Ld[rt, kt])
+    assert _ulps(dy, dy32) <= 1
+    # and against float64: a difference and two products, four roundings of at most |L0| + |L1|
+    dy_abs = 255.0 * np.abs(g)[:, None, None, None] * (np.abs(L[rows, k]) + np.abs(L[rows, k + 1]))
+    assert np.all(np.abs(dy.double().cpu().numpy() - dy_ref) <= 4 * 2.0 ** -24 * dy_abs)
+    # the restatement through autograd, the yardstick of dL
+    y32, L32 = _nchw(yd).requires_grad_(), Ld.clone().requires_grad_()
+    (T.table_bits(y32, L32, groups) * gd).sum().backward()
+    _report(f"dy {shape} {kind}: ulps vs the formula, vs autograd", _ulps(dy, dy32),
+            _ulps(dy, y32.grad.permute(0, 2, 3, 1)))
+    e32 = np.abs(L32.grad.double().cpu().numpy() - dl_ref).max(axis=1)
+    err = np.abs(dl.double().cpu().numpy() - dl_ref).max(axis=1)
+    mag = dl_abs.max(axis=1)
+    _report(f"dL {shape} {kind}", float((err / np.maximum(mag, 1e-30)).max()),
+            float((e32 / np.maximum(mag, 1e-30)).max()))
+    assert np.all(err <= 2 * e32 + EPS * mag)
+    # each alone (the other pointer NULL) and a second run: the same bits
+    dy1, none = train_hip.rate_table_grad(yd, Ld, gd, groups, want_dl=False)
+    assert none is None and torch.equal(dy1, dy)
+    none, dl1 = train_hip.rate_table_grad(yd, Ld, gd, groups, want_dy=False)
+    assert none is None and torch.equal(dl1, dl)
+    assert torch.equal(train_hip.rate_table_grad(yd, Ld, gd, groups)[1], dl)
+
+
+def test_autograd_function_honours_needs_input_grad(monkeypatch):
+    shape = (6, 5, 7, 32, 3)
+    y, L, _, _, grads = _case(shape)
+    g = torch.from_numpy(_g("signs", 6, 3)).cuda()
+    seen = []
+    real = train_hip.rate_table_grad
+
+    def spy(y, L, g, groups, want_dy=True, want_dl=True):
+        seen.append((bool(want_dy), bool(want_dl)))
+        return real(y, L, g, groups, want_dy, want_dl)
+
+    monkeypatch.setattr(train_hip, "rate_table_grad", spy)
+    yd, Ld = torch.from_numpy(y).cuda().requires_grad_(), torch.from_numpy(L).cuda().requires_grad_()
+    (train_hip.rate_table(yd, Ld.detach(), 3) * g).sum().backward()
+    (train_hip.rate_table(yd.detach(), Ld, 3) * g).sum().backward()
+    assert seen == [(True, False), (False, True)]
+    dy_ref, dl_ref, _ = grads["signs"]
+    assert np.abs(yd.grad.double().cpu().numpy() - dy_ref).max() <= 1e-5 * np.abs(dy_ref).max()
+    assert np.abs(Ld.grad.double().cpu().numpy() - dl_ref).max() <= 1e-5 * np.abs(dl_ref).max()
+    # through the public function, from logits
+    _, logits = R.case(shape)
+    z = torch.from_numpy(logits).cuda().requires_grad_()
+    bits = T.table_rate(yd.detach(), z, 3, hip=True)
+    bits.sum().backward()
+    zc = torch.from_numpy(logits).requires_grad_()
+    T.table_rate(_nchw(yd.detach()).cpu(), zc, 3).sum().backward()
+    assert float((z.grad.cpu() - zc.grad).abs().max()) <= 1e-4 * float(zc.grad.abs().max())
+
+
+def test_empty_batch_and_wrong_table():
+    Ld = torch.zeros((96, 256), device="cuda")
+    y0 = torch.zeros((0, 4, 4, 32), device="cuda")
+    assert train_hip.rate_table(y0, Ld, 3).shape == (0,)
+    dy, dl = train_hip.rate_table_grad(y0, Ld, torch.zeros((0,), device="cuda"), 3)
+    assert dy.shape == y0.shape and not bool(dl.any())
+    with pytest.raises(ValueError):
+        train_hip.rate_table(torch.zeros((3, 4, 4, 32), device="cuda"), Ld[:64], 3)
+    with pytest.raises(ValueError):
+        train_hip.rate_table(torch.zeros((4, 4, 4, 32), device="cuda"), Ld, 3)
+
+
+def test_training_step_hip_matches_torch_backend(tmp_path):
+    from neural_network_image_compression_amd import weights as W
+
+    w0 = W.seeded_weights(0, init="glorot")
+    imgs = torch.randint(0, 256, (4, 32, 32, 3), generator=torch.Generator().manual_seed(3), dtype=torch.uint8)
+    out = {}
+    for be in ("hip", "torch"):
+        tr = T.Training(device="cuda", weights=w0, seed=0, checkpoint_dir=str(tmp_path) + "/", backend=be, rate="table")
+        out[be] = ([tr.train_step(imgs, 0.01) for _ in range(2)], tr.table_logits.detach().cpu())
+        assert tr.entropy_model is None
+    for mh, mt in zip(out["hip"][0], out["torch"][0]):
+        assert set(mh) == set(mt)
+        for key in mh:
+            for a, b in zip(np.ravel(mh[key]), np.ravel(mt[key])):
+                assert abs(a - b) <= 1e-4 * max(1.0, abs(b)), (key, a, b)
+    a, b = out["hip"][1], out["torch"][1]
+    assert bool(((a - b).abs() <= 1e-4 * b.abs().clamp_min(1.0)).all()), float((a - b).abs().max())
+    assert bool(b.any())  # the table moved
+
+
+def test_exported_prior_reaches_the_container(tmp_path):
+    from neural_network_image_compression_amd.codec import Codec
+
+    tr = T.Training(device="cuda", seed=0, checkpoint_dir=str(tmp_path) + "/", rate="table")
+    imgs = torch.randint(0, 256, (4, 32, 32, 3), generator=torch.Generator().manual_seed(4), dtype=torch.uint8)
+    for _ in range(3):
+        tr.train_step(imgs, 0.01)
+    p = tr.prior()
+    codec = Codec(0)
+    codec.set_prior(p)
+    z = torch.randint(0, 256, (1, 8, 8, 96), generator=torch.Generator().manual_seed(5), dtype=torch.uint8).cuda()
+    buf, sizes = codec.rans2_encode(z)
+    assert torch.equal(codec.rans2_decode(buf, sizes, 8, 8), z)
+    # the device's normalisation of the same pseudo-counts
+    logits = tr.table_logits.detach().cpu().numpy().astype(np.float64)
+    e = np.exp(logits - logits.max(axis=1, keepdims=True))
+    counts = torch.from_numpy(P.pseudo_counts(e / e.sum(axis=1, keepdims=True))).cuda()
+    assert np.array_equal(codec.prior_build(counts).cpu().numpy(), p.freqs)
+    tr._save()
+    assert P.Prior.load(str(tmp_path / "prior.nicp")) == p

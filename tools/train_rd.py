@@ -10,6 +10,11 @@ is used when present, one epoch = one pass, as training.py:175-179; otherwise th
 1,000-patch subset data/imagenet_patches_1k with --epoch-samples images (default 19,000)
 per epoch drawn from reshuffled passes, so the coefficient schedule keeps the reference's pace.
 
+--rate table trains the rate term against the code length under a learnable table
+(Training(rate="table")) instead of the reference's PNG target; each run then also reports the size
+of kodim21's .nic version 2 file under the prior the run exported ("nic2_bpp_table_prior", beside
+the sweep's own columns), and --save-dir keeps that prior as <label>_prior.nicp.
+
     python tools/train_rd.py [--epochs 30] [--batch 64] [--steps N] [--out FILE] [--save-dir DIR]
 """
 import argparse
@@ -54,6 +59,9 @@ def main():
     ap.add_argument("--distortion", default="ssim", choices=("ssim", "ms_ssim"),
                     help="the codec losses' distortion term (ssim: the reference's; ms_ssim: tf.image.ssim_multiscale)")
     ap.add_argument("--ms-scales", type=int, default=4, help="scales of --distortion ms_ssim (128 px patches: <= 4)")
+    ap.add_argument("--rate", default="png", choices=("png", "table"),
+                    help="the rate term (png: the reference's Entropynet on PNG sizes; table: the .nic prior's code length)")
+    ap.add_argument("--table-lr", type=float, default=1e-2, help="Adam's learning rate of --rate table's table (untuned)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     x = load_patches(args.data)
@@ -68,7 +76,7 @@ def main():
         t0 = time.perf_counter()
         with tempfile.TemporaryDirectory() as d:
             tr = T.Training(device="cuda", weights=W.seeded_weights(seed, init="glorot"), seed=seed, checkpoint_dir=d + "/",
-                            distortion=args.distortion, ms_scales=args.ms_scales)
+                            distortion=args.distortion, ms_scales=args.ms_scales, rate=args.rate, table_lr=args.table_lr)
             tr.png_mode = args.png_mode
             epochs = args.epochs
             if args.steps:
@@ -82,16 +90,31 @@ def main():
             tr._save()
             w = W.load(os.path.join(d, "encoder"), "encoder")
             w.update(W.load(os.path.join(d, "decoder"), "decoder"))
+            table_prior = tr.prior() if args.rate == "table" else None
         label = f"coef{coef:.2f}" + ("" if args.coef_step == 0.01 else f"_step{args.coef_step:g}") + (f"_s{seed}" if seed else "")
         sets[label] = w
         if args.save_dir:
             os.makedirs(args.save_dir, exist_ok=True)
             for kind in ("encoder", "decoder"):  # <dir>/<label>_encoderY.safetensors, ...
                 W.save(w, os.path.join(args.save_dir, f"{label}_{kind}"), kind)
+        nic2 = None
+        if table_prior is not None:  # kodim21 as a .nic version 2 file under the exported prior
+            import torch
+
+            from neural_network_image_compression_amd.codec import Codec
+
+            if args.save_dir:
+                table_prior.save(os.path.join(args.save_dir, f"{label}_prior.nicp"))
+            codec = Codec(0)
+            codec.set_weights(w)
+            codec.set_prior(table_prior)
+            _, sizes = codec.rans2_encode(codec.encode(torch.from_numpy(ev).cuda()))
+            nic2 = {"prior_id": f"{table_prior.id:08x}",
+                    "nic2_bpp_table_prior": round(8.0 * float(sizes.sum()) / (ev.shape[0] * ev.shape[1] * ev.shape[2]), 6)}
         tail = log[-20:]
         train_log[label] = {"steps": len(log), "epochs": epochs, "seed": seed, "png_mode": args.png_mode, "distortion": args.distortion,
                             "ms_scales": args.ms_scales if args.distortion == "ms_ssim" else None, "seconds": round(time.perf_counter() - t0, 1),
-                            "train_seconds": round(t_train, 1),
+                            "train_seconds": round(t_train, 1), "rate": args.rate, "nic2": nic2,
                             "first": {k: log[0][k] for k in ("ssim", "bpp", "entropy_loss")},
                             "last20_mean": {k: [float(np.mean([m[k][j] for m in tail])) for j in range(3)]
                                             for k in ("ssim", "bpp")}}
