@@ -674,6 +674,25 @@ int nic_png_device_read(nic_ctx* ctx, const uint8_t* streams, int64_t stride, co
  * Both take `work` of nic_rate_table_work() floats: max(m ceil(h w channels / 1024),
  *     groups ceil((m / groups) h w / 128) channels 256); nic_rate_table_grad reads it only with dL.
  *     channels <= 64; m h w channels and groups channels 256 must fit an int.
+ * The context rate loss: the same under the row the left neighbour selects, the quantity .nic version
+ * 3 prices.  L is (groups * channels, 3, 256) fp32, L[r][x][j] = -log2 p_{r,x}(j); anchors is
+ * groups * channels bytes on the device; yc (m, h, w, channels), NULL meaning y, is the tensor the
+ * contexts are read from; seg_pixels >= 1.  Element (i, q, c), q the row-major pixel inside plane i:
+ *     x = 0 if q % seg_pixels == 0, otherwise
+ *         min(2, |(int)rintf(fminf(fmaxf(255 yc[i][q-1][c], 0), 255)) - anchors[r]|)
+ *     (rintf: to nearest, ties to even; "left" is the previous pixel in memory order inside the plane,
+ *     across a row end the last pixel of the row above, never a pixel of another plane: q = 0 is
+ *     always context 0 and yc[i][-1] is never read), then v, k, t as above and
+ *     bits = L[r][x][k] + t (L[r][x][k+1] - L[r][x][k]).
+ * nic_rate_ctable: plane_bits[i] as nic_rate_table's, in the same orders: with the three rows of every
+ *     channel equal it returns nic_rate_table's bits bit for bit.
+ * nic_rate_ctable_grad: dy = (255 g[i]) (L[r][x][k+1] - L[r][x][k]); dL[r][x][j] = sum over row r's
+ *     elements in context x of g (1 - t) at j = k plus g t at j = k + 1 (deterministic, no atomics, as
+ *     nic_rate_table_grad's, once per context).  Nothing flows to yc or through the left neighbour: the
+ *     context is piecewise constant.  dy and dL are each nullable, not both; m = 0 zeroes dL.
+ * Both take `work` of nic_rate_ctable_work() floats: max(m ceil(h w channels / 1024),
+ *     3 groups ceil((m / groups) h w / 128) channels 256); nic_rate_ctable_grad reads it only with dL.
+ *     Argument errors are nic_rate_table's, plus NIC_EINVAL for seg_pixels < 1 and NULL anchors.
  * nic_adam_keras: the step's optimiser update (training.py:147-149, tf.keras Adam = TF's
  *     ResourceApplyAdam) over `count` tensors in one launch; table = device int64 records
  *     {var, m, v, grad, n} (pointers to fp32 device buffers, n elements), max_n their largest n:
@@ -716,6 +735,13 @@ int nic_rate_table(const float* y, const float* L, int m, int h, int w, int chan
                    float* work, int64_t work_floats, void* stream);
 int nic_rate_table_grad(const float* y, const float* L, const float* g, int m, int h, int w, int channels, int groups,
                         float* dy, float* dL, float* work, int64_t work_floats, void* stream);
+int nic_rate_ctable_work(int m, int h, int w, int channels, int groups, int64_t* floats);
+int nic_rate_ctable(const float* y, const float* yc, const float* L, const uint8_t* anchors, int m, int h, int w,
+                    int channels, int groups, int seg_pixels, float* plane_bits, float* work, int64_t work_floats,
+                    void* stream);
+int nic_rate_ctable_grad(const float* y, const float* yc, const float* L, const uint8_t* anchors, const float* g, int m,
+                         int h, int w, int channels, int groups, int seg_pixels, float* dy, float* dL, float* work,
+                         int64_t work_floats, void* stream);
 int nic_adam_keras(const int64_t* table, int count, int64_t max_n, float alpha, float beta1, float beta2,
                    float epsilon, void* stream);
 

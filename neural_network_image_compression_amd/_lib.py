@@ -167,6 +167,9 @@ _SIGNATURES = {
     "nic_rate_table_work": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int64)]),
     "nic_rate_table": (ctypes.c_int, [c_vp] * 2 + [ctypes.c_int] * 5 + [c_vp, c_vp, ctypes.c_int64, c_vp]),
     "nic_rate_table_grad": (ctypes.c_int, [c_vp] * 3 + [ctypes.c_int] * 5 + [c_vp] * 3 + [ctypes.c_int64, c_vp]),
+    "nic_rate_ctable_work": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int64)]),
+    "nic_rate_ctable": (ctypes.c_int, [c_vp] * 4 + [ctypes.c_int] * 6 + [c_vp, c_vp, ctypes.c_int64, c_vp]),
+    "nic_rate_ctable_grad": (ctypes.c_int, [c_vp] * 5 + [ctypes.c_int] * 6 + [c_vp] * 3 + [ctypes.c_int64, c_vp]),
     "nic_adam_keras": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int64] + [ctypes.c_float] * 4 + [c_vp]),
 }
 

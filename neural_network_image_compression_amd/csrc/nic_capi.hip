@@ -464,7 +464,7 @@ bool models_ready(const nic_ctx* c, int m0) {
 
 extern "C" {
 
-int nic_version(void) { return 1300; }
+int nic_version(void) { return 1400; }
 
 int nic_constants(float* ycbcr9, float* ycbcr_inv9, float* off3) {
   // host copy of what nic_create uploads; lets tests compare with np.linalg.inv (utils.py:8)
@@ -1952,6 +1952,58 @@ int nic_rate_table_grad(const float* y, const float* L, const float* g, int m, i
                   (long long)need);
   }
   HIP_TRY(launch_rate_table_grad(y, L, g, m, h, w, channels, groups, dy, dL, work, (hipStream_t)stream));
+  return NIC_OK;
+}
+
+// the context rate loss: the static pair's shapes, a table three times as large, seg_pixels >= 1
+static int rate_ctable_shape(const char* who, int m, int h, int w, int channels, int groups) {
+  const int rc = rate_table_shape(who, m, h, w, channels, groups);
+  if (rc != NIC_OK) return rc;
+  if ((int64_t)groups * channels * 3 * 256 > INT32_MAX)
+    return fail(NIC_ESHAPE, "%s: bad shape m=%d %dx%dx%d groups=%d", who, m, h, w, channels, groups);
+  return NIC_OK;
+}
+
+int nic_rate_ctable_work(int m, int h, int w, int channels, int groups, int64_t* floats) {
+  if (!floats) return fail(NIC_EINVAL, "nic_rate_ctable_work: NULL argument");
+  const int rc = rate_ctable_shape("nic_rate_ctable_work", m, h, w, channels, groups);
+  if (rc != NIC_OK) return rc;
+  *floats = (int64_t)train_rate_ctable_work_floats(m, h, w, channels, groups);
+  return NIC_OK;
+}
+
+int nic_rate_ctable(const float* y, const float* yc, const float* L, const uint8_t* anchors, int m, int h, int w,
+                    int channels, int groups, int seg_pixels, float* plane_bits, float* work, int64_t work_floats,
+                    void* stream) {
+  const int rc = rate_ctable_shape("nic_rate_ctable", m, h, w, channels, groups);
+  if (rc != NIC_OK) return rc;
+  if (seg_pixels < 1) return fail(NIC_EINVAL, "nic_rate_ctable: seg_pixels %d < 1", seg_pixels);
+  if (m == 0) return NIC_OK;
+  if (!y || !L || !anchors || !plane_bits || !work) return fail(NIC_EINVAL, "nic_rate_ctable: NULL argument");
+  const int64_t need = (int64_t)train_rate_ctable_work_floats(m, h, w, channels, groups);
+  if (work_floats < need)
+    return fail(NIC_EINVAL, "nic_rate_ctable: work holds %lld floats, needs %lld", (long long)work_floats, (long long)need);
+  HIP_TRY(launch_rate_ctable(y, yc, L, anchors, m, h, w, channels, groups, seg_pixels, plane_bits, work,
+                             (hipStream_t)stream));
+  return NIC_OK;
+}
+
+int nic_rate_ctable_grad(const float* y, const float* yc, const float* L, const uint8_t* anchors, const float* g, int m,
+                         int h, int w, int channels, int groups, int seg_pixels, float* dy, float* dL, float* work,
+                         int64_t work_floats, void* stream) {
+  const int rc = rate_ctable_shape("nic_rate_ctable_grad", m, h, w, channels, groups);
+  if (rc != NIC_OK) return rc;
+  if (seg_pixels < 1) return fail(NIC_EINVAL, "nic_rate_ctable_grad: seg_pixels %d < 1", seg_pixels);
+  if (!dy && !dL) return fail(NIC_EINVAL, "nic_rate_ctable_grad: no gradient requested (dy and dL both NULL)");
+  if (m > 0) {
+    if (!y || !L || !anchors || !g || (dL && !work)) return fail(NIC_EINVAL, "nic_rate_ctable_grad: NULL argument");
+    const int64_t need = (int64_t)train_rate_ctable_work_floats(m, h, w, channels, groups);
+    if (dL && work_floats < need)
+      return fail(NIC_EINVAL, "nic_rate_ctable_grad: work holds %lld floats, needs %lld", (long long)work_floats,
+                  (long long)need);
+  }
+  HIP_TRY(launch_rate_ctable_grad(y, yc, L, anchors, g, m, h, w, channels, groups, seg_pixels, dy, dL, work,
+                                  (hipStream_t)stream));
   return NIC_OK;
 }
 

@@ -331,6 +331,14 @@ hipError_t launch_rate_table(const float* y, const float* L, int m, int h, int w
                              float* work, hipStream_t st);
 hipError_t launch_rate_table_grad(const float* y, const float* L, const float* g, int m, int h, int w, int c,
                                   int groups, float* dy, float* dL, float* work, hipStream_t st);
+// the context rate loss: the same under L (groups * c, 3, 256), the row picked by the left
+// neighbour's code in yc (NULL: y) against anchors (groups * c bytes); segments of seg_pixels
+size_t train_rate_ctable_work_floats(int m, int h, int w, int c, int groups);
+hipError_t launch_rate_ctable(const float* y, const float* yc, const float* L, const unsigned char* anchors, int m, int h,
+                              int w, int c, int groups, int seg_pixels, float* plane_bits, float* work, hipStream_t st);
+hipError_t launch_rate_ctable_grad(const float* y, const float* yc, const float* L, const unsigned char* anchors,
+                                   const float* g, int m, int h, int w, int c, int groups, int seg_pixels, float* dy,
+                                   float* dL, float* work, hipStream_t st);
 hipError_t launch_pool2_prep(const float* x, const float* y, int n, int h, int w, int pool, float* xp, float* yp,
                              float* pxy, float* pss, hipStream_t st);
 hipError_t launch_pool2_prep_grad(const float* dxp, const float* dyp, const float* dp, const float* dq, const float* xp,

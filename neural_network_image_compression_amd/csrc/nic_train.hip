@@ -671,6 +671,124 @@ __global__ __launch_bounds__(256) void rate_table_dl_reduce_kernel(const float* 
   dL[((long long)grp * C + c) * 256 + j] = total;
 }
 
+// ---- The context rate loss: the code length under the row the left neighbour selects ----------
+// L is (groups * C, 3, 256), anchors groups * C bytes.  Element (m, q, c), q the row-major pixel
+// inside plane m, reads row r's context
+//   x = 0 if q % seg == 0, else min(2, |(int)rintf(fminf(fmaxf(255 yc[m][q-1][c], 0), 255)) - anchors[r]|)
+// and then the table rate's element step on L[r][x].  q % seg != 0 implies q >= 1, so the left
+// read stays inside plane m.  The forward and dy keep the static kernels' structure (the same
+// elements per block and thread, the same tree, the same block order), so three equal rows give
+// the static bits and dy bit for bit.
+__device__ __forceinline__ int rate_ctx(const float* __restrict__ yc, long long elem, int C, int q, int seg, int anchor) {
+  if (q % seg == 0) return 0;
+  const float v = fminf(fmaxf(__fmul_rn(255.0f, yc[elem - C]), 0.0f), 255.0f);
+  return min(2, abs((int)rintf(v) - anchor));
+}
+__global__ __launch_bounds__(256) void rate_ctable_kernel(const float* __restrict__ y, const float* __restrict__ yc,
+                                                          const float* __restrict__ L,
+                                                          const unsigned char* __restrict__ anchors, int elems, int C,
+                                                          int ppg, int bpp, int seg, float* __restrict__ part) {
+  __shared__ float red[256];
+  const int m = blockIdx.x / bpp, bk = blockIdx.x - m * bpp, t = threadIdx.x;
+  const int r0 = (m / ppg) * C;
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < kRatePix / 256; ++i) {
+    const int e = bk * kRatePix + i * 256 + t;
+    if (e < elems) {
+      const long long idx = (long long)m * elems + e;
+      const int q = e / C, r = r0 + (e - q * C);
+      const int x = rate_ctx(yc, idx, C, q, seg, anchors[r]);
+      const RateElem el = rate_elem(y[idx]);
+      const float* row = L + ((long long)r * 3 + x) * 256;
+      const float l0 = row[el.k];
+      s = __fadd_rn(s, __fadd_rn(l0, __fmul_rn(el.t, __fsub_rn(row[el.k + 1], l0))));
+    }
+  }
+  red[t] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (t < o) red[t] = __fadd_rn(red[t], red[t + o]);
+    __syncthreads();
+  }
+  if (t == 0) part[blockIdx.x] = red[0];
+}
+__global__ __launch_bounds__(256) void rate_ctable_dy_kernel(const float* __restrict__ y, const float* __restrict__ yc,
+                                                             const float* __restrict__ L,
+                                                             const unsigned char* __restrict__ anchors,
+                                                             const float* __restrict__ g, long long total, int elems,
+                                                             int C, int ppg, int seg, float* __restrict__ dy) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int m = (int)(i / elems), e = (int)(i - (long long)m * elems), q = e / C;
+    const int r = (m / ppg) * C + (e - q * C);
+    const float* row = L + ((long long)r * 3 + rate_ctx(yc, i, C, q, seg, anchors[r])) * 256;
+    const RateElem el = rate_elem(y[i]);
+    dy[i] = __fmul_rn(__fmul_rn(255.0f, g[m]), __fsub_rn(row[el.k + 1], row[el.k]));
+  }
+}
+// dL[r][x][j]: rate_table_dl_kernel once per context.  Block (group, slab, x) is one wave with the
+// static kernel's 64 KB of replicas [replica][j][c]; thread (replica, c) takes the same pixels in
+// the same order and does its two read-modify-writes only where the pixel's context is x, so every
+// word still has one writer and one order.  A slab that begins mid-segment reads its left pixel
+// from the slab before it in global memory (never from before its plane: see rate_ctx).  The
+// block's partial goes to part[(group, slab, x)][j][c]; the reduce adds a (group, x)'s slabs in the
+// static reduce's order.  With every pixel in context 0 the x = 0 blocks do exactly the static
+// kernel's work.
+__global__ __launch_bounds__(64) void rate_ctable_dl_kernel(const float* __restrict__ y, const float* __restrict__ yc,
+                                                            const unsigned char* __restrict__ anchors,
+                                                            const float* __restrict__ g, int C, int hw, long long P,
+                                                            int spg, int seg, float* __restrict__ part) {
+  __shared__ float tab[kRateLdsFloats];
+  const int R = 64 / C, T = C * 256, t = threadIdx.x, rep = t / C, c = t - rep * C;
+  const int x = blockIdx.x % 3, gs = blockIdx.x / 3, grp = gs / spg, slab = gs - grp * spg;
+  for (int i = t; i < R * T; i += 64) tab[i] = 0.f;
+  __syncthreads();
+  if (rep < R) {
+    float* mine = tab + rep * T + c;
+    const int anchor = anchors[grp * C + c];
+    const long long p0 = (long long)slab * kRateSlab, p1 = p0 + kRateSlab < P ? p0 + kRateSlab : P;
+    for (long long p = p0 + rep; p < p1; p += R) {
+      const long long px = (long long)grp * P + p, plane = px / hw;
+      const long long idx = px * C + c;
+      if (rate_ctx(yc, idx, C, (int)(px - plane * hw), seg, anchor) != x) continue;
+      const float gm = g[plane];
+      const RateElem q = rate_elem(y[idx]);
+      float* lo = mine + q.k * C;
+      lo[0] = __fadd_rn(lo[0], __fmul_rn(gm, __fsub_rn(1.0f, q.t)));
+      lo[C] = __fadd_rn(lo[C], __fmul_rn(gm, q.t));
+    }
+  }
+  __syncthreads();
+  for (int i = t; i < T; i += 64) {
+    float s = tab[i];
+    for (int r = 1; r < R; ++r) s = __fadd_rn(s, tab[r * T + i]);
+    part[(long long)blockIdx.x * T + i] = s;
+  }
+}
+__global__ __launch_bounds__(256) void rate_ctable_dl_reduce_kernel(const float* __restrict__ part, int groups, int C,
+                                                                    int spg, float* __restrict__ dL) {
+  const int T = C * 256, i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= groups * 3 * T) return;
+  const int gx = i / T, rem = i - gx * T, grp = gx / 3, x = gx - grp * 3, j = rem / C, c = rem - j * C;
+  const float* src = part + ((long long)grp * spg * 3 + x) * T + rem;  // slab b at src[b * 3 T]
+  const long long step = 3LL * T;
+  float total = 0.f;
+  for (int b0 = 0; b0 < spg; b0 += 64) {
+    float s3 = 0.f;
+    for (int b1 = b0; b1 < b0 + 64 && b1 < spg; b1 += 16) {
+      float s2 = 0.f;
+      for (int b2 = b1; b2 < b1 + 16 && b2 < spg; b2 += 4) {
+        float s1 = 0.f;
+        for (int b = b2; b < b2 + 4 && b < spg; ++b) s1 = __fadd_rn(s1, src[b * step]);
+        s2 = __fadd_rn(s2, s1);
+      }
+      s3 = __fadd_rn(s3, s2);
+    }
+    total = __fadd_rn(total, s3);
+  }
+  dL[(((long long)grp * C + c) * 3 + x) * 256 + j] = total;
+}
+
 // The step between scales (tf.image.ssim_multiscale: an odd height or width SYMMETRIC-padded by
 // one on the far side, i.e. its last row / column repeated, then a 2x2 average pool, stride 2) and
 // the two product planes the Gaussian reads next.  One thread per four output columns of one output
@@ -1248,6 +1366,53 @@ hipError_t launch_rate_table_grad(const float* y, const float* L, const float* g
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(rate_table_dl_reduce_kernel, dim3((unsigned)((groups * c * 256 + 255) / 256)), dim3(256), 0, st,
                        work, groups, c, (int)spg, dL);
+    return hipGetLastError();
+  }
+  return hipSuccess;
+}
+
+// the context rate: the forward's partials as above, or a C x 256 partial table per block of
+// kRateSlab pixels of a group and per context: three times the static backward's term
+size_t train_rate_ctable_work_floats(int m, int h, int w, int c, int groups) {
+  const long long fwd = rate_fwd_blocks(m, h, w, c), bwd = 3LL * groups * rate_slabs(m, h, w, groups) * c * 256;
+  return (size_t)(fwd > bwd ? fwd : bwd);
+}
+
+hipError_t launch_rate_ctable(const float* y, const float* yc, const float* L, const unsigned char* anchors, int m, int h,
+                              int w, int c, int groups, int seg_pixels, float* plane_bits, float* work, hipStream_t st) {
+  if (m == 0) return hipSuccess;
+  const int elems = h * w * c, bpp = (elems + kRatePix - 1) / kRatePix;
+  if ((long long)m * bpp > INT32_MAX) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(rate_ctable_kernel, dim3((unsigned)(m * bpp)), dim3(256), 0, st, y, yc ? yc : y, L, anchors, elems,
+                     c, m / groups, bpp, seg_pixels, work);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(rate_table_sum_kernel, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, st, work, m, bpp, plane_bits);
+  return hipGetLastError();
+}
+
+hipError_t launch_rate_ctable_grad(const float* y, const float* yc, const float* L, const unsigned char* anchors,
+                                   const float* g, int m, int h, int w, int c, int groups, int seg_pixels, float* dy,
+                                   float* dL, float* work, hipStream_t st) {
+  if (m == 0) return dL ? hipMemsetAsync(dL, 0, (size_t)groups * c * 3 * 256 * sizeof(float), st) : hipSuccess;
+  const int elems = h * w * c;
+  if (!yc) yc = y;
+  if (dy) {
+    const long long total = (long long)m * elems, blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(rate_ctable_dy_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, y, yc,
+                       L, anchors, g, total, elems, c, m / groups, seg_pixels, dy);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  if (dL) {
+    const long long spg = rate_slabs(m, h, w, groups);
+    if (3LL * groups * spg > INT32_MAX) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rate_ctable_dl_kernel, dim3((unsigned)(3 * groups * spg)), dim3(64), 0, st, y, yc, anchors, g, c,
+                       h * w, (long long)(m / groups) * h * w, (int)spg, seg_pixels, work);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(rate_ctable_dl_reduce_kernel, dim3((unsigned)((groups * 3 * c * 256 + 255) / 256)), dim3(256), 0,
+                       st, work, groups, c, (int)spg, dL);
     return hipGetLastError();
   }
   return hipSuccess;

@@ -101,14 +101,9 @@ def pseudo_counts(p) -> np.ndarray:
     return np.rint(a * float(1 << PSEUDO_COUNT_BITS)).astype(np.int64)
 
 
-def from_probabilities(p) -> Prior:
-    """A Prior from a (96, 256) float64 table of probabilities (a trained table's softmax,
-    training.Training.prior): pseudo-counts c = rint(p 2^40), normalised on the host by the rule of
-    nic_rans_prior_build (DESIGN section 12): f = max(1, floor(4096 c / N)) with N the row's count;
-    a deficit goes onto the largest entry, a surplus is taken one at a time from the currently
-    largest entry, the lowest symbol on ties; N = 0 gives 16 everywhere."""
-    counts = pseudo_counts(p)
-    freqs = np.empty((CHANNELS, 256), np.int64)
+def _normalise(counts: np.ndarray) -> np.ndarray:
+    """Rows of int64 counts -> freqs by nic_rans_prior_build's rule (from_probabilities states it)."""
+    freqs = np.empty(counts.shape, np.int64)
     for r, c in enumerate(counts):
         n = int(c.sum())
         f = np.maximum(1, (c << 12) // n) if n else np.full(256, 16, np.int64)  # c 4096 < 2^53
@@ -118,7 +113,16 @@ def from_probabilities(p) -> Prior:
         for _ in range(-diff):
             f[np.argmax(f)] -= 1
         freqs[r] = f
-    return Prior(freqs)
+    return freqs
+
+
+def from_probabilities(p) -> Prior:
+    """A Prior from a (96, 256) float64 table of probabilities (a trained table's softmax,
+    training.Training.prior): pseudo-counts c = rint(p 2^40), normalised on the host by the rule of
+    nic_rans_prior_build (DESIGN section 12): f = max(1, floor(4096 c / N)) with N the row's count;
+    a deficit goes onto the largest entry, a surplus is taken one at a time from the currently
+    largest entry, the lowest symbol on ties; N = 0 gives 16 everywhere."""
+    return Prior(_normalise(pseudo_counts(p)))
 
 
 def as_prior(prior):
@@ -282,3 +286,21 @@ class ContextPriorAccumulator:
 
     def build(self) -> ContextPrior:
         return ContextPrior(self.anchors, self.codec.cprior_build(self.counts).cpu().numpy())
+
+
+def context_pseudo_counts(p) -> np.ndarray:
+    """(96, 3, 256) probabilities -> the int64 pseudo-counts rint(p 2^40) that
+    context_from_probabilities normalises (and nic_rans_cprior_build normalises to the same freqs)."""
+    a = np.asarray(p, dtype=np.float64)
+    if a.shape != (CHANNELS, CONTEXTS, 256) or not np.all(np.isfinite(a)) or a.min() < 0 or \
+            np.abs(a.sum(axis=2) - 1.0).max() > 1e-6:
+        raise ValueError("context_from_probabilities: expected (96, 3, 256) probabilities, every row summing to 1")
+    return np.rint(a * float(1 << PSEUDO_COUNT_BITS)).astype(np.int64)
+
+
+def context_from_probabilities(anchors, p) -> ContextPrior:
+    """A ContextPrior from 96 anchors and a (96, 3, 256) float64 table of probabilities (a trained
+    context table's softmax, training.Training.context_prior): from_probabilities' pseudo-count
+    rule applied to every (channel, context) row."""
+    counts = context_pseudo_counts(p)
+    return ContextPrior(anchors, _normalise(counts.reshape(-1, 256)).reshape(CHANNELS, CONTEXTS, 256))

@@ -21,7 +21,9 @@ correlation and its adjoint, ``nic_gauss_1d``) and both per-plane means of the s
 
 The table rate loss (``rate_table``, ``Training(rate="table")``) is ``nic_rate_table`` and
 ``nic_rate_table_grad``: per-plane code lengths under a table of -log2 p, the latent's gradient
-and the table's (no atomics; each only when asked for).
+and the table's (no atomics; each only when asked for).  The context rate loss (``rate_ctable``,
+``Training(rate="context")``) is ``nic_rate_ctable`` and ``nic_rate_ctable_grad``: the same under
+the one of three rows per channel that the left neighbour's code selects, what .nic version 3 prices.
 
 Each operand gets a power-of-two scale (max |t| * scale in [2^13, 2^14)) computed on the
 device once per tensor (x and the kernel in the forward, dy in the backward), so the f16 hi/lo split keeps tiny gradients exact to ~2^-22.  The layers' leaky-ReLU runs in
@@ -314,8 +316,88 @@ def rate_table_grad(y, L, g, groups: int, want_dy: bool = True, want_dl: bool = 
     return dy, dl
 
 
+def _rate_ctable_args(who, y, yc, L, anchors, groups: int, seg_pixels: int):
+    """The checked operands of the context rate calls and nic_rate_ctable_work's count."""
+    torch = _torch()
+    y, L = _check(y, f"{who} y"), _check(L, f"{who} L")
+    m, h, w, c = y.shape
+    if L.dim() != 3 or tuple(L.shape) != (groups * c, 3, 256):
+        raise ValueError(f"{who}: L must be ({groups * c}, 3, 256) for {groups} groups of {c} channels, "
+                         f"got {tuple(L.shape)}")
+    if (not isinstance(anchors, torch.Tensor) or anchors.dtype != torch.uint8 or tuple(anchors.shape) != (groups * c,)
+            or not anchors.is_contiguous()):
+        raise ValueError(f"{who}: anchors must be a contiguous ({groups * c},) torch.uint8 tensor")
+    if yc is not None:
+        yc = _check(yc, f"{who} yc")
+        if yc.shape != y.shape:
+            raise ValueError(f"{who}: yc {tuple(yc.shape)} is not y's shape {tuple(y.shape)}")
+    if int(seg_pixels) < 1:
+        raise ValueError(f"{who}: seg_pixels must be at least 1, not {seg_pixels}")
+    dev = _same_device(y, yc, L, anchors)
+    need = max(m * -(-(h * w * c) // RATE_PIX), 3 * groups * -(-(m // max(groups, 1) * h * w) // RATE_SLAB) * c * 256)
+    return y, yc, L, dev, (m, h, w, c), need
+
+
+def rate_ctable_bits(y, L, anchors, groups: int, seg_pixels: int, yc=None):
+    """nic_rate_ctable: the (m,) code lengths in bits of the planes of y (m, h, w, c) NHWC under the
+    context table L (groups * c, 3, 256) of -log2 p; the row of an element is picked by its left
+    neighbour's code in yc (None: y) against anchors ((groups * c,) u8), segments of seg_pixels."""
+    torch = _torch()
+    y, yc, L, dev, (m, h, w, c), need = _rate_ctable_args("rate_ctable", y, yc, L, anchors, groups, seg_pixels)
+    bits = torch.empty((m,), dtype=torch.float32, device=y.device)
+    work = torch.empty(max(need, 1), dtype=torch.float32, device=y.device)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().nic_rate_ctable(
+            y.data_ptr(), yc.data_ptr() if yc is not None else None, L.data_ptr(), anchors.data_ptr(), m, h, w, c, groups,
+            int(seg_pixels), bits.data_ptr(), work.data_ptr(), need, _stream(dev)), "nic_rate_ctable")
+    return bits
+
+
+def rate_ctable_grad(y, L, anchors, g, groups: int, seg_pixels: int, yc=None, want_dy: bool = True,
+                     want_dl: bool = True):
+    """nic_rate_ctable_grad: (dy, dL) of sum_m g[m] plane_bits[m]; one is None when not wanted (its
+    pointer goes down as NULL and its kernels do not run).  yc and anchors get no gradient."""
+    torch = _torch()
+    y, yc, L, dev, (m, h, w, c), need = _rate_ctable_args("rate_ctable_grad", y, yc, L, anchors, groups, seg_pixels)
+    g = _check(g, "rate_ctable_grad g")
+    _same_device(y, g)
+    if g.numel() != m:
+        raise ValueError("rate_ctable_grad: one g per plane")
+    dy = torch.empty_like(y) if want_dy else None
+    dl = torch.empty_like(L) if want_dl else None
+    work = torch.empty(max(need, 1), dtype=torch.float32, device=y.device) if want_dl else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().nic_rate_ctable_grad(
+            y.data_ptr(), yc.data_ptr() if yc is not None else None, L.data_ptr(), anchors.data_ptr(), g.data_ptr(), m, h,
+            w, c, groups, int(seg_pixels), dy.data_ptr() if want_dy else None, dl.data_ptr() if want_dl else None,
+            work.data_ptr() if want_dl else None, need if want_dl else 0, _stream(dev)), "nic_rate_ctable_grad")
+    return dy, dl
+
+
 def _conv_fn():
     torch = _torch()
+
+    class RateCTable(torch.autograd.Function):
+        """Per-plane code length of y (m, h, w, c) under the context table L (groups * c, 3, 256)
+        (nic_rate_ctable / nic_rate_ctable_grad); a gradient nobody asked for is not computed, and
+        yc and anchors never get one (the context is piecewise constant)."""
+
+        @staticmethod
+        def forward(ctx, y, L, anchors, groups, seg_pixels, yc):
+            y, L = _check(y, "RateCTable y"), _check(L, "RateCTable L")
+            yc = None if yc is None else _check(yc.detach(), "RateCTable yc")
+            ctx.save_for_backward(y, L, anchors, yc)
+            ctx.groups, ctx.seg_pixels = groups, seg_pixels
+            return rate_ctable_bits(y, L, anchors, groups, seg_pixels, yc)
+
+        @staticmethod
+        def backward(ctx, g):
+            y, L, anchors, yc = ctx.saved_tensors
+            want_dy, want_dl = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+            if not (want_dy or want_dl):
+                return None, None, None, None, None, None
+            dy, dl = rate_ctable_grad(y, L, anchors, g.contiguous(), ctx.groups, ctx.seg_pixels, yc, want_dy, want_dl)
+            return dy, dl, None, None, None, None
 
     class RateTable(torch.autograd.Function):
         """Per-plane code length of y (m, h, w, c) under the table L (groups * c, 256) of -log2 p
@@ -468,11 +550,11 @@ def _conv_fn():
                               *ctx.consts, out=out)
             return out, None, None
 
-    return _Fns(Conv2DSame, Conv2DTransposeSame, Gauss1D, Pool2Prep, MsssimTerms, RateTable)
+    return _Fns(Conv2DSame, Conv2DTransposeSame, Gauss1D, Pool2Prep, MsssimTerms, RateTable, RateCTable)
 
 
 # the autograd classes, looked up by name (callers that still index find the two convolutions first)
-_Fns = namedtuple("_Fns", "Conv2DSame Conv2DTransposeSame Gauss1D Pool2Prep MsssimTerms RateTable")
+_Fns = namedtuple("_Fns", "Conv2DSame Conv2DTransposeSame Gauss1D Pool2Prep MsssimTerms RateTable RateCTable")
 _FNS = None
 
 
@@ -498,6 +580,14 @@ def rate_table(y, L, groups: int):
     (groups * c, 256) of -log2 p, plane i reading the rows of group i // (m / groups) (HIP,
     differentiable in y and in L; training.table_rate states the formula)."""
     return _fns().RateTable.apply(y, L, int(groups))
+
+
+def rate_ctable(y, L, anchors, groups: int, seg_pixels: int, yc=None):
+    """The (m,) code lengths in bits of the planes of y (m, h, w, c) NHWC under the context table L
+    (groups * c, 3, 256) of -log2 p: an element reads the row its left neighbour's code in yc (None:
+    y) selects against anchors ((groups * c,) u8), a segment's first pixel row 0 (HIP,
+    differentiable in y and in L, never in yc or anchors; training.context_rate states the formula)."""
+    return _fns().RateCTable.apply(y, L, anchors, int(groups), int(seg_pixels), yc)
 
 
 SSIM_PIX = 1024  # map pixels per block of nic_msssim_terms (its work: two partial sums per block)

@@ -23,6 +23,9 @@ restated so that trained weights exist for the codec and the config-4 RD sweep:
   of the noisy latent under a learnable 96 x 256 table (:func:`table_rate`), the quantity .nic
   version 2 prices; the third tape fits the table instead of an Entropynet, nothing runs on the
   host, and ``Training.prior()`` exports the table as the container's ``.nicp``.
+* ``Training(rate="context")``: the rate term is the code length under a learnable 96 x 3 x 256
+  context table (:func:`context_rate`), the row picked by the left neighbour's code, the quantity
+  .nic version 3 prices; ``Training.context_prior()`` exports the ``.nicc``.
 * ``_save`` (training.py:167-172) writes the reference's own TF checkpoint format
   (``weights.save_tf``), which ``ProClass.load`` / the HIP codec read back.
 
@@ -275,6 +278,69 @@ def table_rate(y, logits, groups: int, hip: bool = False):
     return table_bits(y, table_code_lengths(logits), groups, hip)
 
 
+CONTEXTS = 3  # prior.ContextPrior's rows per channel
+
+
+def context_code_lengths(logits):
+    """L = -log2(softmax(logits, dim=-1)) of context logits (rows, 3, 256); differentiable."""
+    torch = _torch()
+    return -torch.log2(torch.softmax(logits, dim=-1))
+
+
+def context_bits(y, L, anchors, groups: int, seg_pixels: int = 32, yc=None, hip: bool = False):
+    """:func:`context_rate` from the code lengths L (groups * C, 3, 256) themselves."""
+    torch = _torch()
+    if hip:
+        from . import train_hip
+
+        return train_hip.rate_ctable(y, L, anchors, groups, seg_pixels, yc)
+    m, c, h, w = y.shape
+    if groups < 1 or m % groups or L.dim() != 3 or tuple(L.shape) != (groups * c, CONTEXTS, 256):
+        raise ValueError(f"context_rate: {m} planes of {c} channels in {groups} groups need a ({groups * c}, 3, 256) "
+                         f"table, got {tuple(L.shape)}")
+    if tuple(anchors.shape) != (groups * c,) or anchors.dtype != torch.uint8:
+        raise ValueError(f"context_rate: anchors must be ({groups * c},) torch.uint8")
+    if yc is not None and yc.shape != y.shape:
+        raise ValueError("context_rate: yc must have y's shape")
+    if int(seg_pixels) < 1:
+        raise ValueError(f"context_rate: seg_pixels must be at least 1, not {seg_pixels}")
+    zero, top = y.new_zeros(()), y.new_full((), 255.0)
+    group = torch.arange(m, device=y.device) // max(m // groups, 1)
+    rows2 = group[:, None] * c + torch.arange(c, device=y.device)[None, :]  # (M, C)
+    with torch.no_grad():  # the context: piecewise constant, nothing flows through it
+        src = (y if yc is None else yc).detach()
+        code = torch.fmin(torch.fmax(255 * src, zero), top).round().long()  # (M, C, h, w); a NaN becomes 0
+        code = code.reshape(m, c, h * w)
+        ctx = torch.zeros_like(code)
+        ctx[:, :, 1:] = (code[:, :, :-1] - anchors.long()[rows2][:, :, None]).abs().clamp(max=2)
+        ctx[:, :, ::int(seg_pixels)] = 0
+        ctx = ctx.reshape(m, c, h, w)
+    v = torch.fmin(torch.fmax(255 * y, zero), top)  # a NaN becomes 0
+    k = v.detach().floor().clamp(max=254).long()
+    t = v - k.to(v.dtype)
+    rows = rows2[:, :, None, None]
+    l0 = L[rows, ctx, k]
+    bits = l0 + t * (L[rows, ctx, k + 1] - l0)
+    return bits.sum(dim=(1, 2, 3))
+
+
+def context_rate(y, logits, anchors, groups: int, seg_pixels: int = 32, yc=None, hip: bool = False):
+    """The code length in bits of each latent plane under a learnable context table, the quantity
+    .nic version 3 prices: y (M, C, h, w) NCHW in [0, 1] (``hip``: (M, h, w, C) NHWC, on the HIP
+    kernels, train_hip.rate_ctable), logits (groups * C, 3, 256), anchors (groups * C,) u8, M divisible
+    by groups -> (M,); differentiable in y and logits.  With L = -log2(softmax(logits, dim=-1)), rows
+    as :func:`table_rate`'s, element (m, q, c) -- q the row-major pixel inside plane m -- reads context
+        x = 0 if q % seg_pixels == 0, else min(2, |round(fmin(fmax(255 yc[m][q-1][c], 0), 255)) - anchors[r]|)
+    (round to nearest even; yc, the tensor the contexts are read from, defaults to y; the left
+    neighbour is the previous pixel in memory order, never one of another plane) and then
+    :func:`table_rate`'s element step on L[r][x].  At y = yc = code / 255 that is the symbol's ideal
+    code length under the row version 3 codes it with.  The context is computed under no_grad: it is
+    piecewise constant, nothing flows to yc or through the neighbour.  This PyTorch restatement is
+    the CPU path and what the kernels are tested against (its gradient in y is 0 outside [0, 1], where
+    the kernel keeps the end slope; the step's latents are clamped)."""
+    return context_bits(y, context_code_lengths(logits), anchors, groups, seg_pixels, yc, hip)
+
+
 def png_bpp_planes(encoded_u8: np.ndarray, tot_pixels: float, threads: int = 16, mode: str = "tf") -> np.ndarray:
     """get_bpp (training.py:14-21): latent planes (M,h,w,32) u8 -> (M,) 8*len(PNG((4h,8w)))/pixels.
 
@@ -353,7 +419,7 @@ class Training:
     def __init__(self, device: str = "cuda", weights: Optional[W.Weights] = None, seed: int = 0,
                  checkpoint_dir: str = "../checkpoints/", backend: Optional[str] = None,
                  png_threads: int = 16, distortion: str = "ssim", ms_scales: int = 4, rate: str = "png",
-                 table_lr: float = 1e-2):
+                 table_lr: float = 1e-2, anchors=None, seg_pixels: int = 32):
         """backend "hip" (default on a GPU): every convolution of the step, forward and
         backward, on the HIP split-f16x3 MFMA kernels (train_hip, NHWC); "torch" (default on
         the CPU): PyTorch autograd convolutions (MIOpen / oneDNN, NCHW) -- the restatement the
@@ -365,7 +431,14 @@ class Training:
         (:func:`table_rate`; ``table_logits``, zeros: 8 bits per symbol), fitted by maximum
         likelihood in the same step with its own Adam at ``table_lr`` (an untuned choice) and
         exported by :meth:`prior` as the .nicp that .nic version 2 codes under -- no Entropynet, no
-        PNG encode and no host work in the step, and no parameter shaped by the patch size."""
+        PNG encode and no host work in the step, and no parameter shaped by the patch size.
+        "context": the code length under a learnable 96 x 3 x 256 context table (:func:`context_rate`;
+        ``ctx_logits``), the row picked by the clean left neighbour's code against ``anchors``, what
+        .nic version 3 prices; the static table is fitted beside it and :meth:`context_prior`
+        exports the .nicc.  ``anchors``: a prior.Prior (its rows' argmax), a prior.ContextPrior (its
+        anchors) or 96 integers, which then stay fixed; None: zeros, set by :meth:`refresh_anchors`
+        to the static table's argmax at the start of every epoch.  ``seg_pixels``: the container's
+        segment length (a segment's first pixel is context 0)."""
         torch = _torch()
         backend = backend or ("hip" if torch.device(device).type == "cuda" else "torch")
         if backend not in ("hip", "torch"):
@@ -374,8 +447,10 @@ class Training:
             raise ValueError(f"distortion must be 'ssim' or 'ms_ssim', not {distortion!r}")
         if not 1 <= ms_scales <= len(MSSSIM_WEIGHTS):
             raise ValueError(f"ms_scales must be 1..{len(MSSSIM_WEIGHTS)}, not {ms_scales}")
-        if rate not in ("png", "table"):
-            raise ValueError(f"rate must be 'png' or 'table', not {rate!r}")
+        if rate not in ("png", "table", "context"):
+            raise ValueError(f"rate must be 'png', 'table' or 'context', not {rate!r}")
+        if int(seg_pixels) < 1:
+            raise ValueError(f"seg_pixels must be at least 1, not {seg_pixels}")
         self.distortion, self.ms_scales = distortion, ms_scales
         self.rate, self.table_lr = rate, table_lr
         self.hip = backend == "hip"
@@ -389,9 +464,15 @@ class Training:
         self.checkpoint_dir = checkpoint_dir
         self.entropy_model: Optional[Entropynet] = None
         self.table_logits = None
-        if rate == "table":
+        if rate in ("table", "context"):
             self.table_logits = torch.zeros((TABLE_GROUPS * TABLE_CHANNELS, 256), dtype=torch.float32,
                                             device=self.device, requires_grad=True)
+        self.ctx_logits = self.anchors = None
+        self.anchors_fixed, self.seg_pixels = anchors is not None, int(seg_pixels)
+        if rate == "context":
+            self.ctx_logits = torch.zeros((TABLE_GROUPS * TABLE_CHANNELS, CONTEXTS, 256), dtype=torch.float32,
+                                          device=self.device, requires_grad=True)
+            self.anchors = torch.from_numpy(self._anchor_bytes(anchors)).to(self.device)
         self._opt = None
         self._gen = torch.Generator(device=self.device).manual_seed(seed)
         # the PNG-size target (get_bpp, training.py:14-21: 3B PNG encodes per step) runs on
@@ -409,8 +490,36 @@ class Training:
         return [v for k, v in self.params.items() if k.startswith("encoder" + plane + "/") or
                 k.startswith("decoder" + plane + "/")]
 
+    @staticmethod
+    def _anchor_bytes(anchors) -> np.ndarray:
+        """The (96,) u8 anchors of a Prior, a ContextPrior, 96 integers, or None (zeros)."""
+        from . import prior as P
+
+        n = TABLE_GROUPS * TABLE_CHANNELS
+        if anchors is None:
+            return np.zeros(n, np.uint8)
+        if isinstance(anchors, P.Prior):
+            return P.anchors_of(anchors).copy()
+        if isinstance(anchors, P.ContextPrior):
+            return anchors.anchors.copy()
+        a = np.asarray(anchors)
+        if a.shape != (n,) or a.dtype.kind not in "iu" or a.min() < 0 or a.max() > 255:
+            raise ValueError(f"anchors must be a Prior, a ContextPrior or {n} integers in 0..255")
+        return a.astype(np.uint8)
+
+    def refresh_anchors(self) -> None:
+        """Sets the anchors to the argmax of each row of ``table_logits``, the lowest symbol on ties
+        (prior.anchors_of's rule); anchors given to the constructor stay as they are.  A changed
+        anchor re-labels that channel's three rows of ``ctx_logits``."""
+        if self.rate != "context" or self.anchors_fixed:
+            return
+        a = np.argmax(self.table_logits.detach().cpu().numpy(), axis=1).astype(np.uint8)
+        self.anchors.copy_(_torch().from_numpy(a))
+
     def _rate_params(self) -> List[object]:
-        """What the third tape trains: the Entropynet, or the table."""
+        """What the third tape trains: the Entropynet, or the table(s)."""
+        if self.rate == "context":
+            return [self.table_logits, self.ctx_logits]
         return [self.table_logits] if self.rate == "table" else self.entropy_model.parameters()
 
     def _setup(self, hw):
@@ -427,7 +536,7 @@ class Training:
                 mk = lambda ps, lr=1e-4: KerasAdam(ps, lr=lr, beta1=0.9, beta2=ADAM_BETA2, epsilon=KERAS_ADAM_EPS)  # noqa: E731
             else:
                 mk = lambda ps, lr=1e-4: torch.optim.Adam(ps, lr=lr, betas=(0.9, ADAM_BETA2), eps=KERAS_ADAM_EPS)  # noqa: E731
-            third = mk(self._rate_params(), self.table_lr) if self.rate == "table" else mk(self._rate_params())
+            third = mk(self._rate_params(), self.table_lr) if self.rate != "png" else mk(self._rate_params())
             self._opt = (mk(self._variables("Y")), mk(self._variables("CbCr")), third)
 
     def train_step(self, images, entropy_loss_coef: float, flip: bool = True) -> Dict[str, object]:
@@ -442,7 +551,7 @@ class Training:
         gy = torch.autograd.grad(loss0, self._variables("Y"), retain_graph=True)
         gc = torch.autograd.grad(loss1, self._variables("CbCr"), retain_graph=True)
         aprox_entropy_loss = self.finish_entropy_loss(f)
-        ge = torch.autograd.grad(aprox_entropy_loss, ent_params)
+        ge = torch.autograd.grad(f.get("third_loss", aprox_entropy_loss), ent_params)
         for opt, params, grads in ((opt_y, self._variables("Y"), gy), (opt_c, self._variables("CbCr"), gc),
                                    (opt_e, ent_params, ge)):
             if not isinstance(opt, torch.optim.Optimizer):  # train_hip.KerasAdam
@@ -538,6 +647,20 @@ class Training:
             latents = torch.cat([noisy0, noisy1], dim=0).detach()
             rate = {"bpp": aprox.detach().view(-1),
                     "entropy_loss": (table_bits(latents, code_len, TABLE_GROUPS, hip) / pixels).mean()}
+        elif self.rate == "context":
+            # the context table's bpp of the noisy latents, the contexts read from the clean encoder
+            # output (a file's contexts are its real codes); the codec tapes read it through the code
+            # lengths detached, the third tape fits both tables with the latents detached
+            pixels = float(x.shape[1] * x.shape[2])
+            ctx_len, code_len = context_code_lengths(self.ctx_logits), table_code_lengths(self.table_logits)
+            fixed, a, seg, nc = ctx_len.detach(), self.anchors, self.seg_pixels, TABLE_CHANNELS
+            clean0, clean1 = enc0.detach(), enc1.detach()
+            aprox = torch.cat([context_bits(noisy0, fixed[:nc], a[:nc], 1, seg, clean0, hip),
+                               context_bits(noisy1, fixed[nc:], a[nc:], 2, seg, clean1, hip)]).view(-1, 1) / pixels
+            latents, clean = torch.cat([noisy0, noisy1], dim=0).detach(), torch.cat([clean0, clean1], dim=0)
+            ctx_loss = (context_bits(latents, ctx_len, a, TABLE_GROUPS, seg, clean, hip) / pixels).mean()
+            rate = {"bpp": aprox.detach().view(-1), "entropy_loss": ctx_loss,
+                    "third_loss": ctx_loss + (table_bits(latents, code_len, TABLE_GROUPS, hip) / pixels).mean()}
         else:
             batch_enc = torch.cat([enc0, enc1], dim=0)
             aprox = self.entropy_model(batch_enc, hip)  # (3B, 1)
@@ -571,8 +694,10 @@ class Training:
         w = self.weights()
         W.save_tf(w, os.path.join(self.checkpoint_dir, "encoder"), "encoder")
         W.save_tf(w, os.path.join(self.checkpoint_dir, "decoder"), "decoder")
-        if self.rate == "table":
+        if self.rate in ("table", "context"):
             self.prior().save(os.path.join(self.checkpoint_dir, "prior.nicp"))
+        if self.rate == "context":
+            self.context_prior().save(os.path.join(self.checkpoint_dir, "prior.nicc"))
 
     def prior(self):
         """The table as the :class:`prior.Prior` that ``compress(..., container="nic", prior=p)``
@@ -580,11 +705,23 @@ class Training:
         :func:`prior.from_probabilities`."""
         from . import prior as P
 
-        if self.rate != "table":
-            raise ValueError("prior(): only Training(rate='table') has a table to export")
+        if self.rate not in ("table", "context"):
+            raise ValueError("prior(): only Training(rate='table') or 'context' has a table to export")
         z = self.table_logits.detach().cpu().numpy().astype(np.float64)
         e = np.exp(z - z.max(axis=1, keepdims=True))
         return P.from_probabilities(e / e.sum(axis=1, keepdims=True))
+
+    def context_prior(self):
+        """The context table and the anchors as the :class:`prior.ContextPrior` that
+        ``compress(..., container="nic", prior=cp)`` codes version-3 files under:
+        softmax(ctx_logits) in float64 on the host, through :func:`prior.context_from_probabilities`."""
+        from . import prior as P
+
+        if self.rate != "context":
+            raise ValueError("context_prior(): only Training(rate='context') has a context table to export")
+        z = self.ctx_logits.detach().cpu().numpy().astype(np.float64)
+        e = np.exp(z - z.max(axis=2, keepdims=True))
+        return P.context_from_probabilities(self.anchors.cpu().numpy(), e / e.sum(axis=2, keepdims=True))
 
     def __call__(self, x: np.ndarray, x_val_path: Optional[str], max_epochs: int, batch_size: int,
                  entropy_loss_coef: float, verbose: bool = True,
@@ -602,6 +739,7 @@ class Training:
         per_epoch = epoch_samples or len(x)
         for epoch in range(self.epoch, max_epochs):
             self.epoch = epoch
+            self.refresh_anchors()  # rate="context" without given anchors; otherwise nothing
             order = np.concatenate([rng.permutation(len(x)) for _ in range(-(-per_epoch // len(x)))])[:per_epoch]
             for i in range(0, per_epoch, batch_size):
                 m = self.train_step(torch.from_numpy(np.ascontiguousarray(x[order[i:i + batch_size]])),

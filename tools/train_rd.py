@@ -13,7 +13,10 @@ per epoch drawn from reshuffled passes, so the coefficient schedule keeps the re
 --rate table trains the rate term against the code length under a learnable table
 (Training(rate="table")) instead of the reference's PNG target; each run then also reports the size
 of kodim21's .nic version 2 file under the prior the run exported ("nic2_bpp_table_prior", beside
-the sweep's own columns), and --save-dir keeps that prior as <label>_prior.nicp.
+the sweep's own columns), and --save-dir keeps that prior as <label>_prior.nicp.  --rate context
+trains against the code length under a learnable context table (Training(rate="context")); each run
+then also reports kodim21's .nic version 3 file under the exported context prior
+("nic3_bpp_context_prior") and --save-dir keeps <label>_prior.nicc as well.
 
     python tools/train_rd.py [--epochs 30] [--batch 64] [--steps N] [--out FILE] [--save-dir DIR]
 """
@@ -59,9 +62,11 @@ def main():
     ap.add_argument("--distortion", default="ssim", choices=("ssim", "ms_ssim"),
                     help="the codec losses' distortion term (ssim: the reference's; ms_ssim: tf.image.ssim_multiscale)")
     ap.add_argument("--ms-scales", type=int, default=4, help="scales of --distortion ms_ssim (128 px patches: <= 4)")
-    ap.add_argument("--rate", default="png", choices=("png", "table"),
-                    help="the rate term (png: the reference's Entropynet on PNG sizes; table: the .nic prior's code length)")
-    ap.add_argument("--table-lr", type=float, default=1e-2, help="Adam's learning rate of --rate table's table (untuned)")
+    ap.add_argument("--rate", default="png", choices=("png", "table", "context"),
+                    help="the rate term (png: the reference's Entropynet on PNG sizes; table: the .nic prior's code length; "
+                         "context: the .nic version 3 context prior's)")
+    ap.add_argument("--table-lr", type=float, default=1e-2, help="Adam's learning rate of --rate table's / context's tables (untuned)")
+    ap.add_argument("--seg-pixels", type=int, default=32, help="--rate context: the container's segment length")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     x = load_patches(args.data)
@@ -76,7 +81,8 @@ def main():
         t0 = time.perf_counter()
         with tempfile.TemporaryDirectory() as d:
             tr = T.Training(device="cuda", weights=W.seeded_weights(seed, init="glorot"), seed=seed, checkpoint_dir=d + "/",
-                            distortion=args.distortion, ms_scales=args.ms_scales, rate=args.rate, table_lr=args.table_lr)
+                            distortion=args.distortion, ms_scales=args.ms_scales, rate=args.rate, table_lr=args.table_lr,
+                            seg_pixels=args.seg_pixels)
             tr.png_mode = args.png_mode
             epochs = args.epochs
             if args.steps:
@@ -90,7 +96,8 @@ def main():
             tr._save()
             w = W.load(os.path.join(d, "encoder"), "encoder")
             w.update(W.load(os.path.join(d, "decoder"), "decoder"))
-            table_prior = tr.prior() if args.rate == "table" else None
+            table_prior = tr.prior() if args.rate in ("table", "context") else None
+            context_prior = tr.context_prior() if args.rate == "context" else None
         label = f"coef{coef:.2f}" + ("" if args.coef_step == 0.01 else f"_step{args.coef_step:g}") + (f"_s{seed}" if seed else "")
         sets[label] = w
         if args.save_dir:
@@ -111,6 +118,13 @@ def main():
             _, sizes = codec.rans2_encode(codec.encode(torch.from_numpy(ev).cuda()))
             nic2 = {"prior_id": f"{table_prior.id:08x}",
                     "nic2_bpp_table_prior": round(8.0 * float(sizes.sum()) / (ev.shape[0] * ev.shape[1] * ev.shape[2]), 6)}
+            if context_prior is not None:  # and as a version 3 file under the exported context prior
+                if args.save_dir:
+                    context_prior.save(os.path.join(args.save_dir, f"{label}_prior.nicc"))
+                codec.set_context_prior(context_prior)
+                _, sizes = codec.rans3_encode(codec.encode(torch.from_numpy(ev).cuda()), args.seg_pixels)
+                nic2.update({"context_prior_id": f"{context_prior.id:08x}", "seg_pixels": args.seg_pixels,
+                             "nic3_bpp_context_prior": round(8.0 * float(sizes.sum()) / (ev.shape[0] * ev.shape[1] * ev.shape[2]), 6)})
         tail = log[-20:]
         train_log[label] = {"steps": len(log), "epochs": epochs, "seed": seed, "png_mode": args.png_mode, "distortion": args.distortion,
                             "ms_scales": args.ms_scales if args.distortion == "ms_ssim" else None, "seconds": round(time.perf_counter() - t0, 1),
