@@ -263,10 +263,17 @@ int nic_unpack_latent(const uint8_t* packed, int n, int h8, int w8, uint8_t* lat
  *     (h8, w8) (seg_pixels is read per file on the device) -> latent (n,h8,w8,96) and status[i]
  *     (DEVICE int32[n]): 0 ok; bit 0: a segment did not end with its state at 2^23 on its last
  *     byte; bit 1: the header is not a version-1 header of an (h8, w8) latent (that image's
- *     latent is left unwritten); bit 2: a table breaks its invariants.  Tables are parsed on the
- *     device.  No input bytes can take the kernels out of bounds: file reads are clamped to the
- *     segment, table lookups resolve inside the 4096 slots, and stores go to the lane's own
- *     latent bytes.
+ *     latent is left unwritten); bit 2: a stored table is not "symbols ascending, freqs in 1..4096
+ *     summing to 4096" (a freq of 0, a freq or a running sum above 4096 and a sum short of 4096 all
+ *     count).  Tables are parsed on the device.  sizes[i] is clamped to [0, stride] and every read
+ *     of a file byte to [0, sizes[i]): a byte at or past the size reads as 0, whatever the buffer
+ *     holds there, so a file cut short of its header has bit 1 and one cut anywhere behind it has
+ *     bit 0 or bit 2.  No input bytes can take the kernels out of bounds: segment offsets saturate
+ *     at the size, file reads are clamped to the segment, table lookups resolve inside the 4096
+ *     slots (a broken table still yields a row that does), and stores go to the lane's own latent
+ *     bytes.  An image with a non-zero status may hold anything inside its own h8 w8 96 bytes.
+ *     The size sum is nic_rans_inspect's check alone: bytes behind the last segment, or a last
+ *     segment length that runs past the size, have no status bit and the file decodes cleanly.
  * nic_rans_inspect: HOST-only check of one file in host memory (no GPU, no ctx): magic, version,
  *     probability bits, seg_pixels >= 1, h8 w8 in range, every table's invariants, and header +
  *     tables + segment table + sum of segment lengths == size.  NIC_ECORRUPT (nic_last_error

@@ -460,9 +460,10 @@ class Codec:
         i's complete .nic file is buf[i, :sizes[i]] (nic_rans_encode; no host synchronisation)."""
         return self._rans_encode(1, z, seg_pixels)
 
-    def rans_decode_status(self, buf, sizes, h8: int, w8: int):
-        """rans_decode without the check: (latent, status (N,) int32 device tensor; nic.h)."""
-        return self._rans_decode_status(1, buf, sizes, h8, w8)
+    def rans_decode_status(self, buf, sizes, h8: int, w8: int, out=None):
+        """rans_decode without the check: (latent, status (N,) int32 device tensor; nic.h).
+        out: the (N,h8,w8,96) u8 tensor to decode into (default: a new one)."""
+        return self._rans_decode_status(1, buf, sizes, h8, w8, out)
 
     def rans_decode(self, buf, sizes, h8: int, w8: int):
         """.nic files buf[i, :sizes[i]] (device tensors, as rans_encode returns) of (h8, w8)

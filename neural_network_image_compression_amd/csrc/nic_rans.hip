@@ -478,9 +478,10 @@ __global__ __launch_bounds__(256) void rans_assemble(const uint8_t* __restrict__
 // begin, size}.  A header that does not describe an (h8, w8) file of version kVer leaves nseg = 0
 // and status 2 (nothing of that image is decoded); versions 2 and 3 (the 40-byte header) must also
 // describe an H x W image with h8 = ceil(H / 8), w8 = ceil(W / 8), and their prior_id must be the
-// ctx's, else status 8 and nseg = 0 likewise.  A table that breaks the invariants sets status bit 4
-// and still yields cumulative rows that resolve every slot (start[0] = 0, non-decreasing,
-// start[256] = 4096).  Version 1 stores every channel's table; versions 2 and 3 those of the masked
+// ctx's, else status 8 and nseg = 0 likewise.  A table that breaks the invariants (symbols ascending:
+// an entry that does not ascend is never reached, e != nsym; freqs in 1..4096 summing to 4096) sets
+// status bit 4 and still yields cumulative rows that resolve every slot (start[0] = 0, non-decreasing,
+// start[256] = 4096): the running sum saturates at 4096.  Version 1 stores every channel's table; versions 2 and 3 those of the masked
 // channels only, and the other channels' rows are copies of the prior's.  A table is walked once and
 // stored into each of the channel's rows (three in version 3).
 // wintab (per-file windows, else NULL): row img = (h8, w8, r0, c0) replaces the call's (h8, w8), and
@@ -555,10 +556,12 @@ __global__ __launch_bounds__(256) void rans_parse(const uint8_t* __restrict__ fi
     uint16_t* row = rows + tid * R::kPerCh * R::kPitch;
     const uint32_t base = choff[tid], nsym = rd(base) + 1;
     uint32_t e = 0, run = 0, es = rd(base + 1), ef = rd(base + 2) | (rd(base + 3) << 8);
+    bool bad = false;  // a freq outside 1..4096, or a sum past 4096 that the clamp below would hide
     for (uint32_t s = 0; s < 256; ++s) {
 #pragma unroll
       for (int k = 0; k < R::kPerCh; ++k) row[k * R::kPitch + s] = (uint16_t)run;
       if (e < nsym && es == s) {
+        bad |= ef == 0u || run + ef > kProbScale;  // run <= 4096 and ef < 2^16: no wrap
         run = min(run + ef, kProbScale);
         ++e;
         es = rd(base + 1 + 3 * e);
@@ -567,7 +570,7 @@ __global__ __launch_bounds__(256) void rans_parse(const uint8_t* __restrict__ fi
     }
 #pragma unroll
     for (int k = 0; k < R::kPerCh; ++k) row[k * R::kPitch + 256] = (uint16_t)kProbScale;
-    if (e != nsym || run != kProbScale) atomicOr(&s_bad, 4);
+    if (bad || e != nsym || run != kProbScale) atomicOr(&s_bad, 4);
   }
   if constexpr (kPrior) {
     if (nseg > 0)  // the prior's rows (start[0] = 0, non-decreasing, start[256] = 4096 by construction), without a row's pad

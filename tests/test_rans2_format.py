@@ -5,7 +5,6 @@ the argument checks of the device entry points (no GPU calls here)."""
 import ctypes
 import glob
 import os
-import struct
 
 import numpy as np
 import pytest
@@ -16,6 +15,7 @@ from neural_network_image_compression_amd.prior import Prior
 from tests import rans2_ref as R2
 from tests import rans_ref as R
 from tests.conftest import GOLDEN, load_case
+from tests.nic_bad_files import as_file, corruptions, inspector_refuses
 
 CASES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, "*.npz")))
 PRIORS = ("uniform", "self", "other")
@@ -181,53 +181,9 @@ def test_prior_check_and_the_nicp_file(golden, tmp_path):
         Prior.from_bytes(bytes(data[:-1]))
 
 
-def _table_offsets(data):
-    at, offs = 40, {}
-    for c in range(96):
-        if (data[28 + (c >> 3)] >> (c & 7)) & 1:
-            offs[c] = at
-            at += 1 + 3 * (data[at] + 1)
-    return offs, at
-
-
-def _corruptions(data):
-    """name -> a damaged copy of a well-formed version-2 file with at least one own table of two
-    entries and at least one prior channel."""
-    out = {}
-    out["bad magic"] = b"NICX" + data[4:]
-    out["version 1"] = data[:4] + b"\x01" + data[5:]
-    out["version 3"] = data[:4] + b"\x03" + data[5:]
-    out["probability bits 11"] = data[:5] + b"\x0b" + data[6:]
-    out["truncated by one byte"] = data[:-1]
-    out["one byte appended"] = data + b"\x00"
-    offs, segtab = _table_offsets(data)
-    first = struct.unpack("<I", data[segtab:segtab + 4])[0]
-    out["segment length raised by one"] = data[:segtab] + struct.pack("<I", first + 1) + data[segtab + 4:]
-    c = next(i for i in offs if data[offs[i]] >= 1)
-    e0 = offs[c] + 1
-    s0, f0 = struct.unpack("<BH", data[e0:e0 + 3])
-    s1, f1 = struct.unpack("<BH", data[e0 + 3:e0 + 6])
-    low = (s0, f0 - 1) if f0 > 1 else (s0, f0)
-    low2 = (s1, f1) if f0 > 1 else (s1, f1 - 1)
-    out["freqs sum to 4095"] = data[:e0] + struct.pack("<BH", *low) + struct.pack("<BH", *low2) + data[e0 + 6:]
-    out["descending symbols"] = data[:e0] + struct.pack("<BH", s1, f0) + struct.pack("<BH", s0, f1) + data[e0 + 6:]
-    out["equal symbols"] = data[:e0] + struct.pack("<BH", s0, f0) + struct.pack("<BH", s0, f1) + data[e0 + 6:]
-    out["seg_pixels 0"] = data[:6] + b"\x00\x00" + data[8:]
-    out["h8 0"] = data[:8] + struct.pack("<I", 0) + data[12:]
-    out["header only"] = data[:40]
-    out["shorter than the header"] = data[:33]
-    free = next(i for i in range(96) if i not in offs)
-    m = bytearray(data)
-    m[28 + (free >> 3)] |= 1 << (free & 7)
-    out["a mask bit set with no table behind it"] = bytes(m)
-    m = bytearray(data)
-    m[28 + (c >> 3)] &= ~(1 << (c & 7)) & 255
-    out["a mask bit cleared in front of its table"] = bytes(m)
-    h8, = struct.unpack("<I", data[8:12])
-    out["H one row too many for h8"] = data[:16] + struct.pack("<I", 8 * h8 + 1) + data[20:]
-    out["H too small for h8"] = data[:16] + struct.pack("<I", 8 * h8 - 8) + data[20:]
-    out["W 0"] = data[:20] + struct.pack("<I", 0) + data[24:]
-    return out
+def _inspect_sized(d, size):
+    buf = np.frombuffer(d, np.uint8)
+    return _lib.lib().nic_rans2_inspect(buf.ctypes.data, size, None, None, None, None, None, None)
 
 
 def test_inspect_rejects_corrupt_files(golden, v1_files):
@@ -235,15 +191,23 @@ def test_inspect_rejects_corrupt_files(golden, v1_files):
     prior = R2.fit_prior(golden("imagenet4_trained")["latent"])
     data = R2.write_file(z, prior)
     assert 0 < sum(R2.parse_file(data)["mask"]) < 96
-    bad = _corruptions(data)
-    for name, d in bad.items():
-        rc, _ = inspect2(d)
-        assert rc == _lib.NIC_ECORRUPT, name
+    bad = corruptions(2, data, lambda sp: R2.write_file(z, prior, sp))
+    for must in ("bad magic", "version 1", "version 3", "probability bits 11", "truncated by one byte", "one byte appended",
+                 "segment length raised by one", "freqs sum to 4095", "descending symbols", "equal symbols", "seg_pixels 0", "h8 0",
+                 "header only", "shorter than the header", "a mask bit set with no table behind it",
+                 "a mask bit cleared in front of its table", "H one row too many for h8", "H too small for h8", "W 0"):
+        assert must in bad
+    assert len(bad) >= 45
+    for name, (d, size, _) in bad.items():
+        if not inspector_refuses(name):
+            assert _inspect_sized(d, size) == _lib.NIC_OK, name
+            continue
+        assert _inspect_sized(d, size) == _lib.NIC_ECORRUPT, name
         assert "nic_rans2_inspect" in _lib.last_error(), name
         with pytest.raises(ValueError):
-            B.nic2_inspect(d)
+            B.nic2_inspect(as_file(d, size))
         with pytest.raises(ValueError):
-            R2.parse_file(d)
+            R2.parse_file(as_file(d, size))
     # a version-1 file is not a version-2 file, and the other way round
     v1, = v1_files("kodim21_256_trained")
     assert inspect2(v1)[0] == _lib.NIC_ECORRUPT and "version 1" in _lib.last_error()

@@ -18,7 +18,7 @@ from tests import rans2_ref as R2
 from tests import rans3_ref as R3
 from tests import rans_ref as R
 from tests.conftest import GOLDEN, load_case
-from tests.test_rans2_format import _corruptions
+from tests.nic_bad_files import as_file, corruptions, inspector_refuses
 
 CASES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, "*.npz")))
 SEG_PIXELS = (1, 7, 32, 4096)
@@ -196,21 +196,21 @@ def test_inspect_rejects_corrupt_files(golden):
     cprior = R3.fit_context_prior(golden("imagenet4_trained")["latent"])
     data = R3.write_file(z, cprior)
     assert 0 < sum(R3.parse_file(data)["mask"]) < 96
-    # test_rans2_format's list, made on the version-3 file: its "version 3" entry is this file
-    # itself, so it is replaced by "version 2" and "version 4"
-    bad = _corruptions(data)
-    assert bad.pop("version 3") == data
-    bad["version 2"] = data[:4] + b"\x02" + data[5:]
-    bad["version 4"] = data[:4] + b"\x04" + data[5:]
-    assert len(bad) >= 20
-    for name, d in bad.items():
-        rc, _ = inspect3(d)
+    bad = corruptions(3, data, lambda sp: R3.write_file(z, cprior, sp))
+    assert {"version 1", "version 2", "version 4"} <= set(bad) and "version 3" not in bad
+    assert len(bad) >= 45
+    buf_of = lambda d: np.frombuffer(d, np.uint8).ctypes.data  # noqa: E731
+    for name, (d, size, _) in bad.items():
+        rc = _lib.lib().nic_rans3_inspect(buf_of(d), size, None, None, None, None, None, None)
+        if not inspector_refuses(name):
+            assert rc == _lib.NIC_OK, name
+            continue
         assert rc == _lib.NIC_ECORRUPT, name
         assert "nic_rans3_inspect" in _lib.last_error(), name
         with pytest.raises(ValueError):
-            B.nic3_inspect(d)
+            B.nic3_inspect(as_file(d, size))
         with pytest.raises(ValueError):
-            R3.parse_file(d)
+            R3.parse_file(as_file(d, size))
     # version-1 and version-2 files are not version-3 files, and the other way round
     v1 = R.write_file(z)
     v2 = R2.write_file(z, R2.uniform_prior())
