@@ -682,7 +682,7 @@ int nic_png_device_read(nic_ctx* ctx, const uint8_t* streams, int64_t stride, co
  *     groups ceil((m / groups) h w / 128) channels 256); nic_rate_table_grad reads it only with dL.
  *     channels <= 64; m h w channels and groups channels 256 must fit an int.
  * The context rate loss: the same under the row the left neighbour selects, the quantity .nic version
- * 3 prices.  L is (groups * channels, 3, 256) fp32, L[r][x][j] = -log2 p_{r,x}(j); anchors is
+ * 3 prices (one implementation serves both losses: the table rate is its one-context instance).  L is (groups * channels, 3, 256) fp32, L[r][x][j] = -log2 p_{r,x}(j); anchors is
  * groups * channels bytes on the device; yc (m, h, w, channels), NULL meaning y, is the tensor the
  * contexts are read from; seg_pixels >= 1.  Element (i, q, c), q the row-major pixel inside plane i:
  *     x = 0 if q % seg_pixels == 0, otherwise

@@ -1910,101 +1910,90 @@ int nic_msssim_terms_grad(const float* mx, const float* my, const float* sxy, co
   return NIC_OK;
 }
 
-// the table rate loss: m * h * w * channels elements and the groups * channels * 256 table must fit an int
-static int rate_table_shape(const char* who, int m, int h, int w, int channels, int groups) {
+// the rate losses: m * h * w * channels elements and the groups * channels * contexts * 256 table
+// must fit an int.  Each entry point below is the table rate (contexts 1: yc, anchors and
+// seg_pixels unread and unchecked) or the context rate (contexts 3) over one function.
+static int rate_shape(const char* who, int contexts, int m, int h, int w, int channels, int groups) {
   if (m < 0 || h <= 0 || w <= 0 || !train_dims_ok(channels) || groups < 1 || m % groups != 0 ||
-      (int64_t)m * h * w * channels > INT32_MAX || (int64_t)groups * channels * 256 > INT32_MAX)
+      (int64_t)m * h * w * channels > INT32_MAX || (int64_t)groups * channels * contexts * 256 > INT32_MAX)
     return fail(NIC_ESHAPE, "%s: bad shape m=%d %dx%dx%d groups=%d", who, m, h, w, channels, groups);
+  return NIC_OK;
+}
+
+static int rate_work(const char* who, int contexts, int m, int h, int w, int channels, int groups, int64_t* floats) {
+  if (!floats) return fail(NIC_EINVAL, "%s: NULL argument", who);
+  const int rc = rate_shape(who, contexts, m, h, w, channels, groups);
+  if (rc != NIC_OK) return rc;
+  *floats = (int64_t)train_rate_work_floats(m, h, w, channels, groups, contexts);
+  return NIC_OK;
+}
+
+static int rate_bits(const char* who, int contexts, const float* y, const float* yc, const float* L,
+                     const uint8_t* anchors, int m, int h, int w, int channels, int groups, int seg_pixels,
+                     float* plane_bits, float* work, int64_t work_floats, void* stream) {
+  const int rc = rate_shape(who, contexts, m, h, w, channels, groups);
+  if (rc != NIC_OK) return rc;
+  if (contexts > 1 && seg_pixels < 1) return fail(NIC_EINVAL, "%s: seg_pixels %d < 1", who, seg_pixels);
+  if (m == 0) return NIC_OK;
+  if (!y || !L || (contexts > 1 && !anchors) || !plane_bits || !work) return fail(NIC_EINVAL, "%s: NULL argument", who);
+  const int64_t need = (int64_t)train_rate_work_floats(m, h, w, channels, groups, contexts);
+  if (work_floats < need)
+    return fail(NIC_EINVAL, "%s: work holds %lld floats, needs %lld", who, (long long)work_floats, (long long)need);
+  HIP_TRY(launch_rate(y, L, contexts, yc, anchors, seg_pixels, m, h, w, channels, groups, plane_bits, work,
+                      (hipStream_t)stream));
+  return NIC_OK;
+}
+
+static int rate_grad(const char* who, int contexts, const float* y, const float* yc, const float* L,
+                     const uint8_t* anchors, const float* g, int m, int h, int w, int channels, int groups,
+                     int seg_pixels, float* dy, float* dL, float* work, int64_t work_floats, void* stream) {
+  const int rc = rate_shape(who, contexts, m, h, w, channels, groups);
+  if (rc != NIC_OK) return rc;
+  if (contexts > 1 && seg_pixels < 1) return fail(NIC_EINVAL, "%s: seg_pixels %d < 1", who, seg_pixels);
+  if (!dy && !dL) return fail(NIC_EINVAL, "%s: no gradient requested (dy and dL both NULL)", who);
+  if (m > 0) {
+    if (!y || !L || (contexts > 1 && !anchors) || !g || (dL && !work)) return fail(NIC_EINVAL, "%s: NULL argument", who);
+    const int64_t need = (int64_t)train_rate_work_floats(m, h, w, channels, groups, contexts);
+    if (dL && work_floats < need)
+      return fail(NIC_EINVAL, "%s: work holds %lld floats, needs %lld", who, (long long)work_floats, (long long)need);
+  }
+  HIP_TRY(launch_rate_grad(y, L, contexts, yc, anchors, seg_pixels, g, m, h, w, channels, groups, dy, dL, work,
+                           (hipStream_t)stream));
   return NIC_OK;
 }
 
 int nic_rate_table_work(int m, int h, int w, int channels, int groups, int64_t* floats) {
-  if (!floats) return fail(NIC_EINVAL, "nic_rate_table_work: NULL argument");
-  const int rc = rate_table_shape("nic_rate_table_work", m, h, w, channels, groups);
-  if (rc != NIC_OK) return rc;
-  *floats = (int64_t)train_rate_table_work_floats(m, h, w, channels, groups);
-  return NIC_OK;
+  return rate_work("nic_rate_table_work", 1, m, h, w, channels, groups, floats);
 }
 
 int nic_rate_table(const float* y, const float* L, int m, int h, int w, int channels, int groups, float* plane_bits,
                    float* work, int64_t work_floats, void* stream) {
-  const int rc = rate_table_shape("nic_rate_table", m, h, w, channels, groups);
-  if (rc != NIC_OK) return rc;
-  if (m == 0) return NIC_OK;
-  if (!y || !L || !plane_bits || !work) return fail(NIC_EINVAL, "nic_rate_table: NULL argument");
-  const int64_t need = (int64_t)train_rate_table_work_floats(m, h, w, channels, groups);
-  if (work_floats < need)
-    return fail(NIC_EINVAL, "nic_rate_table: work holds %lld floats, needs %lld", (long long)work_floats, (long long)need);
-  HIP_TRY(launch_rate_table(y, L, m, h, w, channels, groups, plane_bits, work, (hipStream_t)stream));
-  return NIC_OK;
+  return rate_bits("nic_rate_table", 1, y, nullptr, L, nullptr, m, h, w, channels, groups, 1, plane_bits, work,
+                   work_floats, stream);
 }
 
 int nic_rate_table_grad(const float* y, const float* L, const float* g, int m, int h, int w, int channels, int groups,
                         float* dy, float* dL, float* work, int64_t work_floats, void* stream) {
-  const int rc = rate_table_shape("nic_rate_table_grad", m, h, w, channels, groups);
-  if (rc != NIC_OK) return rc;
-  if (!dy && !dL) return fail(NIC_EINVAL, "nic_rate_table_grad: no gradient requested (dy and dL both NULL)");
-  if (m > 0) {
-    if (!y || !L || !g || (dL && !work)) return fail(NIC_EINVAL, "nic_rate_table_grad: NULL argument");
-    const int64_t need = (int64_t)train_rate_table_work_floats(m, h, w, channels, groups);
-    if (dL && work_floats < need)
-      return fail(NIC_EINVAL, "nic_rate_table_grad: work holds %lld floats, needs %lld", (long long)work_floats,
-                  (long long)need);
-  }
-  HIP_TRY(launch_rate_table_grad(y, L, g, m, h, w, channels, groups, dy, dL, work, (hipStream_t)stream));
-  return NIC_OK;
-}
-
-// the context rate loss: the static pair's shapes, a table three times as large, seg_pixels >= 1
-static int rate_ctable_shape(const char* who, int m, int h, int w, int channels, int groups) {
-  const int rc = rate_table_shape(who, m, h, w, channels, groups);
-  if (rc != NIC_OK) return rc;
-  if ((int64_t)groups * channels * 3 * 256 > INT32_MAX)
-    return fail(NIC_ESHAPE, "%s: bad shape m=%d %dx%dx%d groups=%d", who, m, h, w, channels, groups);
-  return NIC_OK;
+  return rate_grad("nic_rate_table_grad", 1, y, nullptr, L, nullptr, g, m, h, w, channels, groups, 1, dy, dL, work,
+                   work_floats, stream);
 }
 
 int nic_rate_ctable_work(int m, int h, int w, int channels, int groups, int64_t* floats) {
-  if (!floats) return fail(NIC_EINVAL, "nic_rate_ctable_work: NULL argument");
-  const int rc = rate_ctable_shape("nic_rate_ctable_work", m, h, w, channels, groups);
-  if (rc != NIC_OK) return rc;
-  *floats = (int64_t)train_rate_ctable_work_floats(m, h, w, channels, groups);
-  return NIC_OK;
+  return rate_work("nic_rate_ctable_work", 3, m, h, w, channels, groups, floats);
 }
 
 int nic_rate_ctable(const float* y, const float* yc, const float* L, const uint8_t* anchors, int m, int h, int w,
                     int channels, int groups, int seg_pixels, float* plane_bits, float* work, int64_t work_floats,
                     void* stream) {
-  const int rc = rate_ctable_shape("nic_rate_ctable", m, h, w, channels, groups);
-  if (rc != NIC_OK) return rc;
-  if (seg_pixels < 1) return fail(NIC_EINVAL, "nic_rate_ctable: seg_pixels %d < 1", seg_pixels);
-  if (m == 0) return NIC_OK;
-  if (!y || !L || !anchors || !plane_bits || !work) return fail(NIC_EINVAL, "nic_rate_ctable: NULL argument");
-  const int64_t need = (int64_t)train_rate_ctable_work_floats(m, h, w, channels, groups);
-  if (work_floats < need)
-    return fail(NIC_EINVAL, "nic_rate_ctable: work holds %lld floats, needs %lld", (long long)work_floats, (long long)need);
-  HIP_TRY(launch_rate_ctable(y, yc, L, anchors, m, h, w, channels, groups, seg_pixels, plane_bits, work,
-                             (hipStream_t)stream));
-  return NIC_OK;
+  return rate_bits("nic_rate_ctable", 3, y, yc, L, anchors, m, h, w, channels, groups, seg_pixels, plane_bits, work,
+                   work_floats, stream);
 }
 
 int nic_rate_ctable_grad(const float* y, const float* yc, const float* L, const uint8_t* anchors, const float* g, int m,
                          int h, int w, int channels, int groups, int seg_pixels, float* dy, float* dL, float* work,
                          int64_t work_floats, void* stream) {
-  const int rc = rate_ctable_shape("nic_rate_ctable_grad", m, h, w, channels, groups);
-  if (rc != NIC_OK) return rc;
-  if (seg_pixels < 1) return fail(NIC_EINVAL, "nic_rate_ctable_grad: seg_pixels %d < 1", seg_pixels);
-  if (!dy && !dL) return fail(NIC_EINVAL, "nic_rate_ctable_grad: no gradient requested (dy and dL both NULL)");
-  if (m > 0) {
-    if (!y || !L || !anchors || !g || (dL && !work)) return fail(NIC_EINVAL, "nic_rate_ctable_grad: NULL argument");
-    const int64_t need = (int64_t)train_rate_ctable_work_floats(m, h, w, channels, groups);
-    if (dL && work_floats < need)
-      return fail(NIC_EINVAL, "nic_rate_ctable_grad: work holds %lld floats, needs %lld", (long long)work_floats,
-                  (long long)need);
-  }
-  HIP_TRY(launch_rate_ctable_grad(y, yc, L, anchors, g, m, h, w, channels, groups, seg_pixels, dy, dL, work,
-                                  (hipStream_t)stream));
-  return NIC_OK;
+  return rate_grad("nic_rate_ctable_grad", 3, y, yc, L, anchors, g, m, h, w, channels, groups, seg_pixels, dy, dL,
+                   work, work_floats, stream);
 }
 
 // planes of the scale step: n * h * w elements must fit an int (the callers' tensors do by far)

@@ -324,21 +324,18 @@ hipError_t launch_msssim_terms(const float* mx, const float* my, const float* sx
 hipError_t launch_msssim_terms_grad(const float* mx, const float* my, const float* sxy, const float* sxx,
                                     const float* g_ssim, const float* g_cs, int n, long long hw, float c1, float c2,
                                     float* gmx, float* gmy, float* gsxy, float* gsxx, hipStream_t st);
-// the table rate loss: per-plane code length of y (m, h, w, c) under L (groups * c, 256), its input
-// gradient and the table's (deterministic, no atomics); dy / dL nullable
-size_t train_rate_table_work_floats(int m, int h, int w, int c, int groups);
-hipError_t launch_rate_table(const float* y, const float* L, int m, int h, int w, int c, int groups, float* plane_bits,
-                             float* work, hipStream_t st);
-hipError_t launch_rate_table_grad(const float* y, const float* L, const float* g, int m, int h, int w, int c,
-                                  int groups, float* dy, float* dL, float* work, hipStream_t st);
-// the context rate loss: the same under L (groups * c, 3, 256), the row picked by the left
-// neighbour's code in yc (NULL: y) against anchors (groups * c bytes); segments of seg_pixels
-size_t train_rate_ctable_work_floats(int m, int h, int w, int c, int groups);
-hipError_t launch_rate_ctable(const float* y, const float* yc, const float* L, const unsigned char* anchors, int m, int h,
-                              int w, int c, int groups, int seg_pixels, float* plane_bits, float* work, hipStream_t st);
-hipError_t launch_rate_ctable_grad(const float* y, const float* yc, const float* L, const unsigned char* anchors,
-                                   const float* g, int m, int h, int w, int c, int groups, int seg_pixels, float* dy,
-                                   float* dL, float* work, hipStream_t st);
+// the rate losses: per-plane code length of y (m, h, w, c) under L (groups * c, contexts, 256), its
+// input gradient and the table's (deterministic, no atomics); dy / dL nullable.  contexts = 1 is
+// the table rate (yc, anchors and seg_pixels unread); contexts = 3 the context rate, the row picked
+// by the left neighbour's code in yc (NULL: y) against anchors (groups * c bytes), segments of
+// seg_pixels.  Any other contexts: hipErrorInvalidValue
+size_t train_rate_work_floats(int m, int h, int w, int c, int groups, int contexts);
+hipError_t launch_rate(const float* y, const float* L, int contexts, const float* yc, const unsigned char* anchors,
+                       int seg_pixels, int m, int h, int w, int c, int groups, float* plane_bits, float* work,
+                       hipStream_t st);
+hipError_t launch_rate_grad(const float* y, const float* L, int contexts, const float* yc, const unsigned char* anchors,
+                            int seg_pixels, const float* g, int m, int h, int w, int c, int groups, float* dy,
+                            float* dL, float* work, hipStream_t st);
 hipError_t launch_pool2_prep(const float* x, const float* y, int n, int h, int w, int pool, float* xp, float* yp,
                              float* pxy, float* pss, hipStream_t st);
 hipError_t launch_pool2_prep_grad(const float* dxp, const float* dyp, const float* dp, const float* dq, const float* xp,

@@ -544,16 +544,22 @@ __global__ __launch_bounds__(256) void msssim_terms_grad_kernel(
   }
 }
 
-// ---- The table rate loss: the code length of a latent under a per-channel table ---------------
-// L is (groups * C, 256): L[r][j] = -log2 p_r(j).  Plane m of y (m, h, w, C) belongs to group
-// m / (m_total / groups) and its channel c reads row r = group * C + c.  Per element, every op one
-// fp32 rounding:
+// ---- The rate losses: the code length of a latent under per-channel tables -------------------
+// One kernel set, a template on NX, the number of contexts per row.  L is (groups * C, NX, 256):
+// L[r][x][j] = -log2 p_r(j | x).  Plane m of y (m, h, w, C) belongs to group m / (m_total / groups)
+// and its channel c reads row r = group * C + c.  Per element, every op one fp32 rounding:
 //   v = fminf(fmaxf(255 y, 0), 255) (a NaN becomes 0), k = min((int)floorf(v), 254), t = v - k,
-//   bits = L[r][k] + t (L[r][k+1] - L[r][k])
-// so k + 1 <= 255 whatever y holds.  rate_table_kernel: block bk of plane m sums its kRatePix
-// elements, thread t its elements t, t + 256, t + 512, t + 768 in that order, then the tree over
-// the 256 threads; rate_table_sum_kernel adds a plane's partials in block order.
-constexpr int kRatePix = 1024;  // elements per block of rate_table_kernel
+//   bits = L[r][x][k] + t (L[r][x][k+1] - L[r][x][k])
+// so k + 1 <= 255 whatever y holds.  NX = 1 is the table rate: x = 0, and `if constexpr` leaves no
+// read of yc, anchors or seg in that instantiation.  NX = 3 is the context rate: anchors holds
+// groups * C bytes, and element (m, q, c), q the row-major pixel inside plane m, reads context
+//   x = 0 if q % seg == 0, else min(2, |(int)rintf(fminf(fmaxf(255 yc[m][q-1][c], 0), 255)) - anchors[r]|)
+// q % seg != 0 implies q >= 1, so the left read stays inside plane m.  Both instantiations share
+// every order below, so NX equal rows give the table rate's bits and dy bit for bit.
+// rate_kernel: block bk of plane m sums its kRatePix elements, thread t its elements t, t + 256,
+// t + 512, t + 768 in that order, then the tree over the 256 threads; rate_table_sum_kernel adds a
+// plane's partials in block order.
+constexpr int kRatePix = 1024;  // elements per block of rate_kernel
 struct RateElem {
   int k;
   float t;
@@ -565,20 +571,40 @@ __device__ __forceinline__ RateElem rate_elem(float y) {
   e.t = __fsub_rn(v, (float)e.k);
   return e;
 }
-__global__ __launch_bounds__(256) void rate_table_kernel(const float* __restrict__ y, const float* __restrict__ L,
-                                                         int elems, int C, int ppg, int bpp, float* __restrict__ part) {
+__device__ __forceinline__ int rate_ctx(const float* __restrict__ yc, long long elem, int C, int q, int seg, int anchor) {
+  if (q % seg == 0) return 0;
+  const float v = fminf(fmaxf(__fmul_rn(255.0f, yc[elem - C]), 0.0f), 255.0f);
+  return min(2, abs((int)rintf(v) - anchor));
+}
+// the table of row r for element `elem` (pixel q of its plane): &L[r][x][0]
+template <int NX>
+__device__ __forceinline__ const float* rate_row(const float* __restrict__ L, const float* __restrict__ yc,
+                                                 const unsigned char* __restrict__ anchors, int r, long long elem,
+                                                 int C, int q, int seg) {
+  if constexpr (NX == 1)
+    return L + (long long)r * 256;
+  else
+    return L + ((long long)r * NX + rate_ctx(yc, elem, C, q, seg, anchors[r])) * 256;
+}
+template <int NX>
+__global__ __launch_bounds__(256) void rate_kernel(const float* __restrict__ y, const float* __restrict__ yc,
+                                                   const float* __restrict__ L,
+                                                   const unsigned char* __restrict__ anchors, int elems, int C,
+                                                   int ppg, int bpp, int seg, float* __restrict__ part) {
   __shared__ float red[256];
   const int m = blockIdx.x / bpp, bk = blockIdx.x - m * bpp, t = threadIdx.x;
-  const float* row0 = L + (long long)(m / ppg) * C * 256;
+  const int r0 = (m / ppg) * C;
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < kRatePix / 256; ++i) {
     const int e = bk * kRatePix + i * 256 + t;
     if (e < elems) {
-      const RateElem q = rate_elem(y[(long long)m * elems + e]);
-      const float* row = row0 + (e % C) * 256;
-      const float l0 = row[q.k];
-      s = __fadd_rn(s, __fadd_rn(l0, __fmul_rn(q.t, __fsub_rn(row[q.k + 1], l0))));
+      const long long idx = (long long)m * elems + e;
+      const int q = e / C;
+      const float* row = rate_row<NX>(L, yc, anchors, r0 + (e - q * C), idx, C, q, seg);
+      const RateElem el = rate_elem(y[idx]);
+      const float l0 = row[el.k];
+      s = __fadd_rn(s, __fadd_rn(l0, __fmul_rn(el.t, __fsub_rn(row[el.k + 1], l0))));
     }
   }
   red[t] = s;
@@ -597,160 +623,56 @@ __global__ __launch_bounds__(64) void rate_table_sum_kernel(const float* __restr
   for (int k = 0; k < bpp; ++k) s = __fadd_rn(s, part[(long long)i * bpp + k]);
   plane_bits[i] = s;
 }
-// Backward for an upstream g[m] per plane.  dy = (255 g[m]) (L[r][k+1] - L[r][k]), one thread per
-// element, written once.
-__global__ __launch_bounds__(256) void rate_table_dy_kernel(const float* __restrict__ y, const float* __restrict__ L,
-                                                            const float* __restrict__ g, long long total, int elems,
-                                                            int C, int ppg, float* __restrict__ dy) {
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-    const int m = (int)(i / elems), c = (int)(i % C);  // (elems is a multiple of C)
-    const float* row = L + ((long long)(m / ppg) * C + c) * 256;
-    const RateElem q = rate_elem(y[i]);
-    dy[i] = __fmul_rn(__fmul_rn(255.0f, g[m]), __fsub_rn(row[q.k + 1], row[q.k]));
-  }
-}
-// dL[r][j] = sum over the elements of row r of g (1 - t) at j = k and of g t at j = k + 1, with no
-// atomics: owner-computes in LDS.  A block (one wave) takes kRateSlab consecutive pixels of one
-// group (a group's planes are consecutive, so its pixels are one contiguous range).  Its 64 KB of
-// LDS hold R = 64 / C replicas of the group's C x 256 partial table, laid out [replica][j][c]
-// (channel fastest: the C threads of a replica fall on C different banks).  Thread (replica, c)
-// owns column c of its replica alone: it takes the slab's pixels replica, replica + R, ... in
-// that order and adds its two terms per pixel with plain LDS read-modify-write, so every word has
-// one writer and one order.  The replicas are then added in replica order into the block's partial
-// in `part` ([block][j][c]); rate_table_dl_reduce_kernel adds the blocks of a group in a fixed
-// order (fours of fours of fours in block order, then those sums in order).
-constexpr int kRateSlab = 128;       // pixels per block of rate_table_dl_kernel
-constexpr int kRateLdsFloats = 16384;  // 64 KB: floor(64 / C) replicas of C x 256 floats
-__global__ __launch_bounds__(64) void rate_table_dl_kernel(const float* __restrict__ y, const float* __restrict__ g,
-                                                           int C, int hw, long long P, int spg,
-                                                           float* __restrict__ part) {
-  __shared__ float tab[kRateLdsFloats];
-  const int R = 64 / C, T = C * 256, t = threadIdx.x, rep = t / C, c = t - rep * C;
-  const int grp = blockIdx.x / spg, slab = blockIdx.x - grp * spg;
-  for (int i = t; i < R * T; i += 64) tab[i] = 0.f;
-  __syncthreads();
-  if (rep < R) {
-    float* mine = tab + rep * T + c;
-    const long long p0 = (long long)slab * kRateSlab, p1 = p0 + kRateSlab < P ? p0 + kRateSlab : P;
-    for (long long p = p0 + rep; p < p1; p += R) {
-      const long long px = (long long)grp * P + p;
-      const float gm = g[px / hw];
-      const RateElem q = rate_elem(y[px * C + c]);
-      float* lo = mine + q.k * C;
-      lo[0] = __fadd_rn(lo[0], __fmul_rn(gm, __fsub_rn(1.0f, q.t)));
-      lo[C] = __fadd_rn(lo[C], __fmul_rn(gm, q.t));
-    }
-  }
-  __syncthreads();
-  for (int i = t; i < T; i += 64) {
-    float s = tab[i];
-    for (int r = 1; r < R; ++r) s = __fadd_rn(s, tab[r * T + i]);
-    part[(long long)blockIdx.x * T + i] = s;
-  }
-}
-__global__ __launch_bounds__(256) void rate_table_dl_reduce_kernel(const float* __restrict__ part, int groups, int C,
-                                                                   int spg, float* __restrict__ dL) {
-  const int T = C * 256, i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= groups * T) return;
-  const int grp = i / T, rem = i - grp * T, j = rem / C, c = rem - j * C;
-  const float* src = part + (long long)grp * spg * T + rem;
-  float total = 0.f;
-  for (int b0 = 0; b0 < spg; b0 += 64) {
-    float s3 = 0.f;
-    for (int b1 = b0; b1 < b0 + 64 && b1 < spg; b1 += 16) {
-      float s2 = 0.f;
-      for (int b2 = b1; b2 < b1 + 16 && b2 < spg; b2 += 4) {
-        float s1 = 0.f;
-        for (int b = b2; b < b2 + 4 && b < spg; ++b) s1 = __fadd_rn(s1, src[(long long)b * T]);
-        s2 = __fadd_rn(s2, s1);
-      }
-      s3 = __fadd_rn(s3, s2);
-    }
-    total = __fadd_rn(total, s3);
-  }
-  dL[((long long)grp * C + c) * 256 + j] = total;
-}
-
-// ---- The context rate loss: the code length under the row the left neighbour selects ----------
-// L is (groups * C, 3, 256), anchors groups * C bytes.  Element (m, q, c), q the row-major pixel
-// inside plane m, reads row r's context
-//   x = 0 if q % seg == 0, else min(2, |(int)rintf(fminf(fmaxf(255 yc[m][q-1][c], 0), 255)) - anchors[r]|)
-// and then the table rate's element step on L[r][x].  q % seg != 0 implies q >= 1, so the left
-// read stays inside plane m.  The forward and dy keep the static kernels' structure (the same
-// elements per block and thread, the same tree, the same block order), so three equal rows give
-// the static bits and dy bit for bit.
-__device__ __forceinline__ int rate_ctx(const float* __restrict__ yc, long long elem, int C, int q, int seg, int anchor) {
-  if (q % seg == 0) return 0;
-  const float v = fminf(fmaxf(__fmul_rn(255.0f, yc[elem - C]), 0.0f), 255.0f);
-  return min(2, abs((int)rintf(v) - anchor));
-}
-__global__ __launch_bounds__(256) void rate_ctable_kernel(const float* __restrict__ y, const float* __restrict__ yc,
-                                                          const float* __restrict__ L,
-                                                          const unsigned char* __restrict__ anchors, int elems, int C,
-                                                          int ppg, int bpp, int seg, float* __restrict__ part) {
-  __shared__ float red[256];
-  const int m = blockIdx.x / bpp, bk = blockIdx.x - m * bpp, t = threadIdx.x;
-  const int r0 = (m / ppg) * C;
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < kRatePix / 256; ++i) {
-    const int e = bk * kRatePix + i * 256 + t;
-    if (e < elems) {
-      const long long idx = (long long)m * elems + e;
-      const int q = e / C, r = r0 + (e - q * C);
-      const int x = rate_ctx(yc, idx, C, q, seg, anchors[r]);
-      const RateElem el = rate_elem(y[idx]);
-      const float* row = L + ((long long)r * 3 + x) * 256;
-      const float l0 = row[el.k];
-      s = __fadd_rn(s, __fadd_rn(l0, __fmul_rn(el.t, __fsub_rn(row[el.k + 1], l0))));
-    }
-  }
-  red[t] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o) red[t] = __fadd_rn(red[t], red[t + o]);
-    __syncthreads();
-  }
-  if (t == 0) part[blockIdx.x] = red[0];
-}
-__global__ __launch_bounds__(256) void rate_ctable_dy_kernel(const float* __restrict__ y, const float* __restrict__ yc,
-                                                             const float* __restrict__ L,
-                                                             const unsigned char* __restrict__ anchors,
-                                                             const float* __restrict__ g, long long total, int elems,
-                                                             int C, int ppg, int seg, float* __restrict__ dy) {
+// Backward for an upstream g[m] per plane.  dy = (255 g[m]) (L[r][x][k+1] - L[r][x][k]), one thread
+// per element, written once.
+template <int NX>
+__global__ __launch_bounds__(256) void rate_dy_kernel(const float* __restrict__ y, const float* __restrict__ yc,
+                                                      const float* __restrict__ L,
+                                                      const unsigned char* __restrict__ anchors,
+                                                      const float* __restrict__ g, long long total, int elems, int C,
+                                                      int ppg, int seg, float* __restrict__ dy) {
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int m = (int)(i / elems), e = (int)(i - (long long)m * elems), q = e / C;
-    const int r = (m / ppg) * C + (e - q * C);
-    const float* row = L + ((long long)r * 3 + rate_ctx(yc, i, C, q, seg, anchors[r])) * 256;
+    const float* row = rate_row<NX>(L, yc, anchors, (m / ppg) * C + (e - q * C), i, C, q, seg);
     const RateElem el = rate_elem(y[i]);
     dy[i] = __fmul_rn(__fmul_rn(255.0f, g[m]), __fsub_rn(row[el.k + 1], row[el.k]));
   }
 }
-// dL[r][x][j]: rate_table_dl_kernel once per context.  Block (group, slab, x) is one wave with the
-// static kernel's 64 KB of replicas [replica][j][c]; thread (replica, c) takes the same pixels in
-// the same order and does its two read-modify-writes only where the pixel's context is x, so every
-// word still has one writer and one order.  A slab that begins mid-segment reads its left pixel
-// from the slab before it in global memory (never from before its plane: see rate_ctx).  The
-// block's partial goes to part[(group, slab, x)][j][c]; the reduce adds a (group, x)'s slabs in the
-// static reduce's order.  With every pixel in context 0 the x = 0 blocks do exactly the static
-// kernel's work.
-__global__ __launch_bounds__(64) void rate_ctable_dl_kernel(const float* __restrict__ y, const float* __restrict__ yc,
-                                                            const unsigned char* __restrict__ anchors,
-                                                            const float* __restrict__ g, int C, int hw, long long P,
-                                                            int spg, int seg, float* __restrict__ part) {
+// dL[r][x][j] = sum over the elements of row r in context x of g (1 - t) at j = k and of g t at
+// j = k + 1, with no atomics: owner-computes in LDS.  Block (group, slab, x) is one wave and takes
+// kRateSlab consecutive pixels of one group (a group's planes are consecutive, so its pixels are
+// one contiguous range).  Its 64 KB of LDS hold R = 64 / C replicas of the group's C x 256 partial
+// table, laid out [replica][j][c] (channel fastest: the C threads of a replica fall on C different
+// banks).  Thread (replica, c) owns column c of its replica alone: it takes the slab's pixels
+// replica, replica + R, ... in that order and, where the pixel's context is x, adds its two terms
+// with plain LDS read-modify-write, so every word has one writer and one order.  A slab that begins
+// mid-segment reads its left pixel from the slab before it in global memory (never from before its
+// plane: see above).  The replicas are then added in replica order into the block's partial in
+// `part` ([(group, slab, x)][j][c]); rate_dl_reduce_kernel adds the slabs of a (group, x) in a
+// fixed order (fours of fours of fours in block order, then those sums in order).  With every pixel
+// in context 0 (seg = 1) the x = 0 blocks do exactly the NX = 1 kernel's work.
+constexpr int kRateSlab = 128;         // pixels per block of rate_dl_kernel
+constexpr int kRateLdsFloats = 16384;  // 64 KB: floor(64 / C) replicas of C x 256 floats
+template <int NX>
+__global__ __launch_bounds__(64) void rate_dl_kernel(const float* __restrict__ y, const float* __restrict__ yc,
+                                                     const unsigned char* __restrict__ anchors,
+                                                     const float* __restrict__ g, int C, int hw, long long P, int spg,
+                                                     int seg, float* __restrict__ part) {
   __shared__ float tab[kRateLdsFloats];
   const int R = 64 / C, T = C * 256, t = threadIdx.x, rep = t / C, c = t - rep * C;
-  const int x = blockIdx.x % 3, gs = blockIdx.x / 3, grp = gs / spg, slab = gs - grp * spg;
+  const int x = blockIdx.x % NX, gs = blockIdx.x / NX, grp = gs / spg, slab = gs - grp * spg;
   for (int i = t; i < R * T; i += 64) tab[i] = 0.f;
   __syncthreads();
   if (rep < R) {
     float* mine = tab + rep * T + c;
-    const int anchor = anchors[grp * C + c];
+    int anchor = 0;
+    if constexpr (NX > 1) anchor = anchors[grp * C + c];
     const long long p0 = (long long)slab * kRateSlab, p1 = p0 + kRateSlab < P ? p0 + kRateSlab : P;
     for (long long p = p0 + rep; p < p1; p += R) {
       const long long px = (long long)grp * P + p, plane = px / hw;
       const long long idx = px * C + c;
-      if (rate_ctx(yc, idx, C, (int)(px - plane * hw), seg, anchor) != x) continue;
+      if constexpr (NX > 1)
+        if (rate_ctx(yc, idx, C, (int)(px - plane * hw), seg, anchor) != x) continue;
       const float gm = g[plane];
       const RateElem q = rate_elem(y[idx]);
       float* lo = mine + q.k * C;
@@ -765,13 +687,14 @@ __global__ __launch_bounds__(64) void rate_ctable_dl_kernel(const float* __restr
     part[(long long)blockIdx.x * T + i] = s;
   }
 }
-__global__ __launch_bounds__(256) void rate_ctable_dl_reduce_kernel(const float* __restrict__ part, int groups, int C,
-                                                                    int spg, float* __restrict__ dL) {
+template <int NX>
+__global__ __launch_bounds__(256) void rate_dl_reduce_kernel(const float* __restrict__ part, int groups, int C, int spg,
+                                                             float* __restrict__ dL) {
   const int T = C * 256, i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= groups * 3 * T) return;
-  const int gx = i / T, rem = i - gx * T, grp = gx / 3, x = gx - grp * 3, j = rem / C, c = rem - j * C;
-  const float* src = part + ((long long)grp * spg * 3 + x) * T + rem;  // slab b at src[b * 3 T]
-  const long long step = 3LL * T;
+  if (i >= groups * NX * T) return;
+  const int gx = i / T, rem = i - gx * T, grp = gx / NX, x = gx - grp * NX, j = rem / C, c = rem - j * C;
+  const float* src = part + ((long long)grp * spg * NX + x) * T + rem;  // slab b at src[b * NX T]
+  const long long step = (long long)NX * T;
   float total = 0.f;
   for (int b0 = 0; b0 < spg; b0 += 64) {
     float s3 = 0.f;
@@ -786,7 +709,7 @@ __global__ __launch_bounds__(256) void rate_ctable_dl_reduce_kernel(const float*
     }
     total = __fadd_rn(total, s3);
   }
-  dL[(((long long)grp * C + c) * 3 + x) * 256 + j] = total;
+  dL[(((long long)grp * C + c) * NX + x) * 256 + j] = total;
 }
 
 // The step between scales (tf.image.ssim_multiscale: an odd height or width SYMMETRIC-padded by
@@ -1321,101 +1244,74 @@ hipError_t launch_msssim_terms_grad(const float* mx, const float* my, const floa
 }
 
 // the forward's partial per block of kRatePix elements, or the backward's C x 256 partial table per
-// block of kRateSlab pixels of a group, whichever is more (one `work` serves both calls)
-static long long rate_fwd_blocks(int m, int h, int w, int c) {
-  return (long long)m * (((long long)h * w * c + kRatePix - 1) / kRatePix);
-}
+// block of kRateSlab pixels of a group and per context, whichever is more (one `work` serves both
+// calls)
 static long long rate_slabs(int m, int h, int w, int groups) {
   return ((long long)(m / groups) * h * w + kRateSlab - 1) / kRateSlab;
 }
-size_t train_rate_table_work_floats(int m, int h, int w, int c, int groups) {
-  const long long fwd = rate_fwd_blocks(m, h, w, c), bwd = (long long)groups * rate_slabs(m, h, w, groups) * c * 256;
+size_t train_rate_work_floats(int m, int h, int w, int c, int groups, int contexts) {
+  const long long fwd = (long long)m * (((long long)h * w * c + kRatePix - 1) / kRatePix);
+  const long long bwd = (long long)contexts * groups * rate_slabs(m, h, w, groups) * c * 256;
   return (size_t)(fwd > bwd ? fwd : bwd);
 }
 
-hipError_t launch_rate_table(const float* y, const float* L, int m, int h, int w, int c, int groups, float* plane_bits,
-                             float* work, hipStream_t st) {
-  if (m == 0) return hipSuccess;
+template <int NX>
+static hipError_t rate_fwd(const float* y, const float* yc, const float* L, const unsigned char* anchors, int m, int h,
+                           int w, int c, int groups, int seg_pixels, float* plane_bits, float* work, hipStream_t st) {
   const int elems = h * w * c, bpp = (elems + kRatePix - 1) / kRatePix;
   if ((long long)m * bpp > INT32_MAX) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(rate_table_kernel, dim3((unsigned)(m * bpp)), dim3(256), 0, st, y, L, elems, c, m / groups, bpp,
-                     work);
+  hipLaunchKernelGGL(rate_kernel<NX>, dim3((unsigned)(m * bpp)), dim3(256), 0, st, y, yc, L, anchors, elems, c,
+                     m / groups, bpp, seg_pixels, work);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(rate_table_sum_kernel, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, st, work, m, bpp, plane_bits);
   return hipGetLastError();
 }
 
-hipError_t launch_rate_table_grad(const float* y, const float* L, const float* g, int m, int h, int w, int c,
-                                  int groups, float* dy, float* dL, float* work, hipStream_t st) {
-  if (m == 0) return dL ? hipMemsetAsync(dL, 0, (size_t)groups * c * 256 * sizeof(float), st) : hipSuccess;
+template <int NX>
+static hipError_t rate_bwd(const float* y, const float* yc, const float* L, const unsigned char* anchors, const float* g,
+                           int m, int h, int w, int c, int groups, int seg_pixels, float* dy, float* dL, float* work,
+                           hipStream_t st) {
   const int elems = h * w * c;
   if (dy) {
     const long long total = (long long)m * elems, blocks = (total + 255) / 256;
-    hipLaunchKernelGGL(rate_table_dy_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, y, L,
-                       g, total, elems, c, m / groups, dy);
+    hipLaunchKernelGGL(rate_dy_kernel<NX>, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, y, yc, L,
+                       anchors, g, total, elems, c, m / groups, seg_pixels, dy);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   if (dL) {
     const long long spg = rate_slabs(m, h, w, groups);
-    if (groups * spg > INT32_MAX) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(rate_table_dl_kernel, dim3((unsigned)(groups * spg)), dim3(64), 0, st, y, g, c, h * w,
-                       (long long)(m / groups) * h * w, (int)spg, work);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(rate_table_dl_reduce_kernel, dim3((unsigned)((groups * c * 256 + 255) / 256)), dim3(256), 0, st,
-                       work, groups, c, (int)spg, dL);
-    return hipGetLastError();
-  }
-  return hipSuccess;
-}
-
-// the context rate: the forward's partials as above, or a C x 256 partial table per block of
-// kRateSlab pixels of a group and per context: three times the static backward's term
-size_t train_rate_ctable_work_floats(int m, int h, int w, int c, int groups) {
-  const long long fwd = rate_fwd_blocks(m, h, w, c), bwd = 3LL * groups * rate_slabs(m, h, w, groups) * c * 256;
-  return (size_t)(fwd > bwd ? fwd : bwd);
-}
-
-hipError_t launch_rate_ctable(const float* y, const float* yc, const float* L, const unsigned char* anchors, int m, int h,
-                              int w, int c, int groups, int seg_pixels, float* plane_bits, float* work, hipStream_t st) {
-  if (m == 0) return hipSuccess;
-  const int elems = h * w * c, bpp = (elems + kRatePix - 1) / kRatePix;
-  if ((long long)m * bpp > INT32_MAX) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(rate_ctable_kernel, dim3((unsigned)(m * bpp)), dim3(256), 0, st, y, yc ? yc : y, L, anchors, elems,
-                     c, m / groups, bpp, seg_pixels, work);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(rate_table_sum_kernel, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, st, work, m, bpp, plane_bits);
-  return hipGetLastError();
-}
-
-hipError_t launch_rate_ctable_grad(const float* y, const float* yc, const float* L, const unsigned char* anchors,
-                                   const float* g, int m, int h, int w, int c, int groups, int seg_pixels, float* dy,
-                                   float* dL, float* work, hipStream_t st) {
-  if (m == 0) return dL ? hipMemsetAsync(dL, 0, (size_t)groups * c * 3 * 256 * sizeof(float), st) : hipSuccess;
-  const int elems = h * w * c;
-  if (!yc) yc = y;
-  if (dy) {
-    const long long total = (long long)m * elems, blocks = (total + 255) / 256;
-    hipLaunchKernelGGL(rate_ctable_dy_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, y, yc,
-                       L, anchors, g, total, elems, c, m / groups, seg_pixels, dy);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  if (dL) {
-    const long long spg = rate_slabs(m, h, w, groups);
-    if (3LL * groups * spg > INT32_MAX) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(rate_ctable_dl_kernel, dim3((unsigned)(3 * groups * spg)), dim3(64), 0, st, y, yc, anchors, g, c,
+    if (NX * groups * spg > INT32_MAX) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rate_dl_kernel<NX>, dim3((unsigned)(NX * groups * spg)), dim3(64), 0, st, y, yc, anchors, g, c,
                        h * w, (long long)(m / groups) * h * w, (int)spg, seg_pixels, work);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(rate_ctable_dl_reduce_kernel, dim3((unsigned)((groups * 3 * c * 256 + 255) / 256)), dim3(256), 0,
+    hipLaunchKernelGGL(rate_dl_reduce_kernel<NX>, dim3((unsigned)((groups * NX * c * 256 + 255) / 256)), dim3(256), 0,
                        st, work, groups, c, (int)spg, dL);
     return hipGetLastError();
   }
   return hipSuccess;
+}
+
+hipError_t launch_rate(const float* y, const float* L, int contexts, const float* yc, const unsigned char* anchors,
+                       int seg_pixels, int m, int h, int w, int c, int groups, float* plane_bits, float* work,
+                       hipStream_t st) {
+  if (contexts != 1 && contexts != 3) return hipErrorInvalidValue;
+  if (m == 0) return hipSuccess;
+  if (!yc) yc = y;
+  return contexts == 1 ? rate_fwd<1>(y, yc, L, anchors, m, h, w, c, groups, seg_pixels, plane_bits, work, st)
+                       : rate_fwd<3>(y, yc, L, anchors, m, h, w, c, groups, seg_pixels, plane_bits, work, st);
+}
+
+hipError_t launch_rate_grad(const float* y, const float* L, int contexts, const float* yc, const unsigned char* anchors,
+                            int seg_pixels, const float* g, int m, int h, int w, int c, int groups, float* dy,
+                            float* dL, float* work, hipStream_t st) {
+  if (contexts != 1 && contexts != 3) return hipErrorInvalidValue;
+  if (m == 0) return dL ? hipMemsetAsync(dL, 0, (size_t)groups * c * contexts * 256 * sizeof(float), st) : hipSuccess;
+  if (!yc) yc = y;
+  return contexts == 1 ? rate_bwd<1>(y, yc, L, anchors, g, m, h, w, c, groups, seg_pixels, dy, dL, work, st)
+                       : rate_bwd<3>(y, yc, L, anchors, g, m, h, w, c, groups, seg_pixels, dy, dL, work, st);
 }
 
 hipError_t launch_pool2_prep(const float* x, const float* y, int n, int h, int w, int pool, float* xp, float* yp,

@@ -268,127 +268,129 @@ def msssim_terms_grad(mx, my, sxy, sxx, g_ssim, g_cs, c1: float, c2: float, out=
     return tuple(grads)
 
 
-RATE_PIX, RATE_SLAB = 1024, 128  # nic_rate_table's elements / nic_rate_table_grad's pixels per block
+RATE_PIX, RATE_SLAB = 1024, 128  # the rate forward's elements / the rate backward's pixels per block
 
 
-def _rate_shape(y, L, groups: int):
+def _rate_args(who, y, L, groups: int, anchors, seg_pixels: int, yc):
+    """The checked operands of a rate call and its nic_rate_[c]table_work count.  anchors None: the
+    table rate (one context per row, seg_pixels and yc unused); else the context rate (three)."""
+    torch = _torch()
+    y, L = _check(y, f"{who} y"), _check(L, f"{who} L")
     m, h, w, c = y.shape
-    if L.dim() != 2 or tuple(L.shape) != (groups * c, 256):
-        raise ValueError(f"rate_table: L must be ({groups * c}, 256) for {groups} groups of {c} channels, "
-                         f"got {tuple(L.shape)}")
-    # nic_rate_table_work (checked by the calls)
-    need = max(m * -(-(h * w * c) // RATE_PIX), groups * -(-(m // max(groups, 1) * h * w) // RATE_SLAB) * c * 256)
-    return m, h, w, c, need
+    contexts = 1 if anchors is None else 3
+    want = (groups * c, 256) if anchors is None else (groups * c, 3, 256)
+    if tuple(L.shape) != want:
+        raise ValueError(f"{who}: L must be {want} for {groups} groups of {c} channels, got {tuple(L.shape)}")
+    if anchors is not None:
+        if (not isinstance(anchors, torch.Tensor) or anchors.dtype != torch.uint8
+                or tuple(anchors.shape) != (groups * c,) or not anchors.is_contiguous()):
+            raise ValueError(f"{who}: anchors must be a contiguous ({groups * c},) torch.uint8 tensor")
+        if yc is not None:
+            yc = _check(yc, f"{who} yc")
+            if yc.shape != y.shape:
+                raise ValueError(f"{who}: yc {tuple(yc.shape)} is not y's shape {tuple(y.shape)}")
+        if int(seg_pixels) < 1:
+            raise ValueError(f"{who}: seg_pixels must be at least 1, not {seg_pixels}")
+    dev = _same_device(y, yc, L, anchors)
+    need = max(m * -(-(h * w * c) // RATE_PIX),
+               contexts * groups * -(-(m // max(groups, 1) * h * w) // RATE_SLAB) * c * 256)
+    return y, yc, L, dev, (m, h, w, c), need
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _rate_bits(who, y, L, groups: int, anchors=None, seg_pixels: int = 1, yc=None):
+    torch = _torch()
+    y, yc, L, dev, (m, h, w, c), need = _rate_args(who, y, L, groups, anchors, seg_pixels, yc)
+    bits = torch.empty((m,), dtype=torch.float32, device=y.device)
+    work = torch.empty(max(need, 1), dtype=torch.float32, device=y.device)
+    tail = (bits.data_ptr(), work.data_ptr(), need, _stream(dev))
+    with torch.cuda.device(dev):
+        if anchors is None:
+            rc = _lib.lib().nic_rate_table(y.data_ptr(), L.data_ptr(), m, h, w, c, groups, *tail)
+        else:
+            rc = _lib.lib().nic_rate_ctable(y.data_ptr(), _ptr(yc), L.data_ptr(), anchors.data_ptr(), m, h, w, c, groups,
+                                            int(seg_pixels), *tail)
+        _lib.check(rc, f"nic_{who}")
+    return bits
+
+
+def _rate_grad(who, y, L, g, groups: int, want_dy: bool, want_dl: bool, anchors=None, seg_pixels: int = 1, yc=None):
+    torch = _torch()
+    y, yc, L, dev, (m, h, w, c), need = _rate_args(who, y, L, groups, anchors, seg_pixels, yc)
+    g = _check(g, f"{who} g")
+    _same_device(y, g)
+    if g.numel() != m:
+        raise ValueError(f"{who}: one g per plane")
+    dy = torch.empty_like(y) if want_dy else None
+    dl = torch.empty_like(L) if want_dl else None
+    work = torch.empty(max(need, 1), dtype=torch.float32, device=y.device) if want_dl else None
+    tail = (_ptr(dy), _ptr(dl), _ptr(work), need if want_dl else 0, _stream(dev))
+    with torch.cuda.device(dev):
+        if anchors is None:
+            rc = _lib.lib().nic_rate_table_grad(y.data_ptr(), L.data_ptr(), g.data_ptr(), m, h, w, c, groups, *tail)
+        else:
+            rc = _lib.lib().nic_rate_ctable_grad(y.data_ptr(), _ptr(yc), L.data_ptr(), anchors.data_ptr(), g.data_ptr(),
+                                                 m, h, w, c, groups, int(seg_pixels), *tail)
+        _lib.check(rc, f"nic_{who}")
+    return dy, dl
 
 
 def rate_table_bits(y, L, groups: int):
     """nic_rate_table: the (m,) code lengths in bits of the planes of y (m, h, w, c) NHWC under the
     table L (groups * c, 256) of -log2 p."""
-    torch = _torch()
-    y, L = _check(y, "rate_table y"), _check(L, "rate_table L")
-    dev = _same_device(y, L)
-    m, h, w, c, need = _rate_shape(y, L, groups)
-    bits = torch.empty((m,), dtype=torch.float32, device=y.device)
-    work = torch.empty(max(need, 1), dtype=torch.float32, device=y.device)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().nic_rate_table(y.data_ptr(), L.data_ptr(), m, h, w, c, groups, bits.data_ptr(),
-                                             work.data_ptr(), need, _stream(dev)), "nic_rate_table")
-    return bits
+    return _rate_bits("rate_table", y, L, groups)
 
 
 def rate_table_grad(y, L, g, groups: int, want_dy: bool = True, want_dl: bool = True):
     """nic_rate_table_grad: (dy, dL) of sum_m g[m] plane_bits[m]; one is None when not wanted (its
     pointer goes down as NULL and its kernel does not run)."""
-    torch = _torch()
-    y, L, g = _check(y, "rate_table_grad y"), _check(L, "rate_table_grad L"), _check(g, "rate_table_grad g")
-    dev = _same_device(y, L, g)
-    m, h, w, c, need = _rate_shape(y, L, groups)
-    if g.numel() != m:
-        raise ValueError("rate_table_grad: one g per plane")
-    dy = torch.empty_like(y) if want_dy else None
-    dl = torch.empty_like(L) if want_dl else None
-    work = torch.empty(max(need, 1), dtype=torch.float32, device=y.device) if want_dl else None
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().nic_rate_table_grad(
-            y.data_ptr(), L.data_ptr(), g.data_ptr(), m, h, w, c, groups, dy.data_ptr() if want_dy else None,
-            dl.data_ptr() if want_dl else None, work.data_ptr() if want_dl else None, need if want_dl else 0,
-            _stream(dev)), "nic_rate_table_grad")
-    return dy, dl
-
-
-def _rate_ctable_args(who, y, yc, L, anchors, groups: int, seg_pixels: int):
-    """The checked operands of the context rate calls and nic_rate_ctable_work's count."""
-    torch = _torch()
-    y, L = _check(y, f"{who} y"), _check(L, f"{who} L")
-    m, h, w, c = y.shape
-    if L.dim() != 3 or tuple(L.shape) != (groups * c, 3, 256):
-        raise ValueError(f"{who}: L must be ({groups * c}, 3, 256) for {groups} groups of {c} channels, "
-                         f"got {tuple(L.shape)}")
-    if (not isinstance(anchors, torch.Tensor) or anchors.dtype != torch.uint8 or tuple(anchors.shape) != (groups * c,)
-            or not anchors.is_contiguous()):
-        raise ValueError(f"{who}: anchors must be a contiguous ({groups * c},) torch.uint8 tensor")
-    if yc is not None:
-        yc = _check(yc, f"{who} yc")
-        if yc.shape != y.shape:
-            raise ValueError(f"{who}: yc {tuple(yc.shape)} is not y's shape {tuple(y.shape)}")
-    if int(seg_pixels) < 1:
-        raise ValueError(f"{who}: seg_pixels must be at least 1, not {seg_pixels}")
-    dev = _same_device(y, yc, L, anchors)
-    need = max(m * -(-(h * w * c) // RATE_PIX), 3 * groups * -(-(m // max(groups, 1) * h * w) // RATE_SLAB) * c * 256)
-    return y, yc, L, dev, (m, h, w, c), need
+    return _rate_grad("rate_table_grad", y, L, g, groups, want_dy, want_dl)
 
 
 def rate_ctable_bits(y, L, anchors, groups: int, seg_pixels: int, yc=None):
     """nic_rate_ctable: the (m,) code lengths in bits of the planes of y (m, h, w, c) NHWC under the
     context table L (groups * c, 3, 256) of -log2 p; the row of an element is picked by its left
     neighbour's code in yc (None: y) against anchors ((groups * c,) u8), segments of seg_pixels."""
-    torch = _torch()
-    y, yc, L, dev, (m, h, w, c), need = _rate_ctable_args("rate_ctable", y, yc, L, anchors, groups, seg_pixels)
-    bits = torch.empty((m,), dtype=torch.float32, device=y.device)
-    work = torch.empty(max(need, 1), dtype=torch.float32, device=y.device)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().nic_rate_ctable(
-            y.data_ptr(), yc.data_ptr() if yc is not None else None, L.data_ptr(), anchors.data_ptr(), m, h, w, c, groups,
-            int(seg_pixels), bits.data_ptr(), work.data_ptr(), need, _stream(dev)), "nic_rate_ctable")
-    return bits
+    return _rate_bits("rate_ctable", y, L, groups, _anchors(anchors), seg_pixels, yc)
 
 
 def rate_ctable_grad(y, L, anchors, g, groups: int, seg_pixels: int, yc=None, want_dy: bool = True,
                      want_dl: bool = True):
     """nic_rate_ctable_grad: (dy, dL) of sum_m g[m] plane_bits[m]; one is None when not wanted (its
     pointer goes down as NULL and its kernels do not run).  yc and anchors get no gradient."""
-    torch = _torch()
-    y, yc, L, dev, (m, h, w, c), need = _rate_ctable_args("rate_ctable_grad", y, yc, L, anchors, groups, seg_pixels)
-    g = _check(g, "rate_ctable_grad g")
-    _same_device(y, g)
-    if g.numel() != m:
-        raise ValueError("rate_ctable_grad: one g per plane")
-    dy = torch.empty_like(y) if want_dy else None
-    dl = torch.empty_like(L) if want_dl else None
-    work = torch.empty(max(need, 1), dtype=torch.float32, device=y.device) if want_dl else None
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().nic_rate_ctable_grad(
-            y.data_ptr(), yc.data_ptr() if yc is not None else None, L.data_ptr(), anchors.data_ptr(), g.data_ptr(), m, h,
-            w, c, groups, int(seg_pixels), dy.data_ptr() if want_dy else None, dl.data_ptr() if want_dl else None,
-            work.data_ptr() if want_dl else None, need if want_dl else 0, _stream(dev)), "nic_rate_ctable_grad")
-    return dy, dl
+    return _rate_grad("rate_ctable_grad", y, L, g, groups, want_dy, want_dl, _anchors(anchors), seg_pixels, yc)
+
+
+def _anchors(anchors):
+    """The context rate's anchors as given; a missing one as a value the operand check refuses (None
+    would select the table rate)."""
+    return () if anchors is None else anchors
 
 
 def _conv_fn():
     torch = _torch()
 
-    class RateCTable(torch.autograd.Function):
-        """Per-plane code length of y (m, h, w, c) under the context table L (groups * c, 3, 256)
-        (nic_rate_ctable / nic_rate_ctable_grad); a gradient nobody asked for is not computed, and
-        yc and anchors never get one (the context is piecewise constant)."""
+    class Rate(torch.autograd.Function):
+        """Per-plane code length of y (m, h, w, c) under the table L of -log2 p: anchors None, the
+        table rate on L (groups * c, 256) (nic_rate_table / nic_rate_table_grad); else the context
+        rate on L (groups * c, 3, 256) (nic_rate_ctable / nic_rate_ctable_grad).  A gradient nobody
+        asked for is not computed, and yc and anchors never get one (the context is piecewise
+        constant)."""
 
         @staticmethod
-        def forward(ctx, y, L, anchors, groups, seg_pixels, yc):
-            y, L = _check(y, "RateCTable y"), _check(L, "RateCTable L")
-            yc = None if yc is None else _check(yc.detach(), "RateCTable yc")
+        def forward(ctx, y, L, groups, anchors, seg_pixels, yc):
+            y, L = _check(y, "Rate y"), _check(L, "Rate L")
+            yc = None if yc is None else _check(yc.detach(), "Rate yc")
+            if anchors is None:
+                bits = rate_table_bits(y, L, groups)
+            else:
+                bits = rate_ctable_bits(y, L, anchors, groups, seg_pixels, yc)
             ctx.save_for_backward(y, L, anchors, yc)
             ctx.groups, ctx.seg_pixels = groups, seg_pixels
-            return rate_ctable_bits(y, L, anchors, groups, seg_pixels, yc)
+            return bits
 
         @staticmethod
         def backward(ctx, g):
@@ -396,28 +398,11 @@ def _conv_fn():
             want_dy, want_dl = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
             if not (want_dy or want_dl):
                 return None, None, None, None, None, None
-            dy, dl = rate_ctable_grad(y, L, anchors, g.contiguous(), ctx.groups, ctx.seg_pixels, yc, want_dy, want_dl)
+            if anchors is None:
+                dy, dl = rate_table_grad(y, L, g.contiguous(), ctx.groups, want_dy, want_dl)
+            else:
+                dy, dl = rate_ctable_grad(y, L, anchors, g.contiguous(), ctx.groups, ctx.seg_pixels, yc, want_dy, want_dl)
             return dy, dl, None, None, None, None
-
-    class RateTable(torch.autograd.Function):
-        """Per-plane code length of y (m, h, w, c) under the table L (groups * c, 256) of -log2 p
-        (nic_rate_table / nic_rate_table_grad); a gradient nobody asked for is not computed."""
-
-        @staticmethod
-        def forward(ctx, y, L, groups):
-            y, L = _check(y, "RateTable y"), _check(L, "RateTable L")
-            ctx.save_for_backward(y, L)
-            ctx.groups = groups
-            return rate_table_bits(y, L, groups)
-
-        @staticmethod
-        def backward(ctx, g):
-            y, L = ctx.saved_tensors
-            want_dy, want_dl = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-            if not (want_dy or want_dl):
-                return None, None, None
-            dy, dl = rate_table_grad(y, L, g.contiguous(), ctx.groups, want_dy, want_dl)
-            return dy, dl, None
 
     class Conv2DSame(torch.autograd.Function):
         """Keras Conv2D(padding='SAME'), leaky_relu(0.2) when act, NHWC; kernel (kh, kw, Cin, Cout)."""
@@ -550,11 +535,11 @@ def _conv_fn():
                               *ctx.consts, out=out)
             return out, None, None
 
-    return _Fns(Conv2DSame, Conv2DTransposeSame, Gauss1D, Pool2Prep, MsssimTerms, RateTable, RateCTable)
+    return _Fns(Conv2DSame, Conv2DTransposeSame, Gauss1D, Pool2Prep, MsssimTerms, Rate)
 
 
 # the autograd classes, looked up by name (callers that still index find the two convolutions first)
-_Fns = namedtuple("_Fns", "Conv2DSame Conv2DTransposeSame Gauss1D Pool2Prep MsssimTerms RateTable RateCTable")
+_Fns = namedtuple("_Fns", "Conv2DSame Conv2DTransposeSame Gauss1D Pool2Prep MsssimTerms Rate")
 _FNS = None
 
 
@@ -579,7 +564,7 @@ def rate_table(y, L, groups: int):
     """The (m,) code lengths in bits of the planes of y (m, h, w, c) NHWC under the table L
     (groups * c, 256) of -log2 p, plane i reading the rows of group i // (m / groups) (HIP,
     differentiable in y and in L; training.table_rate states the formula)."""
-    return _fns().RateTable.apply(y, L, int(groups))
+    return _fns().Rate.apply(y, L, int(groups), None, 1, None)
 
 
 def rate_ctable(y, L, anchors, groups: int, seg_pixels: int, yc=None):
@@ -587,7 +572,7 @@ def rate_ctable(y, L, anchors, groups: int, seg_pixels: int, yc=None):
     (groups * c, 3, 256) of -log2 p: an element reads the row its left neighbour's code in yc (None:
     y) selects against anchors ((groups * c,) u8), a segment's first pixel row 0 (HIP,
     differentiable in y and in L, never in yc or anchors; training.context_rate states the formula)."""
-    return _fns().RateCTable.apply(y, L, anchors, int(groups), int(seg_pixels), yc)
+    return _fns().Rate.apply(y, L, int(groups), _anchors(anchors), int(seg_pixels), yc)
 
 
 SSIM_PIX = 1024  # map pixels per block of nic_msssim_terms (its work: two partial sums per block)

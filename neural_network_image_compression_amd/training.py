@@ -242,9 +242,29 @@ def table_code_lengths(logits):
     return -torch.log2(torch.softmax(logits, dim=1))
 
 
+def _table_rows(y, groups: int):
+    """(M, C): the table row group * C + c of each plane's channels, y (M, C, h, w)."""
+    torch = _torch()
+    m, c = y.shape[0], y.shape[1]
+    group = torch.arange(m, device=y.device) // max(m // groups, 1)
+    return group[:, None] * c + torch.arange(c, device=y.device)[None, :]
+
+
+def _interpolated_bits(y, L, rows2, ctx=None):
+    """The rate losses' element step, summed per plane: L[r][k] + t (L[r][k+1] - L[r][k]) on the row
+    L[r] (``ctx`` None, the table rate) or L[r][ctx] (the context rate)."""
+    torch = _torch()
+    v = torch.fmin(torch.fmax(255 * y, y.new_zeros(())), y.new_full((), 255.0))  # a NaN becomes 0
+    k = v.detach().floor().clamp(max=254).long()
+    t = v - k.to(v.dtype)
+    rows = rows2[:, :, None, None]
+    l0, l1 = (L[rows, k], L[rows, k + 1]) if ctx is None else (L[rows, ctx, k], L[rows, ctx, k + 1])
+    bits = l0 + t * (l1 - l0)
+    return bits.sum(dim=(1, 2, 3))
+
+
 def table_bits(y, L, groups: int, hip: bool = False):
     """:func:`table_rate` from the code lengths L (groups * C, 256) themselves."""
-    torch = _torch()
     if hip:
         from . import train_hip
 
@@ -253,14 +273,7 @@ def table_bits(y, L, groups: int, hip: bool = False):
     if groups < 1 or m % groups or L.dim() != 2 or tuple(L.shape) != (groups * c, 256):
         raise ValueError(f"table_rate: {m} planes of {c} channels in {groups} groups need a ({groups * c}, 256) table, "
                          f"got {tuple(L.shape)}")
-    v = torch.fmin(torch.fmax(255 * y, y.new_zeros(())), y.new_full((), 255.0))  # a NaN becomes 0
-    k = v.detach().floor().clamp(max=254).long()
-    t = v - k.to(v.dtype)
-    group = torch.arange(m, device=y.device) // max(m // groups, 1)
-    rows = (group[:, None] * c + torch.arange(c, device=y.device)[None, :])[:, :, None, None]
-    l0 = L[rows, k]
-    bits = l0 + t * (L[rows, k + 1] - l0)
-    return bits.sum(dim=(1, 2, 3))
+    return _interpolated_bits(y, L, _table_rows(y, groups))
 
 
 def table_rate(y, logits, groups: int, hip: bool = False):
@@ -304,24 +317,15 @@ def context_bits(y, L, anchors, groups: int, seg_pixels: int = 32, yc=None, hip:
         raise ValueError("context_rate: yc must have y's shape")
     if int(seg_pixels) < 1:
         raise ValueError(f"context_rate: seg_pixels must be at least 1, not {seg_pixels}")
-    zero, top = y.new_zeros(()), y.new_full((), 255.0)
-    group = torch.arange(m, device=y.device) // max(m // groups, 1)
-    rows2 = group[:, None] * c + torch.arange(c, device=y.device)[None, :]  # (M, C)
+    rows2 = _table_rows(y, groups)
     with torch.no_grad():  # the context: piecewise constant, nothing flows through it
         src = (y if yc is None else yc).detach()
-        code = torch.fmin(torch.fmax(255 * src, zero), top).round().long()  # (M, C, h, w); a NaN becomes 0
+        code = torch.fmin(torch.fmax(255 * src, y.new_zeros(())), y.new_full((), 255.0)).round().long()  # a NaN becomes 0
         code = code.reshape(m, c, h * w)
         ctx = torch.zeros_like(code)
         ctx[:, :, 1:] = (code[:, :, :-1] - anchors.long()[rows2][:, :, None]).abs().clamp(max=2)
         ctx[:, :, ::int(seg_pixels)] = 0
-        ctx = ctx.reshape(m, c, h, w)
-    v = torch.fmin(torch.fmax(255 * y, zero), top)  # a NaN becomes 0
-    k = v.detach().floor().clamp(max=254).long()
-    t = v - k.to(v.dtype)
-    rows = rows2[:, :, None, None]
-    l0 = L[rows, ctx, k]
-    bits = l0 + t * (L[rows, ctx, k + 1] - l0)
-    return bits.sum(dim=(1, 2, 3))
+    return _interpolated_bits(y, L, rows2, ctx.reshape(m, c, h, w))
 
 
 def context_rate(y, logits, anchors, groups: int, seg_pixels: int = 32, yc=None, hip: bool = False):

@@ -13,7 +13,10 @@ product would is not an error of the arithmetic being measured; v and t are then
 """
 import numpy as np
 
-SHAPES = [(3, 1, 1, 32, 3), (6, 5, 7, 32, 3), (2, 3, 3, 32, 1), (4, 2, 2, 8, 2)]  # (M, h, w, C, G)
+SHAPES = [(3, 1, 1, 32, 3), (6, 5, 7, 32, 3), (2, 3, 3, 32, 1), (4, 2, 2, 8, 2),  # (M, h, w, C, G)
+          # the dL kernel's replica count R = 64 // C at its ends: R = 1 (no replica sum), 64 % C != 0
+          # (16 idle lanes), and R = 64 with C x 256 = 256 (the whole LDS array in use)
+          (2, 3, 3, 64, 1), (2, 3, 3, 24, 2), (2, 3, 3, 1, 1)]
 
 
 def code_lengths(logits):

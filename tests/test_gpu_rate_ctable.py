@@ -24,27 +24,13 @@ from neural_network_image_compression_amd import prior as P  # noqa: E402
 from neural_network_image_compression_amd import train_hip  # noqa: E402
 from neural_network_image_compression_amd import training as T  # noqa: E402
 from tests import rate_ctable_ref as RC  # noqa: E402
+from tests.rate_gpu_common import G_KINDS, g as _g, nchw as _nchw, report, ulps as _ulps  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 EPS = 2.0 ** -23
 CASES = [(shape, seg) for shape in RC.SHAPES for seg in RC.segs(shape)]
-G_KINDS = ("equal", "first_group", "signs")
-
-
-def _report(what, *figs):
-    print(f"\n[rate-ctable] {what}: " + " ".join(f"{f:.3e}" if isinstance(f, float) else str(f) for f in figs))
-
-
-def _g(kind, m, groups):
-    if kind == "equal":
-        return np.full(m, 1.0 / 4096, np.float32)
-    if kind == "first_group":  # what loss0 sends down: nothing outside the Y planes
-        g = np.zeros(m, np.float32)
-        g[:m // groups] = 0.01 / 1024
-        return g
-    rng = np.random.default_rng(m)
-    return (rng.standard_normal(m) * 1e-3).astype(np.float32)
+_report = functools.partial(report, "rate-ctable")
 
 
 @functools.lru_cache(maxsize=None)
@@ -67,10 +53,6 @@ def _ref(shape, seg):
     return bits, bits_abs, grads
 
 
-def _nchw(t):
-    return t.permute(0, 3, 1, 2).contiguous()
-
-
 @pytest.mark.parametrize("shape,seg", CASES, ids=str)
 def test_forward_matches_float64(shape, seg):
     m, h, w, c, groups = shape
@@ -84,12 +66,6 @@ def test_forward_matches_float64(shape, seg):
     assert np.all(err <= 2 * e32 + EPS * ref_abs)
     assert torch.equal(train_hip.rate_ctable(yd, Ld, ad, groups, seg, ycd), got)  # deterministic
     assert torch.equal(train_hip.rate_ctable_bits(yd, Ld, ad, groups, seg, ycd), got)
-
-
-def _ulps(a, ref):
-    a, ref = a.double().cpu(), ref.double().cpu()
-    spacing = torch.ldexp(torch.ones_like(ref), torch.floor(torch.log2(ref.abs().clamp_min(1e-37))).int() - 23)
-    return float(((a - ref).abs() / spacing).max())
 
 
 @pytest.mark.parametrize("shape,seg", CASES, ids=str)

@@ -24,6 +24,7 @@ from neural_network_image_compression_amd import prior as P  # noqa: E402
 from neural_network_image_compression_amd import train_hip  # noqa: E402
 from neural_network_image_compression_amd import training as T  # noqa: E402
 from tests import rate_table_ref as R  # noqa: E402
+from tests.rate_gpu_common import G_KINDS, g as _g, nchw as _nchw, report, ulps as _ulps  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -31,22 +32,7 @@ EPS = 2.0 ** -23
 # the CPU test's shapes, and 15 planes of 16 x 16 x 32: eight forward blocks per plane, ten slabs
 # per group (the last one ragged) in the backward
 SHAPES = R.SHAPES + [(15, 16, 16, 32, 3)]
-G_KINDS = ("equal", "first_group", "signs")
-
-
-def _report(what, *figs):
-    print(f"\n[rate-table] {what}: " + " ".join(f"{f:.3e}" if isinstance(f, float) else str(f) for f in figs))
-
-
-def _g(kind, m, groups):
-    if kind == "equal":
-        return np.full(m, 1.0 / 4096, np.float32)
-    if kind == "first_group":  # what loss0 sends down: nothing outside the Y planes
-        g = np.zeros(m, np.float32)
-        g[:m // groups] = 0.01 / 1024
-        return g
-    rng = np.random.default_rng(m)
-    return (rng.standard_normal(m) * 1e-3).astype(np.float32)
+_report = functools.partial(report, "rate-table")
 
 
 @functools.lru_cache(maxsize=None)
@@ -59,10 +45,6 @@ def _case(shape):
     bits, bits_abs = R.rate_table(y, L, groups)
     grads = {kind: R.rate_table_grad(y, L, _g(kind, m, groups), groups) for kind in G_KINDS}
     return y, L, bits, bits_abs, grads
-
-
-def _nchw(t):
-    return t.permute(0, 3, 1, 2).contiguous()
 
 
 @pytest.mark.parametrize("shape", SHAPES, ids=str)
@@ -106,12 +88,6 @@ def test_edge_inputs_equal_the_clamped_reference():
     assert bool(torch.isfinite(dy).all()) and bool(torch.isfinite(dl).all())
     want = R.rate_table_grad(y, L, np.full(3, 1.0 / 64), groups)[1]
     assert np.abs(dl.double().cpu().numpy() - want).max() <= 1e-5 * np.abs(want).max()
-
-
-def _ulps(a, ref):
-    a, ref = a.double().cpu(), ref.double().cpu()
-    spacing = torch.ldexp(torch.ones_like(ref), torch.floor(torch.log2(ref.abs().clamp_min(1e-37))).int() - 23)
-    return float(((a - ref).abs() / spacing).max())
 
 
 @pytest.mark.parametrize("kind", G_KINDS)
