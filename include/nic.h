@@ -32,6 +32,15 @@
  *  - Work is enqueued asynchronously on the caller's hipStream_t (NULL = default
  *    stream).  One nic_ctx must not be used by two threads at once; distinct contexts
  *    are independent.  There is no global mutable state besides the per-thread error.
+ *  - One nic_ctx on several streams of one thread: the caller orders the ctx's calls across
+ *    streams.  The workspace, the histogram and MS-SSIM scratch and the range-guard word belong
+ *    to the ctx, not to a stream, and no call records or waits on an event for another stream
+ *    (nic_encode_host / nic_decode_host alone order their own three streams behind `stream`).
+ *    A call on stream 2 may follow a call of the same ctx on stream 1 once stream 2 waits for
+ *    that call (hipStreamWaitEvent, torch's wait_stream); unordered, the two share scratch and
+ *    race.  Calls that take no ctx (nic_sq_err, nic_pack_latent, the training side path) use
+ *    only their arguments and need no such order.  tests/test_gpu_stream_contract.py holds
+ *    every entry point to "on `stream`, no host synchronisation" (DESIGN.md section 24).
  *  - Layouts are NHWC uint8: images (N, H, W, 3); latents (N, ceil(H/8), ceil(W/8), 96)
  *    with channels Y0..31, Cb0..31, Cr0..31 (encoder.py:45).  Sizes need not be multiples
  *    of 8: like the reference, decode returns (N, 8h, 8w, 3).

@@ -365,7 +365,7 @@ class Codec:
 
     def psnr(self, a, b, max_val: float = 255.0, per_image: bool = False):
         """PSNR in dB over the whole batch (as the oracle's psnr) or per image, from the exact
-        device sum of squared errors."""
+        device sum of squared errors.  Reads the sums back to the host (synchronises)."""
         import math
 
         sse = self.sq_err(a, b).cpu().numpy().astype(np.float64)

@@ -121,11 +121,36 @@ def colour_planes(x_norm):
     return [(((r * k[0] + g * k[1]) + b * k[2]) + off)[:, None] for k, off in zip(YCBCR, YCBCR_OFF)]
 
 
+_DEVICE_CONSTS = {}
+
+
+def _device_const(torch, key, device, dtype, make):
+    """The host tensor make() as a read-only constant on ``device``, uploaded once per (key, device,
+    dtype).  An upload from pageable memory keeps the host until the current stream has drained, so
+    the losses, which run "on the current stream, no host synchronisation", must not repeat it per
+    call.  Every caller gets the same tensor: read it, never write it.  It is
+    made outside any inference_mode or grad mode of the first caller, so that later autograd uses
+    can save it."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        return make().to(device=device, dtype=dtype)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    k = (key, device.index, dtype)
+    t = _DEVICE_CONSTS.get(k)
+    if t is None:
+        with torch.inference_mode(False), torch.no_grad():
+            t = _DEVICE_CONSTS[k] = make().to(device=device, dtype=dtype)
+    return t
+
+
 def _gauss_window(torch, device, dtype, size: int = 11, sigma: float = 1.5):
-    c = torch.arange(size, dtype=torch.float64) - (size - 1) / 2.0
-    g = torch.exp(-0.5 * c * c / sigma ** 2)
-    g = g / g.sum()
-    return g.to(device=device, dtype=dtype)
+    def make():
+        c = torch.arange(size, dtype=torch.float64) - (size - 1) / 2.0
+        g = torch.exp(-0.5 * c * c / sigma ** 2)
+        return g / g.sum()
+
+    return _device_const(torch, ("gauss", size, sigma), device, dtype, make)
 
 
 def ssim(x, y, max_val: float = 1.0, hip: bool = False):
@@ -178,15 +203,59 @@ def ms_ssim_sizes(h: int, w: int, scales: int):
     return sizes
 
 
+_ROW_PROD = None
+
+
+def _row_prod():
+    """t.prod(dim=1) of an (N, K) tensor with a backward that stays on the stream.  torch's own
+    prod backward counts the zeros of its input and reads the count on the host (.item()), which
+    keeps the host until the stream has drained, once per training step.  Here the forward is
+    torch's prod, bit for bit, and the backward is the same g (result / t) where t is not 0; an
+    entry that is 0 gets g times the product of its row's other entries (torch's zero-safe form),
+    picked per element on the device.  The backward is once_differentiable: a second-order pass
+    (create_graph=True) over the MS-SSIM loss, which Tensor.prod allowed and nothing here makes,
+    raises."""
+    global _ROW_PROD
+    if _ROW_PROD is None:
+        torch = _torch()
+
+        class RowProd(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, t):
+                out = t.prod(dim=1)
+                ctx.save_for_backward(t, out)
+                return out
+
+            @staticmethod
+            @torch.autograd.function.once_differentiable
+            def backward(ctx, g):
+                t, out = ctx.saved_tensors
+                zero = t == 0
+                ratio = out[:, None] / torch.where(zero, torch.ones_like(t), t)
+                cols = t.unbind(1)
+                others = []
+                for k in range(len(cols)):
+                    rest = [c for j, c in enumerate(cols) if j != k]
+                    p = rest[0] if rest else torch.ones_like(cols[k])
+                    for c in rest[1:]:
+                        p = p * c
+                    others.append(p)
+                return g[:, None] * torch.where(zero, torch.stack(others, dim=1), ratio)
+
+        _ROW_PROD = RowProd
+    return _ROW_PROD
+
+
 def ms_ssim_combine(terms, scales: int):
     """tf.image.ssim_multiscale's combination of the (N, K) per-scale terms: each clamped at 0,
     raised to its weight, multiplied.  A term <= 0 contributes 0 with a zero (not inf / nan)
-    gradient."""
+    gradient.  No host synchronisation, forward or backward (:func:`_row_prod`)."""
     torch = _torch()
-    wts = torch.tensor(MSSSIM_WEIGHTS[:scales], dtype=terms.dtype, device=terms.device)
+    wts = _device_const(torch, ("msssim_weights", scales), terms.device, terms.dtype,
+                        lambda: torch.tensor(MSSSIM_WEIGHTS[:scales], dtype=terms.dtype))
     pos = terms > 0
     powed = torch.where(pos, terms, torch.ones_like(terms)) ** wts
-    return torch.where(pos, powed, torch.zeros_like(powed)).prod(dim=1)
+    return _row_prod().apply(torch.where(pos, powed, torch.zeros_like(powed)))
 
 
 def ms_ssim(x, y, scales: int = 4, max_val: float = 1.0, hip: bool = False):

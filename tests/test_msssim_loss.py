@@ -99,6 +99,35 @@ def test_negative_term_gives_zero_with_a_finite_gradient():
     assert torch.equal(v, torch.zeros_like(v)) and bool(torch.isfinite(ya.grad).all())
 
 
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+def test_combine_backward_is_torch_prods_without_its_host_read(dtype):
+    """ms_ssim_combine multiplies the K terms with training._row_prod, whose backward does not read a
+    zero count on the host as torch's prod backward does.  Same value bit for bit, and the same
+    gradient as torch's: bit for bit for a tensor without a zero (torch's g (result / t)), and torch's
+    zero-safe values (to rounding: another order of the same products) for one with zeros."""
+    g = torch.Generator().manual_seed(3)
+    t = torch.rand((6, 4), generator=g, dtype=torch.float64).to(dtype) + 0.25
+    up = torch.rand((6,), generator=g, dtype=torch.float64).to(dtype) + 0.5
+    for zeros in (False, True):
+        if zeros:
+            t[1, 2] = 0.0
+            t[4, 0] = t[4, 3] = 0.0
+        a, b = t.clone().requires_grad_(), t.clone().requires_grad_()
+        va, vb = T._row_prod().apply(a), b.prod(dim=1)
+        assert torch.equal(va, vb)
+        (ga,), (gb,) = torch.autograd.grad(va, a, up), torch.autograd.grad(vb, b, up)
+        if not zeros:
+            assert torch.equal(ga, gb)
+        torch.testing.assert_close(ga, gb, rtol=4 * torch.finfo(dtype).eps, atol=0)
+    assert float(ga[1, 2]) != 0 and torch.equal(ga[4], torch.zeros_like(ga[4]))
+    # and through the whole combination: a term <= 0 still gives 0 with a zero gradient
+    terms = torch.tensor([[0.9, 0.8, 0.7], [-0.1, 0.8, 0.7], [0.9, 0.0, 0.7]], dtype=dtype, requires_grad=True)
+    v = T.ms_ssim_combine(terms, 3)
+    v.sum().backward()
+    assert float(v[0]) > 0 and torch.equal(v[1:], torch.zeros_like(v[1:]))
+    assert bool((terms.grad[0] > 0).all()) and torch.equal(terms.grad[1:], torch.zeros_like(terms.grad[1:]))
+
+
 def _smooth(n, h, w, seed):  # as tests/test_training.py
     rng = np.random.default_rng(seed)
     a = np.cumsum(np.cumsum(rng.integers(-2, 3, (n, h, w, 3)), axis=1), axis=2).astype(np.float64)
