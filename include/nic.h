@@ -130,6 +130,13 @@ int nic_range_trips(nic_ctx* ctx, int64_t* passes);
  * (occupancy; informational -- the queued stages need no co-residency), the grid (one block
  * per CU) and whether it uses a cooperative launch (always 0: a plain launch). */
 int nic_rerun_launch_info(nic_ctx* ctx, int* blocks_per_cu, int* grid, int* cooperative);
+/* The grids nic_decode's split-f16 pass launches on ctx's device for n latents of h8 x w8, from
+ * the launches' own split functions (nothing runs): blocks[0..1] dconv1's blocks for the Y and
+ * for the CbCr planes, blocks[2..3] the same for dconv7, blocks[4] the grid of the fused
+ * dconv5+dconv6 pair (0: those planes take two launches).  What a block of these persistent
+ * kernels does depends on how many tiles it walks; the tests place their batches by these
+ * figures.  NIC_ESHAPE for a batch the split-f16 pass does not take. */
+int nic_decode_launch_info(nic_ctx* ctx, int n, int h8, int w8, int* blocks);
 
 /* ABI version: major * 10000 + minor * 100 + patch */
 int nic_version(void);

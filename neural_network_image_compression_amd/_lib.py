@@ -77,6 +77,8 @@ _SIGNATURES = {
                                       ctypes.c_int64, c_vp, ctypes.c_int]),
     "nic_rerun_launch_info": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                              ctypes.POINTER(ctypes.c_int)]),
+    "nic_decode_launch_info": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                              ctypes.POINTER(ctypes.c_int)]),
     "nic_set_timing": (ctypes.c_int, [c_vp, ctypes.c_int]),
     "nic_layer_times": (ctypes.c_int, [c_vp, c_vp, c_vp]),
     "nic_ms_ssim": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),

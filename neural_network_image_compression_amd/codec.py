@@ -208,6 +208,14 @@ class Codec:
         _lib.check(self._L.nic_rerun_launch_info(self._h, *[ctypes.byref(t) for t in v]), "nic_rerun_launch_info")
         return {"blocks_per_cu": v[0].value, "grid": v[1].value, "cooperative": bool(v[2].value)}
 
+    def decode_launch_info(self, n: int, h8: int, w8: int) -> dict:
+        """The grids the f16x3 decode of (n, h8, w8, 96) latents launches here
+        (nic_decode_launch_info): dconv1's and dconv7's blocks for (Y, CbCr), the fused
+        dconv5+dconv6 pair's grid (0: two launches)."""
+        v = (ctypes.c_int * 5)()
+        _lib.check(self._L.nic_decode_launch_info(self._h, n, h8, w8, v), "nic_decode_launch_info")
+        return {"dconv1": (v[0], v[1]), "dconv7": (v[2], v[3]), "pair": v[4]}
+
     def set_timing(self, enable: bool) -> None:
         """Bracket every layer launch with hipEvents on the launch stream (resets the sums)."""
         _lib.check(self._L.nic_set_timing(self._h, int(bool(enable))), "nic_set_timing")

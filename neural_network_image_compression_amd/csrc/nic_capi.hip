@@ -464,7 +464,7 @@ bool models_ready(const nic_ctx* c, int m0) {
 
 extern "C" {
 
-int nic_version(void) { return 1400; }
+int nic_version(void) { return 1500; }
 
 int nic_constants(float* ycbcr9, float* ycbcr_inv9, float* off3) {
   // host copy of what nic_create uploads; lets tests compare with np.linalg.inv (utils.py:8)
@@ -2083,6 +2083,16 @@ int nic_rerun_launch_info(nic_ctx* c, int* blocks_per_cu, int* grid, int* cooper
   if (!c || !blocks_per_cu || !grid || !cooperative) return fail(NIC_EINVAL, "nic_rerun_launch_info: NULL argument");
   DeviceGuard guard(c->device);
   fp32_chain_launch_info(blocks_per_cu, grid, cooperative);
+  return NIC_OK;
+}
+
+int nic_decode_launch_info(nic_ctx* c, int n, int h8, int w8, int* blocks) {
+  if (!c || !blocks) return fail(NIC_EINVAL, "nic_decode_launch_info: NULL argument");
+  if (n <= 0 || h8 <= 0 || w8 <= 0 || 3LL * n > 65535 || !x3_plane_fits(2LL * h8, 2LL * w8))
+    return fail(NIC_ESHAPE, "nic_decode_launch_info: (%d,%d,%d,96) is no batch of the f16x3 decoder", n, h8, w8);
+  DeviceGuard guard(c->device);
+  decoder_launch_info(n, h8, w8, blocks);
+  if (!use_k3pair()) blocks[4] = 0;
   return NIC_OK;
 }
 

@@ -150,6 +150,11 @@ hipError_t launch_dconv8(Dconv8Args a, hipStream_t st);      // exact fp32 VALU
 // of every output pixel instead of its 64 channels, the gather sums them per output pixel
 hipError_t launch_dconv7_proj_x3(const ConvArgs& a, hipStream_t st);
 hipError_t launch_dconv8_gather(Dconv8Args a, hipStream_t st);
+// the grids of the f16x3 decoder's persistent kernels for n latents of h8 x w8 on the current
+// device, from the launches' own split functions: dconv1 (launch_dconv1_all) blocks for the Y
+// and for the CbCr planes, dconv7 (launch_dconv7_proj_x3) the same, the fused dconv5+dconv6
+// pair's grid (0: the planes take the two launches)
+void decoder_launch_info(int n, int h8, int w8, int blocks[5]);
 // histogram entropy: per-block partial counts into `part` (hist_scratch_bytes), then one
 // reduce kernel writes counts (optional) and bits/symbol (optional)
 size_t hist_scratch_bytes(int nimg, int plane_px);

@@ -1197,6 +1197,24 @@ __global__ __launch_bounds__(64 * (COUT / 16), 2) void conv_ws_kernel(ConvArgs a
   }
 }
 
+// launch_ws's blocks per model group (0: the nimg Y planes, 1: the P - nimg CbCr planes): 2
+// resident blocks per CU, shared out in proportion to the groups' tiles, rounded, and at most a
+// block per tile
+static void ws_group_blocks(int nimg, int P, long long per_plane, int blocks[2]) {
+  long long work[2], total = 0;
+  for (int gi = 0; gi < 2; ++gi) {
+    work[gi] = ((gi & 1) ? P - nimg : nimg) * per_plane;
+    total += work[gi];
+  }
+  const int target = 2 * device_cus();  // 2 resident blocks per CU
+  for (int gi = 0; gi < 2; ++gi) {
+    const long long tiles = work[gi];
+    long long b = (work[gi] * target + total / 2) / total;
+    b = b < 1 ? 1 : b > tiles ? tiles : b;
+    blocks[gi] = (int)b;
+  }
+}
+
 // Weight-stationary launch: 2 resident blocks per CU, split into groups (tap set, model)
 // in proportion to each group's MFMA work (planes x taps).
 template <int CIN, int COUT, int TH, int TW, bool RESID, bool TRP, bool PROJ = false>
@@ -1214,19 +1232,10 @@ static hipError_t launch_ws(ConvArgs a, hipStream_t st) {
   // tiles; per-phase groups measured 6 % slower)
   a.ws_taps = TRP ? 25 : 9;
   a.ws_ngrp = 2;
-  long long work[2], total = 0;
-  for (int gi = 0; gi < 2; ++gi) {
-    work[gi] = ((gi & 1) ? a.P - a.nimg : a.nimg) * per_plane;
-    total += work[gi];
-  }
-  const int target = 2 * device_cus();  // 2 resident blocks per CU
+  int blocks[2];
+  ws_group_blocks(a.nimg, a.P, per_plane, blocks);
   a.ws_blk[0] = 0;
-  for (int gi = 0; gi < a.ws_ngrp; ++gi) {
-    const long long tiles = ((gi & 1) ? a.P - a.nimg : a.nimg) * per_plane;
-    long long b = (work[gi] * target + total / 2) / total;
-    b = b < 1 ? 1 : b > tiles ? tiles : b;
-    a.ws_blk[gi + 1] = a.ws_blk[gi] + (int)b;
-  }
+  for (int gi = 0; gi < a.ws_ngrp; ++gi) a.ws_blk[gi + 1] = a.ws_blk[gi] + blocks[gi];
   a.ws_xcd = 1;
   hipLaunchKernelGGL((conv_ws_kernel<CIN, COUT, TH, TW, RESID, TRP, PROJ>), dim3(a.ws_blk[a.ws_ngrp]),
                      dim3(64 * (COUT / 16)), 0, st, a);
@@ -2297,6 +2306,14 @@ __global__ __launch_bounds__(512, 1) void dconv1_all_kernel(ConvArgs a) {
     d1all_wave<2, 3, 4, 0, 1, 3, 2, 10, 1, 0>(a, lds, gi, bi, nb);
 }
 
+// launch_dconv1_all's blocks for the Y planes and for the CbCr planes
+static void dconv1_group_blocks(int nimg, long long per_plane, int* by, int* bc) {
+  const long long target = device_cus();
+  const long long ty = (long long)nimg * per_plane, tc = 2LL * nimg * per_plane;
+  *by = (int)std::max(1LL, std::min(ty, (target + 1) / 3));
+  *bc = (int)std::max(1LL, std::min(tc, target - *by));
+}
+
 // all phases per staged tile: one 8-wave block per CU, blocks split between the models in
 // proportion to their tiles (Y : CbCr = 1 : 2)
 static hipError_t launch_dconv1_all(ConvArgs a, hipStream_t st) {
@@ -2306,9 +2323,8 @@ static hipError_t launch_dconv1_all(ConvArgs a, hipStream_t st) {
   if (nt == 0) return hipSuccess;
   if (nt > INT32_MAX || a.P != 3 * a.nimg || a.OH != 2 * a.H || a.OW != 2 * a.W || !a.in_u8) return hipErrorInvalidValue;
   if ((long long)a.OH * a.OW * 256 >= (1LL << 31)) return hipErrorInvalidValue;  // 32-bit granule offsets
-  const long long target = device_cus();
-  const long long ty = (long long)a.nimg * per_plane, tc = 2LL * a.nimg * per_plane;
-  const int by = (int)std::max(1LL, std::min(ty, (target + 1) / 3)), bc = (int)std::max(1LL, std::min(tc, target - by));
+  int by, bc;
+  dconv1_group_blocks(a.nimg, per_plane, &by, &bc);
   a.ws_ngrp = 2;
   a.ws_blk[0] = 0;
   a.ws_blk[1] = by;
@@ -2700,6 +2716,16 @@ static void k3pair_balance(long long total, int H, int G, K3Ranges& r) {
   fill(hi, true);
 }
 
+// The pair's grid for `rows` rows of the stream of all planes' rows:
+// at most one block per CU, at least 4 rows per block: a block's fixed cost is 3 pipeline fill
+// steps and 2 recomputed conv_a rows, so small batches (the host surface's chunks: 11-21
+// images) are faster spread over every CU with few rows each than on fewer CUs with more (16
+// rows per block left 124 of 256 CUs idle at 11 images)
+static int k3pair_grid(long long rows) {
+  constexpr int sr = 4;
+  return (int)std::max(1LL, std::min<long long>((rows + sr - 1) / sr, device_cus()));
+}
+
 hipError_t launch_k3pair_x3(const ConvArgs& a0, hipStream_t st) {
   ConvArgs a = a0;
   if (!k3pair_supported(a.H, a.W) || a.OH != a.H || a.OW != a.W || !a.wx2 || !a.bias2 || a.P != 3 * a.nimg)
@@ -2707,12 +2733,7 @@ hipError_t launch_k3pair_x3(const ConvArgs& a0, hipStream_t st) {
   a.tiles_x = k3pair_strips(a.W);
   const long long rows = (long long)a.P * a.tiles_x * a.H;
   if (rows == 0) return hipSuccess;
-  // at most one block per CU, at least 4 rows per block: a block's fixed cost is 3 pipeline fill
-  // steps and 2 recomputed conv_a rows, so small batches (the host surface's chunks: 11-21
-  // images) are faster spread over every CU with few rows each than on fewer CUs with more (16
-  // rows per block left 124 of 256 CUs idle at 11 images)
-  constexpr int sr = 4;
-  const int grid = (int)std::max(1LL, std::min<long long>((rows + sr - 1) / sr, device_cus()));
+  const int grid = k3pair_grid(rows);
   const int mt = (a.W + 15) / 16;
   // SKEW: conv_b runs each row's epilogue at the start of the next step, beside conv_a's MFMA
   // stream, instead of after its own stream (the lockstep order measured 1.3 % slower)
@@ -3140,6 +3161,13 @@ hipError_t launch_layer_x3(LayerId id, const ConvArgs& a, hipStream_t st) {
 hipError_t launch_dconv7_proj_x3(const ConvArgs& a, hipStream_t st) {
   if (!a.proj || !a.proj_w || a.OH != 2 * a.H || a.OW != 2 * a.W) return hipErrorInvalidValue;
   return launch_ws<64, 64, 8, 8, false, true, true>(a, st);
+}
+
+void decoder_launch_info(int n, int h8, int w8, int blocks[5]) {
+  const int h2 = 2 * h8, w2 = 2 * w8;
+  dconv1_group_blocks(n, (long long)((h8 + 7) / 8) * ((w8 + 7) / 8), &blocks[0], &blocks[1]);
+  ws_group_blocks(n, 3 * n, (long long)((h2 + 7) / 8) * ((w2 + 7) / 8), &blocks[2]);
+  blocks[4] = k3pair_supported(h2, w2) ? k3pair_grid(3LL * n * k3pair_strips(w2) * h2) : 0;
 }
 
 // ====================================================================================

@@ -15,6 +15,10 @@ Parity contract, stated per test:
     than a tile, every cross-over of tiles per block and every k3-pair form
     (test_encode_padding_residues, test_encode_tiny_images, test_encode_tile_counts_per_block,
     ENCODE_FORMS);
+  * the decoder's persistent kernels (dconv1, dconv7 with dconv8's projections, the fused pair) are
+    swept over every cross-over of 1 .. 4 tiles per block, with whole and partial tiles of different
+    images in one walk (test_decode_tile_counts_*; batch sizes from tests/decoder_walk.py, held
+    against the launches' own grids);
   * decoder fed the oracle's codes: u8 |delta| <= 1 and PSNR(build, oracle) >= 50 dB
     (check_recon), and at fp32 level (check_recon_f32): the clipped fp32 RGB within
     DECODE_F32_ATOL = 2e-5 of the float64 oracle's on every pixel, the u8 output equal to the
@@ -48,6 +52,10 @@ float64 one by 3e-7 .. 6e-7 on these inputs.
       48: 8.6e-7 / 1.7e-6    50: 7.2e-7 / 1.6e-6    64: 8.3e-7 / 1.4e-6    66: 7.8e-7 / 1.2e-6
      116: 7.2e-7 / 1.3e-6   118: 8.3e-7 / 1.3e-6   124: 1.2e-6 / 1.6e-6   126: 7.2e-7 / 1.5e-6
      176: 9.5e-7 / 1.4e-6   186: 3.6e-7 / 6.0e-7     4: 8.3e-7 / 1.1e-6     2: 1.2e-7 / 1.8e-7
+  tile counts per block (256 CUs; records, not bounds), worst of
+      (n,1,1),  n = 85, 86, 170, 171, 172, 255, 256, 257, 340 .. 343, 511 .. 514:   2.7e-7 / 4.8e-7
+      (n,1,9),  n = 42, 43, 56, 57, 58, 85, 86, 113, 114, 115 (partial tiles):       4.2e-7 / 1.0e-6
+      (n,1,17), n = 28, 29, 34, 35, 56, 57, 58, 68, 69 (mixed buffers):              4.2e-7 / 1.1e-6
 Encoder max |f - oracle| on the pre-quant latent, measured the same way (records, not bounds: the
 bound of every case is PREQUANT_ATOL = 2e-5):
   ENCODE_FORMS, by plane width:
@@ -456,6 +464,109 @@ def test_decode_forms_vs_live_oracle(shape, plane_w, fused, why, codecs, weights
     assert r.shape == rf_ref.shape == (n, 8 * h8, 8 * w8, 3)
     report_recon_f32(f"forms{shape} W={plane_w}", c, rf, r, rf_ref, SHARE_SPREAD)
     check_recon(r, O.quantise_u8(rf_ref))
+
+
+DECODE_LAYERS = ("dconv1", "dconv5", "dconv6", "dconv7", "dconv8")
+
+
+def _decode_walk_batch(c, weights, cus, n, h8, w8):
+    """One batch of test_decode_tile_counts_*: n seeded latents of h8 x w8 decoded in one call,
+    against the float64 oracle and against the same images at other places of the blocks' walks.
+    Returns max |rf - oracle|."""
+    from tests import decoder_walk
+    z = np.random.default_rng(1000 * h8 + w8 + 100000 * n).integers(0, 256, (n, h8, w8, 96), dtype=np.uint8)
+    what = f"tilecounts({n},{h8},{w8}) on {cus} CUs: {decoder_walk.describe(cus, n, h8, w8)}"
+    zd = _dev(z)
+    (rd, fd), launches = _launches(c, DECODE_LAYERS, lambda: c.decode(zd, rgb_f32=True))
+    if c.precision == "f16x3":  # one launch per kernel for all n images, dconv5 inside the pair's
+        assert launches == (1, 0, 1, 1, 1), (what, launches)
+        # the grids from the launches' own split functions: the batches stand on the cross-overs
+        # only while decoder_walk restates them
+        grids = c.decode_launch_info(n, h8, w8)
+        assert grids == {"dconv1": decoder_walk.dconv1_groups(cus, n, h8, w8)[1],
+                         "dconv7": decoder_walk.dconv7_groups(cus, n, h8, w8)[1],
+                         "pair": decoder_walk.pair_grid(cus, n, h8, w8)[1]}, (what, "the device launches", grids)
+    r, rf = rd.cpu().numpy(), fd.cpu().numpy()
+    rf_ref = oracle_decode_f32(("dwalk", n, h8, w8), weights, z)
+    assert r.shape == rf.shape == rf_ref.shape == (n, 8 * h8, 8 * w8, 3), (what, r.shape, rf.shape, rf_ref.shape)
+    worst = report_recon_f32(what, c, rf, r, rf_ref, SHARE_SPREAD)
+    check_recon(r, O.quantise_u8(rf_ref))
+    # the batch in reverse order: every image in another block and at another place of a walk
+    rb, fb = c.decode(zd.flip(0).contiguous(), rgb_f32=True)
+    assert torch.equal(rb.flip(0), rd) and torch.equal(fb.flip(0), fd), (
+        what, "reversed batch differs in images", torch.nonzero((fb.flip(0) != fd).flatten(1).any(1)).flatten().tolist()[:16])
+    for i in sorted({0, n - 1}):  # alone: every block walks one tile (or one plane's few)
+        r1, f1 = c.decode(zd[i:i + 1].contiguous(), rgb_f32=True)
+        assert torch.equal(r1[0], rd[i]) and torch.equal(f1[0], fd[i]), (what, "image alone differs", i)
+    return worst
+
+
+def _decode_walk(c, weights, h8, w8, batches):
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    worst = {n: _decode_walk_batch(c, weights, cus, n, h8, w8) for n in batches(cus)}
+    print(f"\ndecode tile counts (n,{h8},{w8}) {c.precision} on {cus} CUs, n = {sorted(worst)}: "
+          f"worst max|delta| {max(worst.values()):.2e}")
+
+
+def test_decode_tile_counts_per_block(codecs, weights_spread):
+    """The tiles a block of the decoder's persistent kernels walks, at every cross-over of 1, 2, 3
+    and 4 tiles per block (dconv1's Y group: 5 as well).  tests/decoder_walk.py restates the
+    launches' splits: dconv1_all_kernel takes one block per CU, (CUs + 1) // 3 for the Y planes and
+    the rest for CbCr (launch_dconv1_all); dconv7 with dconv8's projections takes 2 CUs blocks
+    split 1 : 2 and rounded (launch_ws); block bi of a group of nb walks tiles bi, bi + nb, ...
+    In d1all_wave the count decides the pairs of the loop and its odd tail, the prefetch two tiles
+    ahead (load_codes(cqb, ntile > 1), load_codes(cq, i + 2 < ntile)) and the halo buffer taken by
+    tile parity; in ws_body, four phases one after the other, the halo of tile i + 1 issued only
+    while i + 1 < ntile and tile i - 1's projection stored during tile i, the last at i == ntile.
+    Latents (n, 1, 1): every plane is one dconv1 tile and one dconv7 tile, so consecutive tiles
+    of a block are different planes of different images, and a block of the fused dconv5+dconv6
+    pair streams up to six 2-row planes, one of them across the Y -> CbCr switch
+    (launch_k3pair_x3: 4 rows per block at least, the 6 n rows on at most CUs blocks).  n runs over
+    decoder_walk.crossover_batches(CUs, 1, 1, 3), the batches either side of each step of the
+    most tiles a block walks, for both kernels and both model groups, and dconv1's Y 4 -> 5; on
+    256 CUs that is n = 85, 86, 170, 171, 172, 255, 256, 257, 340, 341, 342, 343, 511 .. 514.
+    Every batch is one decode call; in f16x3 the Codec cuts no batch and takes the pair, asserted
+    through the launch counts of DECODE_LAYERS, (1, 0, 1, 1, 1) (fp32 mode has other kernels and
+    holds the contract alone).  Per batch: the shape, report_recon_f32 against the float64 oracle
+    with the share bound, check_recon; the batch decoded in reverse order bit-equal, u8 and
+    floats, to the forward decode flipped; images 0 and n - 1 decoded alone bit-equal to their
+    places in the batch.  A change to either launch's split moves the cross-overs: in f16x3 the
+    grids the launches' split functions give (Codec.decode_launch_info) must equal decoder_walk's
+    for every batch, so such a change fails here until it is restated in decoder_walk, whose CPU
+    test pins these figures."""
+    from tests import decoder_walk
+
+    def batches(cus):
+        y45 = [n for kernel, group, k, n in decoder_walk.crossovers(cus, 1, 1, 4) if (kernel, group, k) == ("dconv1", "Y", 4)]
+        return sorted(set(decoder_walk.crossover_batches(cus, 1, 1, 3)) | {m for n in y45 for m in (n, n + 1)})
+    _decode_walk(codecs["spread"], weights_spread, 1, 1, batches)
+
+
+def test_decode_tile_counts_partial_tiles(codecs, weights_spread):
+    """The same with latents (n, 1, 9): a plane is 2 dconv1 tiles, the second one column wide, and
+    (input 2 x 18) 3 dconv7 tiles, the last two columns wide; the pair runs MT = 2.  A block's
+    walk mixes whole and partial tiles of different planes and images: a halo slot that a partial
+    tile leaves untouched would still hold the whole tile's record from two tiles before.  Which
+    kinds meet in one LDS buffer (tile i and tile i + 2 of a walk) follows from the group's blocks
+    modulo the tiles per plane; on 256 CUs dconv1's 85 and 171 blocks are odd, so its walks
+    alternate whole and partial tiles and each buffer keeps one kind; dconv7's 341 CbCr blocks
+    (2 mod 3) bring all three kinds of tile through each buffer, its 171 Y blocks (0 mod 3) one
+    kind per block.  test_decode_tile_counts_mixed_buffers changes kind within a buffer in both
+    kernels.  n runs over decoder_walk.crossover_batches(CUs, 1, 9, 2): 42, 43, 56, 57, 58, 85,
+    86, 113, 114, 115 on 256 CUs."""
+    from tests import decoder_walk
+    _decode_walk(codecs["spread"], weights_spread, 1, 9, lambda cus: decoder_walk.crossover_batches(cus, 1, 9, 2))
+
+
+def test_decode_tile_counts_mixed_buffers(codecs, weights_spread):
+    """The same with latents (n, 1, 17): 3 dconv1 tiles per plane, the third one column wide, and
+    (input 2 x 34) 5 dconv7 tiles, the last two columns wide; the pair runs MT = 3.  On 256 CUs
+    dconv1's 85 Y blocks are 1 mod 3 and dconv7's 171 and 341 blocks 1 mod 5, so tiles i and i + 2
+    of a walk, which share an LDS buffer, are different tiles of their planes: whole after
+    partial and partial after whole in the same buffer, in both kernels.  n runs over
+    decoder_walk.crossover_batches(CUs, 1, 17, 2): at most 69 images of 8 x 136 on 256 CUs."""
+    from tests import decoder_walk
+    _decode_walk(codecs["spread"], weights_spread, 1, 17, lambda cus: decoder_walk.crossover_batches(cus, 1, 17, 2))
 
 
 @pytest.mark.parametrize("shape,plane_w,fused,why", ENCODE_FORMS, ids=[f"W{f[1]}" for f in ENCODE_FORMS])
