@@ -396,6 +396,36 @@ int nic_rans3_decode(nic_ctx* ctx, const uint8_t* files, int64_t stride, const i
 int nic_rans3_inspect(const uint8_t* host_file, int64_t size, int* h8, int* w8, int* seg_pixels, int* H, int* W,
                       uint32_t* prior_id);
 
+/* ---- Rate-distortion optimised quantisation against a .nic prior --------------------------------
+ * An encoder-side step between nic_encode and nic_rans2_encode / nic_rans3_encode: every latent byte
+ * keeps its code or moves one step towards its pre-quant value, whichever costs less in distortion
+ * plus lambda times the bits the prior charges.  The file format and the decoder are untouched
+ * (DESIGN.md §25).  Per byte, with r the code (nic_encode's latent) and f its pre-quant value
+ * (nic_encode's prequant, in [0, 1]):
+ *   v = f * 255 and e = v - r, one fp32 multiply and one fp32 subtract, not contracted
+ *   alt = r + 1 if e > 0, r - 1 if e < 0, r if e = 0 (held inside 0..255); candidate 0 is r, 1 is alt
+ *   D(q) = (u64) rintf((v - q) * (v - q) * 65536) << 16, the same unfused fp32 operations
+ *   rate(q | row F) = lam_fix * cost16[F[q]] (nic_rans_cost_table), lam_fix = round(lambda 65536)
+ * contexts = 1, the static prior: every byte on its own under its channel's row; the smaller
+ *   D + rate, a tie to r.  seg_pixels is checked and otherwise unused.
+ * contexts = 3, the context prior: every (segment, channel) chain as a whole, segments and rows
+ *   exactly version 3's under the call's seg_pixels, the row of a pixel chosen by the code KEPT for
+ *   the pixel before it: best[p][b] = min over b' of best[p-1][b'] + D(p, b) + rate(p, b | ctx(b')),
+ *   a tie to b' = 0; the end state is the smaller best, a tie to 0; then the back-pointers are walked.
+ * The prior's rows price every channel; whether a channel then keeps its own table in the file is
+ * the coder's choice as before, which can only make the file smaller than what was priced.
+ * lam_fix = 0 returns latent; the output differs from latent by at most 1 per byte and stays in
+ * 0..255.  Deterministic; on `stream`, no host synchronisation, no workspace.
+ *
+ * nic_rdoq: latent, latent_out (n,h8,w8,96) u8 and prequant (n,h8,w8,96) fp32, all 16-byte aligned
+ *     device buffers.  seg_pixels in 1..64 (the back-pointers of a chain are two 64-bit masks;
+ *     NIC_ESHAPE otherwise), lam_fix in 0..16 * 65536 and contexts 1 or 3 (NIC_EINVAL otherwise).
+ *     latent_out must not overlap latent (NIC_EINVAL).  NIC_ENOPRIOR before nic_rans_prior_set
+ *     (contexts 1) or nic_rans_cprior_set (contexts 3).
+ * Arguments are validated before any HIP call: shape, empty batch (OK), NULL, then the prior. */
+int nic_rdoq(nic_ctx* ctx, const uint8_t* latent, const float* prequant, int n, int h8, int w8, int seg_pixels,
+             uint32_t lam_fix, int contexts, uint8_t* latent_out, void* stream);
+
 /* ---- Region decode: a pixel box out of a .nic file (every container version) --------------------
  * A file's segment table is a random-access index: segment k holds the latent pixels [k S, (k+1) S)
  * of the row-major order (S = seg_pixels), so a window of the latent needs only the segments that

@@ -114,8 +114,10 @@ _SIGNATURES = {
     "nic_rans3_decode": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp] + [ctypes.c_int] * 3 + [c_vp, c_vp, c_vp]),
     "nic_rans3_inspect": (ctypes.c_int, [c_vp, ctypes.c_int64] + [ctypes.POINTER(ctypes.c_int)] * 5
                           + [ctypes.POINTER(ctypes.c_uint32)]),
+    # rate-distortion optimised quantisation against a prior (nic_rdoq.hip)
+    "nic_rdoq": (ctypes.c_int, [c_vp, c_vp, c_vp] + [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_int, c_vp, c_vp]),
     # region decode: a latent window out of .nic files (nic_rans.hip)
-    "nic_region_plan": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_int)] * 2),
+    "nic_region_plan":(ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_int)] * 2),
     "nic_rans_window_segments": (ctypes.c_int, [ctypes.c_int] * 7 + [ctypes.POINTER(ctypes.c_int64)]),
     "nic_rans_decode_window": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp] + [ctypes.c_int] * 7 + [c_vp, c_vp, c_vp]),
     "nic_rans2_decode_window": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp] + [ctypes.c_int] * 7 + [c_vp, c_vp, c_vp]),

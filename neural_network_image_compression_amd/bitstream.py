@@ -689,7 +689,7 @@ def _batches(shapes: Sequence[tuple], batch_size: int):
 
 
 def feed_batch(model, x: np.ndarray, filenames: Sequence[str], output_dir: str, in_cshape: int,
-               pool=None, png_threads: int = 16, container: str = "png", png_writer: str = "pillow") -> list:
+               pool=None, png_threads: int = 16, container: str = "png", png_writer: str = "pillow", rdoq=None) -> list:
     """utils.py:30-44 for one batch: unpack (decoder side), run the codec, pack (encoder side), save.
 
     The batch's PNG files are encoded natively on ``png_threads`` host threads (nic_png_encode,
@@ -700,7 +700,10 @@ def feed_batch(model, x: np.ndarray, filenames: Sequence[str], output_dir: str, 
     (nic_files), copied to the host once, and the writer only writes them.
 
     png_writer "device" (decoder side): the reconstructions are made into PNG files on the device
-    (png_files_device) and never reach the host as pixels; the writer only writes them."""
+    (png_files_device) and never reach the host as pixels; the writer only writes them.
+
+    rdoq (encoder side of container "nic", a prior set on the codec): the codes are chosen by
+    distortion + rdoq x bits under that prior (Encoder.encode_rdoq) before nic_files codes them."""
     import torch
 
     codec = model.codec
@@ -709,7 +712,7 @@ def feed_batch(model, x: np.ndarray, filenames: Sequence[str], output_dir: str, 
     n, h, w, c = dev.shape
     if in_cshape == 96 and c == 3:
         dev = codec.unpack(dev)
-    out = model._device_call(dev)
+    out = model._device_call(dev) if rdoq is None else model.encode_rdoq(dev, rdoq, NIC_SEG_PIXELS)
     if container == "nic" and out.shape[-1] == 96:
         datas = nic_files(codec, out, size=(h, w))  # versions 2 and 3 (a prior is set) record the images' own size
         if pool is None:
@@ -806,7 +809,8 @@ def _set_any_prior(codec, prior) -> None:
 
 def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, in_cshape: int,
               batch_size: int = 64, workers=None, container: str = "png", png_writer: str = "pillow",
-              prior=None, region=None, png_reader: str = "pillow", resize=None, resize_mode: str = "center") -> None:
+              prior=None, region=None, png_reader: str = "pillow", resize=None, resize_mode: str = "center",
+              rdoq=None) -> None:
     """utils.py:46-62: every colour image of ``dataset_path`` (sorted; read_dataset's filter)
     through the codec into ``output_dir``, one PNG per image named after its source.
 
@@ -850,7 +854,12 @@ def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, i
     ``RESIZE_POOL_BYTES`` of source pixels), go up as one pool and are resized to oh x ow on the device
     from the boxes ``codec.fit_boxes(shapes, resize, resize_mode)`` (resize_batch); what is encoded and
     written is the resized image, and version-2 and version-3 ``.nic`` files record oh x ow as its size.
-    A colour image that is not (H, W, 3), such as RGBA, is a ValueError naming the file."""
+    A colour image that is not (H, W, 3), such as RGBA, is a ValueError naming the file.
+
+    ``rdoq=lam`` (the encoder side of ``container="nic"`` with a prior -- ``prior=`` or one set on the
+    codec before -- and lam in [0, 16]; ValueError otherwise): every batch's codes are chosen by
+    distortion + lam x bits under the prior its files are coded with, the context prior first
+    (Encoder.encode_rdoq).  Without it nothing changes, not even the launches."""
     if container not in CONTAINERS:
         raise ValueError(f"container must be one of {CONTAINERS}, got {container!r}")
     _check_png_writer(png_writer, decoder_side=in_cshape == 96)
@@ -867,6 +876,15 @@ def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, i
         if container != "nic":
             raise ValueError('prior applies to container="nic" only: the PNG container has no entropy model')
         _set_any_prior(model.codec, prior)
+    if rdoq is not None:
+        if container != "nic" or in_cshape != 3:
+            raise ValueError('rdoq applies to the encoder side of container="nic" only: it prices the codes under '
+                             "the prior the .nic files are coded with")
+        if model.codec.prior is None and model.codec.context_prior is None:
+            raise ValueError("rdoq needs a prior: pass prior=, or set one on the codec")
+        rdoq = float(rdoq)
+        if not 0.0 <= rdoq <= model.codec.RDOQ_LAM_MAX:
+            raise ValueError(f"rdoq {rdoq} not in [0, {model.codec.RDOQ_LAM_MAX:g}]")
     if container == "nic" and in_cshape == 96:
         more = {"region": region} if region is not None else {}
         return use_model_nic_in(model, dataset_path, checkpoint_path, output_dir, batch_size=batch_size, workers=workers,
@@ -874,6 +892,8 @@ def use_model(model, dataset_path: str, checkpoint_path: str, output_dir: str, i
     extra = {"container": container} if container != "png" else {}
     if png_writer != "pillow":
         extra["png_writer"] = png_writer
+    if rdoq is not None:
+        extra["rdoq"] = rdoq
     os.makedirs(output_dir, exist_ok=True)
     model.load(checkpoint_path)
     device_reader = png_reader == "device"

@@ -616,6 +616,48 @@ class Codec:
         return self._rans_decode(3, buf, sizes, h8, w8)
 
 
+    # -- rate-distortion optimised quantisation against the codec's prior (nic_rdoq) -------------
+    #: the largest lambda of rdoq (lam_fix = round(lam * 65536) stays inside nic_rdoq's range)
+    RDOQ_LAM_MAX = 16.0
+
+    def rdoq(self, z, f, lam: float, seg_pixels: int = 32, prior=None, out=None):
+        """Codes z (N,h,w,96) u8 and their pre-quant values f (N,h,w,96) fp32, as encode(x,
+        prequant=True) returns them -> the codes that cost least in distortion + lam x bits under the
+        codec's prior: every code stays or moves one step towards its pre-quant value (nic_rdoq; no
+        host synchronisation).  prior: "static" (set_prior; every code on its own), "context"
+        (set_context_prior; every (segment, channel) chain of seg_pixels in 1..64 pixels as a whole),
+        or None: whichever is set, the context prior first, as nic_files prefers.  lam in [0, 16]; 0
+        returns z's codes.  out: the (N,h,w,96) u8 tensor to write (not z; default: a new one).
+        NicError(NIC_ENOPRIOR) when that prior is not set."""
+        torch = _torch()
+        z = self._check_dev(z, 4, 96, "rdoq")
+        if (not isinstance(f, torch.Tensor) or f.dtype != torch.float32 or f.device != z.device
+                or tuple(f.shape) != tuple(z.shape)):
+            raise TypeError("rdoq: f must be a torch.float32 tensor of z's shape on the codec's device")
+        if prior not in (None, "static", "context"):
+            raise ValueError(f'rdoq: prior must be "static", "context" or None, got {prior!r}')
+        lam = float(lam)
+        if not 0.0 <= lam <= self.RDOQ_LAM_MAX:  # also refuses NaN
+            raise ValueError(f"rdoq: lam {lam} not in [0, {self.RDOQ_LAM_MAX:g}]")
+        if prior is None:
+            prior = "static" if self.context_prior is None and self.prior is not None else "context"
+        f = f.contiguous()
+        if z.data_ptr() % 16:
+            z = z.clone()
+        if f.data_ptr() % 16:
+            f = f.clone()
+        if out is None:
+            out = torch.empty_like(z)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != tuple(z.shape)
+              or out.device != z.device or not out.is_contiguous()):
+            raise TypeError("rdoq: out must be a contiguous (N,h,w,96) torch.uint8 tensor on the codec's device")
+        n, h8, w8, _ = z.shape
+        _lib.check(self._L.nic_rdoq(self._h, z.data_ptr(), f.data_ptr(), n, h8, w8, int(seg_pixels), int(round(lam * 65536)),
+                                    3 if prior == "context" else 1, out.data_ptr(), _stream_ptr(torch, self.device)),
+                   "nic_rdoq")
+        return out
+
+
     # -- region decode: a latent window out of .nic files (nic_region_plan, nic_rans*_decode_window) --
     @staticmethod
     def region_plan(H: int, W: int, box):
@@ -1139,6 +1181,13 @@ class Encoder(ProClass):
             raise ValueError(f"Encoder: expected shape (N,H,W,3), got {a.shape}")
         return self.codec.encode_host(a, self.host_chunks)
 
+    def encode_rdoq(self, x, lam: float, seg_pixels: int = 32):
+        """(N,H,W,3) u8 on the device -> the latent whose codes are chosen by distortion + lam x bits
+        under the codec's prior: encode(x, prequant=True), then Codec.rdoq (the context prior first).
+        lam = 0 gives encode(x)'s codes."""
+        z, f = self.codec.encode(x, prequant=True)
+        return self.codec.rdoq(z, f, lam, seg_pixels)
+
     #: images per device batch of encode_resized: cut by count, since every batch has one shape
     resized_batch = 64
 
@@ -1180,7 +1229,7 @@ class Encoder(ProClass):
 
     def compress(self, dataset_path: str, checkpoint_path: str, batch_size: int = 64, workers=None,
                  container: str = "png", prior=None, png_reader: str = "pillow", resize=None,
-                 resize_mode: str = "center") -> None:
+                 resize_mode: str = "center", rdoq=None) -> None:
         """encoder.py:49-51: every image in ``dataset_path`` -> ``dataset_path + '_compressed'``.
         Pipelined over the host cores in batches of ``batch_size`` (bitstream.use_model);
         ``workers=0, batch_size=4`` is the reference's serial loop (same files).
@@ -1194,12 +1243,18 @@ class Encoder(ProClass):
         ``resize=(oh, ow)``: every image, whatever its size, is first resized on the device to oh x ow
         from the box fit_boxes(..., resize_mode) gives it, and the directory goes through the device
         ``batch_size`` images at a time whatever their sizes (bitstream.use_model); version-2 and
-        version-3 ``.nic`` files record oh x ow as the image's size.  Without it nothing changes."""
+        version-3 ``.nic`` files record oh x ow as the image's size.  Without it nothing changes.
+        ``rdoq=lam`` (``container="nic"`` with a prior only, lam in [0, 16]; ValueError otherwise):
+        every batch's codes are chosen by distortion + lam x bits under the prior the files are coded
+        with (encode_rdoq) before they are coded; any ``.nic`` reader decodes the files.  Without it
+        nothing changes, not even the launches."""
         from .bitstream import use_model
 
         more = {"png_reader": png_reader} if png_reader != "pillow" else {}
         if resize is not None:
             more.update(resize=resize, resize_mode=resize_mode)
+        if rdoq is not None:
+            more["rdoq"] = rdoq
         use_model(self, dataset_path, checkpoint_path, dataset_path + "_compressed", in_cshape=3,
                   batch_size=batch_size, workers=workers, container=container, prior=prior, **more)
 

@@ -1694,6 +1694,29 @@ int nic_rans_cprior_build(nic_ctx* c, const uint64_t* counts, uint16_t* freqs, v
   return rans_prior_build("nic_rans_cprior_build", true, c, counts, freqs, stream);
 }
 
+// ---- rate-distortion optimised quantisation (nic_rdoq.hip) ----
+int nic_rdoq(nic_ctx* c, const uint8_t* latent, const float* prequant, int n, int h8, int w8, int seg_pixels, uint32_t lam_fix,
+             int contexts, uint8_t* latent_out, void* stream) {
+  const char* fn = "nic_rdoq";
+  int rc = rans_check(fn, n, h8, w8, 1);
+  if (rc) return rc;
+  if (seg_pixels < 1 || seg_pixels > 64) return fail(NIC_ESHAPE, "%s: seg_pixels %d not in 1..64", fn, seg_pixels);
+  if (lam_fix > (16u << 16)) return fail(NIC_EINVAL, "%s: lam_fix %u not in 0..%u (lambda in 0..16)", fn, lam_fix, 16u << 16);
+  if (contexts != 1 && contexts != 3) return fail(NIC_EINVAL, "%s: contexts %d is neither 1 (the prior) nor 3 (the context prior)", fn, contexts);
+  if (n == 0) return NIC_OK;
+  if (!c) return fail(NIC_EINVAL, "%s: NULL ctx", fn);
+  if (!latent || !prequant || !latent_out) return fail(NIC_EINVAL, "%s: NULL buffer", fn);
+  if ((uintptr_t)latent % 16 || (uintptr_t)prequant % 16 || (uintptr_t)latent_out % 16)
+    return fail(NIC_EINVAL, "%s: latent, prequant and latent_out must be 16-byte aligned", fn);
+  const uintptr_t bytes = (uintptr_t)n * h8 * w8 * 96, a = (uintptr_t)latent, b = (uintptr_t)latent_out;
+  if (a < b + bytes && b < a + bytes) return fail(NIC_EINVAL, "%s: latent_out overlaps latent", fn);
+  const int ver = contexts == 3 ? 3 : 2;
+  if ((rc = rans_need_prior(fn, ver, c))) return rc;
+  DeviceGuard guard(c->device);
+  HIP_TRY(launch_rdoq(latent, prequant, n, h8, w8, seg_pixels, lam_fix, ctx_prior(c, ver), latent_out, (hipStream_t)stream));
+  return NIC_OK;
+}
+
 
 // ---- device PNG writer (nic_png_dev.hip; nic_png_device_block_bytes and nic_png_device_bound are host-only there) ----
 static int png_dev_check(const char* fn, int n, int h, int w, int channels, int filter) {

@@ -226,6 +226,14 @@ hipError_t launch_rans_decode(int ver, const uint8_t* files, long long stride, c
 hipError_t launch_cut_boxes(const uint8_t* src, int n, int Hs, int Ws, const int* off, int bh, int bw, uint8_t* dst,
                             hipStream_t st);
 
+// --- rate-distortion optimised quantisation against a .nic prior (nic_rdoq.hip) -------------------
+// out (n, h8, w8, 96) = for every byte of z the cheaper of its code and the neighbouring code on the
+// side of its pre-quant value f, by distortion + lam_fix * cost16 under prior: the static prior (every
+// byte on its own) or, with prior.anchor, the context prior (a two-state Viterbi pass per (segment,
+// channel) chain; seg_pixels in 1..64).  z and out 4-byte, f 16-byte aligned; out does not alias z.
+hipError_t launch_rdoq(const uint8_t* z, const float* f, int n, int h8, int w8, int seg_pixels, unsigned lam_fix,
+                       const RansPrior& prior, uint8_t* out, hipStream_t st);
+
 // --- crops for training (nic_resample.hip) ------------------------------------------------------
 // Row i of table (int32[n][6] = (oy, ox, bh, bw, flip, dst) on the device) names a box of image i of
 // images (n, Hs, Ws, 3) u8; the box is resized to oh x ow (bilinear, antialiased), mirrored where flip
